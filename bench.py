@@ -9,8 +9,13 @@ when N > 1).  Per-GPU batch is fixed (weak scaling); every candidate runs all 4 
 (no early-exit compaction), so one candidate = 23.72 GFLOP of algorithmic denoiser work
 (SURVEY.md section 8(d)).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--precision P] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--precision P] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what else the bench measures: the
+dominant kernel's roofline (events inside the timed region, a second profiling pass), the early-exit and plain-bf16 lines
+and the CPU baseline (the --no-* options drop single ones of them).  --dump-outputs DIR writes what the timed path computed
+in its last step as DIR/<name>.npy (float64; the inputs are seeded, so two builds can be compared output for output).
 
 Other workloads of BASELINE.json's config list (each prints its own one-line JSON with `roofline`):
     --workload rollout       config 5: 65 536 car rollouts x T = 16 steps, the rollout kernel alone (no denoiser);
@@ -950,6 +955,21 @@ def run_ant_round(args):
         dist.destroy_process_group()
 
 
+def dump_outputs(path, arrays, limit=64 << 20):
+    """--dump-outputs: one float64 DIR/<name>.npy per array.  When they exceed `limit` bytes together, every array keeps the
+    same fixed, seeded share of its leading-axis rows, and the kept row numbers go to DIR/<name>_rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v.cpu().numpy() if torch.is_tensor(v) else v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    keep = 1.0 if total <= limit else limit / (2.0 * total)      # half the limit: room for the row-number files
+    for name, a in arrays.items():
+        if keep < 1.0:
+            rows = np.sort(np.random.default_rng(0).choice(len(a), int(len(a) * keep), replace=False))
+            np.save(os.path.join(path, f"{name}_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(path, f"{name}.npy"), a)
+
+
 def dataclass_replace(args, **kw):
     import copy
     a = copy.copy(args)
@@ -983,7 +1003,19 @@ def main():
     ap.add_argument("--no-profile", action="store_true", help="skip the per-launch event timing")
     ap.add_argument("--no-early-exit-line", action="store_true",
                     help="skip the extra (informational) timing with alive-candidate compaction")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what lies beside the headline: roofline / per-kernel times, the early-exit and plain-bf16 "
+                         "lines, the CPU baseline.  Without it the four --no-* options above are all in force")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="expand workload: write the last timed step's results (round buffers, appended tree nodes, counters) "
+                         "as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload != "expand":
+        ap.error("--dump-outputs: the expand workload only")
+    if not args.full:
+        args.no_throughput_line = args.no_cpu_baseline = args.no_profile = args.no_early_exit_line = True
     args.batch_set = any(a == "--batch" or a.startswith("--batch=") for a in sys.argv[1:])
     args.precision_set = any(a == "--precision" or a.startswith("--precision=") for a in sys.argv[1:])
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1045,9 +1077,10 @@ def main():
     c_dev = torch.as_tensor(cond, device=dev)
     n_dev = noise.to(dev)
     torch.cuda.synchronize()
+    last = {}
 
     def step():
-        eng.expand_round(s_dev, c_dev, noise=n_dev)       # includes all-gather (N > 1) and accept
+        last["counters"] = eng.expand_round(s_dev, c_dev, noise=n_dev)       # includes all-gather (N > 1) and accept
         reset_tree()
 
     for _ in range(args.warmup):
@@ -1061,6 +1094,17 @@ def main():
     if eng.exchange_events:
         exch_ms = float(np.mean([a.elapsed_time(b) for a, b in eng.exchange_events]))
     eng.exchange_events = None
+    if args.dump_outputs and rank == 0:
+        # before any further pass overwrites the buffers.  Every rank holds every candidate's record after the exchange;
+        # trajectories stay on the rank that produced them, so these are rank 0's own candidates'
+        lo, hi, _ = eng.shard(Btot)
+        rb, cnt = eng.rb, last["counters"]
+        n_nodes = int(cnt[CNT_NODES])
+        dump_outputs(args.dump_outputs, {
+            "status": rb.status[:Btot], "parent": rb.parent[:Btot], "chunks_run": rb.chunks_run[:Btot],
+            "end_state": rb.end_state[:Btot], "node_id": rb.node_id[:Btot],
+            "states": rb.states[lo:hi], "actions": rb.actions[lo:hi], "chunk_steps": rb.chunk_steps[lo:hi],
+            "tree_state": t.state[N0:n_nodes], "tree_parent": t.parent[N0:n_nodes], "counters": cnt})
     prof = prof_all = None
     if not args.no_profile:
         prof = ctx.profile_read(args.precision)

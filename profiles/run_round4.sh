@@ -7,9 +7,9 @@ part=${1:-1}
 out=$PWD/gpurun_out
 mkdir -p "$out"
 if [ "$part" = 1 ]; then
-  python bench.py > "$out/r04_bench_f16x3.json" 2> "$out/r04_bench_f16x3.err"
-  python bench.py --batch 4096 --steps 4 --warmup 1 --no-cpu-baseline --no-throughput-line > "$out/r04_bench_f16x3_b4096.json" 2> "$out/r04_b4096.err"
-  python bench.py --workload ant-round > "$out/r04_bench_ant_round.json" 2> "$out/r04_ant_round.err"
+  python bench.py --full > "$out/r04_bench_f16x3.json" 2> "$out/r04_bench_f16x3.err"
+  python bench.py --full --batch 4096 --steps 4 --warmup 1 --no-cpu-baseline --no-throughput-line > "$out/r04_bench_f16x3_b4096.json" 2> "$out/r04_b4096.err"
+  python bench.py --full --workload ant-round > "$out/r04_bench_ant_round.json" 2> "$out/r04_ant_round.err"
   python bench.py --workload rollout > "$out/r04_bench_rollout.json" 2> "$out/r04_rollout.err"
   python bench.py --workload rollout --model ant > "$out/r04_bench_rollout_ant.json" 2> "$out/r04_rollout_ant.err"
   python bench.py --workload mppi > "$out/r04_bench_mppi.json" 2> "$out/r04_mppi.err"

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from tests.util import REPO
@@ -82,7 +83,7 @@ def test_bench_mppi_two_ranks_rehearsed_on_one_gpu():
 def test_bench_rccl_path_on_one_gpu():
     """DITREE_FORCE_DIST=1: the record exchange through the nccl backend (RCCL) with a one-rank group -- the collective, its
     event timing and `ranks_seen` run on the real backend, which the gloo rehearsals cannot show."""
-    rc, lines, err = _run(["--steps", "2", "--warmup", "1", "--batch", "256", "--no-cpu-baseline", "--no-throughput-line",
+    rc, lines, err = _run(["--steps", "2", "--warmup", "1", "--batch", "256", "--full", "--no-cpu-baseline", "--no-throughput-line",
                            "--no-early-exit-line"], {"DITREE_FORCE_DIST": "1"}, timeout=600)
     assert rc == 0, err[-3000:]
     out = json.loads(lines[-1])
@@ -97,6 +98,42 @@ def test_bench_rccl_path_on_one_gpu():
     for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "kernel", "avg_launch_ms"):
         assert k in r, k
     assert r["bound"] == "mfma" and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-12 and r["kernel"].startswith("conv3_halo16x3_kernel")
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_round(tmp_path):
+    """Without --full the line carries the headline only; --dump-outputs writes the last timed round's results, and the
+    same arguments give the same inputs, so a second run reproduces the round."""
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        rc, lines, err = _run(["--steps", "3", "--warmup", "1", "--batch", "256", "--dump-outputs", str(d)], {}, timeout=600)
+        assert rc == 0, err[-3000:]
+        assert len(lines) == 1
+        out = json.loads(lines[0])
+        assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["value"] > 0 and out["dtype"] == "f16x3"
+        assert out["unit"] == "candidate expansions/s" and out["higher_is_better"] is True
+        for key in ("roofline", "early_exit", "throughput_mode", "cpu_baseline"):
+            assert key not in out, key
+        dumps.append({f.stem: np.load(f) for f in d.glob("*.npy")})
+    a, b = dumps
+    assert {"status", "parent", "end_state", "states", "actions", "tree_state", "counters"} <= set(a) and set(a) == set(b)
+    assert a["status"].shape == (256,) and a["end_state"].shape == (256, 6) and a["states"].shape == (256, 4, 9, 6)
+    assert a["tree_state"].shape[0] == a["counters"][0] - 1024 and all(v.dtype == np.float64 for v in a.values())
+    assert np.isfinite(a["end_state"]).all() and np.array_equal(a["status"], b["status"]) and np.array_equal(a["parent"], b["parent"])
+    assert np.abs(a["end_state"] - b["end_state"]).max() < 1e-5
+
+
+def test_dump_outputs_keeps_a_seeded_sample_under_the_limit(tmp_path):
+    import bench
+    big = np.arange(200_000 * 16, dtype=np.float64).reshape(200_000, 16)
+    for d in (tmp_path / "a", tmp_path / "b"):
+        bench.dump_outputs(str(d), {"big": big, "small": np.arange(8, dtype=np.int32)}, limit=1 << 20)
+        assert sum(f.stat().st_size for f in d.iterdir()) <= 1 << 20
+    rows = np.load(tmp_path / "a" / "big_rows.npy").astype(np.int64)
+    assert len(rows) > 1000 and np.array_equal(np.load(tmp_path / "a" / "big.npy"), big[rows])
+    assert np.load(tmp_path / "a" / "small.npy").dtype == np.float64
+    assert np.array_equal(np.load(tmp_path / "b" / "big_rows.npy"), rows)
 
 
 def test_launcher_takes_its_ranks_down_when_it_is_terminated(tmp_path):

@@ -3,11 +3,12 @@
 from this package, everything the engine does not replace falls through to the reference checkout, and the
 `common.map_utils.cc_calls` counter the drivers reset / read is the engine's.
 
-Runs in the build container only (it parses the scripts under /root/reference); third-party modules the container lacks
-(minari, gymnasium, gymnasium_robotics, diffusers, playsound, spatialmath, termcolor) are in-memory placeholders, as in
-tests/golden/make_golden.py."""
-import ast
+The import blocks, and the reference modules they reach, are recorded in tests/golden/driver_imports.json
+(tests/golden/extract_driver_imports.py); the test rebuilds a stand-in checkout from them.  Third-party modules the machine
+lacks (minari, gymnasium, gymnasium_robotics, diffusers, playsound, spatialmath, termcolor) are in-memory placeholders, as
+in tests/golden/make_golden.py."""
 import importlib
+import json
 import os
 import subprocess
 import sys
@@ -15,14 +16,14 @@ import textwrap
 
 import pytest
 
-REF = "/root/reference"
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SCRIPTS = ["run_scenarios.py", "run_scenarios_with_lidar_DiTree.py", "run_scenarios_with_lidar_MPPI.py"]
-needs_ref = pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present (GPU box)")
+with open(os.path.join(REPO, "tests", "golden", "driver_imports.json")) as f:
+    RECORD = json.load(f)
 
 CHILD = r'''
-import ast, importlib, importlib.machinery, json, os, sys, types
-ref, repo, script = sys.argv[1:4]
+import importlib, importlib.machinery, json, os, sys, types
+ref, repo, block = sys.argv[1], sys.argv[2], json.loads(sys.argv[3])
 sys.path[:] = [os.path.join(repo, "dropin"), repo, ref] + [p for p in sys.path if p]
 os.environ["DITREE_REFERENCE_ROOT"] = ref
 os.chdir(ref)
@@ -47,18 +48,12 @@ for n in THIRD:
     except ImportError:
         placeholder(n)
 
-tree = ast.parse(open(os.path.join(ref, script)).read())
 out = {}
-for node in tree.body:                       # top-level statements only: the import block
-    if isinstance(node, ast.Import):
-        for a in node.names:
-            m = importlib.import_module(a.name)
-            out[a.name] = getattr(m, "__file__", None) or "<placeholder>"
-    elif isinstance(node, ast.ImportFrom) and node.level == 0:
-        m = importlib.import_module(node.module)
-        for a in node.names:
-            getattr(m, a.name)
-        out[node.module] = getattr(m, "__file__", None) or "<placeholder>"
+for kind, module, names in block:            # the script's top-level import statements, in order
+    m = importlib.import_module(module)
+    for name in names:
+        getattr(m, name)
+    out[module] = getattr(m, "__file__", None) or "<placeholder>"
 import common.map_utils
 common.map_utils.cc_calls = 0
 from ditreeonlineplanner_amd.common import map_utils as engine_mu
@@ -69,18 +64,32 @@ print("RESULT " + json.dumps(out))
 '''
 
 
-def _resolve(script):
-    r = subprocess.run([sys.executable, "-c", CHILD, REF, REPO, script], capture_output=True, text=True, timeout=600)
+@pytest.fixture(scope="module")
+def reference_checkout(tmp_path_factory):
+    """A stand-in reference checkout: every recorded module at its path, running its recorded top-level imports and
+    defining a placeholder for each name imported from it."""
+    root = tmp_path_factory.mktemp("reference")
+    for mod in RECORD["reference_modules"].values():
+        lines = [f"import {m}" if kind == "import" else f"from {m} import {', '.join(names)}" for kind, m, names in mod["imports"]]
+        lines += [f"class {name}:\n    pass" for name in mod["names"]]
+        path = root / mod["file"]
+        path.parent.mkdir(parents=True, exist_ok=True)
+        path.write_text("\n".join(lines) + "\n")
+    return str(root)
+
+
+def _resolve(script, ref):
+    block = json.dumps(RECORD["scripts"][script])
+    r = subprocess.run([sys.executable, "-c", CHILD, ref, REPO, block], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
-    import json
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1]
     return json.loads(line[7:])
 
 
-@needs_ref
 @pytest.mark.parametrize("script", SCRIPTS)
-def test_script_import_block_resolves(script):
-    res = _resolve(script)
+def test_script_import_block_resolves(script, reference_checkout):
+    ref = reference_checkout
+    res = _resolve(script, ref)
     pkg = os.path.join(REPO, "ditreeonlineplanner_amd")
     # engine-backed names come from this repository ...
     for mod in ("car_env", "train_diffusion_policy", "policies.fm_policy", "policies.uniform_policy", "planners.RRT",
@@ -89,10 +98,10 @@ def test_script_import_block_resolves(script):
         assert res[mod].startswith(REPO), (mod, res[mod])
     assert res["common.map_utils"].startswith(pkg)
     # ... what the engine does not replace still comes from the reference checkout
-    assert res["planners.MPC"].startswith(REF), res["planners.MPC"]
+    assert res["planners.MPC"].startswith(ref), res["planners.MPC"]
     for mod in ("obstacle_insertion", "plot_logger"):
         if mod in res:
-            assert res[mod].startswith(REF), (mod, res[mod])
+            assert res[mod].startswith(ref), (mod, res[mod])
     if script.endswith("MPPI.py"):
         assert res["MPPI.mppi"].startswith(REPO)
     # the counter the drivers reset and read (run_scenarios.py:338,343) is the engine's
