@@ -45,6 +45,12 @@ class Round(C.Structure):
                 ("hist", C.c_void_p), ("hist_n", C.c_void_p)]
 
 
+class Forest(C.Structure):
+    """include/ditree.h ditree_forest: T trees of C node slots in one Tree, per-tree counter rows, candidate offsets."""
+    _fields_ = [("n_trees", C.c_int32), ("tree_capacity", C.c_int32), ("counters", C.c_void_p), ("off", C.c_void_p),
+                ("off_host", C.POINTER(C.c_int32))]
+
+
 RECORD_DOUBLES = 12          # include/ditree.h DITREE_RECORD_DOUBLES (the car's record; ditree_record_doubles for any tree)
 
 
@@ -157,6 +163,12 @@ SIGNATURES = {
     "ditree_ant_chunk_step": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Round), C.POINTER(AntRoundParams), _i32, _vp, _vp]),
     "ditree_round_stats": (_i32, [_vp, C.POINTER(_i32)]),
     "ditree_expand_round": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Round), C.POINTER(RoundParams), _vp]),
+    "ditree_forest_expand_round": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), C.POINTER(Round), C.POINTER(RoundParams), _vp]),
+    "ditree_forest_accept": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), C.POINTER(Round), _i32, _vp]),
+    "ditree_forest_chunk_budget": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), _vp, _i32, C.POINTER(_i32), _i32, _vp, _vp,
+                                          _vp]),
+    "ditree_forest_nn_argmin": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), _vp, _i32, _i32, _vp, _vp]),
+    "ditree_forest_fallback": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), _pd, _vp, _vp]),
 }
 
 _LIB = None

@@ -849,16 +849,17 @@ int32_t ditree_round_stats(ditree_ctx* ctx, int32_t* stats4) {
   return DITREE_OK;
 }
 
-int32_t ditree_expand_round(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round,
-                            const ditree_round_params* p, void* stream) {
+// The car round of one tree, or (f != NULL, validated by the caller) of a forest: only the nearest-node step differs.
+static int expand_round_impl(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* f, const ditree_round* round,
+                             const ditree_round_params* p, void* stream) {
   if (!ctx) return DITREE_E_ARG;
   int rc = check_tree(ctx, tree);
   if (rc) return rc;
   rc = check_round(ctx, round);
   if (rc) return rc;
   if (!ctx->maze) return set_err(ctx, DITREE_E_STATE, "expand_round: no maze uploaded");
-  if (!p || !p->samples || !p->cond_goal || !p->norm || !p->goal_xy || !p->axis || p->n_nodes <= 0 ||
-      p->n_nodes > tree->capacity || p->P < tree->A || (!p->noise && !p->inject_actions))
+  if (!p || !p->samples || !p->cond_goal || !p->norm || !p->goal_xy || !p->axis ||
+      (!f && (p->n_nodes <= 0 || p->n_nodes > tree->capacity)) || p->P < tree->A || (!p->noise && !p->inject_actions))
     return set_err(ctx, DITREE_E_ARG, "expand_round: bad parameters");
   if (!p->inject_actions && (!p->t0 || (!p->dt && !p->ddpm_coef) || p->K <= 0))
     return set_err(ctx, DITREE_E_ARG, "expand_round: flow schedule missing");
@@ -886,8 +887,12 @@ int32_t ditree_expand_round(ditree_ctx* ctx, const ditree_tree* tree, const ditr
   NormArg nm;
   fill_norm(p->norm, &nm);
   launch_round_begin(round->status, round->chunks_run, round->chunk_steps, B, nC, s);
-  launch_nn_argmin(p->samples, 6, B, tree->xy, p->n_nodes, round->parent, tree->state, tree->last_action,
-                   tree->has_prev, ctx->cur_state, ctx->prev_action, ctx->has_prev, s);
+  if (f)
+    launch_nn_forest(p->samples, 6, B, tree->xy, f->off, f->n_trees, f->counters, f->tree_capacity, 0, round->parent, tree->state,
+                     tree->last_action, tree->has_prev, ctx->cur_state, ctx->prev_action, ctx->has_prev, s);
+  else
+    launch_nn_argmin(p->samples, 6, B, tree->xy, p->n_nodes, round->parent, tree->state, tree->last_action,
+                     tree->has_prev, ctx->cur_state, ctx->prev_action, ctx->has_prev, s);
   const int64_t st_stride = (int64_t)nC * (A + 1) * 6, ac_stride = (int64_t)nC * A * 2;
   // Early exit (p->early_exit): what the reference does by abandoning a collided edge (planners/RRT.py:179-184) -- a chunk runs
   // only for candidates that are still alive.  A denoiser call costs whole WAVES of tiles (every layer has rows / quantum
@@ -971,6 +976,117 @@ int32_t ditree_expand_round(ditree_ctx* ctx, const ditree_tree* tree, const ditr
   HIP_TRY(ctx, hipMemcpyAsync(round->end_state, ctx->cur_state, (size_t)B * 6 * sizeof(double),
                               hipMemcpyDeviceToDevice, s));
   HIP_TRY(ctx, hipGetLastError());
+  return DITREE_OK;
+}
+
+int32_t ditree_expand_round(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round,
+                            const ditree_round_params* p, void* stream) {
+  return expand_round_impl(ctx, tree, nullptr, round, p, stream);
+}
+
+// ---- forests (include/ditree.h "forests"): every check runs on the host before anything is launched.
+// B >= 0: the round's candidate count must equal off[T]; B < 0: the offsets are not read.
+static int check_forest(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* f, int B, const char* what) {
+  const std::string w(what);
+  int rc = check_tree(ctx, tree);
+  if (rc) return rc;
+  if (!f || f->n_trees < 1 || f->tree_capacity < 1 || !f->counters)
+    return set_err(ctx, DITREE_E_ARG, w + ": forest descriptor incomplete (n_trees >= 1, tree_capacity >= 1, counters)");
+  if ((int64_t)f->n_trees * f->tree_capacity > tree->capacity)
+    return set_err(ctx, DITREE_E_ARG, w + ": n_trees * tree_capacity = " + std::to_string((int64_t)f->n_trees * f->tree_capacity) +
+                   " exceeds the tree's capacity " + std::to_string(tree->capacity));
+  if (tree->state_dim != 6 || tree->action_dim != 2)
+    return set_err(ctx, DITREE_E_ARG, w + ": a forest is a car tree (state_dim 6, action_dim 2)");
+  if (B < 0) return DITREE_OK;
+  if (!f->off || !f->off_host) return set_err(ctx, DITREE_E_ARG, w + ": forest offsets (off, off_host) missing");
+  if (f->off_host[0] != 0) return set_err(ctx, DITREE_E_ARG, w + ": off[0] must be 0");
+  for (int t = 0; t < f->n_trees; ++t)
+    if (f->off_host[t + 1] < f->off_host[t])
+      return set_err(ctx, DITREE_E_ARG, w + ": candidate offsets are not monotone at tree " + std::to_string(t));
+  if (f->off_host[f->n_trees] != B)
+    return set_err(ctx, DITREE_E_ARG, w + ": off[T] = " + std::to_string(f->off_host[f->n_trees]) + " but the round has " +
+                   std::to_string(B) + " candidates");
+  return DITREE_OK;
+}
+
+int32_t ditree_forest_expand_round(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
+                                   const ditree_round* round, const ditree_round_params* p, void* stream) {
+  if (!ctx) return DITREE_E_ARG;
+  int rc = check_round(ctx, round);
+  if (rc) return rc;
+  rc = check_forest(ctx, tree, forest, round->B, "forest_expand_round");
+  if (rc) return rc;
+  return expand_round_impl(ctx, tree, forest, round, p, stream);
+}
+
+int32_t ditree_forest_accept(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const ditree_round* round,
+                             int32_t emulate_sticky, void* stream) {
+  if (!ctx) return DITREE_E_ARG;
+  int rc = check_round(ctx, round);
+  if (rc) return rc;
+  rc = check_forest(ctx, tree, forest, round->B, "forest_accept");
+  if (rc) return rc;
+  if (round->shard > 0 || tree->obstacle_ahead || tree->hist)
+    return set_err(ctx, DITREE_E_ARG, "forest_accept: a forest is one rank's run_type-0 car tree (no shards, obstacle flags or hist)");
+  if (round->B == 0) return DITREE_OK;
+  const AheadArg ts = ahead_samples();
+  launch_forest_accept(*tree, *round, forest->off, forest->counters, forest->n_trees, forest->tree_capacity, emulate_sticky,
+                       ctx->maze, ctx->rows, ctx->cols, ts, (hipStream_t)stream);
+  HIP_TRY(ctx, hipGetLastError());
+  return DITREE_OK;
+}
+
+int32_t ditree_forest_chunk_budget(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const double* samples,
+                                   int32_t B, const int32_t* schedule_chunks, int32_t n_schedule, int32_t* parent_scratch,
+                                   int32_t* budget_out, void* stream) {
+  if (!ctx) return DITREE_E_ARG;
+  int rc = check_forest(ctx, tree, forest, B, "forest_chunk_budget");
+  if (rc) return rc;
+  if (B == 0) return DITREE_OK;
+  if (!samples || !schedule_chunks || !parent_scratch || !budget_out || n_schedule < 1 || n_schedule > 16)
+    return set_err(ctx, DITREE_E_ARG, "forest_chunk_budget: bad argument (1..16 schedule entries)");
+  for (int i = 0; i < n_schedule; ++i)
+    if (schedule_chunks[i] < 1 || schedule_chunks[i] > tree->n_chunks)
+      return set_err(ctx, DITREE_E_ARG, "forest_chunk_budget: a schedule entry exceeds the tree's edge capacity (n_chunks)");
+  hipStream_t s = (hipStream_t)stream;
+  // parents are global node ids: "earlier candidates with the same parent" never crosses trees
+  launch_nn_forest(samples, 6, B, tree->xy, forest->off, forest->n_trees, forest->counters, forest->tree_capacity, 0, parent_scratch,
+                   nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, s);
+  launch_chunk_budget(parent_scratch, B, tree->num_visit, schedule_chunks, n_schedule, budget_out, s);
+  HIP_TRY(ctx, hipGetLastError());
+  return DITREE_OK;
+}
+
+int32_t ditree_forest_nn_argmin(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const double* queries,
+                                int32_t q_stride, int32_t B, int32_t* out_idx, void* stream) {
+  if (!ctx) return DITREE_E_ARG;
+  int rc = check_forest(ctx, tree, forest, B, "forest_nn_argmin");
+  if (rc) return rc;
+  if (B == 0) return DITREE_OK;
+  if (!queries || !out_idx || q_stride < 2) return set_err(ctx, DITREE_E_ARG, "forest_nn_argmin: bad argument");
+  launch_nn_forest(queries, q_stride, B, tree->xy, forest->off, forest->n_trees, forest->counters, forest->tree_capacity, 0, out_idx,
+                   nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream);
+  HIP_TRY(ctx, hipGetLastError());
+  return DITREE_OK;
+}
+
+int32_t ditree_forest_fallback(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const double* goal_xy,
+                               int32_t* out_node, void* stream) {
+  if (!ctx) return DITREE_E_ARG;
+  int rc = check_forest(ctx, tree, forest, -1, "forest_fallback");
+  if (rc) return rc;
+  if (!goal_xy || !out_node) return set_err(ctx, DITREE_E_ARG, "forest_fallback: bad argument");
+  hipStream_t s = (hipStream_t)stream;
+  const int T = forest->n_trees;
+  rc = ensure_scratch(ctx, T, 1, 1);                   // T copies of the goal as the queries (ctx->cur_state, (T, 6))
+  if (rc) return rc;
+  std::vector<double> q((size_t)T * 2);
+  for (int t = 0; t < T; ++t) { q[(size_t)t * 2] = goal_xy[0]; q[(size_t)t * 2 + 1] = goal_xy[1]; }
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->cur_state, q.data(), q.size() * sizeof(double), hipMemcpyHostToDevice, s));
+  launch_nn_forest(ctx->cur_state, 2, T, tree->xy, nullptr, T, forest->counters, forest->tree_capacity, 1, out_node, nullptr, nullptr,
+                   nullptr, nullptr, nullptr, nullptr, s);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipStreamSynchronize(s));               // `q` is a temporary
   return DITREE_OK;
 }
 

@@ -85,6 +85,10 @@ void launch_nn_argmin(const double* queries, int q_stride, int B, const double* 
                       int32_t* out_idx, const double* node_state, const double* node_last_action,
                       const uint8_t* node_has_prev, double* out_state, double* out_prev_action,
                       uint8_t* out_has_prev, hipStream_t s, int S = 6, int D = 2);
+void launch_nn_forest(const double* queries, int q_stride, int B, const double* node_xy, const int32_t* off, int T,
+                      const int32_t* counters, int C, int skip, int32_t* out_idx, const double* node_state,
+                      const double* node_last_action, const uint8_t* node_has_prev, double* out_state, double* out_prev_action,
+                      uint8_t* out_has_prev, hipStream_t s, int S = 6, int D = 2);
 void launch_local_map(const unsigned char* maze, int rows, int cols, const double* state,
                       const int32_t* active, const int32_t* idx, int B, int n, const AxisArg& axis,
                       double s_global, int scaled, float* out, hipStream_t s, int state_stride = 6);
@@ -140,6 +144,8 @@ int record_doubles(const ditree_tree& t);
 struct AheadArg { double t[30]; };
 void launch_accept(const ditree_tree& t, const ditree_round& r, int emulate_sticky, const unsigned char* maze, int rows,
                    int cols, const AheadArg& ts, hipStream_t s);
+void launch_forest_accept(const ditree_tree& t, const ditree_round& r, const int32_t* off, int32_t* counters, int T, int C,
+                          int emulate_sticky, const unsigned char* maze, int rows, int cols, const AheadArg& ts, hipStream_t s);
 void launch_obstacle_ahead(const unsigned char* maze, int rows, int cols, const double* state, int stride, int B,
                            const AheadArg& ts, uint8_t* out, hipStream_t s);
 void launch_fallback_select(const ditree_tree& t, int n_nodes, double gx, double gy, const double* path_dev, int P,

@@ -114,6 +114,79 @@ void launch_nn_argmin(const double* queries, int q_stride, int B, const double* 
                      out_prev_action, out_has_prev, S, D);
 }
 
+// Segmented nearest node of a forest (include/ditree.h ditree_forest): query q belongs to tree t -- the t whose candidate range
+// [off[t], off[t+1]) holds q, or t = q without offsets (one query per tree) -- and searches only that tree's node slots
+// [t*C + skip, t*C + n_t), n_t read from the tree's counter row.  Queries of one wave may belong to different trees (at one
+// candidate per run they always do), so every wave takes one query; the scan keeps nn_argmin_kernel's eight independent node
+// loads per trip, strict '<' per lane and the (distance, index) reduction, so the result is nn_argmin_kernel's on the segment
+// alone (an all-NaN scan clamps to the segment's first slot).  A segment with no node gives -1 and gathers nothing.
+__global__ void __launch_bounds__(256)
+nn_forest_kernel(const double* __restrict__ queries, int q_stride, int B, const double2* __restrict__ node_xy,
+                 const int32_t* __restrict__ off, int T, const int32_t* __restrict__ counters, int C, int skip,
+                 int32_t* __restrict__ out_idx, const double* __restrict__ node_state,
+                 const double* __restrict__ node_last_action, const uint8_t* __restrict__ node_has_prev,
+                 double* __restrict__ out_state, double* __restrict__ out_prev_action,
+                 uint8_t* __restrict__ out_has_prev, int S, int D) {
+  const int lane = threadIdx.x & 63;
+  const int q = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  if (q >= B) return;
+  int t = q;
+  if (off != nullptr) {                                // the last tree whose range starts at or before q (skips empty ranges)
+    int lo = 0, hi = T - 1;
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (off[mid] <= q) lo = mid; else hi = mid - 1;
+    }
+    t = lo;
+  }
+  const int base = t * C + skip;
+  int n = counters[t * 8] - skip;
+  n = n > C - skip ? C - skip : n;                     // never past the tree's own slots
+  const double qx = queries[(size_t)q * q_stride + 0], qy = queries[(size_t)q * q_stride + 1];
+  double best = __builtin_huge_val();
+  int bidx = 0x7fffffff;
+  for (int i = lane; i < n; i += 8 * WAVE) {
+    double2 p[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) p[u] = node_xy[base + min(i + u * WAVE, n - 1)];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int iu = i + u * WAVE;
+      if (iu < n) {
+        double dx = qx - p[u].x, dy = qy - p[u].y;
+        double d = dx * dx + dy * dy;
+        if (d < best) { best = d; bidx = iu; }
+      }
+    }
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    double od = __shfl_xor(best, m);
+    int oi = __shfl_xor(bidx, m);
+    if (od < best || (od == best && oi < bidx)) { best = od; bidx = oi; }
+  }
+  if (n <= 0) {
+    if (lane == 0) out_idx[q] = -1;
+    return;
+  }
+  if (bidx == 0x7fffffff) bidx = 0;
+  const int ix = base + bidx;
+  if (lane == 0) out_idx[q] = ix;
+  if (node_state != nullptr) {
+    if (lane < S) out_state[(size_t)q * S + lane] = node_state[(size_t)ix * S + lane];
+    if (lane >= 32 && lane < 32 + D) out_prev_action[(size_t)q * D + (lane - 32)] = node_last_action[(size_t)ix * D + (lane - 32)];
+    if (lane == 63) out_has_prev[q] = node_has_prev[ix];
+  }
+}
+void launch_nn_forest(const double* queries, int q_stride, int B, const double* node_xy, const int32_t* off, int T,
+                      const int32_t* counters, int C, int skip, int32_t* out_idx, const double* node_state,
+                      const double* node_last_action, const uint8_t* node_has_prev, double* out_state, double* out_prev_action,
+                      uint8_t* out_has_prev, hipStream_t s, int S, int D) {
+  hipLaunchKernelGGL(nn_forest_kernel, dim3((B + 3) / 4), dim3(256), 0, s, queries, q_stride, B, (const double2*)node_xy, off, T,
+                     counters, C, skip, out_idx, node_state, node_last_action, node_has_prev, out_state, out_prev_action,
+                     out_has_prev, S, D);
+}
+
 // ------------------------------------------------------------------------- local map
 // One workgroup per candidate; maze staged in LDS; one thread per output cell.
 __global__ void __launch_bounds__(256)
@@ -1070,23 +1143,27 @@ void launch_fallback_select(const ditree_tree& t, int n_nodes, double gx, double
 // Phase 1 (one workgroup): the reference's sequential accept order (RRT.py:179-217) as a
 // scan.  counters: [0] n_nodes [1] goal node [2] env.done latched [3] chunk iterations
 // [4] candidates [5] sticky triggered [6] capacity overflow [7] phantom candidate (scratch).
-__global__ void __launch_bounds__(1024)
-accept_scan_kernel(ditree_tree t, ditree_round r, int emulate_sticky) {
+// The scan of one tree over its B candidates (status / chunks_run / parent / node_id already offset to the tree's first
+// candidate): counters is the tree's row, its nodes are slots [node_base, node_base + cap); node ids, the goal node and the
+// phantom are written in the global numbering (node_base + local slot, cand_base + local candidate).
+__device__ __forceinline__ void accept_scan_tree(int32_t* __restrict__ counters, int32_t* __restrict__ num_visit,
+                                                 const int32_t* __restrict__ status, const int32_t* __restrict__ chunks_run,
+                                                 const int32_t* __restrict__ parent, int32_t* __restrict__ node_id, int B,
+                                                 int node_base, int cap, int cand_base, int emulate_sticky) {
   __shared__ int s_first_goal, s_first_gac, s_total, s_iters;
   __shared__ int s_wave_sum[16];
-  const int B = r.B;
   const int tid = threadIdx.x;
   if (tid == 0) { s_first_goal = 0x7fffffff; s_first_gac = 0x7fffffff; s_total = 0; s_iters = 0; }
   __syncthreads();
   for (int b = tid; b < B; b += blockDim.x) {
-    int st = r.status[b];
+    int st = status[b];
     if ((st & 0xff) == DITREE_ST_GOAL) atomicMin(&s_first_goal, b);
     if (emulate_sticky && (st & 0xff) == DITREE_ST_COLLIDED && (st & DITREE_ST_FLAG_GOAL_AT_COLLISION))
       atomicMin(&s_first_gac, b);
   }
   __syncthreads();
   const int g = s_first_goal, c = s_first_gac;
-  const bool latched_in = emulate_sticky && t.counters[2] != 0;
+  const bool latched_in = emulate_sticky && counters[2] != 0;
   int last = B - 1, phantom = -1, goal_cand = -1;
   bool latch_out = latched_in;
   if (latched_in) {
@@ -1097,17 +1174,17 @@ accept_scan_kernel(ditree_tree t, ditree_round r, int emulate_sticky) {
   } else if (g != 0x7fffffff) {
     last = g; goal_cand = g;
   }
-  const int n0 = t.counters[0];
+  const int n0 = counters[0];
   // ordered prefix sum of accepted flags over candidates 0..last, 1024 at a time
   int base = 0;
   for (int start = 0; start <= last; start += blockDim.x) {
     int b = start + tid;
     int acc = 0, it = 0;
     if (b <= last) {
-      int st = r.status[b] & 0xff;
+      int st = status[b] & 0xff;
       acc = (b == phantom) ? 1 : (st != DITREE_ST_COLLIDED);
-      it = (b == phantom) ? 1 : r.chunks_run[b];
-      atomicAdd(&t.num_visit[r.parent[b]], 1);
+      it = (b == phantom) ? 1 : chunks_run[b];
+      atomicAdd(&num_visit[parent[b]], 1);
     }
     // wave inclusive scan
     int v = acc;
@@ -1129,43 +1206,60 @@ accept_scan_kernel(ditree_tree t, ditree_round r, int emulate_sticky) {
     if (b <= last) {
       int rank = base + woff + v - acc;                 // exclusive rank
       int id = acc ? (n0 + rank) : -1;
-      if (id >= t.capacity) id = -1;
-      r.node_id[b] = id;
+      if (id >= cap) id = -1;
+      node_id[b] = id < 0 ? -1 : node_base + id;
     }
     base += chunk_total;
     __syncthreads();
   }
-  for (int b = last + 1 + tid; b < B; b += blockDim.x) r.node_id[b] = -1;
+  for (int b = last + 1 + tid; b < B; b += blockDim.x) node_id[b] = -1;
   __syncthreads();
   if (tid == 0) {
     int total = base;
     int n1 = n0 + total;
-    if (n1 > t.capacity) { n1 = t.capacity; t.counters[6] = 1; }
-    t.counters[0] = n1;
+    if (n1 > cap) { n1 = cap; counters[6] = 1; }
+    counters[0] = n1;
     if (goal_cand >= 0) {
-      int gid = r.node_id[goal_cand];
-      t.counters[1] = gid;
+      int gid = node_id[goal_cand];
+      counters[1] = gid;
     }
-    t.counters[2] = (emulate_sticky && latch_out && phantom < 0) ? 1 : ((phantom >= 0) ? 1 : t.counters[2]);
-    t.counters[3] += s_iters;
-    t.counters[4] += last + 1;
-    if (phantom >= 0) t.counters[5] = 1;
-    t.counters[7] = phantom;
+    counters[2] = (emulate_sticky && latch_out && phantom < 0) ? 1 : ((phantom >= 0) ? 1 : counters[2]);
+    counters[3] += s_iters;
+    counters[4] += last + 1;
+    if (phantom >= 0) counters[5] = 1;
+    counters[7] = phantom < 0 ? -1 : cand_base + phantom;
   }
+}
+__global__ void __launch_bounds__(1024)
+accept_scan_kernel(ditree_tree t, ditree_round r, int emulate_sticky) {
+  accept_scan_tree(t.counters, t.num_visit, r.status, r.chunks_run, r.parent, r.node_id, r.B, 0, t.capacity, 0, emulate_sticky);
+}
+// A forest: one work-group per tree over its candidate range [off[t], off[t+1]); trees run in parallel.  An empty range leaves
+// the tree untouched (as ditree_accept does for an empty round).
+__global__ void __launch_bounds__(1024)
+forest_accept_scan_kernel(ditree_tree t, ditree_round r, const int32_t* __restrict__ off, int32_t* __restrict__ counters, int C,
+                          int emulate_sticky) {
+  const int tr = blockIdx.x;
+  const int lo = off[tr], n = off[tr + 1] - lo;
+  if (n <= 0) return;
+  accept_scan_tree(counters + (size_t)tr * 8, t.num_visit, r.status + lo, r.chunks_run + lo, r.parent + lo, r.node_id + lo, n,
+                   tr * C, C, lo, emulate_sticky);
 }
 
 // Phase 2: one wave per candidate copies the accepted edge into its node slot, dropping
 // all-zero rows (RRT.py:196-199).  State / action width S / D at run time (car 6 / 2, ant 29 / 8; S, D <= 64: a lane per
 // component, the zero-row test is one ballot).
+// FOREST: the phantom candidate is the one in the counter row of the node's own tree (id / C of the forest's counters).
+template <bool FOREST>
 __global__ void __launch_bounds__(64)
 accept_commit_kernel(ditree_tree t, ditree_round r, const unsigned char* __restrict__ maze, int rows, int cols,
-                     AheadArg ts) {
+                     AheadArg ts, const int32_t* __restrict__ forest_counters, int C) {
   const int b = blockIdx.x;
   const int id = r.node_id[b];
   if (id < 0) return;
   const int lane = threadIdx.x;
   const int A = t.A, nC = t.n_chunks, S = t.state_dim, D = t.action_dim;
-  const int phantom = t.counters[7];
+  const int phantom = FOREST ? forest_counters[(size_t)(id / C) * 8 + 7] : t.counters[7];
   const int par = r.parent[b];
   const size_t es_cap = (size_t)nC * (A + 1), ea_cap = (size_t)nC * A;
   double* es = t.edge_states + (size_t)id * es_cap * S;
@@ -1324,5 +1418,10 @@ void launch_round_unpack(const ditree_tree& t, const ditree_round& r, const doub
 void launch_accept(const ditree_tree& t, const ditree_round& r, int emulate_sticky, const unsigned char* maze, int rows,
                    int cols, const AheadArg& ts, hipStream_t s) {
   hipLaunchKernelGGL(accept_scan_kernel, dim3(1), dim3(1024), 0, s, t, r, emulate_sticky);
-  hipLaunchKernelGGL(accept_commit_kernel, dim3(r.B), dim3(64), 0, s, t, r, maze, rows, cols, ts);
+  hipLaunchKernelGGL(accept_commit_kernel<false>, dim3(r.B), dim3(64), 0, s, t, r, maze, rows, cols, ts, nullptr, 0);
+}
+void launch_forest_accept(const ditree_tree& t, const ditree_round& r, const int32_t* off, int32_t* counters, int T, int C,
+                          int emulate_sticky, const unsigned char* maze, int rows, int cols, const AheadArg& ts, hipStream_t s) {
+  hipLaunchKernelGGL(forest_accept_scan_kernel, dim3(T), dim3(1024), 0, s, t, r, off, counters, C, emulate_sticky);
+  hipLaunchKernelGGL(accept_commit_kernel<true>, dim3(r.B), dim3(64), 0, s, t, r, maze, rows, cols, ts, counters, C);
 }

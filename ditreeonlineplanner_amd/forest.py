@@ -1,0 +1,246 @@
+"""Many independent runs in one round: a forest of T trees in one device tree (include/ditree.h "forests").
+
+The reference's benchmark is a loop of independent runs (run_scenarios.py:336-343: ``planner.reset(); planner.plan()`` on the
+same maze, start and goal, only the random stream differs).  A round of a few candidates costs as much as a round of a few
+hundred, so runs one after another leave the GPU idle.  Here T runs are T trees of C node slots in one
+``ditree_tree`` of capacity T * C -- tree t owns slots [t*C, (t+1)*C), its root at t*C, parents stay global -- and one round
+expands the candidates of every active run, grouped by tree.  Only what knows about "the tree" has a per-tree form: the
+nearest-node search (segmented by tree), accept / commit (one work-group per tree, a (T, 8) counter block), the chunk-budget
+visit count and the fallback choice.  Every per-candidate kernel is the single-tree round's, and its result does not depend on
+the batch, so each tree grows exactly as it would in its own ``ExpansionEngine`` fed the same rows.
+
+Scope: the car, run_type 0, one GPU, one maze / start / goal for every tree.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import torch
+
+from ._lib import Forest, RoundParams, check, lib
+from .engine import CNT_GOAL, CNT_NODES, CNT_PHANTOM, ExpansionEngine
+from .ops import CAR_NORM, Context, _dbl
+
+
+class ForestEngine(ExpansionEngine):
+    """T independent car trees of ``tree_capacity`` node slots, expanded together.  Node numbers in this class's results
+    (``goal_node``, ``fallback_node``, ``path_to``, ``tree_snapshot``) are LOCAL to their tree (root = 0), as a single-tree
+    engine reports them; the device arrays (``tree.parent``, ``counters``' goal node, the round's ``node_id``) hold global
+    slot numbers."""
+
+    def __init__(self, ctx: Context, maze, start_state, goal_state, n_trees, tree_capacity, edge_length=64, action_horizon=8,
+                 pred_horizon=64, local_map_size=20, local_map_scale=0.2, s_global=1.0, batch=1024, k_steps=1,
+                 emulate_sticky_done=True, norm=CAR_NORM, early_exit=False, goal_scale=None, prop_duration=None):
+        T, Cap = int(n_trees), int(tree_capacity)
+        if T < 1 or Cap < 1:
+            raise ValueError("a forest needs n_trees >= 1 and tree_capacity >= 1")
+        if T * Cap >= 2 ** 31:
+            raise ValueError(f"n_trees * tree_capacity = {T * Cap} does not fit the int32 node numbering")
+        self.T, self.C = T, Cap
+        dev = ctx.device
+        self.fcounters = torch.zeros(T, 8, dtype=torch.int32, device=dev)
+        self.off_host = (C.c_int32 * (T + 1))()
+        self.off_dev = torch.zeros(T + 1, dtype=torch.int32, device=dev)
+        self.n_nodes_host = np.ones(T, dtype=np.int64)
+        self.cnt_host = np.zeros((T, 8), dtype=np.int32)
+        self.fdesc = Forest(T, Cap, self.fcounters.data_ptr(), self.off_dev.data_ptr(), self.off_host)
+        super().__init__(ctx, maze, start_state, goal_state, edge_length=edge_length, action_horizon=action_horizon,
+                         pred_horizon=pred_horizon, local_map_size=local_map_size, local_map_scale=local_map_scale,
+                         s_global=s_global, batch=batch, capacity=T * Cap, k_steps=k_steps,
+                         emulate_sticky_done=emulate_sticky_done, norm=norm, early_exit=early_exit, run_type=0,
+                         goal_scale=goal_scale, prop_duration=prop_duration)
+
+    # ------------------------------------------------------------------ state
+    def reset(self, start_state, goal_state):
+        """Every tree back to its root (the shared start and goal)."""
+        self.start_state = np.asarray(start_state, dtype=np.float64).copy()
+        self.goal_state = np.asarray(goal_state, dtype=np.float64).copy()
+        if self.start_state.shape != (self.STATE_DIM,):
+            raise ValueError(f"start_state must have {self.STATE_DIM} elements")
+        self._derive_env_goal()
+        self.tree.reset(self.start_state)            # slot 0, num_visit, the (unused) single-tree counters
+        for t in range(self.T):
+            self.reset_tree(t)
+        self.generation = getattr(self, "generation", 0) + 1
+
+    def reset_tree(self, t):
+        """Tree t back to its root, so a finished run's slot can take the next run (DeviceTree.reset for one tree)."""
+        t = self._tree_index(t)
+        tr, r = self.tree, t * self.C
+        s = torch.as_tensor(self.start_state, device=tr.state.device)
+        tr.state[r] = s
+        tr.xy[r] = s[:2]
+        tr.parent[r] = -1
+        tr.last_action[r] = 0
+        tr.has_prev[r] = 0
+        tr.num_visit[r:r + self.C].zero_()
+        tr.edge_nstates[r] = 0
+        tr.edge_nactions[r] = 0
+        tr.edge_owner[r] = -1
+        self.fcounters[t] = self._root_row
+        self.cnt_host[t] = self._ROOT
+        self.n_nodes_host[t] = 1
+
+    _ROOT = np.array([1, -1, 0, 0, 0, 0, 0, -1], dtype=np.int32)
+
+    @property
+    def _root_row(self):
+        row = getattr(self, "_root_row_dev", None)
+        if row is None:
+            row = self._root_row_dev = torch.as_tensor(self._ROOT, device=self.fcounters.device)
+        return row
+
+    def _tree_index(self, t):
+        t = int(t)
+        if not 0 <= t < self.T:
+            raise IndexError(f"tree {t} of a forest of {self.T}")
+        return t
+
+    # ------------------------------------------------------------------ one round
+    def _set_offsets(self, counts_per_tree):
+        counts = np.asarray(counts_per_tree, dtype=np.int64).reshape(-1)
+        if counts.shape != (self.T,):
+            raise ValueError(f"counts_per_tree must have one entry per tree ({self.T})")
+        if (counts < 0).any():
+            raise ValueError("counts_per_tree must be >= 0")
+        off = np.zeros(self.T + 1, dtype=np.int64)
+        np.cumsum(counts, out=off[1:])
+        for i, v in enumerate(off):
+            self.off_host[i] = int(v)
+        self.off_dev.copy_(torch.from_numpy(off.astype(np.int32)))
+        return off
+
+    def expand_round(self, samples, cond_goal, noise=None, inject_actions=None, counts_per_tree=None, step_noise=None,
+                     accept=True):
+        """samples (B, 6) f64, cond_goal (B, 2) f64, noise (B, n_chunks, P, 2) f32 or inject_actions (B, n_chunks, P, 2) f64,
+        step_noise (B, n_chunks, K, P, 2) f32 with ``self.ddpm`` [device tensors]: the rows of tree t are
+        [off[t], off[t+1]), off = the running sum of ``counts_per_tree`` (T,), each tree's rows in its run's own order.
+        Returns the (T, 8) counter block after the accept."""
+        if counts_per_tree is None:
+            raise ValueError("counts_per_tree is required (T entries, the candidates of each tree this round)")
+        off = self._set_offsets(counts_per_tree)
+        B = int(off[-1])
+        if samples.shape[0] != B or cond_goal.shape[0] != B:
+            raise ValueError(f"samples / cond_goal must have sum(counts_per_tree) = {B} rows")
+        if B > self.batch:
+            raise ValueError(f"round of {B} candidates exceeds engine batch {self.batch}")
+        if B == 0:                                    # no tree has a candidate: nothing to expand or accept
+            return self.cnt_host.copy() if accept else None
+        self.ensure_maze()
+        h, L, st = self.ctx._h, lib(), self.ctx.stream
+        rp = RoundParams()
+        rp.n_nodes = 1                                # not read: each tree's size comes from its counter row
+        rp.samples, rp.cond_goal = samples.data_ptr(), cond_goal.data_ptr()
+        rp.noise = noise.data_ptr() if noise is not None else None
+        rp.inject_actions = inject_actions.data_ptr() if inject_actions is not None else None
+        rp.P = self.P
+        keep = [samples, cond_goal, noise, inject_actions, step_noise]
+        if self.ddpm is None or noise is None:
+            self._flow_only(rp, keep)
+        else:
+            self._sampler_schedule(rp, keep, step_noise, 0, B)
+        for name, arr in (("norm", self.norm), ("goal_xy", self.env_goal), ("axis", self.axis)):
+            a, p = _dbl(arr)
+            keep.append(a)
+            setattr(rp, name, p)
+        rp.lm_n, rp.lm_size, rp.s_global = self.lm_n, self.goal_scale, float(self.s_global)
+        rp.early_exit = self.early_exit
+        rp.chunk_budget = None
+        if self._budget is not None:
+            check(h, L.ditree_forest_chunk_budget(h, C.byref(self.tree.desc), C.byref(self.fdesc), samples.data_ptr(), B,
+                                                  self._sched_chunks, len(self.schedule), self._budget_parent.data_ptr(),
+                                                  self._budget.data_ptr(), st), "forest_chunk_budget")
+            rp.chunk_budget = self._budget.data_ptr()
+        rd = self.rb.desc(0, B)
+        check(h, L.ditree_forest_expand_round(h, C.byref(self.tree.desc), C.byref(self.fdesc), C.byref(rd), C.byref(rp), st),
+              "forest_expand_round")
+        del keep
+        self._used_denoiser = noise is not None
+        self._B = B
+        return self.accept(B) if accept else None
+
+    def accept(self, B=None):
+        B = self._B if B is None else int(B)
+        self.ensure_maze()
+        rd = self.rb.desc(0, B)
+        check(self.ctx._h, lib().ditree_forest_accept(self.ctx._h, C.byref(self.tree.desc), C.byref(self.fdesc), C.byref(rd),
+                                                       self.sticky, self.ctx.stream), "forest_accept")
+        cnt = self.read_counters().copy()             # one small D2H per round: every tree's row
+        if getattr(self, "_used_denoiser", False):
+            layers = self.ctx.denoise_status(clear=True)          # f16 range guard (ExpansionEngine.accept)
+            if layers:
+                self.ctx.raise_range_error(layers)
+        return cnt
+
+    def read_counters(self):
+        self.cnt_host = self.fcounters.cpu().numpy()
+        self.n_nodes_host = self.cnt_host[:, CNT_NODES].astype(np.int64)
+        return self.cnt_host
+
+    # ------------------------------------------------------------------ results (local node numbers)
+    def counters(self, t):
+        """Tree t's counter row as of the last accept (goal node and phantom in the global numbering, as on the device)."""
+        return self.cnt_host[self._tree_index(t)].copy()
+
+    def goal_node(self, t):
+        t = self._tree_index(t)
+        g = int(self.cnt_host[t, CNT_GOAL])
+        return None if g < 0 else g - t * self.C
+
+    def phantom(self, t):
+        """The round row of tree t's sticky-done phantom in the last round, or None."""
+        p = int(self.cnt_host[self._tree_index(t), CNT_PHANTOM])
+        return None if p < 0 else p
+
+    def fallback_nodes(self):
+        """planners/RRT.py:227-254 (run_type 0) for every tree in one launch: local node nearest to the goal among nodes 1..,
+        None for a tree that holds only its root."""
+        out = torch.empty(self.T, dtype=torch.int32, device=self.tree.xy.device)
+        ga, gp = _dbl(self.goal_state[:2])
+        check(self.ctx._h, lib().ditree_forest_fallback(self.ctx._h, C.byref(self.tree.desc), C.byref(self.fdesc), gp,
+                                                         out.data_ptr(), self.ctx.stream), "forest_fallback")
+        del ga
+        ids = out.cpu().numpy()
+        return [None if v < 0 else int(v) - t * self.C for t, v in enumerate(ids)]
+
+    def fallback_node(self, t):
+        return self.fallback_nodes()[self._tree_index(t)]
+
+    def path_to(self, t, node):
+        """planners/base_planner.py:342-363 for tree t's local ``node``: float32 path and actions."""
+        t = self._tree_index(t)
+        tr, base, n = self.tree, t * self.C, int(self.n_nodes_host[t])
+        parents = tr.parent[base: base + n].cpu().numpy()
+        chain = []
+        k = int(node)
+        while k != -1:
+            chain.append(k)
+            p = int(parents[k])
+            k = -1 if p < 0 else p - base
+        chain = chain[::-1]
+        idx = torch.as_tensor(chain, device=tr.state.device, dtype=torch.long) + base
+        st = tr.state[idx].cpu().numpy()
+        es, ea = tr.edge_states[idx].cpu().numpy(), tr.edge_actions[idx].cpu().numpy()
+        ns, na = tr.edge_nstates[idx].cpu().numpy(), tr.edge_nactions[idx].cpu().numpy()
+        path, actions = [], []
+        for j, nd in enumerate(chain):
+            if nd != 0:
+                path.extend(es[j, : ns[j]])
+                actions.extend(ea[j, : na[j]])
+            path.append(st[j])
+        path = np.array(path, dtype=np.float32) if path else None
+        actions = np.array(actions, dtype=np.float32) if actions else None
+        return path, actions
+
+    def tree_snapshot(self, t):
+        """Tree t as a single-tree engine reports it: local parents (root -1), states, its counter row."""
+        t = self._tree_index(t)
+        base, n = t * self.C, int(self.n_nodes_host[t])
+        par = self.tree.parent[base: base + n].cpu().numpy()
+        return dict(parents=np.where(par < 0, par, par - base), states=self.tree.state[base: base + n].cpu().numpy(),
+                    counters=self.counters(t))
+
+    def shard(self, B):                               # one rank
+        return 0, B, B
+

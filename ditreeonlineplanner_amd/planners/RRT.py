@@ -368,3 +368,138 @@ class RRT_Planner(BasePlanner):
         if node is None:
             return self.handle_goal_not_reached(iters, start_time)
         return self.handle_goal_reached(node, iters, start_time)
+
+    # ------------------------------------------------------------------ many seeded runs at once
+    def _forest_engine(self, T, tree_capacity, batch):
+        """The ForestEngine of ``plan_runs`` (kept between calls of the same shape): the single-tree engine's settings."""
+        from ..forest import ForestEngine
+        e = self._engine
+        key = (T, tree_capacity, batch)
+        f = getattr(self, "_forest", None)
+        if f is None or self._forest_key != key:
+            self._forest = f = None                      # free the previous forest's slots first
+            f = ForestEngine(self.ctx, self.maze, self.start_node.state, self.goal_state, T, tree_capacity, action_horizon=e.A,
+                             pred_horizon=e.P, local_map_size=e.lm_n, local_map_scale=e.lm_scale, s_global=e.s_global,
+                             batch=batch, k_steps=e.k_steps, emulate_sticky_done=bool(e.sticky), norm=e.norm,
+                             early_exit=bool(e.early_exit), goal_scale=e.goal_scale, prop_duration=e.schedule)
+            self._forest, self._forest_key = f, key
+        f.ddpm = e.ddpm
+        f.update_maze(self.maze)
+        return f
+
+    def plan_runs(self, seeds, concurrent=None, tree_capacity=None):
+        """N independent seeded runs of this scenario, expanded together as a forest of trees on one GPU (forest.py).
+
+        Run i returns what ``random.seed(s); np.random.seed(s); torch.manual_seed(s); planner.reset(); planner.plan()`` leaves
+        in ``results``, s = seeds[i] -- the same tree, path and actions -- as one dict per seed with ``seed``, ``success`` (a
+        path came back: run_scenarios.py:350-353), ``goal_reached``, ``iterations``, ``time``, ``path``, ``actions``,
+        ``number_of_nodes``, ``path_time`` (None without a path) and ``cc_calls``.  At most ``concurrent`` runs are in flight
+        (default: all); a finished run's tree takes the next seed.  Each round gives every active run min(batch, what is left
+        of its max_candidates) candidates; ``time_budget`` counts from a run's own start, so ``time`` is wall time inside a
+        shared forest.  ``tree_capacity``: node slots per run (default: max_candidates + 1, at most ``capacity``).  The
+        caller's ``random`` / ``np.random`` / torch generator states are left as they were; the summed collision-check count
+        is added to ``common.map_utils.cc_calls`` once.  Scope: the car, run_type 0, one rank, a network sampler or one with
+        ``sample_round`` (a plain callable draws from its own generator and cannot be split per run)."""
+        from ._runs import RunStreams, caller_states_kept, draw_runs
+        if self.is_ant:
+            raise NotImplementedError("plan_runs: the car (carmaze) only")
+        if self.run_type != 0:
+            raise NotImplementedError("plan_runs: run_type 0 only (the online re-planning driver plans one run at a time)")
+        if self.world_size > 1:
+            raise NotImplementedError("plan_runs: one rank (a forest is not sharded)")
+        network = hasattr(self.sampler, "ensure_bound")
+        if not network and not hasattr(self.sampler, "sample_round"):
+            raise NotImplementedError("plan_runs: a plain-callable sampler draws from its own generator and cannot be split per run; "
+                                      "give it a sample_round(first_candidate, B, n_chunks, pred_horizon) method")
+        seeds = [int(s) for s in seeds]
+        if not seeds:
+            return []
+        T = len(seeds) if concurrent is None else max(1, min(int(concurrent), len(seeds)))
+        if tree_capacity is None:
+            tree_capacity = self.capacity if self.max_candidates is None else min(self.capacity, int(self.max_candidates) + 1)
+        dev = self.ctx.device
+        eng = self._forest_engine(T, int(tree_capacity), T * self.batch)
+        self.reset()                                        # env.reset(options) as before every sequential plan()
+        eng.reset(self.start_node.state, self.goal_state)
+        eng.env_goal = np.asarray(self.env.goal, dtype=np.float64)
+        if network:
+            self.sampler.ensure_bound(T * self.batch)
+        shape = (eng.n_chunks, eng.P, eng.ACTION_DIM)
+        K = len(eng.ddpm[0]) if (network and eng.ddpm is not None) else 0
+        results = [None] * len(seeds)
+        queue = list(range(len(seeds)))[::-1]
+        slots = [None] * T                                  # per tree: [run index, RunStreams, drawn, start time]
+        steps_dev = torch.zeros(T, dtype=torch.int64, device=dev)
+        total_cc = 0
+
+        def start(t):
+            slots[t] = None
+            if queue:
+                i = queue.pop()
+                eng.reset_tree(t)
+                steps_dev[t] = 0
+                slots[t] = [i, RunStreams(seeds[i], dev), 0, time.time()]
+
+        def finish(t, goal):
+            nonlocal total_cc
+            i, _, _, t0 = slots[t]
+            row = eng.counters(t)
+            node = goal if goal is not None else eng.fallback_node(t)          # RRT.py:227-254
+            elapsed = time.time() - t0
+            path = actions = None
+            if node is not None:
+                path, actions = eng.path_to(t, node)
+            cc = int(steps_dev[t].item())
+            total_cc += cc
+            results[i] = {"seed": seeds[i], "success": path is not None, "goal_reached": goal is not None,
+                          "iterations": int(row[CNT_ITERS]), "time": elapsed, "path": path, "actions": actions,
+                          "number_of_nodes": int(eng.n_nodes_host[t]),
+                          "path_time": None if path is None else len(path) * self.env_dt, "cc_calls": cc}
+            start(t)
+
+        with caller_states_kept():
+            for t in range(T):
+                start(t)
+            while True:
+                # the loop head of plan(): a run goes on while its own wall-clock budget and candidate budget last
+                sizes = [0] * T
+                for t in range(T):
+                    while slots[t] is not None:
+                        _, _, drawn, t0 = slots[t]
+                        if (time.time() - t0) < self.time_budget and (self.max_candidates is None or drawn < self.max_candidates):
+                            sizes[t] = self.batch if self.max_candidates is None else min(self.batch, self.max_candidates - drawn)
+                            break
+                        finish(t, None)
+                if not any(sizes):
+                    break
+                active = [t for t in range(T) if sizes[t] > 0]
+                drawn_sc = draw_runs(self.draw_round, [slots[t][1] for t in active], [sizes[t] for t in active])
+                s = torch.as_tensor(np.concatenate([d[0] for d in drawn_sc]), device=dev)
+                c = torch.as_tensor(np.concatenate([d[1] for d in drawn_sc]), device=dev)
+                B = int(sum(sizes))
+                noise = acts = step_noise = None
+                if network:
+                    # each run's own generator, plan()'s shapes and order: start noise, then the DDPM step noise
+                    noise = torch.empty((B, *shape), dtype=torch.float32, device=dev)
+                    if K:
+                        step_noise = torch.empty((B, eng.n_chunks, K, eng.P, eng.ACTION_DIM), dtype=torch.float32, device=dev)
+                    lo = 0
+                    for t in active:
+                        g = slots[t][1].gen
+                        noise[lo:lo + sizes[t]].normal_(generator=g)
+                        if K:
+                            step_noise[lo:lo + sizes[t]].normal_(generator=g)
+                        lo += sizes[t]
+                else:
+                    acts = torch.cat([self._host_actions(slots[t][2], sizes[t]) for t in active])
+                cnt = eng.expand_round(s, c, noise=noise, inject_actions=acts, counts_per_tree=sizes, step_noise=step_noise)
+                tree_of = torch.as_tensor(np.repeat(np.arange(T), sizes), device=dev)
+                steps_dev.index_add_(0, tree_of, eng.rb.chunk_steps[:B].sum(dim=1, dtype=torch.int64))
+                for t in active:
+                    slots[t][2] += sizes[t]
+                    if int(cnt[t, CNT_GOAL]) >= 0:
+                        finish(t, eng.goal_node(t))
+        from ..common import map_utils as _mu
+        _mu.add_cc_calls(total_cc)                  # the counter the drivers read (run_scenarios.py:338,343), once
+        return results
+

@@ -537,6 +537,44 @@ int32_t ditree_expand_round(ditree_ctx* ctx, const ditree_tree* tree, const ditr
  * n * ceil(B / quantum) waves. */
 int32_t ditree_round_stats(ditree_ctx* ctx, int32_t* stats4);
 
+/* ------------------------------------------------------------------ forests: many independent runs in one round
+ * A forest of T trees with C node slots each is one ordinary ditree_tree with capacity >= T * C (car: state_dim 6,
+ * action_dim 2).  Tree t owns node slots [t * C, (t + 1) * C) and its root sits at t * C; parent indices stay global, so edge
+ * storage, num_visit and every per-candidate kernel work unchanged.  Each tree has its own row of a (T, 8) counter block in the
+ * layout of ditree_tree.counters, with the goal node in the global numbering and [7] the phantom candidate as a row of the round.
+ * The candidates of one round are grouped by tree: tree t's are rows [off[t], off[t + 1]) (empty: no candidate this round),
+ * in that run's own order.  All trees share the maze, the start and the goal (the goal test lives in the rollout).
+ * The tree argument's own `counters` is not read by the forest calls. */
+typedef struct {
+  int32_t n_trees;               /* T >= 1 */
+  int32_t tree_capacity;         /* C >= 1 node slots per tree; T * C <= tree->capacity */
+  int32_t* counters;             /* [dev] (T, 8) */
+  const int32_t* off;            /* [dev] (T + 1) candidate offsets */
+  const int32_t* off_host;       /* [host] (T + 1) the same offsets: validated before anything is launched */
+} ditree_forest;
+
+/* ditree_expand_round on a forest: each candidate's nearest node is searched in its own tree only (nodes
+ * [t * C, t * C + n_t), n_t from the tree's counter row on the device -- no host round trip; p->n_nodes is not read).  Every
+ * other step treats rows independently and is the single-tree round's.  round->B must equal off[T]. */
+int32_t ditree_forest_expand_round(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
+                                   const ditree_round* round, const ditree_round_params* p, void* stream);
+/* ditree_accept per tree: one work-group per tree applies the single-tree rules (first goal, sticky-done phantom, accepted prefix,
+ * iteration / candidate counts, overflow at the tree's own C) to its counter row and writes global node ids from t * C + n_t. */
+int32_t ditree_forest_accept(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const ditree_round* round,
+                             int32_t emulate_sticky, void* stream);
+/* ditree_chunk_budget on a forest: samples [dev] (off[T], 6), nearest nodes searched per tree; B = off[T]. */
+int32_t ditree_forest_chunk_budget(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const double* samples,
+                                   int32_t B, const int32_t* schedule_chunks, int32_t n_schedule, int32_t* parent_scratch,
+                                   int32_t* budget_out, void* stream);
+/* Segmented nearest node: queries [dev] (B, q_stride >= 2) grouped by forest->off (B = off[T]) -> out_idx [dev] (B,) global node
+ * ids; minimum squared distance, ties to the lowest index, an all-NaN scan -> the tree's root. */
+int32_t ditree_forest_nn_argmin(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const double* queries,
+                                int32_t q_stride, int32_t B, int32_t* out_idx, void* stream);
+/* The run_type-0 fallback of every tree (planners/RRT.py:227-254): among nodes t * C + 1 .. t * C + n_t - 1 the one nearest to
+ * goal_xy [host 2] -> out_node [dev] (T,) global ids, -1 for a tree that holds only its root.  forest->off is not read. */
+int32_t ditree_forest_fallback(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const double* goal_xy,
+                               int32_t* out_node, void* stream);
+
 /* One expansion round of the ANT (BASELINE config 3; cfgs/antmaze.yaml + run_scenarios.py:123-132: action_horizon 2, edge
  * length 48 = 24 chunks, pred_horizon 16, obs_history 3, local map 16 x 16 @ 0.8, s_global 4) against a tree with state_dim
  * 29, action_dim 8 and `hist`: planners/RRT.py:131-194 batched --
