@@ -51,6 +51,15 @@ class Forest(C.Structure):
                 ("off_host", C.POINTER(C.c_int32))]
 
 
+class ForestScenes(C.Structure):
+    """include/ditree.h ditree_forest_scenes: the scene id of every tree of a scene forest."""
+    _fields_ = [("tree_scene", C.c_void_p), ("tree_scene_host", C.POINTER(C.c_int32))]
+
+
+MAX_SCENES = 64              # include/ditree.h DITREE_MAX_SCENES
+MAX_ATLAS_CELLS = 16384      # include/ditree.h DITREE_MAX_ATLAS_CELLS
+
+
 RECORD_DOUBLES = 12          # include/ditree.h DITREE_RECORD_DOUBLES (the car's record; ditree_record_doubles for any tree)
 
 
@@ -169,6 +178,10 @@ SIGNATURES = {
                                           _vp]),
     "ditree_forest_nn_argmin": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), _vp, _i32, _i32, _vp, _vp]),
     "ditree_forest_fallback": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), _pd, _vp, _vp]),
+    "ditree_upload_scenes": (_i32, [_vp, _i32, C.POINTER(C.c_float), C.POINTER(_i32), C.POINTER(_i32), _pd, _vp]),
+    "ditree_forest_expand_round_scenes": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), C.POINTER(ForestScenes), C.POINTER(Round),
+                                                 C.POINTER(RoundParams), _vp]),
+    "ditree_forest_fallback_goals": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), _pd, _vp, _vp]),
 }
 
 _LIB = None

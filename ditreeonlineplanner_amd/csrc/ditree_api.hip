@@ -15,7 +15,7 @@ void launch_car_rollout_ex(const unsigned char* maze, int rows, int cols, double
                            double* states_out, ditree_strides states_stride, double* actions_out, ditree_strides actout_stride,
                            int32_t* steps_out, int64_t steps_stride, int32_t* chunks_run, double* prev_action_io,
                            uint8_t* has_prev_io, const int32_t* idx, int act_dense, hipStream_t s, const int32_t* budget,
-                           int chunk_j, ChunkStrides cs = ChunkStrides{0, 0, 0});
+                           int chunk_j, ChunkStrides cs = ChunkStrides{0, 0, 0}, const SceneArg* scenes = nullptr);
 int denoise_run(ditree_ctx* ctx, const float* noise, int64_t noise_stride, const int32_t* noise_idx, const float* local_map,
                 const float* cond, int B, int K, const float* t0, const float* dt, const double* act_norm, double* actions,
                 float* x_out, hipStream_t s);
@@ -83,6 +83,8 @@ void ditree_ctx_destroy(ditree_ctx* ctx) {
   if (ctx->mppi_partial) hipFree(ctx->mppi_partial);
   if (ctx->mppi_ant_partial) hipFree(ctx->mppi_ant_partial);
   if (ctx->mppi_minkey) hipFree(ctx->mppi_minkey);
+  if (ctx->scene_tab) hipFree(ctx->scene_tab);
+  if (ctx->row_scene) hipFree(ctx->row_scene);
   void* ant[] = {ctx->ant_hist, ctx->ant_hist_n, ctx->ant_idx, ctx->ant_nrow, ctx->ant_prev, ctx->ant_hasprev, ctx->ant_cond, ctx->ant_lmap, ctx->ant_act};
   for (void* q : ant) if (q) hipFree(q);
   delete ctx;
@@ -849,16 +851,31 @@ int32_t ditree_round_stats(ditree_ctx* ctx, int32_t* stats4) {
   return DITREE_OK;
 }
 
-// The car round of one tree, or (f != NULL, validated by the caller) of a forest: only the nearest-node step differs.
+// The (B,) row -> scene scratch of scene-forest rounds; its address lives in the device scene table's header.
+static int ensure_row_scene(ditree_ctx* ctx, int B, hipStream_t s) {
+  if (B <= ctx->row_scene_cap) return DITREE_OK;
+  HIP_TRY(ctx, hipStreamSynchronize(s));                // the previous scratch may still be read
+  if (ctx->row_scene) HIP_TRY(ctx, hipFree(ctx->row_scene));
+  ctx->row_scene = nullptr;
+  ctx->row_scene_cap = 0;
+  HIP_TRY(ctx, hipMalloc((void**)&ctx->row_scene, (size_t)B * sizeof(int32_t)));
+  ctx->row_scene_cap = B;
+  HIP_TRY(ctx, hipMemcpyAsync(&ctx->scene_tab->row_scene, &ctx->row_scene, sizeof(ctx->row_scene), hipMemcpyHostToDevice, s));
+  HIP_TRY(ctx, hipStreamSynchronize(s));                // the source is a ctx field that the next growth overwrites
+  return DITREE_OK;
+}
+
+// The car round of one tree, or (f != NULL, validated by the caller) of a forest: only the nearest-node step differs.  A scene
+// forest (tree_scene != NULL, validated by the caller) reads each row's maze and goal from the scene table instead.
 static int expand_round_impl(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* f, const ditree_round* round,
-                             const ditree_round_params* p, void* stream) {
+                             const ditree_round_params* p, void* stream, const int32_t* tree_scene = nullptr) {
   if (!ctx) return DITREE_E_ARG;
   int rc = check_tree(ctx, tree);
   if (rc) return rc;
   rc = check_round(ctx, round);
   if (rc) return rc;
-  if (!ctx->maze) return set_err(ctx, DITREE_E_STATE, "expand_round: no maze uploaded");
-  if (!p || !p->samples || !p->cond_goal || !p->norm || !p->goal_xy || !p->axis ||
+  if (!tree_scene && !ctx->maze) return set_err(ctx, DITREE_E_STATE, "expand_round: no maze uploaded");
+  if (!p || !p->samples || !p->cond_goal || !p->norm || (!tree_scene && !p->goal_xy) || !p->axis ||
       (!f && (p->n_nodes <= 0 || p->n_nodes > tree->capacity)) || p->P < tree->A || (!p->noise && !p->inject_actions))
     return set_err(ctx, DITREE_E_ARG, "expand_round: bad parameters");
   if (!p->inject_actions && (!p->t0 || (!p->dt && !p->ddpm_coef) || p->K <= 0))
@@ -886,6 +903,16 @@ static int expand_round_impl(ditree_ctx* ctx, const ditree_tree* tree, const dit
   if (rc) return rc;
   NormArg nm;
   fill_norm(p->norm, &nm);
+  SceneArg sc{};
+  const SceneArg* scp = nullptr;
+  if (tree_scene) {
+    rc = ensure_row_scene(ctx, B, s);
+    if (rc) return rc;
+    sc = SceneArg{ctx->scene_tab, ctx->atlas_cells, ctx->max_scene_cells};
+    scp = &sc;
+    launch_row_scene(f->off, f->n_trees, tree_scene, B, ctx->row_scene, s);
+  }
+  const double gx = tree_scene ? 0.0 : p->goal_xy[0], gy = tree_scene ? 0.0 : p->goal_xy[1];   // scenes: each row's own goal
   launch_round_begin(round->status, round->chunks_run, round->chunk_steps, B, nC, s);
   if (f)
     launch_nn_forest(p->samples, 6, B, tree->xy, f->off, f->n_trees, f->counters, f->tree_capacity, 0, round->parent, tree->state,
@@ -925,8 +952,11 @@ static int expand_round_impl(ditree_ctx* ctx, const ditree_tree* tree, const dit
         act_stride = (int64_t)nC * P * 2;
         act_dense = 0;
       } else {
-        launch_local_map(ctx->maze, ctx->rows, ctx->cols, ctx->cur_state, round->status, idx, take, p->lm_n, ax, p->s_global, 1,
-                         ctx->lmap, s);
+        if (scp)
+          launch_local_map_scenes(sc, ctx->cur_state, round->status, idx, take, p->lm_n, ax, p->s_global, ctx->lmap, s);
+        else
+          launch_local_map(ctx->maze, ctx->rows, ctx->cols, ctx->cur_state, round->status, idx, take, p->lm_n, ax, p->s_global, 1,
+                           ctx->lmap, s);
         launch_cond_vector(ctx->cur_state, ctx->prev_action, ctx->has_prev, p->cond_goal, idx, take, nm, p->lm_size, ctx->cond, s);
         double an[4] = {p->norm[12], p->norm[13], p->norm[14], p->norm[15]};
         // rows of the (B * n_chunks, ...) views: start noise (P, 2) and, for the DDPM branch, step noise (K, P, 2)
@@ -937,9 +967,9 @@ static int expand_round_impl(ditree_ctx* ctx, const ditree_tree* tree, const dit
         act_stride = (int64_t)P * 2;
       }
       launch_car_rollout_ex(ctx->maze, ctx->rows, ctx->cols, ctx->cur_state, acts, act_stride, round->status, take, A,
-                            p->goal_xy[0], p->goal_xy[1], round->states, ditree_strides{st_stride, 6, 1}, round->actions,
+                            gx, gy, round->states, ditree_strides{st_stride, 6, 1}, round->actions,
                             ditree_strides{ac_stride, 2, 1}, round->chunk_steps, nC, round->chunks_run, ctx->prev_action,
-                            ctx->has_prev, idx, act_dense, s, p->chunk_budget, -1, cs);
+                            ctx->has_prev, idx, act_dense, s, p->chunk_budget, -1, cs, scp);
     }
     ctx->ee_calls = calls;
     ctx->ee_waves = waves;
@@ -956,8 +986,11 @@ static int expand_round_impl(ditree_ctx* ctx, const ditree_tree* tree, const dit
       act_stride = (int64_t)nC * P * 2;
       act_dense = 0;                          // the tape is indexed by candidate
     } else {
-      launch_local_map(ctx->maze, ctx->rows, ctx->cols, ctx->cur_state, round->status, nullptr, B, p->lm_n, ax,
-                       p->s_global, 1, ctx->lmap, s);
+      if (scp)
+        launch_local_map_scenes(sc, ctx->cur_state, round->status, nullptr, B, p->lm_n, ax, p->s_global, ctx->lmap, s);
+      else
+        launch_local_map(ctx->maze, ctx->rows, ctx->cols, ctx->cur_state, round->status, nullptr, B, p->lm_n, ax,
+                         p->s_global, 1, ctx->lmap, s);
       launch_cond_vector(ctx->cur_state, ctx->prev_action, ctx->has_prev, p->cond_goal, nullptr, B, nm, p->lm_size,
                          ctx->cond, s);
       double an[4] = {p->norm[12], p->norm[13], p->norm[14], p->norm[15]};
@@ -969,9 +1002,10 @@ static int expand_round_impl(ditree_ctx* ctx, const ditree_tree* tree, const dit
       act_stride = (int64_t)P * 2;
     }
     launch_car_rollout_ex(ctx->maze, ctx->rows, ctx->cols, ctx->cur_state, acts, act_stride, round->status, B, A,
-                          p->goal_xy[0], p->goal_xy[1], round->states + (size_t)j * (A + 1) * 6, ditree_strides{st_stride, 6, 1},
+                          gx, gy, round->states + (size_t)j * (A + 1) * 6, ditree_strides{st_stride, 6, 1},
                           round->actions + (size_t)j * A * 2, ditree_strides{ac_stride, 2, 1}, round->chunk_steps + j, nC,
-                          round->chunks_run, ctx->prev_action, ctx->has_prev, nullptr, act_dense, s, p->chunk_budget, j);
+                          round->chunks_run, ctx->prev_action, ctx->has_prev, nullptr, act_dense, s, p->chunk_budget, j, ChunkStrides{0, 0, 0},
+                          scp);
   }
   HIP_TRY(ctx, hipMemcpyAsync(round->end_state, ctx->cur_state, (size_t)B * 6 * sizeof(double),
                               hipMemcpyDeviceToDevice, s));
@@ -1087,6 +1121,105 @@ int32_t ditree_forest_fallback(ditree_ctx* ctx, const ditree_tree* tree, const d
                    nullptr, nullptr, nullptr, nullptr, s);
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipStreamSynchronize(s));               // `q` is a temporary
+  return DITREE_OK;
+}
+
+// ---- scene forests (include/ditree.h "scene forests")
+int32_t ditree_upload_scenes(ditree_ctx* ctx, int32_t n, const float* mazes, const int32_t* rows, const int32_t* cols,
+                             const double* goal_xy, void* stream) {
+  if (!ctx) return DITREE_E_ARG;
+  if (n < 1 || n > DITREE_MAX_SCENES)
+    return set_err(ctx, DITREE_E_ARG, "upload_scenes: " + std::to_string(n) + " scenes (need 1.." + std::to_string(DITREE_MAX_SCENES) + ")");
+  if (!mazes || !rows || !cols || !goal_xy) return set_err(ctx, DITREE_E_ARG, "upload_scenes: mazes, rows, cols and goal_xy are required");
+  int64_t total = 0;
+  for (int i = 0; i < n; ++i) {
+    if (rows[i] < 1 || cols[i] < 1)
+      return set_err(ctx, DITREE_E_ARG, "upload_scenes: scene " + std::to_string(i) + " has rows / cols < 1");
+    total += (int64_t)rows[i] * cols[i];
+  }
+  if (total > DITREE_MAX_ATLAS_CELLS)
+    return set_err(ctx, DITREE_E_ARG, "upload_scenes: the mazes hold " + std::to_string(total) + " cells, more than the atlas's " +
+                   std::to_string(DITREE_MAX_ATLAS_CELLS));
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (!ctx->scene_tab) HIP_TRY(ctx, hipMalloc((void**)&ctx->scene_tab, sizeof(SceneTable) + DITREE_MAX_ATLAS_CELLS));
+  // the host image of the whole block: header, records, atlas; a map equal to an earlier scene's (dims and codes) shares its bytes
+  std::vector<unsigned char> blk(sizeof(SceneTable) + (size_t)total, 0);
+  SceneTable* tab = reinterpret_cast<SceneTable*>(blk.data());
+  unsigned char* atlas = blk.data() + sizeof(SceneTable);
+  tab->row_scene = ctx->row_scene;
+  tab->n = n;
+  int used = 0, max_cells = 0;
+  const float* src = mazes;
+  for (int i = 0; i < n; ++i) {
+    const int cells = rows[i] * cols[i];
+    unsigned char* dst = atlas + used;
+    for (int k = 0; k < cells; ++k) {                  // ditree_upload_maze's rule
+      const float v = src[k];
+      const int c = (int)v;
+      dst[k] = (v == (float)c && c >= 0 && c < 256) ? (unsigned char)c : (unsigned char)255;
+    }
+    src += cells;
+    int offset = used;
+    for (int j = 0; j < i; ++j)
+      if (rows[j] == rows[i] && cols[j] == cols[i] && memcmp(atlas + tab->rec[j].offset, dst, cells) == 0) {
+        offset = tab->rec[j].offset;
+        break;
+      }
+    if (offset == used) used += cells;
+    tab->rec[i] = SceneRec{offset, rows[i], cols[i], 0, goal_xy[2 * i], goal_xy[2 * i + 1]};
+    max_cells = cells > max_cells ? cells : max_cells;
+  }
+  tab->atlas_cells = used;
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->scene_tab, blk.data(), sizeof(SceneTable) + used, hipMemcpyHostToDevice, s));
+  HIP_TRY(ctx, hipStreamSynchronize(s));               // `blk` is a temporary
+  ctx->n_scenes = n;
+  ctx->atlas_cells = used;
+  ctx->max_scene_cells = max_cells;
+  return DITREE_OK;
+}
+
+static int check_scenes(ditree_ctx* ctx, const ditree_forest* f, const ditree_forest_scenes* sc, const char* what) {
+  const std::string w(what);
+  if (ctx->n_scenes < 1) return set_err(ctx, DITREE_E_STATE, w + ": no scene table uploaded (ditree_upload_scenes)");
+  if (!sc || !sc->tree_scene || !sc->tree_scene_host)
+    return set_err(ctx, DITREE_E_ARG, w + ": scene descriptor incomplete (tree_scene, tree_scene_host)");
+  for (int t = 0; t < f->n_trees; ++t)
+    if (sc->tree_scene_host[t] < 0 || sc->tree_scene_host[t] >= ctx->n_scenes)
+      return set_err(ctx, DITREE_E_ARG, w + ": tree " + std::to_string(t) + " has scene id " + std::to_string(sc->tree_scene_host[t]) +
+                     ", out of range [0, " + std::to_string(ctx->n_scenes) + ")");
+  return DITREE_OK;
+}
+
+int32_t ditree_forest_expand_round_scenes(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
+                                          const ditree_forest_scenes* scenes, const ditree_round* round,
+                                          const ditree_round_params* p, void* stream) {
+  if (!ctx) return DITREE_E_ARG;
+  int rc = check_round(ctx, round);
+  if (rc) return rc;
+  rc = check_forest(ctx, tree, forest, round->B, "forest_expand_round_scenes");
+  if (rc) return rc;
+  rc = check_scenes(ctx, forest, scenes, "forest_expand_round_scenes");
+  if (rc) return rc;
+  return expand_round_impl(ctx, tree, forest, round, p, stream, scenes->tree_scene);
+}
+
+int32_t ditree_forest_fallback_goals(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const double* goal_xy,
+                                     int32_t* out_node, void* stream) {
+  if (!ctx) return DITREE_E_ARG;
+  int rc = check_forest(ctx, tree, forest, -1, "forest_fallback_goals");
+  if (rc) return rc;
+  if (!goal_xy) return set_err(ctx, DITREE_E_ARG, "forest_fallback_goals: goals array (T, 2) missing");
+  if (!out_node) return set_err(ctx, DITREE_E_ARG, "forest_fallback_goals: out_node missing");
+  hipStream_t s = (hipStream_t)stream;
+  const int T = forest->n_trees;
+  rc = ensure_scratch(ctx, T, 1, 1);                   // the T goals as the queries (ctx->cur_state, (T, 6))
+  if (rc) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->cur_state, goal_xy, (size_t)T * 2 * sizeof(double), hipMemcpyHostToDevice, s));
+  launch_nn_forest(ctx->cur_state, 2, T, tree->xy, nullptr, T, forest->counters, forest->tree_capacity, 1, out_node, nullptr, nullptr,
+                   nullptr, nullptr, nullptr, nullptr, s);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipStreamSynchronize(s));               // goal_xy is the caller's host memory
   return DITREE_OK;
 }
 

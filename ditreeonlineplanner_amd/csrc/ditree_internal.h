@@ -24,6 +24,29 @@ struct AntNormArg {
 
 struct DenoiserState;   // denoise_host.hip
 
+// One scene of a scene table (ditree_upload_scenes): its maze at atlas[offset], rows x cols, and its goal.
+struct SceneRec {
+  int32_t offset, rows, cols, pad;
+  double gx, gy;
+};
+// The scene table on the device, one block: the scene of every candidate row of the current round (ctx scratch), the records,
+// then the atlas bytes.  The scene variants of the round's kernels take it in place of the maze pointer.
+struct SceneTable {
+  const int32_t* row_scene;
+  int32_t n, atlas_cells;
+  SceneRec rec[DITREE_MAX_SCENES];
+};
+static_assert(sizeof(SceneTable) % 16 == 0, "the atlas follows the records 16-byte aligned");
+__host__ __device__ inline const unsigned char* scene_atlas(const SceneTable* t) {
+  return reinterpret_cast<const unsigned char*>(t + 1);
+}
+// What the scene launchers need: the table, the atlas size (the rollout stages it whole), the largest maze (the local map
+// stages one).
+struct SceneArg {
+  const SceneTable* table;
+  int atlas_cells, max_cells;
+};
+
 struct ditree_ctx {
   int device = 0;
   std::string err;
@@ -65,6 +88,11 @@ struct ditree_ctx {
   double* mppi_ant_partial = nullptr;   // the same for ditree_mppi_step_ant (3 + 8 T per slice)
   unsigned long long* mppi_minkey = nullptr;   // running minimum of the rollout costs (order-preserving integer image)
   DenoiserState* dn = nullptr;
+  // scene table (ditree_upload_scenes): atlas of u8 cell codes, (n_scenes,) records, and a (row_scene_cap,) row -> scene scratch
+  SceneTable* scene_tab = nullptr;                 // device block: header, records, atlas (DITREE_MAX_ATLAS_CELLS bytes)
+  int n_scenes = 0, atlas_cells = 0, max_scene_cells = 0;
+  int32_t* row_scene = nullptr;
+  int row_scene_cap = 0;
   // optional RCCL communicator (ditree_comm_*): librccl opened at run time
   void* rccl_lib = nullptr;
   void* comm = nullptr;
@@ -89,6 +117,9 @@ void launch_nn_forest(const double* queries, int q_stride, int B, const double* 
                       const int32_t* counters, int C, int skip, int32_t* out_idx, const double* node_state,
                       const double* node_last_action, const uint8_t* node_has_prev, double* out_state, double* out_prev_action,
                       uint8_t* out_has_prev, hipStream_t s, int S = 6, int D = 2);
+void launch_local_map_scenes(const SceneArg& sc, const double* state, const int32_t* active, const int32_t* idx, int B, int n,
+                             const AxisArg& axis, double s_global, float* out, hipStream_t s);
+void launch_row_scene(const int32_t* off, int T, const int32_t* tree_scene, int B, int32_t* row_scene, hipStream_t s);
 void launch_local_map(const unsigned char* maze, int rows, int cols, const double* state,
                       const int32_t* active, const int32_t* idx, int B, int n, const AxisArg& axis,
                       double s_global, int scaled, float* out, hipStream_t s, int state_stride = 6);

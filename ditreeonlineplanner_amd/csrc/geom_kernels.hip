@@ -189,6 +189,9 @@ void launch_nn_forest(const double* queries, int q_stride, int B, const double* 
 
 // ------------------------------------------------------------------------- local map
 // One workgroup per candidate; maze staged in LDS; one thread per output cell.
+// SCENES (a scene forest, include/ditree.h "scene forests"): `maze` is the scene table (SceneTable); the work-group stages only
+// its candidate's maze from the atlas and uses that scene's dims for the centre and the clipping.
+template <bool SCENES>
 __global__ void __launch_bounds__(256)
 local_map_kernel(const unsigned char* __restrict__ maze, int rows, int cols, const double* __restrict__ state,
                  int state_stride, const int32_t* __restrict__ active, const int32_t* __restrict__ idx, int n, AxisArg axis,
@@ -197,7 +200,15 @@ local_map_kernel(const unsigned char* __restrict__ maze, int rows, int cols, con
   const int ob = blockIdx.x;                                        // dense output row
   const int b = idx ? idx[ob] : ob;                                 // candidate (compacted rounds pass an index list)
   if (active != nullptr && active[b] != DITREE_ST_OK) return;      // block-uniform
-  stage_maze(lds, maze, rows * cols);
+  if constexpr (SCENES) {
+    const SceneTable* tab = reinterpret_cast<const SceneTable*>(maze);
+    const SceneRec sc = tab->rec[tab->row_scene[b]];
+    rows = sc.rows;
+    cols = sc.cols;
+    stage_maze(lds, scene_atlas(tab) + sc.offset, rows * cols);
+  } else {
+    stage_maze(lds, maze, rows * cols);
+  }
   // RRT.py:158-166 passes curr_state[0], curr_state[1], curr_state[2] for every env (for the ant, element 2 is the torso
   // height, not a heading -- the reference's own behaviour, kept)
   const double x = state[(size_t)b * state_stride + 0], y = state[(size_t)b * state_stride + 1], th = state[(size_t)b * state_stride + 2];
@@ -223,8 +234,30 @@ void launch_local_map(const unsigned char* maze, int rows, int cols, const doubl
                       const int32_t* idx, int B, int n, const AxisArg& axis, double s_global, int scaled, float* out,
                       hipStream_t s, int state_stride) {
   size_t lds = ((size_t)rows * cols + 15) & ~(size_t)15;
-  hipLaunchKernelGGL(local_map_kernel, dim3(B), dim3(256), lds, s, maze, rows, cols, state, state_stride, active, idx, n, axis,
+  hipLaunchKernelGGL(local_map_kernel<false>, dim3(B), dim3(256), lds, s, maze, rows, cols, state, state_stride, active, idx, n, axis,
                      s_global, scaled, out);
+}
+void launch_local_map_scenes(const SceneArg& sc, const double* state, const int32_t* active, const int32_t* idx, int B, int n,
+                             const AxisArg& axis, double s_global, float* out, hipStream_t s) {
+  const size_t lds = ((size_t)sc.max_cells + 15) & ~(size_t)15;
+  hipLaunchKernelGGL(local_map_kernel<true>, dim3(B), dim3(256), lds, s, (const unsigned char*)sc.table, 0, 0, state, 6, active,
+                     idx, n, axis, s_global, 1, out);
+}
+// The scene of every candidate row: tree_scene[t] for the tree whose range [off[t], off[t+1]) holds the row (the last tree
+// whose range starts at or before it: empty ranges are skipped, as in nn_forest_kernel).
+__global__ void row_scene_kernel(const int32_t* __restrict__ off, int T, const int32_t* __restrict__ tree_scene, int B,
+                                 int32_t* __restrict__ row_scene) {
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= B) return;
+  int lo = 0, hi = T - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (off[mid] <= q) lo = mid; else hi = mid - 1;
+  }
+  row_scene[q] = tree_scene[lo];
+}
+void launch_row_scene(const int32_t* off, int T, const int32_t* tree_scene, int B, int32_t* row_scene, hipStream_t s) {
+  hipLaunchKernelGGL(row_scene_kernel, dim3((B + 255) / 256), dim3(256), 0, s, off, T, tree_scene, B, row_scene);
 }
 
 // ------------------------------------------------------------------------- conditioning vector
@@ -416,7 +449,10 @@ void launch_path_after_obstacle(const float* path, int stride, int P, double cx,
 // G lanes per candidate (1 or 2).  G = 2: both lanes of a pair integrate the (identical) dynamics, lane g tests ball g and the
 // pair ORs by one lane exchange, lane 0 stores the state rows and lane 1 the action rows -- twice the waves for the same batch
 // (two per SIMD at 65 536 candidates), each with a shorter chain per step.  Same arithmetic, same results.
-template <int G, bool LOCKSTEP, bool STAGE>
+// SCENES (a scene forest, include/ditree.h "scene forests"): `maze` is the scene table (SceneTable) and rows x cols its atlas
+// size; the whole atlas is staged, and each lane reads its candidate's scene record -- atlas offset, dims, goal -- next to its
+// state, before the vmcnt(0) below.  From there on every test is the single-maze kernel's on that scene's bytes, dims and goal.
+template <int G, bool LOCKSTEP, bool STAGE, bool SCENES>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2)))   // the action burst holds 64 registers: no spills
 car_rollout_kernel(const unsigned char* __restrict__ maze, int rows, int cols, double* __restrict__ state_io,
                    const double* __restrict__ actions, int64_t act_stride, int32_t* __restrict__ status_io, int B,
@@ -426,11 +462,25 @@ car_rollout_kernel(const unsigned char* __restrict__ maze, int rows, int cols, d
                    uint8_t* __restrict__ has_prev_io, const int32_t* __restrict__ idx, int act_dense,
                    const int32_t* __restrict__ budget, int chunk_j, ChunkStrides cs) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-  stage_maze(lds, maze, rows * cols);
+  if constexpr (SCENES)
+    stage_maze(lds, scene_atlas(reinterpret_cast<const SceneTable*>(maze)), rows * cols);
+  else
+    stage_maze(lds, maze, rows * cols);
   const int ob = (blockIdx.x * blockDim.x + threadIdx.x) / G, g = threadIdx.x & (G - 1);
   if (ob >= B) return;
   const int b = idx ? idx[ob] : ob;                 // compacted rounds: actions are dense (row ob), the rest per candidate
   if (status_io[b] != DITREE_ST_OK) return;
+  const unsigned char* mz = lds;                    // this candidate's maze in LDS and its dims
+  int H = rows, W = cols;
+  if constexpr (SCENES) {
+    const SceneTable* tab = reinterpret_cast<const SceneTable*>(maze);
+    const SceneRec sc = tab->rec[tab->row_scene[b]];
+    mz = lds + sc.offset;
+    H = sc.rows;
+    W = sc.cols;
+    gx = sc.gx;
+    gy = sc.gy;
+  }
   // chunk_j < 0 (pool-scheduled early-exit rounds: one launch holds candidates at DIFFERENT chunks of their edges): the chunk
   // is the number of chunks this candidate has finished; the chunk-0 bases are offset by it
   if (chunk_j < 0) {
@@ -525,11 +575,11 @@ car_rollout_kernel(const unsigned char* __restrict__ maze, int rows, int cols, d
           double sps, cps;
           sincos(s[2], &sps, &cps);
           const double ox = off * cps, oy = off * sps;
-          mine = ball_collides(s[0] + sgn * ox, s[1] + sgn * oy, lds, rows, cols) ? 1 : 0;
+          mine = ball_collides(s[0] + sgn * ox, s[1] + sgn * oy, mz, H, W) ? 1 : 0;
         }
         coll = (mine | __shfl_xor(mine, 1)) != 0;
       } else if (alive) {
-        coll = car_collides(s[0], s[1], s[2], lds, rows, cols);                   // base_planner.py:306
+        coll = car_collides(s[0], s[1], s[2], mz, H, W);                           // base_planner.py:306
       }
       if (alive && coll) {
         status = DITREE_ST_COLLIDED | (done ? DITREE_ST_FLAG_GOAL_AT_COLLISION : 0);
@@ -559,10 +609,10 @@ car_rollout_kernel(const unsigned char* __restrict__ maze, int rows, int cols, d
         double sps, cps;
         sincos(s[2], &sps, &cps);
         const double ox = off * cps, oy = off * sps;
-        const int mine = ball_collides(s[0] + sgn * ox, s[1] + sgn * oy, lds, rows, cols) ? 1 : 0;
+        const int mine = ball_collides(s[0] + sgn * ox, s[1] + sgn * oy, mz, H, W) ? 1 : 0;
         coll = (mine | __shfl_xor(mine, 1)) != 0;
       } else {
-        coll = car_collides(s[0], s[1], s[2], lds, rows, cols);
+        coll = car_collides(s[0], s[1], s[2], mz, H, W);
       }
       if (coll) {
         status = DITREE_ST_COLLIDED | (done ? DITREE_ST_FLAG_GOAL_AT_COLLISION : 0);
@@ -607,7 +657,12 @@ void launch_car_rollout_ex(const unsigned char* maze, int rows, int cols, double
                            double* states_out, ditree_strides states_stride, double* actions_out, ditree_strides actout_stride,
                            int32_t* steps_out, int64_t steps_stride, int32_t* chunks_run, double* prev_action_io,
                            uint8_t* has_prev_io, const int32_t* idx, int act_dense, hipStream_t s, const int32_t* budget,
-                           int chunk_j, ChunkStrides cs) {
+                           int chunk_j, ChunkStrides cs, const SceneArg* scenes) {
+  if (scenes) {                                              // the whole atlas is staged (rows = 1 x cols = its cells)
+    maze = (const unsigned char*)scenes->table;
+    rows = 1;
+    cols = scenes->atlas_cells;
+  }
   size_t lds = ((size_t)rows * cols + 15) & ~(size_t)15;
   // lane-private LDS staging of the action rows (DITREE_ROLLOUT_STAGE=0 turns it off; needs 16-byte aligned rows): 65 536 x 16,
   // candidate-minor rows: 114 -> 20.4 MB fetched per launch (total 188 -> 94.3 MB = 1.005 x the algorithmic 93.8 MB), and no
@@ -628,10 +683,14 @@ void launch_car_rollout_ex(const unsigned char* maze, int rows, int cols, double
   const bool attr_done = dev >= 0 && dev < 64 && attr_done_dev[dev];
   if (!attr_done) {                                          // 256 threads x 256 B of staged actions + the maze exceed 64 KB
     const hipFuncAttribute at = hipFuncAttributeMaxDynamicSharedMemorySize;
-    (void)hipFuncSetAttribute((const void*)car_rollout_kernel<1, true, true>, at, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)car_rollout_kernel<1, false, true>, at, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)car_rollout_kernel<2, true, true>, at, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)car_rollout_kernel<2, false, true>, at, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)car_rollout_kernel<1, true, true, false>, at, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)car_rollout_kernel<1, true, true, true>, at, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)car_rollout_kernel<1, false, true, false>, at, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)car_rollout_kernel<1, false, true, true>, at, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)car_rollout_kernel<2, true, true, false>, at, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)car_rollout_kernel<2, true, true, true>, at, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)car_rollout_kernel<2, false, true, false>, at, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)car_rollout_kernel<2, false, true, true>, at, 160 * 1024);
     if (dev >= 0 && dev < 64) attr_done_dev[dev] = true;
   }
   if (lds + (size_t)blk * 256 > 160 * 1024) stage = 0;        // a maze that leaves no room for the staged actions: per-step loads
@@ -646,16 +705,20 @@ void launch_car_rollout_ex(const unsigned char* maze, int rows, int cols, double
   // (dead lanes keep storing zero rows step by step: profiles/r04_rollout_layout_probe.json) -- chosen by the layout
   const bool lock = (states_out && states_stride.cand == 1) || (!states_out && actions_out && actout_stride.cand == 1);
   const int G = lanes_env == 1 ? 1 : (lanes_env == 2 ? 2 : (B <= 32768 ? 2 : 1));
-#define CAR_ROLLOUT_LAUNCH(GG, PP, SS)                                                                                          \
-  hipLaunchKernelGGL((car_rollout_kernel<GG, PP, SS>), dim3((GG * B + blk - 1) / blk), dim3(blk), lds + (SS ? (size_t)blk * 256 : 0), s, maze, \
+#define CAR_ROLLOUT_LAUNCH(GG, PP, SS, SC)                                                                                      \
+  hipLaunchKernelGGL((car_rollout_kernel<GG, PP, SS, SC>), dim3((GG * B + blk - 1) / blk), dim3(blk), lds + (SS ? (size_t)blk * 256 : 0), s, maze, \
                      rows, cols, state_io, actions, act_stride, status_io, B, A, gx, gy, states_out, states_stride, actions_out,  \
                      actout_stride, steps_out, steps_stride, chunks_run, prev_action_io, has_prev_io, idx, act_dense, budget, chunk_j, cs)
-#define CAR_ROLLOUT_PICK(GG)                                                                        \
+#define CAR_ROLLOUT_PICK(GG, SC)                                                                    \
   do {                                                                                              \
-    if (lock) { if (stage) CAR_ROLLOUT_LAUNCH(GG, true, true); else CAR_ROLLOUT_LAUNCH(GG, true, false); }   \
-    else { if (stage) CAR_ROLLOUT_LAUNCH(GG, false, true); else CAR_ROLLOUT_LAUNCH(GG, false, false); }      \
+    if (lock) { if (stage) CAR_ROLLOUT_LAUNCH(GG, true, true, SC); else CAR_ROLLOUT_LAUNCH(GG, true, false, SC); }   \
+    else { if (stage) CAR_ROLLOUT_LAUNCH(GG, false, true, SC); else CAR_ROLLOUT_LAUNCH(GG, false, false, SC); }      \
   } while (0)
-  if (G == 2) CAR_ROLLOUT_PICK(2); else CAR_ROLLOUT_PICK(1);
+  if (scenes) {
+    if (G == 2) CAR_ROLLOUT_PICK(2, true); else CAR_ROLLOUT_PICK(1, true);
+  } else {
+    if (G == 2) CAR_ROLLOUT_PICK(2, false); else CAR_ROLLOUT_PICK(1, false);
+  }
 #undef CAR_ROLLOUT_PICK
 #undef CAR_ROLLOUT_LAUNCH
 }
@@ -665,7 +728,7 @@ void launch_car_rollout(const unsigned char* maze, int rows, int cols, double* s
                         int32_t* steps_out, double* prev_action_io, uint8_t* has_prev_io, hipStream_t s) {
   launch_car_rollout_ex(maze, rows, cols, state_io, actions, act_stride, status_io, B, A, gx, gy, states_out,
                         ditree_strides{states_stride, 6, 1}, actions_out, ditree_strides{actout_stride, 2, 1}, steps_out, 1,
-                        nullptr, prev_action_io, has_prev_io, nullptr, 1, s, nullptr, 0, ChunkStrides{0, 0, 0});
+                        nullptr, prev_action_io, has_prev_io, nullptr, 1, s, nullptr, 0, ChunkStrides{0, 0, 0}, nullptr);
 }
 
 // ------------------------------------------------------------------------- lidar

@@ -9,7 +9,8 @@ nearest-node search (segmented by tree), accept / commit (one work-group per tre
 visit count and the fallback choice.  Every per-candidate kernel is the single-tree round's, and its result does not depend on
 the batch, so each tree grows exactly as it would in its own ``ExpansionEngine`` fed the same rows.
 
-Scope: the car, run_type 0, one GPU, one maze / start / goal for every tree.
+Scope: the car, run_type 0, one GPU, one maze / start / goal for every tree -- or, in a ``SceneForestEngine``, each tree on
+its own scene (maze, start, goal) of a scenario set (run_scenarios.py:203-250), the mazes in one scene table on the device.
 """
 from __future__ import annotations
 
@@ -18,7 +19,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import Forest, RoundParams, check, lib
+from ._lib import MAX_ATLAS_CELLS, MAX_SCENES, Forest, ForestScenes, RoundParams, check, lib
 from .engine import CNT_GOAL, CNT_NODES, CNT_PHANTOM, ExpansionEngine
 from .ops import CAR_NORM, Context, _dbl
 
@@ -64,11 +65,13 @@ class ForestEngine(ExpansionEngine):
             self.reset_tree(t)
         self.generation = getattr(self, "generation", 0) + 1
 
-    def reset_tree(self, t):
-        """Tree t back to its root, so a finished run's slot can take the next run (DeviceTree.reset for one tree)."""
+    def reset_tree(self, t, start_state=None):
+        """Tree t back to its root, so a finished run's slot can take the next run (DeviceTree.reset for one tree).
+        ``start_state``: the root's state (default: the forest's start)."""
         t = self._tree_index(t)
         tr, r = self.tree, t * self.C
-        s = torch.as_tensor(self.start_state, device=tr.state.device)
+        s = torch.as_tensor(self.start_state if start_state is None else np.asarray(start_state, dtype=np.float64),
+                            device=tr.state.device)
         tr.state[r] = s
         tr.xy[r] = s[:2]
         tr.parent[r] = -1
@@ -153,12 +156,16 @@ class ForestEngine(ExpansionEngine):
                                                   self._budget.data_ptr(), st), "forest_chunk_budget")
             rp.chunk_budget = self._budget.data_ptr()
         rd = self.rb.desc(0, B)
-        check(h, L.ditree_forest_expand_round(h, C.byref(self.tree.desc), C.byref(self.fdesc), C.byref(rd), C.byref(rp), st),
-              "forest_expand_round")
+        self._launch_round(rd, rp)
         del keep
         self._used_denoiser = noise is not None
         self._B = B
         return self.accept(B) if accept else None
+
+    def _launch_round(self, rd, rp):
+        h = self.ctx._h
+        check(h, lib().ditree_forest_expand_round(h, C.byref(self.tree.desc), C.byref(self.fdesc), C.byref(rd), C.byref(rp),
+                                                  self.ctx.stream), "forest_expand_round")
 
     def accept(self, B=None):
         B = self._B if B is None else int(B)
@@ -244,3 +251,122 @@ class ForestEngine(ExpansionEngine):
     def shard(self, B):                               # one rank
         return 0, B, B
 
+
+
+# ---------------------------------------------------------------------- scene forests
+def cell_codes(maze):
+    """The u8 cell codes the device stores for a maze (ditree_upload_maze's rule: integral values 0..255, else 255)."""
+    m = np.asarray(maze, dtype=np.float32)
+    c = m.astype(np.int64)
+    ok = (m == c.astype(np.float32)) & (c >= 0) & (c < 256)
+    return np.where(ok, c, 255).astype(np.uint8)
+
+
+def atlas_layout(mazes):
+    """The atlas ditree_upload_scenes builds: a map equal to an earlier scene's (dims and cell codes) shares its bytes.
+    -> (offsets (n,), dims (n, 2), atlas cells)."""
+    offsets, dims, seen, used = [], [], [], 0
+    for m in mazes:
+        codes = cell_codes(m)
+        off = next((o for o, k in seen if k.shape == codes.shape and np.array_equal(k, codes)), None)
+        if off is None:
+            off = used
+            seen.append((off, codes))
+            used += codes.size
+        offsets.append(off)
+        dims.append(codes.shape)
+    return np.array(offsets, dtype=np.int64), np.array(dims, dtype=np.int64).reshape(-1, 2), used
+
+
+def env_goal_of(maze, goal_state):
+    """env.goal after planner.reset -> env.reset(options): the centre of the goal cell (car_env.py:189-201,225-226)."""
+    H, W = np.asarray(maze).shape
+    gi = np.floor((H / 2 - goal_state[1]) / 1.0)
+    gj = np.floor((goal_state[0] + W / 2) / 1.0)
+    return np.array([(gj + 0.5) * 1.0 - W / 2, H / 2 - (gi + 0.5) * 1.0])
+
+
+class SceneForestEngine(ForestEngine):
+    """A forest whose trees belong to different scenes of a scenario set.  ``scenes``: a list of ``(maze, start_state,
+    goal_state, env_goal)`` (env_goal None: the goal cell's centre, as env.reset sets it).  Tree t grows on scene
+    ``tree_scene(t)``: its root is that scene's start, its local map, collision and goal tests use that scene's maze and goal,
+    and its fallback is the node nearest to that scene's goal -- exactly as its own ``ExpansionEngine`` on that scene.  All
+    mazes sit in one scene table on the device (include/ditree.h "scene forests"); no single maze is read."""
+
+    def __init__(self, ctx: Context, scenes, n_trees, tree_capacity, **kw):
+        scenes = list(scenes)
+        if not 1 <= len(scenes) <= MAX_SCENES:
+            raise ValueError(f"a scene forest holds 1..{MAX_SCENES} scenes, got {len(scenes)}")
+        self.scene_mazes, self.scene_starts, self.scene_goals, self.scene_env_goals = [], [], [], []
+        for sc in scenes:
+            maze, start, goal = sc[0], sc[1], sc[2]
+            env_goal = sc[3] if len(sc) > 3 else None
+            maze = np.asarray(maze, dtype=np.float32)
+            goal = np.asarray(goal, dtype=np.float64).copy()
+            self.scene_mazes.append(maze)
+            self.scene_starts.append(np.asarray(start, dtype=np.float64).copy())
+            self.scene_goals.append(goal)
+            self.scene_env_goals.append(np.asarray(env_goal_of(maze, goal) if env_goal is None else env_goal, dtype=np.float64)[:2].copy())
+        cells = sum(m.size for m in self.scene_mazes)
+        if cells > MAX_ATLAS_CELLS:
+            raise ValueError(f"the scenes' mazes hold {cells} cells, more than the atlas's {MAX_ATLAS_CELLS}")
+        self.atlas_offsets, self.atlas_dims, self.atlas_cells = atlas_layout(self.scene_mazes)
+        T = int(n_trees)
+        self.tree_scene_host = (C.c_int32 * max(T, 1))()
+        self.tree_scene_dev = torch.zeros(max(T, 1), dtype=torch.int32, device=ctx.device)
+        self.sdesc = ForestScenes(self.tree_scene_dev.data_ptr(), self.tree_scene_host)
+        self.ctx = ctx
+        self.upload_scenes()
+        super().__init__(ctx, self.scene_mazes[0], self.scene_starts[0], self.scene_goals[0], n_trees, tree_capacity, **kw)
+
+    def upload_scenes(self):
+        self.ctx.upload_scenes(self.scene_mazes, np.stack(self.scene_env_goals), owner=self)
+
+    def ensure_maze(self):
+        """The ctx's scene table must be this forest's before any launch (the single maze is not read)."""
+        if self.ctx.scenes_owner is not self:
+            self.upload_scenes()
+
+    def update_maze(self, maze):
+        raise NotImplementedError("a scene forest's mazes are fixed at construction")
+
+    @property
+    def n_scenes(self):
+        return len(self.scene_mazes)
+
+    def reset(self, start_state=None, goal_state=None):
+        """Every tree back to the root of its scene (start_state / goal_state are not read: each scene has its own)."""
+        self.start_state, self.goal_state = self.scene_starts[0].copy(), self.scene_goals[0].copy()
+        self.env_goal = self.scene_env_goals[0].copy()
+        self.tree.reset(self.start_state)
+        for t in range(self.T):
+            self.reset_tree(t, self.tree_scene_host[t])
+        self.generation = getattr(self, "generation", 0) + 1
+
+    def reset_tree(self, t, scene=None):
+        """Tree t back to a root: the start of ``scene`` (default: the tree's current scene), which the tree then grows on."""
+        t = self._tree_index(t)
+        scene = int(self.tree_scene_host[t] if scene is None else scene)
+        if not 0 <= scene < self.n_scenes:
+            raise IndexError(f"scene {scene} of {self.n_scenes}")
+        self.tree_scene_host[t] = scene
+        self.tree_scene_dev[t] = scene
+        super().reset_tree(t, self.scene_starts[scene])
+
+    def tree_scene(self, t):
+        return int(self.tree_scene_host[self._tree_index(t)])
+
+    def _launch_round(self, rd, rp):
+        h = self.ctx._h
+        check(h, lib().ditree_forest_expand_round_scenes(h, C.byref(self.tree.desc), C.byref(self.fdesc), C.byref(self.sdesc),
+                                                         C.byref(rd), C.byref(rp), self.ctx.stream), "forest_expand_round_scenes")
+
+    def fallback_nodes(self):
+        """planners/RRT.py:227-254 (run_type 0) for every tree, each against its own scene's goal_state[:2]."""
+        out = torch.empty(self.T, dtype=torch.int32, device=self.tree.xy.device)
+        ga, gp = _dbl(np.stack([self.scene_goals[self.tree_scene(t)][:2] for t in range(self.T)]))
+        check(self.ctx._h, lib().ditree_forest_fallback_goals(self.ctx._h, C.byref(self.tree.desc), C.byref(self.fdesc), gp,
+                                                               out.data_ptr(), self.ctx.stream), "forest_fallback_goals")
+        del ga
+        ids = out.cpu().numpy()
+        return [None if v < 0 else int(v) - t * self.C for t, v in enumerate(ids)]

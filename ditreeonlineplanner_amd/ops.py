@@ -65,6 +65,7 @@ class Context:
         # default_context): whoever uploaded last is recorded here, and every user re-uploads when it is not the owner.
         self.maze_owner = None
         self.weights_owner = None
+        self.scenes_owner = None            # the same for the scene table of scene forests (upload_scenes)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -92,6 +93,22 @@ class Context:
                                                  m.shape[1], self.stream), "upload_maze")
         self.maze_shape = m.shape
         self.maze_owner = owner
+
+    def upload_scenes(self, mazes, goal_xy, owner=None):
+        """Copy a scene table to the device (ditree_upload_scenes): ``mazes`` one 2-D map per scene, ``goal_xy`` (n, 2) each
+        scene's env.goal.  Identical maps share their atlas bytes.  Separate from the single maze of ``upload_maze``;
+        ``owner`` is recorded as ``scenes_owner``."""
+        ms = [np.ascontiguousarray(np.asarray(m, dtype=np.float32)) for m in mazes]
+        if any(m.ndim != 2 for m in ms):
+            raise ValueError("every maze must be 2-D")
+        n = len(ms)
+        g = np.ascontiguousarray(np.asarray(goal_xy, dtype=np.float64).reshape(n, 2))
+        flat = np.ascontiguousarray(np.concatenate([m.reshape(-1) for m in ms]) if ms else np.zeros(0, np.float32))
+        rows = (C.c_int32 * max(n, 1))(*[m.shape[0] for m in ms])
+        cols = (C.c_int32 * max(n, 1))(*[m.shape[1] for m in ms])
+        check(self._h, lib().ditree_upload_scenes(self._h, n, flat.ctypes.data_as(C.POINTER(C.c_float)), rows, cols,
+                                                   g.ctypes.data_as(C.POINTER(C.c_double)), self.stream), "upload_scenes")
+        self.scenes_owner = owner
 
     # ------------------------------------------------------------------ nearest node
     def nn_argmin(self, queries, node_xy, n_nodes=None, gather=None):

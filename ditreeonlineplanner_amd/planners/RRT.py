@@ -503,3 +503,161 @@ class RRT_Planner(BasePlanner):
         _mu.add_cc_calls(total_cc)                  # the counter the drivers read (run_scenarios.py:338,343), once
         return results
 
+
+
+# ---------------------------------------------------------------------- a scenario set at once
+def _scene_settings(pl):
+    """What every planner of one scene forest must share (the forest runs one round program for all its trees)."""
+    e = pl._engine
+    return [("ctx", pl.ctx), ("sampler", pl.sampler), ("action_horizon", e.A), ("pred_horizon", e.P), ("local map size", e.lm_n),
+            ("local map scale", float(e.lm_scale)), ("s_global", float(e.s_global)), ("k_steps", e.k_steps),
+            ("norm", e.norm.tobytes()), ("emulate_sticky_done", e.sticky), ("early_exit", e.early_exit),
+            ("prop_duration", tuple(e.schedule)), ("batch", pl.batch)]
+
+
+def _check_scene_planners(planners):
+    for pl in planners:
+        if pl.is_ant:
+            raise NotImplementedError("plan_scenario_runs: the car (carmaze) only")
+        if pl.run_type != 0:
+            raise NotImplementedError("plan_scenario_runs: run_type 0 only (the online re-planning driver plans one run at a time)")
+        if pl.world_size > 1:
+            raise NotImplementedError("plan_scenario_runs: one rank (a forest is not sharded)")
+        if not hasattr(pl.sampler, "ensure_bound") and not hasattr(pl.sampler, "sample_round"):
+            raise NotImplementedError("plan_scenario_runs: a plain-callable sampler draws from its own generator and cannot be split "
+                                      "per run; give it a sample_round(first_candidate, B, n_chunks, pred_horizon) method")
+    ref = _scene_settings(planners[0])
+    for i, pl in enumerate(planners[1:], 1):
+        for (name, a), (_, b) in zip(ref, _scene_settings(pl)):
+            same = a is b if name in ("ctx", "sampler") else a == b
+            if not same:
+                raise ValueError(f"plan_scenario_runs: planner {i} differs from planner 0 in {name}"
+                                 + ("" if name in ("ctx", "sampler") else f" ({b!r} != {a!r})")
+                                 + ("; all planners must share one object" if name in ("ctx", "sampler") else ""))
+
+
+def plan_scenario_runs(planners, seeds, concurrent=None, tree_capacity=None):
+    """Seeded runs of several scenarios (one ``RRT_Planner`` each: its own maze, start and goal) expanded together as one
+    scene forest (forest.SceneForestEngine) on one GPU -- the whole benchmark loop of run_scenarios.py:203-250,336-343 as
+    one stream of rounds.
+
+    ``seeds``: one list per planner.  Returns one list per planner of ``plan_runs``-shaped dicts: run (i, s) is what
+    ``random.seed(s); np.random.seed(s); torch.manual_seed(s); planners[i].reset(); planners[i].plan()`` leaves.  Each run
+    draws through its own planner's ``draw_round`` (sampling bounds and goal bias are per maze), with its own random streams,
+    its planner's ``time_budget`` and ``max_candidates``, and is rolled out against its planner's ``env.goal``.  Runs queue
+    planner by planner; at most ``concurrent`` are in flight (default: all), and a finished tree takes the next queued run,
+    whatever its scenario.  ``tree_capacity``: node slots per run (default: the largest max_candidates + 1, at most the
+    planners' ``capacity``).  The caller's ``random`` / ``np.random`` / torch generator states are left as they were; the
+    summed collision-check count is added to ``common.map_utils.cc_calls`` once.  All planners must share one ctx and one
+    sampler object and agree on the round settings (ValueError names the first difference); the scope is ``plan_runs``'."""
+    from ..forest import SceneForestEngine
+    from ._runs import RunStreams, caller_states_kept
+    planners = list(planners)
+    if not planners:
+        return []
+    if len(seeds) != len(planners):
+        raise ValueError(f"seeds: one list per planner ({len(planners)}), got {len(seeds)}")
+    _check_scene_planners(planners)
+    seeds = [[int(s) for s in ss] for ss in seeds]
+    jobs = [(i, k) for i, ss in enumerate(seeds) for k in range(len(ss))]
+    results = [[None] * len(ss) for ss in seeds]
+    if not jobs:
+        return results
+    p0 = planners[0]
+    ctx, sampler, batch = p0.ctx, p0.sampler, p0.batch
+    T = len(jobs) if concurrent is None else max(1, min(int(concurrent), len(jobs)))
+    if tree_capacity is None:
+        caps = [pl.capacity if pl.max_candidates is None else min(pl.capacity, int(pl.max_candidates) + 1) for pl in planners]
+        tree_capacity = max(caps)
+    dev = ctx.device
+    network = hasattr(sampler, "ensure_bound")
+    for pl in planners:
+        pl.reset()                                           # env.reset(options) as before every sequential plan()
+    scenes = [(pl.maze, pl.start_node.state, pl.goal_state, np.asarray(pl.env.goal, dtype=np.float64)) for pl in planners]
+    e = p0._engine
+    eng = SceneForestEngine(ctx, scenes, T, int(tree_capacity), action_horizon=e.A, pred_horizon=e.P, local_map_size=e.lm_n,
+                            local_map_scale=e.lm_scale, s_global=e.s_global, batch=T * batch, k_steps=e.k_steps,
+                            emulate_sticky_done=bool(e.sticky), norm=e.norm, early_exit=bool(e.early_exit),
+                            goal_scale=e.goal_scale, prop_duration=e.schedule)
+    eng.ddpm = e.ddpm
+    if network:
+        sampler.ensure_bound(T * batch)
+    shape = (eng.n_chunks, eng.P, eng.ACTION_DIM)
+    K = len(eng.ddpm[0]) if (network and eng.ddpm is not None) else 0
+    queue = jobs[::-1]
+    slots = [None] * T                                       # per tree: [(planner, seed index), RunStreams, drawn, start time]
+    steps_dev = torch.zeros(T, dtype=torch.int64, device=dev)
+    total_cc = 0
+
+    def start(t):
+        slots[t] = None
+        if queue:
+            i, k = queue.pop()
+            eng.reset_tree(t, i)
+            steps_dev[t] = 0
+            slots[t] = [(i, k), RunStreams(seeds[i][k], dev), 0, time.time()]
+
+    def finish(t, goal):
+        nonlocal total_cc
+        (i, k), _, _, t0 = slots[t]
+        row = eng.counters(t)
+        node = goal if goal is not None else eng.fallback_node(t)          # RRT.py:227-254, against the scene's own goal
+        elapsed = time.time() - t0
+        path = actions = None
+        if node is not None:
+            path, actions = eng.path_to(t, node)
+        cc = int(steps_dev[t].item())
+        total_cc += cc
+        results[i][k] = {"seed": seeds[i][k], "success": path is not None, "goal_reached": goal is not None,
+                         "iterations": int(row[CNT_ITERS]), "time": elapsed, "path": path, "actions": actions,
+                         "number_of_nodes": int(eng.n_nodes_host[t]),
+                         "path_time": None if path is None else len(path) * planners[i].env_dt, "cc_calls": cc}
+        start(t)
+
+    with caller_states_kept():
+        for t in range(T):
+            start(t)
+        while True:
+            sizes = [0] * T
+            for t in range(T):
+                while slots[t] is not None:
+                    (i, _), _, drawn, t0 = slots[t]
+                    pl = planners[i]
+                    if (time.time() - t0) < pl.time_budget and (pl.max_candidates is None or drawn < pl.max_candidates):
+                        sizes[t] = batch if pl.max_candidates is None else min(batch, pl.max_candidates - drawn)
+                        break
+                    finish(t, None)
+            if not any(sizes):
+                break
+            active = [t for t in range(T) if sizes[t] > 0]
+            drawn_sc = []
+            for t in active:                                 # each run on its own streams, through its own planner
+                with slots[t][1].active():
+                    drawn_sc.append(planners[slots[t][0][0]].draw_round(int(sizes[t])))
+            s = torch.as_tensor(np.concatenate([d[0] for d in drawn_sc]), device=dev)
+            c = torch.as_tensor(np.concatenate([d[1] for d in drawn_sc]), device=dev)
+            B = int(sum(sizes))
+            noise = acts = step_noise = None
+            if network:
+                noise = torch.empty((B, *shape), dtype=torch.float32, device=dev)
+                if K:
+                    step_noise = torch.empty((B, eng.n_chunks, K, eng.P, eng.ACTION_DIM), dtype=torch.float32, device=dev)
+                lo = 0
+                for t in active:
+                    g = slots[t][1].gen
+                    noise[lo:lo + sizes[t]].normal_(generator=g)
+                    if K:
+                        step_noise[lo:lo + sizes[t]].normal_(generator=g)
+                    lo += sizes[t]
+            else:
+                acts = torch.cat([planners[slots[t][0][0]]._host_actions(slots[t][2], sizes[t]) for t in active])
+            cnt = eng.expand_round(s, c, noise=noise, inject_actions=acts, counts_per_tree=sizes, step_noise=step_noise)
+            tree_of = torch.as_tensor(np.repeat(np.arange(T), sizes), device=dev)
+            steps_dev.index_add_(0, tree_of, eng.rb.chunk_steps[:B].sum(dim=1, dtype=torch.int64))
+            for t in active:
+                slots[t][2] += sizes[t]
+                if int(cnt[t, CNT_GOAL]) >= 0:
+                    finish(t, eng.goal_node(t))
+    from ..common import map_utils as _mu
+    _mu.add_cc_calls(total_cc)                   # the counter the drivers read (run_scenarios.py:338,343), once
+    return results

@@ -575,6 +575,31 @@ int32_t ditree_forest_nn_argmin(ditree_ctx* ctx, const ditree_tree* tree, const 
 int32_t ditree_forest_fallback(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const double* goal_xy,
                                int32_t* out_node, void* stream);
 
+/* ------------------------------------------------------------------ scene forests: trees of different scenarios in one round
+ * A scene table holds n scenes (maze, goal) of a scenario set (run_scenarios.py:203-250: one maze, start and goal per row of
+ * the scenario file).  The mazes are stored once each, as u8 cell codes (ditree_upload_maze's rule) in one atlas that the
+ * rollout stages into LDS whole; identical maps (same dims, same codes) share their atlas bytes.  The table lives next to the
+ * single maze of ditree_upload_maze and does not replace it.  A scene forest is a ditree_forest plus a scene id per tree; every
+ * row of a round uses its tree's maze (local map, collision tests) and goal (goal test). */
+#define DITREE_MAX_SCENES 64
+#define DITREE_MAX_ATLAS_CELLS 16384
+/* mazes [host] f32: the n row-major maps concatenated (scene i: rows[i] x cols[i]); rows, cols [host] (n,); goal_xy [host] (n, 2):
+ * each scene's env.goal.  1 <= n <= DITREE_MAX_SCENES, every rows / cols >= 1, sum of rows * cols <= DITREE_MAX_ATLAS_CELLS. */
+int32_t ditree_upload_scenes(ditree_ctx* ctx, int32_t n, const float* mazes, const int32_t* rows, const int32_t* cols,
+                             const double* goal_xy, void* stream);
+typedef struct {
+  const int32_t* tree_scene;        /* [dev] (T,) the scene of every tree */
+  const int32_t* tree_scene_host;   /* [host] (T,) the same ids: each in [0, n uploaded), validated before anything is launched */
+} ditree_forest_scenes;
+/* ditree_forest_expand_round with each tree's own scene: p->goal_xy is not read, and no single maze is needed.  DITREE_E_STATE
+ * without an uploaded scene table.  Each candidate's arithmetic is the single-maze round's on its scene's bytes, dims and goal. */
+int32_t ditree_forest_expand_round_scenes(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
+                                          const ditree_forest_scenes* scenes, const ditree_round* round,
+                                          const ditree_round_params* p, void* stream);
+/* ditree_forest_fallback with one goal per tree: goal_xy [host] (T, 2). */
+int32_t ditree_forest_fallback_goals(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const double* goal_xy,
+                                     int32_t* out_node, void* stream);
+
 /* One expansion round of the ANT (BASELINE config 3; cfgs/antmaze.yaml + run_scenarios.py:123-132: action_horizon 2, edge
  * length 48 = 24 chunks, pred_horizon 16, obs_history 3, local map 16 x 16 @ 0.8, s_global 4) against a tree with state_dim
  * 29, action_dim 8 and `hist`: planners/RRT.py:131-194 batched --
