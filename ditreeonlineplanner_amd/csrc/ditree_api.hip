@@ -1117,8 +1117,7 @@ int32_t ditree_forest_fallback(ditree_ctx* ctx, const ditree_tree* tree, const d
   std::vector<double> q((size_t)T * 2);
   for (int t = 0; t < T; ++t) { q[(size_t)t * 2] = goal_xy[0]; q[(size_t)t * 2 + 1] = goal_xy[1]; }
   HIP_TRY(ctx, hipMemcpyAsync(ctx->cur_state, q.data(), q.size() * sizeof(double), hipMemcpyHostToDevice, s));
-  launch_nn_forest(ctx->cur_state, 2, T, tree->xy, nullptr, T, forest->counters, forest->tree_capacity, 1, out_node, nullptr, nullptr,
-                   nullptr, nullptr, nullptr, nullptr, s);
+  launch_forest_fallback(ctx->cur_state, T, tree->xy, forest->counters, forest->tree_capacity, out_node, s);
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipStreamSynchronize(s));               // `q` is a temporary
   return DITREE_OK;
@@ -1216,8 +1215,7 @@ int32_t ditree_forest_fallback_goals(ditree_ctx* ctx, const ditree_tree* tree, c
   rc = ensure_scratch(ctx, T, 1, 1);                   // the T goals as the queries (ctx->cur_state, (T, 6))
   if (rc) return rc;
   HIP_TRY(ctx, hipMemcpyAsync(ctx->cur_state, goal_xy, (size_t)T * 2 * sizeof(double), hipMemcpyHostToDevice, s));
-  launch_nn_forest(ctx->cur_state, 2, T, tree->xy, nullptr, T, forest->counters, forest->tree_capacity, 1, out_node, nullptr, nullptr,
-                   nullptr, nullptr, nullptr, nullptr, s);
+  launch_forest_fallback(ctx->cur_state, T, tree->xy, forest->counters, forest->tree_capacity, out_node, s);
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipStreamSynchronize(s));               // goal_xy is the caller's host memory
   return DITREE_OK;

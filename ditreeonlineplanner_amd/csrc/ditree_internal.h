@@ -117,6 +117,8 @@ void launch_nn_forest(const double* queries, int q_stride, int B, const double* 
                       const int32_t* counters, int C, int skip, int32_t* out_idx, const double* node_state,
                       const double* node_last_action, const uint8_t* node_has_prev, double* out_state, double* out_prev_action,
                       uint8_t* out_has_prev, hipStream_t s, int S = 6, int D = 2);
+void launch_forest_fallback(const double* goals, int T, const double* node_xy, const int32_t* counters, int C, int32_t* out_idx,
+                            hipStream_t s);
 void launch_local_map_scenes(const SceneArg& sc, const double* state, const int32_t* active, const int32_t* idx, int B, int n,
                              const AxisArg& axis, double s_global, float* out, hipStream_t s);
 void launch_row_scene(const int32_t* off, int T, const int32_t* tree_scene, int B, int32_t* row_scene, hipStream_t s);

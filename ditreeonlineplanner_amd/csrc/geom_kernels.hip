@@ -120,6 +120,12 @@ void launch_nn_argmin(const double* queries, int q_stride, int B, const double* 
 // candidate per run they always do), so every wave takes one query; the scan keeps nn_argmin_kernel's eight independent node
 // loads per trip, strict '<' per lane and the (distance, index) reduction, so the result is nn_argmin_kernel's on the segment
 // alone (an all-NaN scan clamps to the segment's first slot).  A segment with no node gives -1 and gathers nothing.
+// NORM: the key of the fallback choice (planners/RRT.py:233-237, np.argmin of np.linalg.norm(state[:2] - goal)) instead of the
+// squared distance: sqrt(fma(dy, dy, dx*dx)) as fallback_select_kernel and oracle/rrt.py::fallback_node compute it.  sqrt merges
+// neighbouring doubles, so two nodes whose squares differ in the last place can have equal norms; the reference then returns
+// the lower index, which the square's strict '<' would not.  The expansion search (NORM = false) keeps the squared distance:
+// it is pinned bit for bit to the KDTree goldens, and its instantiation is the kernel as it was before the flag.
+template <bool NORM>
 __global__ void __launch_bounds__(256)
 nn_forest_kernel(const double* __restrict__ queries, int q_stride, int B, const double2* __restrict__ node_xy,
                  const int32_t* __restrict__ off, int T, const int32_t* __restrict__ counters, int C, int skip,
@@ -154,7 +160,9 @@ nn_forest_kernel(const double* __restrict__ queries, int q_stride, int B, const 
       const int iu = i + u * WAVE;
       if (iu < n) {
         double dx = qx - p[u].x, dy = qy - p[u].y;
-        double d = dx * dx + dy * dy;
+        double d;
+        if constexpr (NORM) d = sqrt(fma(dy, dy, dx * dx));
+        else d = dx * dx + dy * dy;
         if (d < best) { best = d; bidx = iu; }
       }
     }
@@ -182,9 +190,16 @@ void launch_nn_forest(const double* queries, int q_stride, int B, const double* 
                       const int32_t* counters, int C, int skip, int32_t* out_idx, const double* node_state,
                       const double* node_last_action, const uint8_t* node_has_prev, double* out_state, double* out_prev_action,
                       uint8_t* out_has_prev, hipStream_t s, int S, int D) {
-  hipLaunchKernelGGL(nn_forest_kernel, dim3((B + 3) / 4), dim3(256), 0, s, queries, q_stride, B, (const double2*)node_xy, off, T,
-                     counters, C, skip, out_idx, node_state, node_last_action, node_has_prev, out_state, out_prev_action,
+  hipLaunchKernelGGL(nn_forest_kernel<false>, dim3((B + 3) / 4), dim3(256), 0, s, queries, q_stride, B, (const double2*)node_xy,
+                     off, T, counters, C, skip, out_idx, node_state, node_last_action, node_has_prev, out_state, out_prev_action,
                      out_has_prev, S, D);
+}
+// The fallback choice of every tree (planners/RRT.py:233-237): query t is tree t's goal, the scan covers its nodes 1.. with the
+// norm as the key.
+void launch_forest_fallback(const double* goals, int T, const double* node_xy, const int32_t* counters, int C, int32_t* out_idx,
+                            hipStream_t s) {
+  hipLaunchKernelGGL(nn_forest_kernel<true>, dim3((T + 3) / 4), dim3(256), 0, s, goals, 2, T, (const double2*)node_xy, nullptr, T,
+                     counters, C, 1, out_idx, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 6, 2);
 }
 
 // ------------------------------------------------------------------------- local map

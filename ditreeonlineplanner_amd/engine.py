@@ -449,28 +449,26 @@ class ExpansionEngine:
         return None if g < 0 else g
 
     def fallback_node(self):
-        """planners/RRT.py:227-254.  run_type 0: among nodes 1.., the one nearest to goal_state xy (arg-min
-        reduction on the device: the nearest-node kernel with the goal as the single query).  run_type > 0:
+        """planners/RRT.py:227-254.  run_type 0: among nodes 1.., the first one with the smallest
+        np.linalg.norm(xy - goal_state xy) (ditree_fallback_select without obstacle flags: the norm, not the nearest-node
+        kernel's squared distance -- two squares that differ in the last place can have equal norms, and np.argmin then
+        returns the lower index).  run_type > 0:
         None when every node has an obstacle ahead; else nearest to the goal with +1e4 on flagged nodes, or --
         with a reference path -- the unflagged node whose nearest path point lies furthest along it."""
         n = self.tree.n_nodes_host
         if n < 2:
             return None
-        if self.run_type > 0:
-            out = torch.empty(1, dtype=torch.int32, device=self.tree.xy.device)
-            g, gp = _dbl(self.goal_state[:2])
-            if self.init_main_path is not None:
-                pa, pp = _dbl(np.asarray(self.init_main_path)[:, :2])
-                P = pa.shape[0]
-            else:
-                pa, pp, P = None, None, 0
-            check(self.ctx._h, lib().ditree_fallback_select(self.ctx._h, C.byref(self.tree.desc), n, gp, pp, P,
-                                                             out.data_ptr(), self.ctx.stream), "fallback_select")
-            node = int(out.item())
-            return None if node < 0 else node
-        q = torch.as_tensor(self.goal_state[:2].reshape(1, 2).copy(), device=self.tree.xy.device)
-        idx = self.ctx.nn_argmin(q, self.tree.xy[1:n].contiguous(), n_nodes=n - 1)
-        return 1 + int(idx[0].item())
+        out = torch.empty(1, dtype=torch.int32, device=self.tree.xy.device)
+        g, gp = _dbl(self.goal_state[:2])
+        if self.run_type > 0 and self.init_main_path is not None:
+            pa, pp = _dbl(np.asarray(self.init_main_path)[:, :2])
+            P = pa.shape[0]
+        else:
+            pa, pp, P = None, None, 0
+        check(self.ctx._h, lib().ditree_fallback_select(self.ctx._h, C.byref(self.tree.desc), n, gp, pp, P,
+                                                         out.data_ptr(), self.ctx.stream), "fallback_select")
+        node = int(out.item())
+        return None if node < 0 else node
 
     def path_to(self, node):
         """planners/base_planner.py:342-363: float32 path (edge states + node states) and actions."""

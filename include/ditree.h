@@ -571,7 +571,10 @@ int32_t ditree_forest_chunk_budget(ditree_ctx* ctx, const ditree_tree* tree, con
 int32_t ditree_forest_nn_argmin(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const double* queries,
                                 int32_t q_stride, int32_t B, int32_t* out_idx, void* stream);
 /* The run_type-0 fallback of every tree (planners/RRT.py:227-254): among nodes t * C + 1 .. t * C + n_t - 1 the one nearest to
- * goal_xy [host 2] -> out_node [dev] (T,) global ids, -1 for a tree that holds only its root.  forest->off is not read. */
+ * goal_xy [host 2] -> out_node [dev] (T,) global ids, -1 for a tree that holds only its root.  forest->off is not read.
+ * The key is the reference's, np.linalg.norm(state[:2] - goal) = sqrt(fma(dy, dy, dx*dx)) as ditree_fallback_select computes it,
+ * first occurrence on ties -- not the squared distance of ditree_forest_nn_argmin: two nodes whose squares differ in the last
+ * place can have equal norms, and the reference then returns the lower index. */
 int32_t ditree_forest_fallback(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const double* goal_xy,
                                int32_t* out_node, void* stream);
 
