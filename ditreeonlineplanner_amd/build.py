@@ -32,6 +32,7 @@ UNITS = [
     ("mppi_ant_kernels.hip", ["-ffp-contract=off"]),
     ("ditree_api.hip", []),
     ("denoise_kernels.hip", []),
+    ("encoder_kernels.hip", []),
     ("denoise_host.hip", []),
 ]
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",

@@ -67,6 +67,7 @@ struct ConvGemmParams {
 };
 
 void denoise_set_dry_run(bool on);   // launchers check their contracts but enqueue nothing (plan validation at reserve time)
+bool denoise_dry_run();
 void launch_conv_gemm(const ConvGemmParams& p, int fmt, hipStream_t s);
 bool conv2d_small_eligible(int fmt);                    // implicit Conv2d layers run on the 64 x 64-tile kernel
 int conv_gemm_kind(const ConvGemmParams& p, int fmt);   // 0 halo kernel, 1 gemm16 / generic, 2 implicit Conv2d
@@ -113,3 +114,23 @@ void launch_avgpool2d(const void* in, void* out, int B, int HW, int C, int fmt, 
                       hipStream_t s);
 void launch_unpack_act(const void* in, int ld, int coff, int Lp, int roff, float* out, int B, int L, int C, int fmt,
                        long long plane, hipStream_t s);
+
+// The reference's small local-map encoders (encoder_kernels.hip), f32 in every DITREE_PREC_*: one launch writes
+// out[b, 0:E] (row stride E) for B maps of n x n.  Parameter pointers by kind:
+//   identity, max   none (max: k x k cells, E = k * k)
+//   mlp             w[0..2] = fc1..fc3 weights TRANSPOSED to [in][out], b[0..2] the biases; E = fc3's outputs
+//   grid            w[0..2], b[0..2] = conv1..conv3 as stored ([Cout][Cin][3][3]); E = 144
+//   cnn             w[0..3], b[0..3] = conv1..conv4 as stored; E = 4 (n - 8)^2
+// A size the kernels do not cover throws std::runtime_error (also in dry-run mode: it surfaces at reserve time).
+enum { ENC_RESNET = 0, ENC_IDENTITY = 1, ENC_MLP = 2, ENC_MAX = 3, ENC_GRID = 4, ENC_CNN = 5 };
+struct SmallEncoderParams {
+  int kind;
+  const float* lm;
+  float* out;
+  int B, n, E, k;
+  const float* w[4];
+  const float* b[4];
+};
+const char* small_encoder_name(int kind);
+int small_encoder_width(int kind, int n, int k);   // embedding width of a kind (0: none)
+void launch_small_encoder(const SmallEncoderParams& p, hipStream_t s);

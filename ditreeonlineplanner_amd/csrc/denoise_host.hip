@@ -64,6 +64,9 @@ struct DenoiserState {
   std::map<std::string, HostParam> params;
   // architecture (derived from the parameter shapes)
   int D = 2, P = 64, E = 400, G = 7, cond_dim = 663, lm = 20;
+  int enc_kind = ENC_RESNET;   // "#encoder <name> <E>" of the manifest (none: resnet)
+  int enc_E = -1;              // the width that line declares (-1: none)
+  int enc_k = 0;               // max: cells per side
   int dims[3] = {512, 1024, 2048};
   bool loaded = false;
   // DDPM loop of the NEXT denoise call (set by denoise_run_ddpm around denoise_core): coef (K, 5) = sb, sa, c0, c1, sigma per step
@@ -554,7 +557,7 @@ void DenoiserState::build(int prec_, int Bmax_) {
   // the FiLM GEMM runs on whole 256-row tiles: rows padded (zero rows in, ignored rows out)
   const int Brows = (Bmax + 255) / 256 * 256;
   // split encoder: its fc layer runs on the gemm16 tiles too (rows and columns padded to 256)
-  E_ld = fmt_split(efmt) ? (E + 255) / 256 * 256 : E;
+  E_ld = (enc_kind == ENC_RESNET && fmt_split(efmt)) ? (E + 255) / 256 * 256 : E;      // the small encoders write E columns, no fc tile
   map_emb = (float*)dalloc((size_t)Brows * E_ld * 4);
   cond_plane = planes() == 2 ? (long long)Brows * condK * es() : 0;
   condA = dalloc((size_t)Brows * condK * es() * planes());
@@ -697,17 +700,67 @@ void DenoiserState::build(int prec_, int Bmax_) {
   vec("unet.diffusion_step_encoder.3.weight");
   vec("unet.diffusion_step_encoder.3.bias");
 
-  // ---------------- encoder: ResNet-18 with GroupNorm(C/16), NHWC, im2col + GEMM + GN kernels ------------
-  // Every op works on a sub-batch [b0, b0 + Bn) with its own im2col / GEMM-output scratch region, so that
-  // several sub-batches can run concurrently on different streams (the layers are small: 8..100 tiles
-  // each, far fewer than the 256 CUs).
-  {
+  // ---------------- encoder ---------------------------------------------------------------------------
+  // Every op works on a sub-batch [b0, b0 + Bn) (ResNet: with its own im2col / GEMM-output scratch region), so that
+  // several sub-batches can run concurrently on different streams.
+  sub_cap = ((Bmax + ENC_SUBS - 1) / ENC_SUBS + 15) / 16 * 16;
+  if (enc_kind != ENC_RESNET) {
+    // one of the five small encoders: a single f32 launch (encoder_kernels.hip), whatever the precision
+    SmallEncoderParams q{};
+    q.kind = enc_kind; q.n = lm; q.E = E; q.k = enc_k;
+    auto transposed = [&](const std::string& name, int out_f, int in_f) {       // Linear weight (out, in) -> [in][out]
+      const HostParam& w = P_(name);
+      if (w.dims.size() != 2 || w.dims[0] != out_f || w.dims[1] != in_f)
+        throw std::runtime_error(name + " must be (" + std::to_string(out_f) + ", " + std::to_string(in_f) + ")");
+      std::vector<float> t((size_t)out_f * in_f);
+      for (int o = 0; o < out_f; ++o)
+        for (int i = 0; i < in_f; ++i) t[(size_t)i * out_f + o] = w.data[(size_t)o * in_f + i];
+      return upload_f32(name + "#t", t.data(), (int64_t)t.size());
+    };
+    auto conv_w = [&](const std::string& name, int co, int ci) {
+      const HostParam& w = P_(name + ".weight");
+      const HostParam& b = P_(name + ".bias");
+      if (w.dims.size() != 4 || w.dims[0] != co || w.dims[1] != ci || w.dims[2] != 3 || w.dims[3] != 3 || b.n != co)
+        throw std::runtime_error(name + " must be a Conv2d(" + std::to_string(ci) + ", " + std::to_string(co) + ", 3)");
+    };
+    if (enc_kind == ENC_MLP) {
+      const int in_f = lm * lm;
+      q.w[0] = transposed("encoder.fc1.weight", 128, in_f);
+      q.w[1] = transposed("encoder.fc2.weight", 256, 128);
+      q.w[2] = transposed("encoder.fc3.weight", E, 256);
+      const int outs[3] = {128, 256, E};
+      for (int l = 0; l < 3; ++l) {
+        const std::string bn = "encoder.fc" + std::to_string(l + 1) + ".bias";
+        if (P_(bn).n != outs[l]) throw std::runtime_error(bn + " must have " + std::to_string(outs[l]) + " elements");
+        q.b[l] = vec(bn);
+      }
+    } else if (enc_kind == ENC_GRID || enc_kind == ENC_CNN) {
+      const bool g = enc_kind == ENC_GRID;
+      const int nl = g ? 3 : 4;
+      const int ci[4] = {1, g ? 3 : 2, g ? 6 : 4, 4}, co[4] = {g ? 3 : 2, g ? 6 : 4, 4, 4};
+      for (int l = 0; l < nl; ++l) {
+        const std::string nm = "encoder.conv" + std::to_string(l + 1);
+        conv_w(nm, co[l], ci[l]);
+        q.w[l] = vec(nm + ".weight");
+        q.b[l] = vec(nm + ".bias");
+      }
+    }
+    const float** lm_slot = &lm_ptr;
+    float* op = map_emb;
+    const int LM = lm * lm, Ew = E;
+    enc_ops.push_back([=, this](int b0, int Bn, int, hipStream_t s) {
+      note_other();
+      SmallEncoderParams r = q;
+      r.lm = *lm_slot + (size_t)b0 * LM; r.out = op + (size_t)b0 * Ew; r.B = Bn;
+      launch_small_encoder(r, s);
+    });
+  } else {
+    // ResNet-18 with GroupNorm(C/16), NHWC, im2col + GEMM + GN kernels (the layers are small: 8..100 tiles each, far fewer
+    // than the 256 CUs)
     const std::string R = "encoder.resnet18.";
     const int pr = efmt;
     const size_t E_ = ees();
     zero_row = dalloc(256);
-    sub_cap = (Bmax + ENC_SUBS - 1) / ENC_SUBS;
-    sub_cap = (sub_cap + 15) / 16 * 16;
     const size_t col_per_sample = 25 * 576;                         // largest im2col footprint per sample (layer1)
     const size_t gout_per_sample = 9216;                            // f32 GEMM output per sample: stem 100*64, or up to 8 split-K slabs of 9*128
     col_region = (size_t)sub_cap * col_per_sample;
@@ -996,6 +1049,18 @@ static int parse_manifest(DenoiserState* st, const char* manifest, int64_t n_flo
       }
       continue;
     }
+    if (line.rfind("#encoder", 0) == 0) {         // "#encoder cnn 576": the local-map encoder and its embedding width
+      std::istringstream cs(line.substr(8));
+      std::string kind;
+      if (!(cs >> kind)) return -1;
+      st->enc_kind = -1;
+      for (int k = ENC_RESNET; k <= ENC_CNN; ++k)
+        if (kind == small_encoder_name(k)) st->enc_kind = k;
+      if (st->enc_kind < 0) return -3;
+      int e;
+      if (cs >> e) st->enc_E = e;
+      continue;
+    }
     if (line.rfind("#checksum", 0) == 0) {        // "#checksum <s1 hex> <s2 hex>": Fletcher-style sums over the blob's 32-bit words
       std::istringstream cs(line.substr(9));
       std::string a, b;
@@ -1223,6 +1288,7 @@ int32_t ditree_load_weights(ditree_ctx* ctx, const float* blob, int64_t n_floats
     st->blob.assign(blob, blob + n_floats);
     const int prc = parse_manifest(st, manifest, n_floats);
     if (prc == -2) throw std::runtime_error("weight blob does not match the manifest checksum");
+    if (prc == -3) throw std::runtime_error("unknown encoder in the manifest (identity, mlp, max, grid, cnn or resnet)");
     if (prc != 0) throw std::runtime_error("malformed manifest");
     const HostParam& w0 = st->P_("unet.down_modules.0.0.blocks.0.block.0.weight");
     st->D = (int)w0.dims[1];
@@ -1230,10 +1296,31 @@ int32_t ditree_load_weights(ditree_ctx* ctx, const float* blob, int64_t n_floats
       st->dims[i] = (int)st->P_("unet.down_modules." + std::to_string(i) + ".0.blocks.0.block.0.weight").dims[0];
     if (st->has("unet.down_modules.3.0.blocks.0.block.0.weight")) throw std::runtime_error("only 3 U-Net levels supported");
     st->cond_dim = (int)st->P_("unet.down_modules.0.0.cond_encoder.1.weight").dims[1];
-    st->E = (int)st->P_("encoder.resnet18.fc.weight").dims[0];
-    st->G = st->cond_dim - 256 - st->E;
-    if (st->G < 0 || (st->D != 2 && st->D != 8)) throw std::runtime_error("unsupported dimensions (action_dim 2 or 8)");
     if (st->lm != 20 && st->lm != 16) throw std::runtime_error("local_map_size must be 20 (car) or 16 (ant)");
+    if (st->enc_kind == ENC_RESNET) {
+      st->E = (int)st->P_("encoder.resnet18.fc.weight").dims[0];
+      if (st->enc_E >= 0 && st->enc_E != st->E) throw std::runtime_error("the manifest's encoder width differs from encoder.resnet18.fc");
+    } else {
+      // the width follows from the kind and the map size; 'max' pools to k x k cells and takes k from the declared width
+      const std::string kn = small_encoder_name(st->enc_kind);
+      if (st->enc_E < 1) throw std::runtime_error("the manifest's #encoder line must carry the embedding width");
+      st->enc_k = 0;
+      if (st->enc_kind == ENC_MAX) {
+        int k = 1;
+        while ((k + 1) * (k + 1) <= st->enc_E) ++k;
+        if (k * k != st->enc_E) throw std::runtime_error("encoder 'max': the embedding width must be a perfect square, got " + std::to_string(st->enc_E));
+        st->enc_k = k;
+      }
+      st->E = small_encoder_width(st->enc_kind, st->lm, st->enc_k);
+      if (st->E != st->enc_E)
+        throw std::runtime_error("encoder '" + kn + "' produces " + std::to_string(st->E) + " columns at local_map_size " +
+                                 std::to_string(st->lm) + ", the manifest declares " + std::to_string(st->enc_E));
+    }
+    st->G = st->cond_dim - 256 - st->E;
+    if (st->G < 0 && st->enc_kind != ENC_RESNET)
+      throw std::runtime_error("the U-Net's cond_dim " + std::to_string(st->cond_dim) + " is narrower than 256 + the encoder's " +
+                               std::to_string(st->E) + " columns");
+    if (st->G < 0 || (st->D != 2 && st->D != 8)) throw std::runtime_error("unsupported dimensions (action_dim 2 or 8)");
     if (st->P_("unet.diffusion_step_encoder.1.weight").dims[1] != 256) throw std::runtime_error("diffusion_step_embed_dim must be 256");
     for (int i = 0; i < 3; ++i)
       if (st->dims[i] % 64 != 0 || st->dims[i] > 4096) throw std::runtime_error("down_dims must be multiples of 64, <= 4096");

@@ -34,6 +34,7 @@
 // dry-run flag is set -- an unsupported layer shape fails at reserve time, and the validation leaves no launches in a profile.
 static thread_local bool g_dn_dry_run = false;
 void denoise_set_dry_run(bool on) { g_dn_dry_run = on; }
+bool denoise_dry_run() { return g_dn_dry_run; }
 #define DN_LAUNCH(...) do { if (!g_dn_dry_run) hipLaunchKernelGGL(__VA_ARGS__); } while (0)
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;

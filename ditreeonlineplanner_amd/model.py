@@ -2,9 +2,9 @@
 
 ``NoisePredNet`` stands where the reference's ``ConditionalUnet1DWithLocalMap``
 (local_map_encoder.py:78-109) stands: an ``nn.Module`` whose ``state_dict()`` keys are
-``encoder.resnet18.*`` / ``unet.*``, so ``load_state_dict(ckpt['noise_pred_net_state_dict'])``
+``encoder.*`` (the reference's for the chosen local-map encoder) / ``unet.*``, so ``load_state_dict(ckpt['noise_pred_net_state_dict'])``
 works unchanged, and whose ``forward(sample, local_map, timestep, global_cond)`` runs the
-HIP engine (MFMA implicit-GEMM kernels) instead of torch.nn layers.
+HIP engine (MFMA implicit-GEMM kernels; f32 kernels for the five small encoders) instead of torch.nn layers.
 """
 from __future__ import annotations
 
@@ -15,7 +15,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .weights import noise_pred_net_param_shapes, pack_state_dict
+from .weights import encoder_embedding_dim, noise_pred_net_param_shapes, pack_state_dict
 
 
 class _Node(nn.Module):
@@ -34,18 +34,29 @@ def _attach(root: nn.Module, dotted: str, param: nn.Parameter):
 
 class NoisePredNet(nn.Module):
     def __init__(self, input_dim=2, embedding_dim=400, additional_global_cond_dim=7,
-                 down_dims=(512, 1024, 2048), pred_horizon=64, local_map_size=20, seed=None, init=True):
-        """``init=False``: parameters are allocated but not initialised -- for a net that is filled by ``load_state_dict`` right
+                 down_dims=(512, 1024, 2048), pred_horizon=64, local_map_size=20, seed=None, init=True, encoder="resnet"):
+        """``encoder``: one of the reference's six local-map encoders (``weights.ENCODERS``); ``embedding_dim`` must be the width
+        that encoder produces (``weights.encoder_embedding_dim``), else ``ValueError``.  ``init=False``: parameters are allocated but not initialised -- for a net that is filled by ``load_state_dict`` right
         away (initialising 184 M parameters takes longer than loading them)."""
         super().__init__()
+        self.encoder_name = encoder
+        embedding_dim = encoder_embedding_dim(encoder, local_map_size, embedding_dim)
         self.input_dim, self.embedding_dim = input_dim, embedding_dim
         self.down_dims = tuple(int(d) for d in down_dims)
         self.global_cond_dim = additional_global_cond_dim
         self.pred_horizon, self.local_map_size = pred_horizon, local_map_size
         gen = torch.Generator().manual_seed(0 if seed is None else seed)
-        for name, shape in noise_pred_net_param_shapes(input_dim, embedding_dim, additional_global_cond_dim,
-                                                        down_dims).items():
-            value = self._init(name, shape, gen) if init else torch.empty(shape)
+        shapes = noise_pred_net_param_shapes(input_dim, embedding_dim, additional_global_cond_dim, down_dims,
+                                             encoder=encoder, local_map_size=local_map_size)
+        for name, shape in shapes.items():
+            if not init:
+                value = torch.empty(shape)
+            elif name.startswith("encoder.") and encoder != "resnet":
+                # torch's defaults for Linear / Conv2d: weight and bias uniform in +-1 / sqrt(fan_in)
+                fan_in = int(np.prod(shapes[name.rsplit(".", 1)[0] + ".weight"][1:]))
+                value = (torch.rand(shape, generator=gen) * 2 - 1) / math.sqrt(fan_in)
+            else:
+                value = self._init(name, shape, gen)
             _attach(self, name, nn.Parameter(value, requires_grad=False))
         self._ctx = None
         self.precision = _lib.PREC_BF16
@@ -77,7 +88,8 @@ class NoisePredNet(nn.Module):
         # in-memory hand-over: no checksum line (it guards blobs that were stored or shipped -- weights.pack_state_dict's
         # default -- and costs seconds on 0.7 GB in numpy)
         blob, manifest = pack_state_dict(self.state_dict(), pred_horizon=self.pred_horizon,
-                                         local_map_size=self.local_map_size, checksum=False)
+                                         local_map_size=self.local_map_size, checksum=False,
+                                         encoder=self.encoder_name, embedding_dim=self.embedding_dim)
         ctx.load_weights(blob, manifest)
         ctx.weights_owner = self
         self._ctx = ctx

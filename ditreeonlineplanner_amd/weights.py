@@ -2,10 +2,11 @@
 
 The reference stores weights as ``torch.save({'noise_pred_net_state_dict': ...})``
 (train_diffusion_policy.py:468-476) and loads them with ``load_state_dict``
-(run_scenarios.py:175-177); key prefixes ``encoder.resnet18.*`` and ``unet.*``.
+(run_scenarios.py:175-177); key prefixes ``encoder.*`` (``encoder.resnet18.*``, ``encoder.fc1.*``, ``encoder.conv1.*`` ... by encoder) and ``unet.*``.
 """
 from __future__ import annotations
 
+import math
 from collections import OrderedDict
 
 import numpy as np
@@ -87,11 +88,75 @@ def resnet18_gn_param_shapes(embedding_dim=400):
     return sh
 
 
-def noise_pred_net_param_shapes(input_dim=2, embedding_dim=400, additional_global_cond_dim=7,
-                                down_dims=(512, 1024, 2048)):
+ENCODERS = ("identity", "mlp", "max", "grid", "cnn", "resnet")        # local_map_encoder.py:82-97
+
+
+def encoder_embedding_dim(encoder, local_map_size, embedding_dim):
+    """Width of the embedding the encoder really produces (local_map_encoder.py:137-218).  The U-Net is built for
+    ``embedding_dim`` columns, so a value the encoder cannot produce is a ``ValueError`` here -- the reference fails with a
+    shape error in its first forward."""
+    n = int(local_map_size)
+    if encoder not in ENCODERS:
+        raise ValueError(f"Unknown encoder: {encoder}")
+    if encoder == "resnet":
+        return int(embedding_dim)
+    if encoder in ("identity", "mlp"):
+        need = n * n
+    elif encoder == "grid":
+        need = 4 * 6 * 6
+    elif encoder == "cnn":
+        if n < 9:
+            raise ValueError(f"the 'cnn' encoder needs local_map_size >= 9, got {n}")
+        need = 4 * (n - 8) ** 2
+    else:
+        k = math.isqrt(max(int(embedding_dim), 0))
+        if k < 1 or k * k != int(embedding_dim):
+            raise ValueError(f"the 'max' encoder pools to k x k cells: local_map_embedding_dim must be a perfect square "
+                             f"(got {embedding_dim}; {max(k, 1) ** 2} or {(k + 1) ** 2} would do)")
+        need = k * k
+    if int(embedding_dim) != need:
+        raise ValueError(f"the '{encoder}' encoder produces {need} columns at local_map_size {n}: "
+                         f"local_map_embedding_dim must be {need}, got {embedding_dim}")
+    return need
+
+
+def small_encoder_param_shapes(encoder, local_map_size=20, embedding_dim=None):
+    """Parameter names/shapes under ``encoder.`` of the reference's MLPEncoder / GridEncoder / CNNEncoder
+    (local_map_encoder.py:137-192); MaxEncoder and IdentityEncoder have none."""
     sh = OrderedDict()
-    for k, v in resnet18_gn_param_shapes(embedding_dim).items():
-        sh[f"encoder.resnet18.{k}"] = v
+    n = int(local_map_size)
+
+    def layer(name, *shape):
+        sh[f"{name}.weight"] = tuple(shape)
+        sh[f"{name}.bias"] = (shape[0],)
+
+    if encoder == "mlp":
+        layer("fc1", 128, n * n)
+        layer("fc2", 256, 128)
+        layer("fc3", n * n if embedding_dim is None else int(embedding_dim), 256)
+    elif encoder == "grid":
+        layer("conv1", 3, 1, 3, 3)
+        layer("conv2", 6, 3, 3, 3)
+        layer("conv3", 4, 6, 3, 3)
+    elif encoder == "cnn":
+        layer("conv1", 2, 1, 3, 3)
+        layer("conv2", 4, 2, 3, 3)
+        layer("conv3", 4, 4, 3, 3)
+        layer("conv4", 4, 4, 3, 3)
+    elif encoder not in ("identity", "max"):
+        raise ValueError(f"Unknown encoder: {encoder}")
+    return sh
+
+
+def noise_pred_net_param_shapes(input_dim=2, embedding_dim=400, additional_global_cond_dim=7,
+                                down_dims=(512, 1024, 2048), encoder="resnet", local_map_size=20):
+    sh = OrderedDict()
+    if encoder == "resnet":
+        for k, v in resnet18_gn_param_shapes(embedding_dim).items():
+            sh[f"encoder.resnet18.{k}"] = v
+    else:
+        for k, v in small_encoder_param_shapes(encoder, local_map_size, embedding_dim).items():
+            sh[f"encoder.{k}"] = v
     for k, v in unet_param_shapes(input_dim, embedding_dim + additional_global_cond_dim, down_dims).items():
         sh[f"unet.{k}"] = v
     return sh
@@ -111,10 +176,20 @@ def blob_checksum(blob: np.ndarray):
     return s1, s2
 
 
-def pack_state_dict(state_dict, pred_horizon=None, local_map_size=None, checksum=True):
+def manifest_encoder(manifest):
+    """(encoder name, embedding width or None) a manifest declares; one without an ``#encoder`` line is a 'resnet' net."""
+    for line in manifest.splitlines():
+        if line.startswith("#encoder"):
+            f = line.split()
+            return f[1], (int(f[2]) if len(f) > 2 else None)
+    return "resnet", None
+
+
+def pack_state_dict(state_dict, pred_horizon=None, local_map_size=None, checksum=True, encoder=None, embedding_dim=None):
     """-> (blob float32 ndarray, manifest text) in the format ditree_load_weights parses:
     one line per tensor: ``name offset n_elems ndim d0 d1 ...``; ``#config`` carries what the tensor shapes do not
-    tell (pred_horizon, local_map_size), ``#checksum`` guards the blob."""
+    tell (pred_horizon, local_map_size), ``#encoder <name> <embedding width>`` the local-map encoder ('identity' and 'max' have
+    no parameters, so the keys do not tell; without the line the net is a 'resnet' one), ``#checksum`` guards the blob."""
     lines, chunks, off = [], [], 0
     for name, t in state_dict.items():
         a = t.detach().to("cpu", torch.float32).contiguous().numpy().reshape(-1)
@@ -132,6 +207,12 @@ def pack_state_dict(state_dict, pred_horizon=None, local_map_size=None, checksum
         cfg.append(f"local_map_size {int(local_map_size)}")
     if cfg:
         lines.append("#config " + " ".join(cfg))
+    if encoder is not None:
+        if encoder not in ENCODERS:
+            raise ValueError(f"Unknown encoder: {encoder}")
+        if encoder != "resnet" and embedding_dim is None:
+            raise ValueError("pack_state_dict: the small encoders need embedding_dim")
+        lines.append(f"#encoder {encoder}" + (f" {int(embedding_dim)}" if embedding_dim is not None else ""))
     if checksum:
         s1, s2 = blob_checksum(blob)
         lines.append(f"#checksum {s1:x} {s2:x}")

@@ -403,10 +403,25 @@ int32_t ditree_mppi_step_ant(ditree_ctx* ctx, const ditree_mppi_ant_params* p, d
 /* ------------------------------------------------------------------ denoiser */
 
 /* Upload the denoiser weights (reference: run_scenarios.py:157-185, state-dict keys
- * `encoder.resnet18.*`, `unet.*`).  `blob` [host] is the flat fp32 parameter blob and
+ * `encoder.*`, `unet.*`).  `blob` [host] is the flat fp32 parameter blob and
  * `manifest` [host] a NUL-terminated text table "name offset n_elems dims...\n" built by
  * ditreeonlineplanner_amd/weights.py; the library repacks into MFMA-friendly bf16
- * (and, for the f32 parity instantiation, fp32) tiles on the device. */
+ * (and, for the f32 parity instantiation, fp32) tiles on the device.
+ *
+ * Meta lines of the manifest (what the tensor shapes do not tell):
+ *   #config pred_horizon <P> local_map_size <N>
+ *   #encoder <name> <E>      the local-map encoder (local_map_encoder.py:78-97) and its embedding width; without the
+ *                            line the net is a 'resnet' one (every blob stored before the line existed keeps loading)
+ *   #checksum <s1> <s2>      Fletcher-style sums over the blob's 32-bit words (optional)
+ * Encoders and the parameters they read:
+ *   resnet    encoder.resnet18.*                      E = rows of encoder.resnet18.fc.weight
+ *   identity  none                                    E = N * N
+ *   mlp       encoder.fc{1,2,3}.{weight,bias}         E = N * N   (Linear(N*N, 128), ReLU, Linear(128, 256), ReLU, Linear(256, E))
+ *   max       none                                    E = k * k   (AdaptiveMaxPool2d(k); E must be a perfect square)
+ *   grid      encoder.conv{1,2,3}.{weight,bias}       E = 144     (3x3 convs 1 -> 3 -> 6 -> 4, ReLU, AdaptiveMaxPool2d(6))
+ *   cnn       encoder.conv{1..4}.{weight,bias}        E = 4 (N - 8)^2   (3x3 convs 1 -> 2 -> 4 -> 4 -> 4, Mish after each)
+ * The five small encoders run in f32 in every DITREE_PREC_* (encoder_kernels.hip); E must equal the width the kind
+ * produces at N and cond_dim - 256 - E (the observation-conditioning width) must not be negative: DITREE_E_ARG otherwise. */
 int32_t ditree_load_weights(ditree_ctx* ctx, const float* blob, int64_t n_floats,
                             const char* manifest, void* stream);
 
