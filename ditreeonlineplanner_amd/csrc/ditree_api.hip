@@ -39,6 +39,33 @@ int set_err(ditree_ctx* ctx, int code, const std::string& msg) {
   return code;
 }
 
+// The pool scheduler of an early-exit round (car and ant; the rule is explained in expand_round_impl): rebuild the ready list
+// (idx / nrow, furthest behind first), read its length back, take the largest multiple of `quantum` from its head -- everything,
+// once less than one quantum is left -- and run `body(take)`, which launches one call for those rows, until nothing is ready.
+// Calls and tile-waves of a drained round go to ctx->ee_calls / ee_waves (ditree_round_stats).
+template <class Body>
+static int run_ready_pool(ditree_ctx* ctx, const char* who, const ditree_round* round, const int32_t* budget, int nC, int quantum,
+                          int32_t* idx, int32_t* nrow, hipStream_t s, Body body) {
+  const int B = round->B;
+  int calls = 0, waves = 0;
+  for (;;) {
+    launch_compact_ready(round->status, round->chunks_run, budget, nC, B, idx, nrow, ctx->alive_cnt, s);
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->alive_cnt_host, ctx->alive_cnt, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    const int n_ready = *ctx->alive_cnt_host;
+    if (n_ready <= 0) break;
+    const int take = n_ready < quantum ? n_ready : (n_ready / quantum) * quantum;
+    if (++calls > nC * (B / quantum + 2) + 8)
+      return set_err(ctx, DITREE_E_STATE, std::string(who) + ": early-exit scheduler did not drain");
+    waves += (take + quantum - 1) / quantum;
+    const int rc = body(take);
+    if (rc) return rc;
+  }
+  ctx->ee_calls = calls;
+  ctx->ee_waves = waves;
+  return DITREE_OK;
+}
+
 extern "C" {
 
 int32_t ditree_version(void) { return DITREE_VERSION; }
@@ -159,6 +186,18 @@ int32_t ditree_local_map(ditree_ctx* ctx, const double* state, int32_t state_str
   return DITREE_OK;
 }
 
+static void fill_norm(const double* norm, NormArg* nm) {
+  for (int i = 0; i < 6; ++i) nm->obs_mean[i] = norm[i];
+  for (int i = 0; i < 6; ++i) nm->obs_std[i] = norm[6 + i];
+  for (int i = 0; i < 2; ++i) nm->act_mean[i] = norm[12 + i];
+  for (int i = 0; i < 2; ++i) nm->act_std[i] = norm[14 + i];
+}
+
+static void fill_ant_norm(const double* norm, AntNormArg* nm) {
+  for (int i = 0; i < 27; ++i) { nm->obs_mean[i] = norm[i]; nm->obs_std[i] = norm[27 + i]; }
+  for (int i = 0; i < 8; ++i) { nm->act_mean[i] = norm[54 + i]; nm->act_std[i] = norm[62 + i]; }
+}
+
 int32_t ditree_cond_vector_ant(ditree_ctx* ctx, const double* obs, int32_t n_hist, const double* prev_action,
                                const uint8_t* has_prev, const double* cond_goal, int32_t B, const double* norm,
                                double local_map_size, float* out, void* stream) {
@@ -167,18 +206,10 @@ int32_t ditree_cond_vector_ant(ditree_ctx* ctx, const double* obs, int32_t n_his
   if (!obs || !prev_action || !has_prev || !cond_goal || !norm || !out || B < 0 || n_hist < 1 || n_hist > 3)
     return set_err(ctx, DITREE_E_ARG, "cond_vector_ant: bad argument (1 <= n_hist <= 3)");
   AntNormArg nm;
-  for (int i = 0; i < 27; ++i) { nm.obs_mean[i] = norm[i]; nm.obs_std[i] = norm[27 + i]; }
-  for (int i = 0; i < 8; ++i) { nm.act_mean[i] = norm[54 + i]; nm.act_std[i] = norm[62 + i]; }
+  fill_ant_norm(norm, &nm);
   launch_cond_vector_ant(obs, n_hist, nullptr, prev_action, has_prev, cond_goal, nullptr, B, nm, local_map_size, out, (hipStream_t)stream);
   HIP_TRY(ctx, hipGetLastError());
   return DITREE_OK;
-}
-
-static void fill_norm(const double* norm, NormArg* nm) {
-  for (int i = 0; i < 6; ++i) nm->obs_mean[i] = norm[i];
-  for (int i = 0; i < 6; ++i) nm->obs_std[i] = norm[6 + i];
-  for (int i = 0; i < 2; ++i) nm->act_mean[i] = norm[12 + i];
-  for (int i = 0; i < 2; ++i) nm->act_std[i] = norm[14 + i];
 }
 
 int32_t ditree_cond_vector(ditree_ctx* ctx, const double* state, const double* prev_action, const uint8_t* has_prev,
@@ -668,8 +699,7 @@ int32_t ditree_ant_chunk_sample(ditree_ctx* ctx, const ditree_tree* tree, const 
   rc = fill_axis(ctx, p->axis, p->lm_n, &ax);
   if (rc) return rc;
   AntNormArg nm;
-  for (int i = 0; i < 27; ++i) { nm.obs_mean[i] = p->norm[i]; nm.obs_std[i] = p->norm[27 + i]; }
-  for (int i = 0; i < 8; ++i) { nm.act_mean[i] = p->norm[54 + i]; nm.act_std[i] = p->norm[62 + i]; }
+  fill_ant_norm(p->norm, &nm);
   // RRT.py:158-166: the local map is cut at the chunk's start state (x, y, element 2)
   launch_local_map(ctx->maze, ctx->rows, ctx->cols, round->end_state, round->status, idx, n_run, p->lm_n, ax, p->s_global, 1,
                    ctx->ant_lmap, s, ANT_S);
@@ -762,26 +792,15 @@ int32_t ditree_expand_round_ant(ditree_ctx* ctx, const ditree_tree* tree, const 
     // candidates for the ant network) from the ready list, rows of one launch at different chunks of their edges
     if (p->cond_out) return set_err(ctx, DITREE_E_ARG, "expand_round_ant: cond_out is a test output of rounds without early_exit");
     hipStream_t s = (hipStream_t)stream;
-    const int B = round->B;
     const int quantum = p->inject_actions ? 64 : denoise_wave_quantum(ctx);
     AxisArg ax;
     rc = fill_axis(ctx, p->axis, p->lm_n, &ax);
     if (rc) return rc;
     AntNormArg nm;
-    for (int i = 0; i < 27; ++i) { nm.obs_mean[i] = p->norm[i]; nm.obs_std[i] = p->norm[27 + i]; }
-    for (int i = 0; i < 8; ++i) { nm.act_mean[i] = p->norm[54 + i]; nm.act_std[i] = p->norm[62 + i]; }
+    fill_ant_norm(p->norm, &nm);
     const int64_t st_stride = (int64_t)nC * (A + 1) * ANT_S, ac_stride = (int64_t)nC * A * ANT_D;
     const AntChunkStrides cs{(int64_t)(A + 1) * ANT_S, (int64_t)A * ANT_D, (int64_t)P * ANT_D, (int64_t)A * ANT_S};
-    int calls = 0, waves = 0;
-    for (;;) {
-      launch_compact_ready(round->status, round->chunks_run, nullptr, nC, B, ctx->ant_idx, ctx->ant_nrow, ctx->alive_cnt, s);
-      HIP_TRY(ctx, hipMemcpyAsync(ctx->alive_cnt_host, ctx->alive_cnt, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-      HIP_TRY(ctx, hipStreamSynchronize(s));
-      const int n_ready = *ctx->alive_cnt_host;
-      if (n_ready <= 0) break;
-      const int take = n_ready < quantum ? n_ready : (n_ready / quantum) * quantum;
-      if (++calls > nC * (B / quantum + 2) + 8) return set_err(ctx, DITREE_E_STATE, "expand_round_ant: early-exit scheduler did not drain");
-      waves += (take + quantum - 1) / quantum;
+    rc = run_ready_pool(ctx, "expand_round_ant", round, nullptr, nC, quantum, ctx->ant_idx, ctx->ant_nrow, s, [&](int take) -> int {
       const double* acts;
       int64_t act_stride;
       int act_dense = 1;
@@ -794,9 +813,10 @@ int32_t ditree_expand_round_ant(ditree_ctx* ctx, const ditree_tree* tree, const 
                          1, ctx->ant_lmap, s, ANT_S);
         launch_cond_vector_ant(ctx->ant_hist, 3, ctx->ant_hist_n, ctx->ant_prev, ctx->ant_hasprev, p->cond_goal, ctx->ant_idx, take, nm,
                                p->lm_size, ctx->ant_cond, s);
-        rc = round_sampler(ctx, p->noise, (int64_t)P * ANT_D, ctx->ant_nrow, ctx->ant_lmap, ctx->ant_cond, take, p->K, p->t0, p->dt,
-                           p->ddpm_coef, p->step_noise, (int64_t)p->K * P * ANT_D, (int64_t)P * ANT_D, p->norm + 54, ctx->ant_act, s);
-        if (rc) return rc;
+        const int src = round_sampler(ctx, p->noise, (int64_t)P * ANT_D, ctx->ant_nrow, ctx->ant_lmap, ctx->ant_cond, take, p->K, p->t0,
+                                      p->dt, p->ddpm_coef, p->step_noise, (int64_t)p->K * P * ANT_D, (int64_t)P * ANT_D, p->norm + 54,
+                                      ctx->ant_act, s);
+        if (src) return src;
         acts = ctx->ant_act;
         act_stride = (int64_t)P * ANT_D;
       }
@@ -805,9 +825,9 @@ int32_t ditree_expand_round_ant(ditree_ctx* ctx, const ditree_tree* tree, const 
                          p->ball_radius, p->s_global, round->states, ditree_strides{st_stride, ANT_S, 1}, round->actions,
                          ditree_strides{ac_stride, ANT_D, 1}, round->chunk_steps, nC, round->chunks_run, ctx->ant_prev, ctx->ant_hasprev,
                          ctx->ant_hist, ctx->ant_hist_n, ctx->ant_idx, act_dense, s, 1, cs);
-    }
-    ctx->ee_calls = calls;
-    ctx->ee_waves = waves;
+      return DITREE_OK;
+    });
+    if (rc) return rc;
     HIP_TRY(ctx, hipGetLastError());
     return DITREE_OK;
   }
@@ -921,6 +941,41 @@ static int expand_round_impl(ditree_ctx* ctx, const ditree_tree* tree, const dit
     launch_nn_argmin(p->samples, 6, B, tree->xy, p->n_nodes, round->parent, tree->state, tree->last_action,
                      tree->has_prev, ctx->cur_state, ctx->prev_action, ctx->has_prev, s);
   const int64_t st_stride = (int64_t)nC * (A + 1) * 6, ac_stride = (int64_t)nC * A * 2;
+  // One call of the round's chunk body on n rows: local map -> conditioning -> sampler (or the action tape) -> rollout.  Plain
+  // chunk loop: every row at chunk j (idx = nrow = NULL, n = B).  Pool: the rows idx[0..n) with noise rows nrow, each at the chunk
+  // its chunks_run counter names (j = -1, cs = the per-chunk strides the kernel then adds itself).
+  auto chunk_body = [&](const int32_t* idx, const int32_t* nrow, int n, int j, ChunkStrides cs) -> int {
+    const size_t jo = j < 0 ? 0 : (size_t)j;              // the chunk offset the host adds
+    const int64_t nrows = j < 0 ? 1 : nC;                 // noise rows per index step: the (B * n_chunks, ...) view, or candidates
+    const double* acts;
+    int64_t act_stride;
+    int act_dense = 1;
+    if (p->inject_actions) {
+      acts = p->inject_actions + jo * P * 2;              // (B, n_chunks, P, 2), indexed by candidate
+      act_stride = (int64_t)nC * P * 2;
+      act_dense = 0;
+    } else {
+      if (scp)
+        launch_local_map_scenes(sc, ctx->cur_state, round->status, idx, n, p->lm_n, ax, p->s_global, ctx->lmap, s);
+      else
+        launch_local_map(ctx->maze, ctx->rows, ctx->cols, ctx->cur_state, round->status, idx, n, p->lm_n, ax, p->s_global, 1,
+                         ctx->lmap, s);
+      launch_cond_vector(ctx->cur_state, ctx->prev_action, ctx->has_prev, p->cond_goal, idx, n, nm, p->lm_size, ctx->cond, s);
+      double an[4] = {p->norm[12], p->norm[13], p->norm[14], p->norm[15]};
+      // start noise rows of (P, 2) and, for the DDPM branch, step noise rows of (K, P, 2)
+      const int src = round_sampler(ctx, p->noise + jo * P * 2, nrows * P * 2, nrow, ctx->lmap, ctx->cond, n, p->K, p->t0, p->dt,
+                                    p->ddpm_coef, p->step_noise ? p->step_noise + jo * p->K * P * 2 : nullptr,
+                                    nrows * p->K * P * 2, (int64_t)P * 2, an, ctx->act64, s);
+      if (src) return src;
+      acts = ctx->act64;
+      act_stride = (int64_t)P * 2;
+    }
+    launch_car_rollout_ex(ctx->maze, ctx->rows, ctx->cols, ctx->cur_state, acts, act_stride, round->status, n, A, gx, gy,
+                          round->states + jo * (A + 1) * 6, ditree_strides{st_stride, 6, 1}, round->actions + jo * A * 2,
+                          ditree_strides{ac_stride, 2, 1}, round->chunk_steps + jo, nC, round->chunks_run, ctx->prev_action,
+                          ctx->has_prev, idx, act_dense, s, p->chunk_budget, j, cs, scp);
+    return DITREE_OK;
+  };
   // Early exit (p->early_exit): what the reference does by abandoning a collided edge (planners/RRT.py:179-184) -- a chunk runs
   // only for candidates that are still alive.  A denoiser call costs whole WAVES of tiles (every layer has rows / quantum
   // tile-waves on the 256 CUs, quantum = 512 candidates for the car network), so the calls are packed to whole waves from a
@@ -933,82 +988,13 @@ static int expand_round_impl(ditree_ctx* ctx, const ditree_tree* tree, const dit
   if (p->early_exit) {
     const int quantum = p->inject_actions ? 64 : denoise_wave_quantum(ctx);
     const ChunkStrides cs{(int64_t)(A + 1) * 6, (int64_t)A * 2, (int64_t)P * 2};
-    int calls = 0, waves = 0;
-    for (;;) {
-      launch_compact_ready(round->status, round->chunks_run, p->chunk_budget, nC, B, ctx->alive_idx, ctx->alive_nrow, ctx->alive_cnt, s);
-      HIP_TRY(ctx, hipMemcpyAsync(ctx->alive_cnt_host, ctx->alive_cnt, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-      HIP_TRY(ctx, hipStreamSynchronize(s));
-      const int n_ready = *ctx->alive_cnt_host;
-      if (n_ready <= 0) break;
-      const int take = n_ready < quantum ? n_ready : (n_ready / quantum) * quantum;
-      if (++calls > nC * (B / quantum + 2) + 8) return set_err(ctx, DITREE_E_STATE, "expand_round: early-exit scheduler did not drain");
-      waves += (take + quantum - 1) / quantum;
-      const int32_t* idx = ctx->alive_idx;
-      const double* acts;
-      int64_t act_stride;
-      int act_dense = 1;
-      if (p->inject_actions) {
-        acts = p->inject_actions;                 // (B, n_chunks, P, 2): the kernel adds the candidate's chunk offset
-        act_stride = (int64_t)nC * P * 2;
-        act_dense = 0;
-      } else {
-        if (scp)
-          launch_local_map_scenes(sc, ctx->cur_state, round->status, idx, take, p->lm_n, ax, p->s_global, ctx->lmap, s);
-        else
-          launch_local_map(ctx->maze, ctx->rows, ctx->cols, ctx->cur_state, round->status, idx, take, p->lm_n, ax, p->s_global, 1,
-                           ctx->lmap, s);
-        launch_cond_vector(ctx->cur_state, ctx->prev_action, ctx->has_prev, p->cond_goal, idx, take, nm, p->lm_size, ctx->cond, s);
-        double an[4] = {p->norm[12], p->norm[13], p->norm[14], p->norm[15]};
-        // rows of the (B * n_chunks, ...) views: start noise (P, 2) and, for the DDPM branch, step noise (K, P, 2)
-        rc = round_sampler(ctx, p->noise, (int64_t)P * 2, ctx->alive_nrow, ctx->lmap, ctx->cond, take, p->K, p->t0, p->dt,
-                           p->ddpm_coef, p->step_noise, (int64_t)p->K * P * 2, (int64_t)P * 2, an, ctx->act64, s);
-        if (rc) return rc;
-        acts = ctx->act64;
-        act_stride = (int64_t)P * 2;
-      }
-      launch_car_rollout_ex(ctx->maze, ctx->rows, ctx->cols, ctx->cur_state, acts, act_stride, round->status, take, A,
-                            gx, gy, round->states, ditree_strides{st_stride, 6, 1}, round->actions,
-                            ditree_strides{ac_stride, 2, 1}, round->chunk_steps, nC, round->chunks_run, ctx->prev_action,
-                            ctx->has_prev, idx, act_dense, s, p->chunk_budget, -1, cs, scp);
-    }
-    ctx->ee_calls = calls;
-    ctx->ee_waves = waves;
-    HIP_TRY(ctx, hipMemcpyAsync(round->end_state, ctx->cur_state, (size_t)B * 6 * sizeof(double), hipMemcpyDeviceToDevice, s));
-    HIP_TRY(ctx, hipGetLastError());
-    return DITREE_OK;
+    rc = run_ready_pool(ctx, "expand_round", round, p->chunk_budget, nC, quantum, ctx->alive_idx, ctx->alive_nrow, s,
+                        [&](int take) { return chunk_body(ctx->alive_idx, ctx->alive_nrow, take, -1, cs); });
+  } else {
+    for (int j = 0; j < nC && !rc; ++j) rc = chunk_body(nullptr, nullptr, B, j, ChunkStrides{0, 0, 0});
   }
-  for (int j = 0; j < nC; ++j) {
-    const double* acts;
-    int64_t act_stride;
-    int act_dense = 1;
-    if (p->inject_actions) {
-      acts = p->inject_actions + (size_t)j * P * 2;
-      act_stride = (int64_t)nC * P * 2;
-      act_dense = 0;                          // the tape is indexed by candidate
-    } else {
-      if (scp)
-        launch_local_map_scenes(sc, ctx->cur_state, round->status, nullptr, B, p->lm_n, ax, p->s_global, ctx->lmap, s);
-      else
-        launch_local_map(ctx->maze, ctx->rows, ctx->cols, ctx->cur_state, round->status, nullptr, B, p->lm_n, ax,
-                         p->s_global, 1, ctx->lmap, s);
-      launch_cond_vector(ctx->cur_state, ctx->prev_action, ctx->has_prev, p->cond_goal, nullptr, B, nm, p->lm_size,
-                         ctx->cond, s);
-      double an[4] = {p->norm[12], p->norm[13], p->norm[14], p->norm[15]};
-      rc = round_sampler(ctx, p->noise + (size_t)j * P * 2, (int64_t)nC * P * 2, nullptr, ctx->lmap, ctx->cond, B, p->K, p->t0, p->dt,
-                         p->ddpm_coef, p->step_noise ? p->step_noise + (size_t)j * p->K * P * 2 : nullptr,
-                         (int64_t)nC * p->K * P * 2, (int64_t)P * 2, an, ctx->act64, s);
-      if (rc) return rc;
-      acts = ctx->act64;
-      act_stride = (int64_t)P * 2;
-    }
-    launch_car_rollout_ex(ctx->maze, ctx->rows, ctx->cols, ctx->cur_state, acts, act_stride, round->status, B, A,
-                          gx, gy, round->states + (size_t)j * (A + 1) * 6, ditree_strides{st_stride, 6, 1},
-                          round->actions + (size_t)j * A * 2, ditree_strides{ac_stride, 2, 1}, round->chunk_steps + j, nC,
-                          round->chunks_run, ctx->prev_action, ctx->has_prev, nullptr, act_dense, s, p->chunk_budget, j, ChunkStrides{0, 0, 0},
-                          scp);
-  }
-  HIP_TRY(ctx, hipMemcpyAsync(round->end_state, ctx->cur_state, (size_t)B * 6 * sizeof(double),
-                              hipMemcpyDeviceToDevice, s));
+  if (rc) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(round->end_state, ctx->cur_state, (size_t)B * 6 * sizeof(double), hipMemcpyDeviceToDevice, s));
   HIP_TRY(ctx, hipGetLastError());
   return DITREE_OK;
 }
@@ -1104,23 +1090,29 @@ int32_t ditree_forest_nn_argmin(ditree_ctx* ctx, const ditree_tree* tree, const 
   return DITREE_OK;
 }
 
+// planners/RRT.py:227-254 for every tree of a checked forest: the T query rows `goals` (T, 2) on the host (a temporary or the
+// caller's memory, hence the sync) -> ctx->cur_state (T, 6) -> one launch.
+static int forest_fallback_impl(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const double* goals,
+                                int32_t* out_node, hipStream_t s) {
+  const int T = forest->n_trees;
+  const int rc = ensure_scratch(ctx, T, 1, 1);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->cur_state, goals, (size_t)T * 2 * sizeof(double), hipMemcpyHostToDevice, s));
+  launch_forest_fallback(ctx->cur_state, T, tree->xy, forest->counters, forest->tree_capacity, out_node, s);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipStreamSynchronize(s));
+  return DITREE_OK;
+}
+
 int32_t ditree_forest_fallback(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const double* goal_xy,
                                int32_t* out_node, void* stream) {
   if (!ctx) return DITREE_E_ARG;
   int rc = check_forest(ctx, tree, forest, -1, "forest_fallback");
   if (rc) return rc;
   if (!goal_xy || !out_node) return set_err(ctx, DITREE_E_ARG, "forest_fallback: bad argument");
-  hipStream_t s = (hipStream_t)stream;
-  const int T = forest->n_trees;
-  rc = ensure_scratch(ctx, T, 1, 1);                   // T copies of the goal as the queries (ctx->cur_state, (T, 6))
-  if (rc) return rc;
-  std::vector<double> q((size_t)T * 2);
-  for (int t = 0; t < T; ++t) { q[(size_t)t * 2] = goal_xy[0]; q[(size_t)t * 2 + 1] = goal_xy[1]; }
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->cur_state, q.data(), q.size() * sizeof(double), hipMemcpyHostToDevice, s));
-  launch_forest_fallback(ctx->cur_state, T, tree->xy, forest->counters, forest->tree_capacity, out_node, s);
-  HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipStreamSynchronize(s));               // `q` is a temporary
-  return DITREE_OK;
+  std::vector<double> q((size_t)forest->n_trees * 2);   // T copies of the goal as the queries
+  for (int t = 0; t < forest->n_trees; ++t) { q[(size_t)t * 2] = goal_xy[0]; q[(size_t)t * 2 + 1] = goal_xy[1]; }
+  return forest_fallback_impl(ctx, tree, forest, q.data(), out_node, (hipStream_t)stream);
 }
 
 // ---- scene forests (include/ditree.h "scene forests")
@@ -1210,15 +1202,7 @@ int32_t ditree_forest_fallback_goals(ditree_ctx* ctx, const ditree_tree* tree, c
   if (rc) return rc;
   if (!goal_xy) return set_err(ctx, DITREE_E_ARG, "forest_fallback_goals: goals array (T, 2) missing");
   if (!out_node) return set_err(ctx, DITREE_E_ARG, "forest_fallback_goals: out_node missing");
-  hipStream_t s = (hipStream_t)stream;
-  const int T = forest->n_trees;
-  rc = ensure_scratch(ctx, T, 1, 1);                   // the T goals as the queries (ctx->cur_state, (T, 6))
-  if (rc) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->cur_state, goal_xy, (size_t)T * 2 * sizeof(double), hipMemcpyHostToDevice, s));
-  launch_forest_fallback(ctx->cur_state, T, tree->xy, forest->counters, forest->tree_capacity, out_node, s);
-  HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipStreamSynchronize(s));               // goal_xy is the caller's host memory
-  return DITREE_OK;
+  return forest_fallback_impl(ctx, tree, forest, goal_xy, out_node, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -197,6 +197,43 @@ def default_shard():
     return 0, 1, None
 
 
+def env_goal_of(maze, goal_state):
+    """env.goal after planner.reset -> env.reset(options): the centre of the goal cell (car_env.py:189-201,225-226)."""
+    H, W = np.asarray(maze).shape
+    gi = np.floor((H / 2 - goal_state[1]) / 1.0)
+    gj = np.floor((goal_state[0] + W / 2) / 1.0)
+    return np.array([(gj + 0.5) * 1.0 - W / 2, H / 2 - (gi + 0.5) * 1.0])
+
+
+def tree_path(tr, node, n_nodes, base=0, edge_rows=None):
+    """planners/base_planner.py:342-363 on a ``DeviceTree``: float32 path (edge states + node states) and actions from the
+    root to ``node``.  The tree is the ``n_nodes`` slots from ``base`` (a forest's tree; ``node`` is local to it, the stored
+    parents are global).  ``edge_rows(idx, es, ea, ns, na)``: what a sharded engine does to the chain's edge rows first."""
+    parents = tr.parent[base: base + n_nodes].cpu().numpy()
+    chain = []
+    k = int(node)
+    while k != -1:
+        chain.append(k)
+        p = int(parents[k])
+        k = -1 if p < 0 else p - base
+    chain = chain[::-1]
+    idx = torch.as_tensor(chain, device=tr.state.device, dtype=torch.long) + base
+    st = tr.state[idx].cpu().numpy()
+    rows = (tr.edge_states[idx], tr.edge_actions[idx], tr.edge_nstates[idx], tr.edge_nactions[idx])
+    if edge_rows is not None:
+        rows = edge_rows(idx, *rows)
+    es, ea, ns, na = (x.cpu().numpy() for x in rows)
+    path, actions = [], []
+    for j, nd in enumerate(chain):
+        if nd != 0:
+            path.extend(es[j, : ns[j]])
+            actions.extend(ea[j, : na[j]])
+        path.append(st[j])
+    path = np.array(path, dtype=np.float32) if path else None
+    actions = np.array(actions, dtype=np.float32) if actions else None
+    return path, actions
+
+
 class ExpansionEngine:
     """Batched RRT expansion on one GPU (optionally one shard of a multi-GPU round)."""
     STATE_DIM, ACTION_DIM, HIST = 6, 2, False
@@ -258,11 +295,7 @@ class ExpansionEngine:
         self.generation = getattr(self, "generation", 0) + 1      # consumers caching per-tree data (node_list) key on it
 
     def _derive_env_goal(self):
-        H, W = self.maze.shape
-        # planner.reset -> env.reset(options): env.goal = centre of the goal cell (car_env.py:189-201,225-226)
-        gi = np.floor((H / 2 - self.goal_state[1]) / 1.0)
-        gj = np.floor((self.goal_state[0] + W / 2) / 1.0)
-        self.env_goal = np.array([(gj + 0.5) * 1.0 - W / 2, H / 2 - (gi + 0.5) * 1.0])
+        self.env_goal = env_goal_of(self.maze, self.goal_state)
 
     def update_maze(self, maze):
         self.maze = np.asarray(maze, dtype=np.float32)
@@ -326,6 +359,41 @@ class ExpansionEngine:
             raise ValueError(f"step_noise must be a contiguous float32 (B, {want[0]}, {want[1]}, {want[2]}, {want[3]}) tensor")
         rp.step_noise = step_noise[lo:hi].data_ptr() if hi > lo else None
 
+    def _round_params(self, rp, samples, cond_goal, noise, inject_actions, step_noise, lo, hi, goal_field="goal_xy"):
+        """What every round type's parameter block shares, for rows [lo, hi) of the round: the sample, goal, noise and action
+        pointers, the sampler schedule, norm / goal / axis, the local-map fields, early_exit and -- with a ``prop_duration``
+        schedule -- the chunk budgets.  Returns the list that keeps the pointed-to arrays alive until the launch has been issued."""
+        n = hi - lo
+        rp.n_nodes = self.tree.n_nodes_host           # a forest round does not read it: each tree's size is in its counter row
+        rp.samples = samples[lo:hi].data_ptr() if n else None
+        rp.cond_goal = cond_goal[lo:hi].data_ptr() if n else None
+        rp.noise = noise[lo:hi].data_ptr() if (noise is not None and n) else None
+        rp.inject_actions = inject_actions[lo:hi].data_ptr() if (inject_actions is not None and n) else None
+        rp.P = self.P
+        keep = [samples, cond_goal, noise, inject_actions, step_noise]
+        if self.ddpm is None or noise is None:
+            self._flow_only(rp, keep)
+        else:
+            self._sampler_schedule(rp, keep, step_noise, lo, hi)
+        for name, arr in (("norm", self.norm), (goal_field, self.env_goal), ("axis", self.axis)):
+            a, ptr = _dbl(arr)
+            keep.append(a)
+            setattr(rp, name, ptr)
+        rp.lm_n, rp.lm_size, rp.s_global = self.lm_n, self.goal_scale, float(self.s_global)
+        rp.early_exit = self.early_exit
+        if self._budget is not None:                  # else the field keeps its NULL
+            # every rank derives the budgets of the WHOLE round (a candidate's place in its parent's visit order is global)
+            self._chunk_budget(samples, samples.shape[0])
+            rp.chunk_budget = self._budget[lo:hi].data_ptr() if n else None
+        return keep
+
+    def _chunk_budget(self, samples, B):
+        """planners/RRT.py:149-152 for the B candidates of a round -> ``self._budget`` (the single tree's entry point)."""
+        check(self.ctx._h, lib().ditree_chunk_budget(self.ctx._h, C.byref(self.tree.desc), samples.data_ptr(), B,
+                                                      self.tree.n_nodes_host, self._sched_chunks, len(self.schedule),
+                                                      self._budget_parent.data_ptr(), self._budget.data_ptr(),
+                                                      self.ctx.stream), "chunk_budget")
+
     def expand_round(self, samples, cond_goal, noise=None, inject_actions=None, accept=True, step_noise=None):
         """samples (B,6) f64, cond_goal (B,2) f64 [device tensors, all candidates of the round];
         noise (B, n_chunks, P, 2) f32 or inject_actions (B, n_chunks, P, 2) f64 for this round; step_noise
@@ -337,35 +405,12 @@ class ExpansionEngine:
         n = hi - lo
         self.ensure_maze()
         rp = RoundParams()
-        rp.n_nodes = self.tree.n_nodes_host
-        rp.samples = samples[lo:hi].data_ptr() if n else None
-        rp.cond_goal = cond_goal[lo:hi].data_ptr() if n else None
-        rp.noise = noise[lo:hi].data_ptr() if (noise is not None and n) else None
-        rp.inject_actions = inject_actions[lo:hi].data_ptr() if (inject_actions is not None and n) else None
-        rp.P = self.P
-        keep = []
-        if self.ddpm is None or noise is None:
-            self._flow_only(rp, keep)
-        else:
-            self._sampler_schedule(rp, keep, step_noise, lo, hi)
-        for name, arr, conv in (("norm", self.norm, _dbl), ("goal_xy", self.env_goal, _dbl), ("axis", self.axis, _dbl)):
-            a, p = conv(arr)
-            keep.append(a)
-            setattr(rp, name, p)
-        rp.lm_n, rp.lm_size, rp.s_global = self.lm_n, self.goal_scale, float(self.s_global)
-        rp.early_exit = self.early_exit
-        rp.chunk_budget = None
-        if self._budget is not None:
-            # every rank derives the budgets of the WHOLE round (a candidate's place in its parent's visit order is global)
-            check(self.ctx._h, lib().ditree_chunk_budget(self.ctx._h, C.byref(self.tree.desc), samples.data_ptr(), B,
-                                                          self.tree.n_nodes_host, self._sched_chunks, len(self.schedule),
-                                                          self._budget_parent.data_ptr(), self._budget.data_ptr(),
-                                                          self.ctx.stream), "chunk_budget")
-            rp.chunk_budget = self._budget[lo:hi].data_ptr() if n else None
+        keep = self._round_params(rp, samples, cond_goal, noise, inject_actions, step_noise, lo, hi)
         if n > 0:
             rd = self.rb.desc(lo, n)
             check(self.ctx._h, lib().ditree_expand_round(self.ctx._h, C.byref(self.tree.desc), C.byref(rd),
                                                           C.byref(rp), self.ctx.stream), "expand_round")
+        del keep
         return self._finish_round(B, per, noise is not None, accept)
 
     def _flow_only(self, rp, keep):
@@ -429,18 +474,23 @@ class ExpansionEngine:
         check(self.ctx._h, lib().ditree_accept(self.ctx._h, C.byref(self.tree.desc), C.byref(rd), self.sticky,
                                                 self.ctx.stream), "accept")
         cnt = self.tree.read_counters()           # one small D2H per round: n_nodes / goal
-        if getattr(self, "_used_denoiser", False):
-            # f16 range guard: the stream is drained already, one more tiny D2H.  Sharded: a rank whose shard saturated must
-            # not raise alone (the others would wait in the next collective until the launcher kills them) -- the ranks agree
-            # on the worst count first and then all raise.
-            layers = self.ctx.denoise_status(clear=True)
-            worst = self.sum_over_ranks(len(layers), op="max")
-            if worst:
-                if not layers:
-                    raise _lib.DitreeError(f"f16 range guard: another rank clamped activations in {worst} layer(s) of this round; "
-                                           "bind the checkpoint with precision=PREC_BF16X3 or PREC_F32")
-                self.ctx.raise_range_error(layers)
+        self._range_guard()
         return cnt
+
+    def _range_guard(self):
+        """The tail of every accept: a round that ran the denoiser raises if the f16 range guard clamped activations."""
+        if not getattr(self, "_used_denoiser", False):
+            return
+        # the stream is drained already, one more tiny D2H.  Sharded: a rank whose shard saturated must not raise alone (the
+        # others would wait in the next collective until the launcher kills them) -- the ranks agree on the worst count first
+        # and then all raise.
+        layers = self.ctx.denoise_status(clear=True)
+        worst = self.sum_over_ranks(len(layers), op="max")
+        if worst:
+            if not layers:
+                raise _lib.DitreeError(f"f16 range guard: another rank clamped activations in {worst} layer(s) of this round; "
+                                       "bind the checkpoint with precision=PREC_BF16X3 or PREC_F32")
+            self.ctx.raise_range_error(layers)
 
     # ------------------------------------------------------------------ results
     @property
@@ -472,47 +522,27 @@ class ExpansionEngine:
 
     def path_to(self, node):
         """planners/base_planner.py:342-363: float32 path (edge states + node states) and actions."""
-        t = self.tree
-        parents = t.parent[: t.n_nodes_host].cpu().numpy()
-        chain = []
-        n = int(node)
-        while n != -1:
-            chain.append(n)
-            n = int(parents[n])
-        chain = chain[::-1]
-        idx = torch.as_tensor(chain, device=t.state.device, dtype=torch.long)
-        st = t.state[idx].cpu().numpy()
-        es_t, ea_t = t.edge_states[idx], t.edge_actions[idx]
-        ns_t, na_t = t.edge_nstates[idx], t.edge_nactions[idx]
-        if self.world > 1 and getattr(self, "_sharded", False):
-            # collective (every rank walks the same chain): each edge comes from the rank that expanded it; rows a rank
-            # does not hold are zeroed, the sum over ranks is then exact (x + 0 + ... + 0)
-            import torch.distributed as dist
-            owner = t.edge_owner[idx]
-            mine = (owner == self.rank) | ((owner < 0) & (self.rank == 0))
-            mask = mine.to(es_t.dtype)
-            es_t = es_t * mask[:, None, None]
-            ea_t = ea_t * mask[:, None, None]
-            ns_t = torch.where(mine, ns_t, torch.zeros_like(ns_t))
-            na_t = torch.where(mine, na_t, torch.zeros_like(na_t))
-            gloo = dist.get_backend(self.pg) == "gloo"
-            bufs = []
-            for x in (es_t, ea_t, ns_t, na_t):
-                y = x.cpu() if gloo else x.contiguous()
-                dist.all_reduce(y, op=dist.ReduceOp.SUM, group=self.pg)
-                bufs.append(y)
-            es_t, ea_t, ns_t, na_t = bufs
-        es, ea = es_t.cpu().numpy(), ea_t.cpu().numpy()
-        ns, na = ns_t.cpu().numpy(), na_t.cpu().numpy()
-        path, actions = [], []
-        for k, nd in enumerate(chain):
-            if nd != 0:
-                path.extend(es[k, : ns[k]])
-                actions.extend(ea[k, : na[k]])
-            path.append(st[k])
-        path = np.array(path, dtype=np.float32) if path else None
-        actions = np.array(actions, dtype=np.float32) if actions else None
-        return path, actions
+        sharded = self.world > 1 and getattr(self, "_sharded", False)
+        return tree_path(self.tree, node, self.tree.n_nodes_host, edge_rows=self._reduce_edge_rows if sharded else None)
+
+    def _reduce_edge_rows(self, idx, es_t, ea_t, ns_t, na_t):
+        """Collective (every rank walks the same chain): each edge comes from the rank that expanded it; rows a rank does not
+        hold are zeroed, the sum over ranks is then exact (x + 0 + ... + 0)."""
+        import torch.distributed as dist
+        owner = self.tree.edge_owner[idx]
+        mine = (owner == self.rank) | ((owner < 0) & (self.rank == 0))
+        mask = mine.to(es_t.dtype)
+        es_t = es_t * mask[:, None, None]
+        ea_t = ea_t * mask[:, None, None]
+        ns_t = torch.where(mine, ns_t, torch.zeros_like(ns_t))
+        na_t = torch.where(mine, na_t, torch.zeros_like(na_t))
+        gloo = dist.get_backend(self.pg) == "gloo"
+        bufs = []
+        for x in (es_t, ea_t, ns_t, na_t):
+            y = x.cpu() if gloo else x.contiguous()
+            dist.all_reduce(y, op=dist.ReduceOp.SUM, group=self.pg)
+            bufs.append(y)
+        return bufs
 
     def tree_snapshot(self):
         n = self.tree.n_nodes_host
@@ -571,28 +601,12 @@ class AntExpansionEngine(ExpansionEngine):
     def _params(self, samples, cond_goal, noise, inject_actions, lo, hi, next_obs_tape=None, cond_out=None, step_noise=None):
         n = hi - lo
         rp = _lib.AntRoundParams()
-        rp.n_nodes = self.tree.n_nodes_host
-        rp.samples = samples[lo:hi].data_ptr() if n else None
-        rp.cond_goal = cond_goal[lo:hi].data_ptr() if n else None
-        rp.noise = noise[lo:hi].data_ptr() if (noise is not None and n) else None
-        rp.inject_actions = inject_actions[lo:hi].data_ptr() if (inject_actions is not None and n) else None
-        rp.P = self.P
-        keep = [samples, cond_goal, noise, inject_actions, next_obs_tape, cond_out]
-        if self.ddpm is None or noise is None:
-            self._flow_only(rp, keep)
-        else:
-            self._sampler_schedule(rp, keep, step_noise, lo, hi)
-        for name, arr, conv in (("norm", self.norm, _dbl),
-                                ("desired_goal", self.env_goal, _dbl), ("axis", self.axis, _dbl)):
-            a, p = conv(arr)
-            keep.append(a)
-            setattr(rp, name, p)
+        keep = self._round_params(rp, samples, cond_goal, noise, inject_actions, step_noise, lo, hi, goal_field="desired_goal")
+        keep += [next_obs_tape, cond_out]
         rp.goal_radius, rp.ball_radius = self.goal_radius, self.ball_radius
-        rp.lm_n, rp.lm_size, rp.s_global = self.lm_n, self.goal_scale, float(self.s_global)
         rp.dynamics = _lib.ANT_DYN_MODEL if self.dynamics == "model" else _lib.ANT_DYN_TAPE
         rp.next_obs_tape = next_obs_tape[lo:hi].data_ptr() if (next_obs_tape is not None and n) else None
         rp.model = C.pointer(self.model)
-        rp.early_exit = self.early_exit
         rp.cond_out = cond_out[lo:hi].data_ptr() if (cond_out is not None and n) else None
         return rp, keep
 

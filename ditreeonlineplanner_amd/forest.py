@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from ._lib import MAX_ATLAS_CELLS, MAX_SCENES, Forest, ForestScenes, RoundParams, check, lib
-from .engine import CNT_GOAL, CNT_NODES, CNT_PHANTOM, ExpansionEngine
+from .engine import CNT_GOAL, CNT_NODES, CNT_PHANTOM, ExpansionEngine, env_goal_of, tree_path
 from .ops import CAR_NORM, Context, _dbl
 
 
@@ -131,36 +131,19 @@ class ForestEngine(ExpansionEngine):
         if B == 0:                                    # no tree has a candidate: nothing to expand or accept
             return self.cnt_host.copy() if accept else None
         self.ensure_maze()
-        h, L, st = self.ctx._h, lib(), self.ctx.stream
         rp = RoundParams()
-        rp.n_nodes = 1                                # not read: each tree's size comes from its counter row
-        rp.samples, rp.cond_goal = samples.data_ptr(), cond_goal.data_ptr()
-        rp.noise = noise.data_ptr() if noise is not None else None
-        rp.inject_actions = inject_actions.data_ptr() if inject_actions is not None else None
-        rp.P = self.P
-        keep = [samples, cond_goal, noise, inject_actions, step_noise]
-        if self.ddpm is None or noise is None:
-            self._flow_only(rp, keep)
-        else:
-            self._sampler_schedule(rp, keep, step_noise, 0, B)
-        for name, arr in (("norm", self.norm), ("goal_xy", self.env_goal), ("axis", self.axis)):
-            a, p = _dbl(arr)
-            keep.append(a)
-            setattr(rp, name, p)
-        rp.lm_n, rp.lm_size, rp.s_global = self.lm_n, self.goal_scale, float(self.s_global)
-        rp.early_exit = self.early_exit
-        rp.chunk_budget = None
-        if self._budget is not None:
-            check(h, L.ditree_forest_chunk_budget(h, C.byref(self.tree.desc), C.byref(self.fdesc), samples.data_ptr(), B,
-                                                  self._sched_chunks, len(self.schedule), self._budget_parent.data_ptr(),
-                                                  self._budget.data_ptr(), st), "forest_chunk_budget")
-            rp.chunk_budget = self._budget.data_ptr()
-        rd = self.rb.desc(0, B)
-        self._launch_round(rd, rp)
+        keep = self._round_params(rp, samples, cond_goal, noise, inject_actions, step_noise, 0, B)
+        self._launch_round(self.rb.desc(0, B), rp)
         del keep
         self._used_denoiser = noise is not None
         self._B = B
         return self.accept(B) if accept else None
+
+    def _chunk_budget(self, samples, B):
+        h = self.ctx._h
+        check(h, lib().ditree_forest_chunk_budget(h, C.byref(self.tree.desc), C.byref(self.fdesc), samples.data_ptr(), B,
+                                                  self._sched_chunks, len(self.schedule), self._budget_parent.data_ptr(),
+                                                  self._budget.data_ptr(), self.ctx.stream), "forest_chunk_budget")
 
     def _launch_round(self, rd, rp):
         h = self.ctx._h
@@ -174,10 +157,7 @@ class ForestEngine(ExpansionEngine):
         check(self.ctx._h, lib().ditree_forest_accept(self.ctx._h, C.byref(self.tree.desc), C.byref(self.fdesc), C.byref(rd),
                                                        self.sticky, self.ctx.stream), "forest_accept")
         cnt = self.read_counters().copy()             # one small D2H per round: every tree's row
-        if getattr(self, "_used_denoiser", False):
-            layers = self.ctx.denoise_status(clear=True)          # f16 range guard (ExpansionEngine.accept)
-            if layers:
-                self.ctx.raise_range_error(layers)
+        self._range_guard()
         return cnt
 
     def read_counters(self):
@@ -203,10 +183,14 @@ class ForestEngine(ExpansionEngine):
     def fallback_nodes(self):
         """planners/RRT.py:227-254 (run_type 0) for every tree in one launch: local node nearest to the goal among nodes 1..,
         None for a tree that holds only its root."""
+        return self._fallback_launch(lib().ditree_forest_fallback, "forest_fallback", self.goal_state[:2])
+
+    def _fallback_launch(self, entry, what, goals):
+        """``entry`` (one of the two forest fallback calls) on its goal array -> each tree's local node id or None."""
         out = torch.empty(self.T, dtype=torch.int32, device=self.tree.xy.device)
-        ga, gp = _dbl(self.goal_state[:2])
-        check(self.ctx._h, lib().ditree_forest_fallback(self.ctx._h, C.byref(self.tree.desc), C.byref(self.fdesc), gp,
-                                                         out.data_ptr(), self.ctx.stream), "forest_fallback")
+        ga, gp = _dbl(goals)
+        check(self.ctx._h, entry(self.ctx._h, C.byref(self.tree.desc), C.byref(self.fdesc), gp, out.data_ptr(), self.ctx.stream),
+              what)
         del ga
         ids = out.cpu().numpy()
         return [None if v < 0 else int(v) - t * self.C for t, v in enumerate(ids)]
@@ -217,28 +201,7 @@ class ForestEngine(ExpansionEngine):
     def path_to(self, t, node):
         """planners/base_planner.py:342-363 for tree t's local ``node``: float32 path and actions."""
         t = self._tree_index(t)
-        tr, base, n = self.tree, t * self.C, int(self.n_nodes_host[t])
-        parents = tr.parent[base: base + n].cpu().numpy()
-        chain = []
-        k = int(node)
-        while k != -1:
-            chain.append(k)
-            p = int(parents[k])
-            k = -1 if p < 0 else p - base
-        chain = chain[::-1]
-        idx = torch.as_tensor(chain, device=tr.state.device, dtype=torch.long) + base
-        st = tr.state[idx].cpu().numpy()
-        es, ea = tr.edge_states[idx].cpu().numpy(), tr.edge_actions[idx].cpu().numpy()
-        ns, na = tr.edge_nstates[idx].cpu().numpy(), tr.edge_nactions[idx].cpu().numpy()
-        path, actions = [], []
-        for j, nd in enumerate(chain):
-            if nd != 0:
-                path.extend(es[j, : ns[j]])
-                actions.extend(ea[j, : na[j]])
-            path.append(st[j])
-        path = np.array(path, dtype=np.float32) if path else None
-        actions = np.array(actions, dtype=np.float32) if actions else None
-        return path, actions
+        return tree_path(self.tree, node, int(self.n_nodes_host[t]), base=t * self.C)
 
     def tree_snapshot(self, t):
         """Tree t as a single-tree engine reports it: local parents (root -1), states, its counter row."""
@@ -276,14 +239,6 @@ def atlas_layout(mazes):
         offsets.append(off)
         dims.append(codes.shape)
     return np.array(offsets, dtype=np.int64), np.array(dims, dtype=np.int64).reshape(-1, 2), used
-
-
-def env_goal_of(maze, goal_state):
-    """env.goal after planner.reset -> env.reset(options): the centre of the goal cell (car_env.py:189-201,225-226)."""
-    H, W = np.asarray(maze).shape
-    gi = np.floor((H / 2 - goal_state[1]) / 1.0)
-    gj = np.floor((goal_state[0] + W / 2) / 1.0)
-    return np.array([(gj + 0.5) * 1.0 - W / 2, H / 2 - (gi + 0.5) * 1.0])
 
 
 class SceneForestEngine(ForestEngine):
@@ -363,10 +318,5 @@ class SceneForestEngine(ForestEngine):
 
     def fallback_nodes(self):
         """planners/RRT.py:227-254 (run_type 0) for every tree, each against its own scene's goal_state[:2]."""
-        out = torch.empty(self.T, dtype=torch.int32, device=self.tree.xy.device)
-        ga, gp = _dbl(np.stack([self.scene_goals[self.tree_scene(t)][:2] for t in range(self.T)]))
-        check(self.ctx._h, lib().ditree_forest_fallback_goals(self.ctx._h, C.byref(self.tree.desc), C.byref(self.fdesc), gp,
-                                                               out.data_ptr(), self.ctx.stream), "forest_fallback_goals")
-        del ga
-        ids = out.cpu().numpy()
-        return [None if v < 0 else int(v) - t * self.C for t, v in enumerate(ids)]
+        goals = np.stack([self.scene_goals[self.tree_scene(t)][:2] for t in range(self.T)])
+        return self._fallback_launch(lib().ditree_forest_fallback_goals, "forest_fallback_goals", goals)

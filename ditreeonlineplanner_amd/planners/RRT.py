@@ -400,109 +400,23 @@ class RRT_Planner(BasePlanner):
         caller's ``random`` / ``np.random`` / torch generator states are left as they were; the summed collision-check count
         is added to ``common.map_utils.cc_calls`` once.  Scope: the car, run_type 0, one rank, a network sampler or one with
         ``sample_round`` (a plain callable draws from its own generator and cannot be split per run)."""
-        from ._runs import RunStreams, caller_states_kept, draw_runs
-        if self.is_ant:
-            raise NotImplementedError("plan_runs: the car (carmaze) only")
-        if self.run_type != 0:
-            raise NotImplementedError("plan_runs: run_type 0 only (the online re-planning driver plans one run at a time)")
-        if self.world_size > 1:
-            raise NotImplementedError("plan_runs: one rank (a forest is not sharded)")
-        network = hasattr(self.sampler, "ensure_bound")
-        if not network and not hasattr(self.sampler, "sample_round"):
-            raise NotImplementedError("plan_runs: a plain-callable sampler draws from its own generator and cannot be split per run; "
-                                      "give it a sample_round(first_candidate, B, n_chunks, pred_horizon) method")
+        from ._runs import Job, check_forest_scope, run_jobs
+        check_forest_scope(self, "plan_runs")
         seeds = [int(s) for s in seeds]
         if not seeds:
             return []
         T = len(seeds) if concurrent is None else max(1, min(int(concurrent), len(seeds)))
         if tree_capacity is None:
             tree_capacity = self.capacity if self.max_candidates is None else min(self.capacity, int(self.max_candidates) + 1)
-        dev = self.ctx.device
         eng = self._forest_engine(T, int(tree_capacity), T * self.batch)
         self.reset()                                        # env.reset(options) as before every sequential plan()
         eng.reset(self.start_node.state, self.goal_state)
         eng.env_goal = np.asarray(self.env.goal, dtype=np.float64)
-        if network:
+        if hasattr(self.sampler, "ensure_bound"):
             self.sampler.ensure_bound(T * self.batch)
-        shape = (eng.n_chunks, eng.P, eng.ACTION_DIM)
-        K = len(eng.ddpm[0]) if (network and eng.ddpm is not None) else 0
         results = [None] * len(seeds)
-        queue = list(range(len(seeds)))[::-1]
-        slots = [None] * T                                  # per tree: [run index, RunStreams, drawn, start time]
-        steps_dev = torch.zeros(T, dtype=torch.int64, device=dev)
-        total_cc = 0
-
-        def start(t):
-            slots[t] = None
-            if queue:
-                i = queue.pop()
-                eng.reset_tree(t)
-                steps_dev[t] = 0
-                slots[t] = [i, RunStreams(seeds[i], dev), 0, time.time()]
-
-        def finish(t, goal):
-            nonlocal total_cc
-            i, _, _, t0 = slots[t]
-            row = eng.counters(t)
-            node = goal if goal is not None else eng.fallback_node(t)          # RRT.py:227-254
-            elapsed = time.time() - t0
-            path = actions = None
-            if node is not None:
-                path, actions = eng.path_to(t, node)
-            cc = int(steps_dev[t].item())
-            total_cc += cc
-            results[i] = {"seed": seeds[i], "success": path is not None, "goal_reached": goal is not None,
-                          "iterations": int(row[CNT_ITERS]), "time": elapsed, "path": path, "actions": actions,
-                          "number_of_nodes": int(eng.n_nodes_host[t]),
-                          "path_time": None if path is None else len(path) * self.env_dt, "cc_calls": cc}
-            start(t)
-
-        with caller_states_kept():
-            for t in range(T):
-                start(t)
-            while True:
-                # the loop head of plan(): a run goes on while its own wall-clock budget and candidate budget last
-                sizes = [0] * T
-                for t in range(T):
-                    while slots[t] is not None:
-                        _, _, drawn, t0 = slots[t]
-                        if (time.time() - t0) < self.time_budget and (self.max_candidates is None or drawn < self.max_candidates):
-                            sizes[t] = self.batch if self.max_candidates is None else min(self.batch, self.max_candidates - drawn)
-                            break
-                        finish(t, None)
-                if not any(sizes):
-                    break
-                active = [t for t in range(T) if sizes[t] > 0]
-                drawn_sc = draw_runs(self.draw_round, [slots[t][1] for t in active], [sizes[t] for t in active])
-                s = torch.as_tensor(np.concatenate([d[0] for d in drawn_sc]), device=dev)
-                c = torch.as_tensor(np.concatenate([d[1] for d in drawn_sc]), device=dev)
-                B = int(sum(sizes))
-                noise = acts = step_noise = None
-                if network:
-                    # each run's own generator, plan()'s shapes and order: start noise, then the DDPM step noise
-                    noise = torch.empty((B, *shape), dtype=torch.float32, device=dev)
-                    if K:
-                        step_noise = torch.empty((B, eng.n_chunks, K, eng.P, eng.ACTION_DIM), dtype=torch.float32, device=dev)
-                    lo = 0
-                    for t in active:
-                        g = slots[t][1].gen
-                        noise[lo:lo + sizes[t]].normal_(generator=g)
-                        if K:
-                            step_noise[lo:lo + sizes[t]].normal_(generator=g)
-                        lo += sizes[t]
-                else:
-                    acts = torch.cat([self._host_actions(slots[t][2], sizes[t]) for t in active])
-                cnt = eng.expand_round(s, c, noise=noise, inject_actions=acts, counts_per_tree=sizes, step_noise=step_noise)
-                tree_of = torch.as_tensor(np.repeat(np.arange(T), sizes), device=dev)
-                steps_dev.index_add_(0, tree_of, eng.rb.chunk_steps[:B].sum(dim=1, dtype=torch.int64))
-                for t in active:
-                    slots[t][2] += sizes[t]
-                    if int(cnt[t, CNT_GOAL]) >= 0:
-                        finish(t, eng.goal_node(t))
-        from ..common import map_utils as _mu
-        _mu.add_cc_calls(total_cc)                  # the counter the drivers read (run_scenarios.py:338,343), once
+        run_jobs(eng, [Job(self, s, (results, i)) for i, s in enumerate(seeds)], self.batch, self.ctx.device)
         return results
-
 
 
 # ---------------------------------------------------------------------- a scenario set at once
@@ -516,16 +430,9 @@ def _scene_settings(pl):
 
 
 def _check_scene_planners(planners):
+    from ._runs import check_forest_scope
     for pl in planners:
-        if pl.is_ant:
-            raise NotImplementedError("plan_scenario_runs: the car (carmaze) only")
-        if pl.run_type != 0:
-            raise NotImplementedError("plan_scenario_runs: run_type 0 only (the online re-planning driver plans one run at a time)")
-        if pl.world_size > 1:
-            raise NotImplementedError("plan_scenario_runs: one rank (a forest is not sharded)")
-        if not hasattr(pl.sampler, "ensure_bound") and not hasattr(pl.sampler, "sample_round"):
-            raise NotImplementedError("plan_scenario_runs: a plain-callable sampler draws from its own generator and cannot be split "
-                                      "per run; give it a sample_round(first_candidate, B, n_chunks, pred_horizon) method")
+        check_forest_scope(pl, "plan_scenario_runs")
     ref = _scene_settings(planners[0])
     for i, pl in enumerate(planners[1:], 1):
         for (name, a), (_, b) in zip(ref, _scene_settings(pl)):
@@ -551,7 +458,7 @@ def plan_scenario_runs(planners, seeds, concurrent=None, tree_capacity=None):
     summed collision-check count is added to ``common.map_utils.cc_calls`` once.  All planners must share one ctx and one
     sampler object and agree on the round settings (ValueError names the first difference); the scope is ``plan_runs``'."""
     from ..forest import SceneForestEngine
-    from ._runs import RunStreams, caller_states_kept
+    from ._runs import Job, run_jobs
     planners = list(planners)
     if not planners:
         return []
@@ -559,8 +466,8 @@ def plan_scenario_runs(planners, seeds, concurrent=None, tree_capacity=None):
         raise ValueError(f"seeds: one list per planner ({len(planners)}), got {len(seeds)}")
     _check_scene_planners(planners)
     seeds = [[int(s) for s in ss] for ss in seeds]
-    jobs = [(i, k) for i, ss in enumerate(seeds) for k in range(len(ss))]
     results = [[None] * len(ss) for ss in seeds]
+    jobs = [Job(planners[i], s, (results[i], k), (i,)) for i, ss in enumerate(seeds) for k, s in enumerate(ss)]
     if not jobs:
         return results
     p0 = planners[0]
@@ -569,7 +476,6 @@ def plan_scenario_runs(planners, seeds, concurrent=None, tree_capacity=None):
     if tree_capacity is None:
         caps = [pl.capacity if pl.max_candidates is None else min(pl.capacity, int(pl.max_candidates) + 1) for pl in planners]
         tree_capacity = max(caps)
-    dev = ctx.device
     network = hasattr(sampler, "ensure_bound")
     for pl in planners:
         pl.reset()                                           # env.reset(options) as before every sequential plan()
@@ -582,82 +488,5 @@ def plan_scenario_runs(planners, seeds, concurrent=None, tree_capacity=None):
     eng.ddpm = e.ddpm
     if network:
         sampler.ensure_bound(T * batch)
-    shape = (eng.n_chunks, eng.P, eng.ACTION_DIM)
-    K = len(eng.ddpm[0]) if (network and eng.ddpm is not None) else 0
-    queue = jobs[::-1]
-    slots = [None] * T                                       # per tree: [(planner, seed index), RunStreams, drawn, start time]
-    steps_dev = torch.zeros(T, dtype=torch.int64, device=dev)
-    total_cc = 0
-
-    def start(t):
-        slots[t] = None
-        if queue:
-            i, k = queue.pop()
-            eng.reset_tree(t, i)
-            steps_dev[t] = 0
-            slots[t] = [(i, k), RunStreams(seeds[i][k], dev), 0, time.time()]
-
-    def finish(t, goal):
-        nonlocal total_cc
-        (i, k), _, _, t0 = slots[t]
-        row = eng.counters(t)
-        node = goal if goal is not None else eng.fallback_node(t)          # RRT.py:227-254, against the scene's own goal
-        elapsed = time.time() - t0
-        path = actions = None
-        if node is not None:
-            path, actions = eng.path_to(t, node)
-        cc = int(steps_dev[t].item())
-        total_cc += cc
-        results[i][k] = {"seed": seeds[i][k], "success": path is not None, "goal_reached": goal is not None,
-                         "iterations": int(row[CNT_ITERS]), "time": elapsed, "path": path, "actions": actions,
-                         "number_of_nodes": int(eng.n_nodes_host[t]),
-                         "path_time": None if path is None else len(path) * planners[i].env_dt, "cc_calls": cc}
-        start(t)
-
-    with caller_states_kept():
-        for t in range(T):
-            start(t)
-        while True:
-            sizes = [0] * T
-            for t in range(T):
-                while slots[t] is not None:
-                    (i, _), _, drawn, t0 = slots[t]
-                    pl = planners[i]
-                    if (time.time() - t0) < pl.time_budget and (pl.max_candidates is None or drawn < pl.max_candidates):
-                        sizes[t] = batch if pl.max_candidates is None else min(batch, pl.max_candidates - drawn)
-                        break
-                    finish(t, None)
-            if not any(sizes):
-                break
-            active = [t for t in range(T) if sizes[t] > 0]
-            drawn_sc = []
-            for t in active:                                 # each run on its own streams, through its own planner
-                with slots[t][1].active():
-                    drawn_sc.append(planners[slots[t][0][0]].draw_round(int(sizes[t])))
-            s = torch.as_tensor(np.concatenate([d[0] for d in drawn_sc]), device=dev)
-            c = torch.as_tensor(np.concatenate([d[1] for d in drawn_sc]), device=dev)
-            B = int(sum(sizes))
-            noise = acts = step_noise = None
-            if network:
-                noise = torch.empty((B, *shape), dtype=torch.float32, device=dev)
-                if K:
-                    step_noise = torch.empty((B, eng.n_chunks, K, eng.P, eng.ACTION_DIM), dtype=torch.float32, device=dev)
-                lo = 0
-                for t in active:
-                    g = slots[t][1].gen
-                    noise[lo:lo + sizes[t]].normal_(generator=g)
-                    if K:
-                        step_noise[lo:lo + sizes[t]].normal_(generator=g)
-                    lo += sizes[t]
-            else:
-                acts = torch.cat([planners[slots[t][0][0]]._host_actions(slots[t][2], sizes[t]) for t in active])
-            cnt = eng.expand_round(s, c, noise=noise, inject_actions=acts, counts_per_tree=sizes, step_noise=step_noise)
-            tree_of = torch.as_tensor(np.repeat(np.arange(T), sizes), device=dev)
-            steps_dev.index_add_(0, tree_of, eng.rb.chunk_steps[:B].sum(dim=1, dtype=torch.int64))
-            for t in active:
-                slots[t][2] += sizes[t]
-                if int(cnt[t, CNT_GOAL]) >= 0:
-                    finish(t, eng.goal_node(t))
-    from ..common import map_utils as _mu
-    _mu.add_cc_calls(total_cc)                   # the counter the drivers read (run_scenarios.py:338,343), once
+    run_jobs(eng, jobs, batch, ctx.device)
     return results

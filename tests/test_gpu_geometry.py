@@ -289,3 +289,75 @@ def test_prop_duration_schedule_rounds_vs_oracle(ctx, batch, early_exit):
     assert np.array_equal(eng.tree.num_visit[: len(pl.tree)].cpu().numpy(), np.array(pl.tree.num_visit))
     lens = np.array([0 if e is None else len(e) for e in pl.tree.edge_actions])
     assert np.array_equal(eng.tree.edge_nactions[: len(pl.tree)].cpu().numpy()[1:], lens[1:])
+
+
+# ------------------------------------------------------------------------------------------ the pool scheduler's accounting
+def _pool_restatement(final, quantum=64):
+    """The early-exit pool scheduler's rule replayed from a round's final ``chunks_run``: the ready list is the candidates with
+    chunks still to run, ordered by chunks finished and then by index; a call takes everything when less than one quantum is
+    ready, else the largest multiple of the quantum from the head.  -> (calls, waves, rows taken per call, rows ready per call)."""
+    final = np.asarray(final)
+    done = np.zeros_like(final)
+    order = np.arange(len(final))
+    calls = waves = 0
+    taken, ready_n = [], []
+    while True:
+        ready = [b for b in np.lexsort((order, done)) if done[b] < final[b]]
+        n = len(ready)
+        if n == 0:
+            return calls, waves, taken, ready_n
+        take = n if n < quantum else (n // quantum) * quantum
+        done[ready[:take]] += 1
+        calls += 1
+        waves += -(-take // quantum)
+        taken.append(take)
+        ready_n.append(n)
+
+
+def _assert_pool_stats(ctx, final, n_chunks):
+    calls, waves, taken, ready_n = _pool_restatement(final)
+    rs = ctx.round_stats()
+    print("round_stats", rs, "restated", calls, waves, "taken", taken, "ready", ready_n)
+    assert (rs["denoiser_calls"], rs["tile_waves"]) == (calls, waves)
+    return (final < n_chunks).any() and any(t < n for t, n in zip(taken, ready_n))
+
+
+def test_pool_scheduler_accounting_car_tape_round(ctx):
+    """ditree_round_stats after early-exit action-tape rounds of B = 200 = 3 * 64 + 8 candidates with four chunks (quantum 64
+    for tapes) equals the rule restated from each round's own final chunks_run.  The first two rounds grow the tree from the
+    root (nobody collides within 32 steps of the start); in the third, tape seed 99 ends candidates after 1, 2 and 3 chunks
+    (oracle/rrt.py: 35 / 1 / 3 of 200) and every first call takes 192 of 200 ready rows -- asserted below, so a wrong ``take``
+    or ready order cannot pass unseen."""
+    from ditreeonlineplanner_amd.engine import ExpansionEngine
+    maze = load_maze("boxes")
+    start = np.array([*G.cell_rowcol_to_xy([17, 2], maze), np.deg2rad(45.0), 0, 0, 0])
+    goal = np.array([*G.cell_rowcol_to_xy([2, 17], maze), 0, 0, 0, 0])
+    B = 200
+    eng = ExpansionEngine(ctx, maze, start, goal, edge_length=32, batch=B, capacity=4096, early_exit=True)
+    assert eng.n_chunks == 4
+    rt, at = ORRT.RandomTape(42), ActionTape(99)
+    for k in range(3):
+        s, c = rt.draw_round(B, maze.shape[1], maze.shape[0], goal)
+        acts = np.stack([at.actions(np.arange(k * B, (k + 1) * B), j) for j in range(eng.n_chunks)], axis=1)
+        eng.expand_round(dev(s), dev(c), inject_actions=dev(acts))
+        sees = _assert_pool_stats(ctx, eng.rb.chunks_run[:B].cpu().numpy(), eng.n_chunks)
+    assert sees                                     # the third round: early enders and a call shorter than its ready list
+
+
+def test_pool_scheduler_accounting_ant_tape_round(ctx):
+    """The same for one ant tape round (24 chunks): 200 - 3 * 64 = 8 rows remain after the first call."""
+    from tests.test_gpu_ant_round import _engine
+    from tests.test_oracle_ant import trace_setup
+    from oracle import ant as OA
+    g, pre, _, atape, otape, m = trace_setup("tape_boxes")
+    B = 200
+    eng = _engine(ctx, g, pre, m, B, "tape", early_exit=True)
+    tape = ORRT.RandomTape(42)
+    H, W = m["maze"].shape
+    s, c = np.zeros((B, 29)), np.zeros((B, 2))
+    for i in range(B):
+        s[i], c[i] = OA.draw_candidate_ant(tape, W, H, 4.0, g[pre + "goal"])
+    cand = np.arange(B)
+    acts = np.stack([atape.actions(cand, j) for j in range(eng.n_chunks)], axis=1)
+    eng.expand_round(dev(s), dev(c), inject_actions=dev(acts), next_obs_tape=dev(otape.rows(cand)))
+    assert _assert_pool_stats(ctx, eng.rb.chunks_run[:B].cpu().numpy(), eng.n_chunks)

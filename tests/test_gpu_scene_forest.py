@@ -262,3 +262,28 @@ def test_plan_scenario_runs_equals_sequential_seeded_plans_tape():
     planners = [_scenario_planner(sampler, k, batch=8, max_candidates=40) for k in (0, 1, 2)]
     runs = check_scenario_runs_equal_sequential(planners, [[11, 12], [13, 14], [15]], concurrent=2)
     assert any(r["goal_reached"] for r in runs[0])
+
+
+def test_plan_scenario_runs_of_one_planner_equals_its_plan_runs():
+    """The shared run loop on both engine kinds: ``plan_scenario_runs([pl], [seeds])`` (a SceneForestEngine) equals
+    ``pl.plan_runs(seeds)`` (a ForestEngine) run for run -- both are tied to sequential ``plan()`` by the tests above and in
+    test_gpu_forest."""
+    from ditreeonlineplanner_amd.planners.RRT import plan_scenario_runs
+
+    class Tape:
+        def __init__(self):
+            self.tape = ActionTape(5)
+
+        def sample_round(self, first, B, n_chunks, P):
+            return np.stack([self.tape.actions(np.arange(first, first + B), j) for j in range(n_chunks)], axis=1)
+    pl = _scenario_planner(Tape(), 0, batch=8, max_candidates=40)
+    seeds = [11, 12, 13, 14]
+    want = pl.plan_runs(seeds, concurrent=2)
+    (got,) = plan_scenario_runs([pl], [seeds], concurrent=2)
+    assert [r["seed"] for r in got] == seeds == [r["seed"] for r in want]
+    for r, q in zip(got, want):
+        for k in ("iterations", "number_of_nodes", "cc_calls", "success", "goal_reached"):
+            assert r[k] == q[k], (r["seed"], k, r[k], q[k])
+        for k in ("path", "actions"):
+            assert (r[k] is None) == (q[k] is None) and (r[k] is None or np.array_equal(r[k], q[k])), (r["seed"], k)
+    assert all(r["iterations"] > 0 for r in got) and any(r["goal_reached"] for r in got)
