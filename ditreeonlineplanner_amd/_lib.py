@@ -182,6 +182,10 @@ SIGNATURES = {
     "ditree_forest_expand_round_scenes": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), C.POINTER(ForestScenes), C.POINTER(Round),
                                                  C.POINTER(RoundParams), _vp]),
     "ditree_forest_fallback_goals": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), _pd, _vp, _vp]),
+    "ditree_forest_expand_round_ant": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), C.POINTER(Round), C.POINTER(AntRoundParams),
+                                              _vp]),
+    "ditree_forest_accept_ant": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), C.POINTER(Round), _vp]),
+    "ditree_forest_fallback_ant": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), _pd, _vp, _vp]),
 }
 
 _LIB = None

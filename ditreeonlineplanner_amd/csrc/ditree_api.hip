@@ -637,13 +637,15 @@ static int ensure_ant_scratch(ditree_ctx* ctx, int B, int P, int lm) {
   return DITREE_OK;
 }
 
-int32_t ditree_ant_round_begin(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round,
-                               const ditree_ant_round_params* p, void* stream) {
+// The begin step of an ant round on one tree, or (f != NULL, validated by the caller) on a forest: only the nearest-node search
+// differs -- the first p->n_nodes nodes, or each candidate's own tree up to its counter row's node count.
+static int ant_round_begin_impl(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* f, const ditree_round* round,
+                                const ditree_ant_round_params* p, void* stream) {
   if (!ctx) return DITREE_E_ARG;
   int P = 0;
   int rc = check_ant_round(ctx, tree, round, p, 0, &P);
   if (rc) return rc;
-  if (!p->samples || p->n_nodes <= 0 || p->n_nodes > tree->capacity)
+  if (!p->samples || (!f && (p->n_nodes <= 0 || p->n_nodes > tree->capacity)))
     return set_err(ctx, DITREE_E_ARG, "ant_round_begin: samples / n_nodes");
   const int B = round->B;
   if (B == 0) return DITREE_OK;
@@ -653,13 +655,22 @@ int32_t ditree_ant_round_begin(ditree_ctx* ctx, const ditree_tree* tree, const d
   if (rc) return rc;
   launch_round_begin(round->status, round->chunks_run, round->chunk_steps, B, tree->n_chunks, s);
   // RRT.py:141-147: nearest node -> curr_state (the live state of the round: round->end_state), prev_actions, prev_states
-  launch_nn_argmin(p->samples, ANT_S, B, tree->xy, p->n_nodes, round->parent, tree->state, tree->last_action, tree->has_prev,
-                   round->end_state, ctx->ant_prev, ctx->ant_hasprev, s, ANT_S, ANT_D);
-  launch_ant_gather_hist(round->parent, tree->hist, tree->hist_n, B, ctx->ant_hist, ctx->ant_hist_n, s);
+  if (f)
+    launch_nn_forest(p->samples, ANT_S, B, tree->xy, f->off, f->n_trees, f->counters, f->tree_capacity, 0, round->parent, tree->state,
+                     tree->last_action, tree->has_prev, round->end_state, ctx->ant_prev, ctx->ant_hasprev, s, ANT_S, ANT_D);
+  else
+    launch_nn_argmin(p->samples, ANT_S, B, tree->xy, p->n_nodes, round->parent, tree->state, tree->last_action, tree->has_prev,
+                     round->end_state, ctx->ant_prev, ctx->ant_hasprev, s, ANT_S, ANT_D);
+  launch_ant_gather_hist(round->parent, tree->hist, tree->hist_n, B, ctx->ant_hist, ctx->ant_hist_n, s);   // parents are global ids
   ctx->ant_n_run = B;
   ctx->ant_run_idx = nullptr;
   HIP_TRY(ctx, hipGetLastError());
   return DITREE_OK;
+}
+
+int32_t ditree_ant_round_begin(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round,
+                               const ditree_ant_round_params* p, void* stream) {
+  return ant_round_begin_impl(ctx, tree, nullptr, round, p, stream);
 }
 
 int32_t ditree_ant_chunk_sample(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round,
@@ -766,8 +777,9 @@ int32_t ditree_ant_chunk_step(ditree_ctx* ctx, const ditree_tree* tree, const di
   return ant_chunk_step_impl(ctx, tree, round, p, j, next_obs, (int64_t)tree->A * ANT_S, nullptr, (hipStream_t)stream);
 }
 
-int32_t ditree_expand_round_ant(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round,
-                                const ditree_ant_round_params* p, void* stream) {
+// The ant round of one tree, or (f != NULL, validated by the caller) of a forest: only the begin step differs.
+static int expand_round_ant_impl(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* f, const ditree_round* round,
+                                 const ditree_ant_round_params* p, void* stream) {
   if (!ctx) return DITREE_E_ARG;
   int P = 0;
   int rc = check_ant_round(ctx, tree, round, p, 1, &P);
@@ -784,7 +796,7 @@ int32_t ditree_expand_round_ant(ditree_ctx* ctx, const ditree_tree* tree, const 
   } else {
     return set_err(ctx, DITREE_E_ARG, "expand_round_ant: dynamics must be DITREE_ANT_DYN_TAPE or DITREE_ANT_DYN_MODEL");
   }
-  rc = ditree_ant_round_begin(ctx, tree, round, p, stream);
+  rc = ant_round_begin_impl(ctx, tree, f, round, p, stream);
   if (rc) return rc;
   const int nC = tree->n_chunks, A = tree->A;
   if (p->early_exit && round->B > 0) {
@@ -840,6 +852,11 @@ int32_t ditree_expand_round_ant(ditree_ctx* ctx, const ditree_tree* tree, const 
     if (rc) return rc;
   }
   return DITREE_OK;
+}
+
+int32_t ditree_expand_round_ant(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round,
+                                const ditree_ant_round_params* p, void* stream) {
+  return expand_round_ant_impl(ctx, tree, nullptr, round, p, stream);
 }
 
 int32_t ditree_chunk_budget(ditree_ctx* ctx, const ditree_tree* tree, const double* samples, int32_t B, int32_t n_nodes,
@@ -1006,7 +1023,8 @@ int32_t ditree_expand_round(ditree_ctx* ctx, const ditree_tree* tree, const ditr
 
 // ---- forests (include/ditree.h "forests"): every check runs on the host before anything is launched.
 // B >= 0: the round's candidate count must equal off[T]; B < 0: the offsets are not read.
-static int check_forest(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* f, int B, const char* what) {
+// ant: the tree must be an ant forest's (check_ant_forest) instead of a car tree.
+static int check_forest(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* f, int B, const char* what, bool ant = false) {
   const std::string w(what);
   int rc = check_tree(ctx, tree);
   if (rc) return rc;
@@ -1015,8 +1033,14 @@ static int check_forest(ditree_ctx* ctx, const ditree_tree* tree, const ditree_f
   if ((int64_t)f->n_trees * f->tree_capacity > tree->capacity)
     return set_err(ctx, DITREE_E_ARG, w + ": n_trees * tree_capacity = " + std::to_string((int64_t)f->n_trees * f->tree_capacity) +
                    " exceeds the tree's capacity " + std::to_string(tree->capacity));
-  if (tree->state_dim != 6 || tree->action_dim != 2)
+  if (ant) {
+    if (tree->state_dim != ANT_S || tree->action_dim != ANT_D || !tree->hist || !tree->hist_n)
+      return set_err(ctx, DITREE_E_ARG, w + ": an ant forest is an ant tree (state_dim 29, action_dim 8, hist and hist_n present)");
+    if (tree->obstacle_ahead)
+      return set_err(ctx, DITREE_E_ARG, w + ": an ant forest is one rank's run_type-0 tree (no obstacle flags)");
+  } else if (tree->state_dim != 6 || tree->action_dim != 2) {
     return set_err(ctx, DITREE_E_ARG, w + ": a forest is a car tree (state_dim 6, action_dim 2)");
+  }
   if (B < 0) return DITREE_OK;
   if (!f->off || !f->off_host) return set_err(ctx, DITREE_E_ARG, w + ": forest offsets (off, off_host) missing");
   if (f->off_host[0] != 0) return set_err(ctx, DITREE_E_ARG, w + ": off[0] must be 0");
@@ -1203,6 +1227,55 @@ int32_t ditree_forest_fallback_goals(ditree_ctx* ctx, const ditree_tree* tree, c
   if (!goal_xy) return set_err(ctx, DITREE_E_ARG, "forest_fallback_goals: goals array (T, 2) missing");
   if (!out_node) return set_err(ctx, DITREE_E_ARG, "forest_fallback_goals: out_node missing");
   return forest_fallback_impl(ctx, tree, forest, goal_xy, out_node, (hipStream_t)stream);
+}
+
+// ---- ant forests (include/ditree.h "ant forests")
+// The check of the three ant forest calls: an ant tree with hist, no obstacle flags, an unsharded round, the descriptor and
+// the offsets as check_forest validates them.  round == NULL: a call without a round (the fallback; B < 0, offsets not read).
+static int check_ant_forest(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* f, const ditree_round* round,
+                            const char* what) {
+  int rc = round ? check_round(ctx, round) : DITREE_OK;
+  if (rc) return rc;
+  rc = check_forest(ctx, tree, f, round ? round->B : -1, what, true);
+  if (rc) return rc;
+  if (round && round->shard > 0)
+    return set_err(ctx, DITREE_E_ARG, std::string(what) + ": an ant forest is one rank's run_type-0 tree (no shards)");
+  return DITREE_OK;
+}
+
+// planners/RRT.py:131-194 for the candidates of every run of an ant forest
+int32_t ditree_forest_expand_round_ant(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
+                                       const ditree_round* round, const ditree_ant_round_params* p, void* stream) {
+  if (!ctx) return DITREE_E_ARG;
+  const int rc = check_ant_forest(ctx, tree, forest, round, "forest_expand_round_ant");
+  if (rc) return rc;
+  return expand_round_ant_impl(ctx, tree, forest, round, p, stream);
+}
+
+// planners/RRT.py:195-217 per tree; the commit's `hist` branch writes every new node's history rows
+int32_t ditree_forest_accept_ant(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const ditree_round* round,
+                                 void* stream) {
+  if (!ctx) return DITREE_E_ARG;
+  const int rc = check_ant_forest(ctx, tree, forest, round, "forest_accept_ant");
+  if (rc) return rc;
+  if (round->B == 0) return DITREE_OK;
+  const AheadArg ts = ahead_samples();               // not read: the tree has no obstacle flags
+  launch_forest_accept(*tree, *round, forest->off, forest->counters, forest->n_trees, forest->tree_capacity, 0, ctx->maze, ctx->rows,
+                       ctx->cols, ts, (hipStream_t)stream);
+  HIP_TRY(ctx, hipGetLastError());
+  return DITREE_OK;
+}
+
+// planners/RRT.py:227-254 (run_type 0) for every tree of an ant forest
+int32_t ditree_forest_fallback_ant(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const double* goal_xy,
+                                   int32_t* out_node, void* stream) {
+  if (!ctx) return DITREE_E_ARG;
+  const int rc = check_ant_forest(ctx, tree, forest, nullptr, "forest_fallback_ant");
+  if (rc) return rc;
+  if (!goal_xy || !out_node) return set_err(ctx, DITREE_E_ARG, "forest_fallback_ant: bad argument");
+  std::vector<double> q((size_t)forest->n_trees * 2);   // T copies of the goal as the queries
+  for (int t = 0; t < forest->n_trees; ++t) { q[(size_t)t * 2] = goal_xy[0]; q[(size_t)t * 2 + 1] = goal_xy[1]; }
+  return forest_fallback_impl(ctx, tree, forest, q.data(), out_node, (hipStream_t)stream);
 }
 
 }  // extern "C"

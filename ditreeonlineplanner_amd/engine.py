@@ -610,14 +610,7 @@ class AntExpansionEngine(ExpansionEngine):
         rp.cond_out = cond_out[lo:hi].data_ptr() if (cond_out is not None and n) else None
         return rp, keep
 
-    def expand_round(self, samples, cond_goal, noise=None, inject_actions=None, accept=True, next_obs_tape=None, step_fn=None,
-                     cond_out=None, step_noise=None):
-        """samples (B, 29) f64, cond_goal (B, 2) f64, noise (B, n_chunks, P, 8) f32 or inject_actions (B, n_chunks, P, 8) f64
-        [device tensors, all candidates of the round]; next_obs_tape (B, n_chunks, A, 29) f64 for dynamics='tape'; step_fn for
-        dynamics='host'; cond_out (B, n_chunks, 97) f32: receives every sampler call's conditioning vector (tests)."""
-        B = samples.shape[0]
-        if B > self.batch:
-            raise ValueError(f"round of {B} candidates exceeds engine batch {self.batch}")
+    def _check_round_shapes(self, B, samples, cond_goal, noise, inject_actions, next_obs_tape):
         if tuple(samples.shape) != (B, 29) or tuple(cond_goal.shape) != (B, 2):
             raise ValueError("samples must be (B, 29), cond_goal (B, 2)")
         shape = (B, self.n_chunks, self.P, 8)
@@ -626,6 +619,16 @@ class AntExpansionEngine(ExpansionEngine):
                 raise ValueError(f"{nm} must be {shape}, got {tuple(t.shape)}")
         if self.dynamics == "tape" and (next_obs_tape is None or tuple(next_obs_tape.shape) != (B, self.n_chunks, self.A, 29)):
             raise ValueError(f"dynamics='tape': next_obs_tape must be ({B}, {self.n_chunks}, {self.A}, 29)")
+
+    def expand_round(self, samples, cond_goal, noise=None, inject_actions=None, accept=True, next_obs_tape=None, step_fn=None,
+                     cond_out=None, step_noise=None):
+        """samples (B, 29) f64, cond_goal (B, 2) f64, noise (B, n_chunks, P, 8) f32 or inject_actions (B, n_chunks, P, 8) f64
+        [device tensors, all candidates of the round]; next_obs_tape (B, n_chunks, A, 29) f64 for dynamics='tape'; step_fn for
+        dynamics='host'; cond_out (B, n_chunks, 97) f32: receives every sampler call's conditioning vector (tests)."""
+        B = samples.shape[0]
+        if B > self.batch:
+            raise ValueError(f"round of {B} candidates exceeds engine batch {self.batch}")
+        self._check_round_shapes(B, samples, cond_goal, noise, inject_actions, next_obs_tape)
         if self.dynamics == "host" and step_fn is None:
             raise ValueError("dynamics='host': step_fn is required")
         lo, hi, per = self.shard(B)

@@ -9,8 +9,10 @@ nearest-node search (segmented by tree), accept / commit (one work-group per tre
 visit count and the fallback choice.  Every per-candidate kernel is the single-tree round's, and its result does not depend on
 the batch, so each tree grows exactly as it would in its own ``ExpansionEngine`` fed the same rows.
 
-Scope: the car, run_type 0, one GPU, one maze / start / goal for every tree -- or, in a ``SceneForestEngine``, each tree on
+Scope: run_type 0, one GPU.  The car: one maze / start / goal for every tree -- or, in a ``SceneForestEngine``, each tree on
 its own scene (maze, start, goal) of a scenario set (run_scenarios.py:203-250), the mazes in one scene table on the device.
+The ant (BASELINE config 3): ``AntForestEngine``, one maze / start / goal, tape or model dynamics (a host-stepped simulator
+steps one candidate at a time and has no forest form).  ``ForestTrees`` holds what both share.
 """
 from __future__ import annotations
 
@@ -20,19 +22,22 @@ import numpy as np
 import torch
 
 from ._lib import MAX_ATLAS_CELLS, MAX_SCENES, Forest, ForestScenes, RoundParams, check, lib
-from .engine import CNT_GOAL, CNT_NODES, CNT_PHANTOM, ExpansionEngine, env_goal_of, tree_path
+from .engine import CNT_GOAL, CNT_NODES, CNT_PHANTOM, AntExpansionEngine, ExpansionEngine, env_goal_of, tree_path
 from .ops import CAR_NORM, Context, _dbl
 
 
-class ForestEngine(ExpansionEngine):
-    """T independent car trees of ``tree_capacity`` node slots, expanded together.  Node numbers in this class's results
-    (``goal_node``, ``fallback_node``, ``path_to``, ``tree_snapshot``) are LOCAL to their tree (root = 0), as a single-tree
-    engine reports them; the device arrays (``tree.parent``, ``counters``' goal node, the round's ``node_id``) hold global
-    slot numbers."""
+class ForestTrees:
+    """The per-tree bookkeeping of a forest, mixed in over a single-tree engine (``ExpansionEngine`` for the car,
+    ``AntExpansionEngine`` for the ant): the (T, 8) counter block and the candidate offsets, ``reset`` / ``reset_tree``, the
+    accept and the per-tree results.  Node numbers in its results (``goal_node``, ``fallback_node``, ``path_to``,
+    ``tree_snapshot``) are LOCAL to their tree (root = 0), as a single-tree engine reports them; the device arrays
+    (``tree.parent``, ``counters``' goal node, the round's ``node_id``) hold global slot numbers.  The engine class names its
+    entry points: ``_ACCEPT`` / ``_FALLBACK`` = (symbol, what) and ``_accept_args`` (what follows the round descriptor)."""
+    _ACCEPT = ("ditree_forest_accept", "forest_accept")
+    _FALLBACK = ("ditree_forest_fallback", "forest_fallback")
 
-    def __init__(self, ctx: Context, maze, start_state, goal_state, n_trees, tree_capacity, edge_length=64, action_horizon=8,
-                 pred_horizon=64, local_map_size=20, local_map_scale=0.2, s_global=1.0, batch=1024, k_steps=1,
-                 emulate_sticky_done=True, norm=CAR_NORM, early_exit=False, goal_scale=None, prop_duration=None):
+    def _init_forest(self, ctx, n_trees, tree_capacity):
+        """Before the engine's own constructor (which ends in ``reset``): -> the capacity of the one device tree."""
         T, Cap = int(n_trees), int(tree_capacity)
         if T < 1 or Cap < 1:
             raise ValueError("a forest needs n_trees >= 1 and tree_capacity >= 1")
@@ -46,11 +51,7 @@ class ForestEngine(ExpansionEngine):
         self.n_nodes_host = np.ones(T, dtype=np.int64)
         self.cnt_host = np.zeros((T, 8), dtype=np.int32)
         self.fdesc = Forest(T, Cap, self.fcounters.data_ptr(), self.off_dev.data_ptr(), self.off_host)
-        super().__init__(ctx, maze, start_state, goal_state, edge_length=edge_length, action_horizon=action_horizon,
-                         pred_horizon=pred_horizon, local_map_size=local_map_size, local_map_scale=local_map_scale,
-                         s_global=s_global, batch=batch, capacity=T * Cap, k_steps=k_steps,
-                         emulate_sticky_done=emulate_sticky_done, norm=norm, early_exit=early_exit, run_type=0,
-                         goal_scale=goal_scale, prop_duration=prop_duration)
+        return T * Cap
 
     # ------------------------------------------------------------------ state
     def reset(self, start_state, goal_state):
@@ -81,6 +82,10 @@ class ForestEngine(ExpansionEngine):
         tr.edge_nstates[r] = 0
         tr.edge_nactions[r] = 0
         tr.edge_owner[r] = -1
+        if tr.hist is not None:                       # the ant: the root's history, as DeviceTree.reset leaves it
+            tr.hist[r].zero_()
+            tr.hist[r, 2] = s
+            tr.hist_n[r] = 1
         self.fcounters[t] = self._root_row
         self.cnt_host[t] = self._ROOT
         self.n_nodes_host[t] = 1
@@ -114,12 +119,8 @@ class ForestEngine(ExpansionEngine):
         self.off_dev.copy_(torch.from_numpy(off.astype(np.int32)))
         return off
 
-    def expand_round(self, samples, cond_goal, noise=None, inject_actions=None, counts_per_tree=None, step_noise=None,
-                     accept=True):
-        """samples (B, 6) f64, cond_goal (B, 2) f64, noise (B, n_chunks, P, 2) f32 or inject_actions (B, n_chunks, P, 2) f64,
-        step_noise (B, n_chunks, K, P, 2) f32 with ``self.ddpm`` [device tensors]: the rows of tree t are
-        [off[t], off[t+1]), off = the running sum of ``counts_per_tree`` (T,), each tree's rows in its run's own order.
-        Returns the (T, 8) counter block after the accept."""
+    def _begin_round(self, samples, cond_goal, counts_per_tree):
+        """The head of every forest round: the offsets of ``counts_per_tree`` on the host and the device -> B = their sum."""
         if counts_per_tree is None:
             raise ValueError("counts_per_tree is required (T entries, the candidates of each tree this round)")
         off = self._set_offsets(counts_per_tree)
@@ -128,34 +129,23 @@ class ForestEngine(ExpansionEngine):
             raise ValueError(f"samples / cond_goal must have sum(counts_per_tree) = {B} rows")
         if B > self.batch:
             raise ValueError(f"round of {B} candidates exceeds engine batch {self.batch}")
-        if B == 0:                                    # no tree has a candidate: nothing to expand or accept
-            return self.cnt_host.copy() if accept else None
-        self.ensure_maze()
-        rp = RoundParams()
-        keep = self._round_params(rp, samples, cond_goal, noise, inject_actions, step_noise, 0, B)
-        self._launch_round(self.rb.desc(0, B), rp)
-        del keep
-        self._used_denoiser = noise is not None
+        return B
+
+    def _end_round(self, B, used_denoiser, accept):
+        self._used_denoiser = bool(used_denoiser)
         self._B = B
         return self.accept(B) if accept else None
 
-    def _chunk_budget(self, samples, B):
-        h = self.ctx._h
-        check(h, lib().ditree_forest_chunk_budget(h, C.byref(self.tree.desc), C.byref(self.fdesc), samples.data_ptr(), B,
-                                                  self._sched_chunks, len(self.schedule), self._budget_parent.data_ptr(),
-                                                  self._budget.data_ptr(), self.ctx.stream), "forest_chunk_budget")
-
-    def _launch_round(self, rd, rp):
-        h = self.ctx._h
-        check(h, lib().ditree_forest_expand_round(h, C.byref(self.tree.desc), C.byref(self.fdesc), C.byref(rd), C.byref(rp),
-                                                  self.ctx.stream), "forest_expand_round")
+    def _accept_args(self):
+        return (self.sticky,)
 
     def accept(self, B=None):
         B = self._B if B is None else int(B)
         self.ensure_maze()
         rd = self.rb.desc(0, B)
-        check(self.ctx._h, lib().ditree_forest_accept(self.ctx._h, C.byref(self.tree.desc), C.byref(self.fdesc), C.byref(rd),
-                                                       self.sticky, self.ctx.stream), "forest_accept")
+        entry, what = self._ACCEPT
+        check(self.ctx._h, getattr(lib(), entry)(self.ctx._h, C.byref(self.tree.desc), C.byref(self.fdesc), C.byref(rd),
+                                                 *self._accept_args(), self.ctx.stream), what)
         cnt = self.read_counters().copy()             # one small D2H per round: every tree's row
         self._range_guard()
         return cnt
@@ -183,7 +173,8 @@ class ForestEngine(ExpansionEngine):
     def fallback_nodes(self):
         """planners/RRT.py:227-254 (run_type 0) for every tree in one launch: local node nearest to the goal among nodes 1..,
         None for a tree that holds only its root."""
-        return self._fallback_launch(lib().ditree_forest_fallback, "forest_fallback", self.goal_state[:2])
+        entry, what = self._FALLBACK
+        return self._fallback_launch(getattr(lib(), entry), what, self.goal_state[:2])
 
     def _fallback_launch(self, entry, what, goals):
         """``entry`` (one of the two forest fallback calls) on its goal array -> each tree's local node id or None."""
@@ -213,6 +204,92 @@ class ForestEngine(ExpansionEngine):
 
     def shard(self, B):                               # one rank
         return 0, B, B
+
+
+class ForestEngine(ForestTrees, ExpansionEngine):
+    """T independent car trees of ``tree_capacity`` node slots, expanded together (per-tree surface: ``ForestTrees``)."""
+
+    def __init__(self, ctx: Context, maze, start_state, goal_state, n_trees, tree_capacity, edge_length=64, action_horizon=8,
+                 pred_horizon=64, local_map_size=20, local_map_scale=0.2, s_global=1.0, batch=1024, k_steps=1,
+                 emulate_sticky_done=True, norm=CAR_NORM, early_exit=False, goal_scale=None, prop_duration=None):
+        capacity = self._init_forest(ctx, n_trees, tree_capacity)
+        super().__init__(ctx, maze, start_state, goal_state, edge_length=edge_length, action_horizon=action_horizon,
+                         pred_horizon=pred_horizon, local_map_size=local_map_size, local_map_scale=local_map_scale,
+                         s_global=s_global, batch=batch, capacity=capacity, k_steps=k_steps,
+                         emulate_sticky_done=emulate_sticky_done, norm=norm, early_exit=early_exit, run_type=0,
+                         goal_scale=goal_scale, prop_duration=prop_duration)
+
+    def expand_round(self, samples, cond_goal, noise=None, inject_actions=None, counts_per_tree=None, step_noise=None,
+                     accept=True):
+        """samples (B, 6) f64, cond_goal (B, 2) f64, noise (B, n_chunks, P, 2) f32 or inject_actions (B, n_chunks, P, 2) f64,
+        step_noise (B, n_chunks, K, P, 2) f32 with ``self.ddpm`` [device tensors]: the rows of tree t are
+        [off[t], off[t+1]), off = the running sum of ``counts_per_tree`` (T,), each tree's rows in its run's own order.
+        Returns the (T, 8) counter block after the accept."""
+        B = self._begin_round(samples, cond_goal, counts_per_tree)
+        if B == 0:                                    # no tree has a candidate: nothing to expand or accept
+            return self.cnt_host.copy() if accept else None
+        self.ensure_maze()
+        rp = RoundParams()
+        keep = self._round_params(rp, samples, cond_goal, noise, inject_actions, step_noise, 0, B)
+        self._launch_round(self.rb.desc(0, B), rp)
+        del keep
+        return self._end_round(B, noise is not None, accept)
+
+    def _chunk_budget(self, samples, B):
+        h = self.ctx._h
+        check(h, lib().ditree_forest_chunk_budget(h, C.byref(self.tree.desc), C.byref(self.fdesc), samples.data_ptr(), B,
+                                                  self._sched_chunks, len(self.schedule), self._budget_parent.data_ptr(),
+                                                  self._budget.data_ptr(), self.ctx.stream), "forest_chunk_budget")
+
+    def _launch_round(self, rd, rp):
+        h = self.ctx._h
+        check(h, lib().ditree_forest_expand_round(h, C.byref(self.tree.desc), C.byref(self.fdesc), C.byref(rd), C.byref(rp),
+                                                  self.ctx.stream), "forest_expand_round")
+
+
+class AntForestEngine(ForestTrees, AntExpansionEngine):
+    """T independent ant trees (BASELINE config 3: 29-d states, 8-d actions, every node's three history rows) of
+    ``tree_capacity`` node slots, expanded together: ``AntExpansionEngine``'s round settings and dynamics ("tape" | "model")
+    with ``ForestTrees``' per-tree surface.  Each tree grows exactly as in its own ``AntExpansionEngine`` fed the same rows.
+    The ant env has no sticky-done latch, so no tree ever has a phantom candidate."""
+    _ACCEPT = ("ditree_forest_accept_ant", "forest_accept_ant")
+    _FALLBACK = ("ditree_forest_fallback_ant", "forest_fallback_ant")
+
+    def __init__(self, ctx: Context, maze, start_state, goal_state, n_trees, tree_capacity, desired_goal=None, norm=None,
+                 edge_length=48, action_horizon=2, pred_horizon=16, local_map_size=16, local_map_scale=0.8, s_global=4.0,
+                 batch=4096, k_steps=1, early_exit=False, goal_scale=None, dynamics="tape", model=None, ball_radius=1.2,
+                 goal_factor=0.45):
+        if dynamics not in ("tape", "model"):
+            raise ValueError("an ant forest's dynamics must be 'tape' or 'model' (a host-stepped round has no forest form)")
+        capacity = self._init_forest(ctx, n_trees, tree_capacity)
+        super().__init__(ctx, maze, start_state, goal_state, desired_goal=desired_goal, norm=norm, edge_length=edge_length,
+                         action_horizon=action_horizon, pred_horizon=pred_horizon, local_map_size=local_map_size,
+                         local_map_scale=local_map_scale, s_global=s_global, batch=batch, capacity=capacity, k_steps=k_steps,
+                         early_exit=early_exit, goal_scale=goal_scale, dynamics=dynamics, model=model, ball_radius=ball_radius,
+                         goal_factor=goal_factor)
+
+    def _accept_args(self):
+        return ()
+
+    def expand_round(self, samples, cond_goal, noise=None, inject_actions=None, counts_per_tree=None, step_noise=None,
+                     accept=True, next_obs_tape=None, cond_out=None):
+        """samples (B, 29) f64, cond_goal (B, 2) f64, noise (B, n_chunks, P, 8) f32 or inject_actions (B, n_chunks, P, 8) f64,
+        step_noise (B, n_chunks, K, P, 8) f32 with ``self.ddpm``, next_obs_tape (B, n_chunks, A, 29) f64 for
+        dynamics='tape', cond_out (B, n_chunks, 97) f32 (tests) [device tensors]: the rows of tree t are [off[t], off[t+1]),
+        off = the running sum of ``counts_per_tree`` (T,), each tree's rows in its run's own order.  Returns the (T, 8)
+        counter block after the accept."""
+        B = self._begin_round(samples, cond_goal, counts_per_tree)
+        if B == 0:
+            return self.cnt_host.copy() if accept else None
+        self._check_round_shapes(B, samples, cond_goal, noise, inject_actions, next_obs_tape)
+        self.ensure_maze()
+        rp, keep = self._params(samples, cond_goal, noise, inject_actions, 0, B, next_obs_tape, cond_out, step_noise)
+        rd = self.rb.desc(0, B)
+        h = self.ctx._h
+        check(h, lib().ditree_forest_expand_round_ant(h, C.byref(self.tree.desc), C.byref(self.fdesc), C.byref(rd), C.byref(rp),
+                                                      self.ctx.stream), "forest_expand_round_ant")
+        del keep
+        return self._end_round(B, noise is not None, accept)
 
 
 

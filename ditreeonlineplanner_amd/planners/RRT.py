@@ -371,17 +371,26 @@ class RRT_Planner(BasePlanner):
 
     # ------------------------------------------------------------------ many seeded runs at once
     def _forest_engine(self, T, tree_capacity, batch):
-        """The ForestEngine of ``plan_runs`` (kept between calls of the same shape): the single-tree engine's settings."""
-        from ..forest import ForestEngine
+        """The ForestEngine (ant: AntForestEngine) of ``plan_runs`` (kept between calls of the same shape): the single-tree
+        engine's settings."""
+        from ..forest import AntForestEngine, ForestEngine
         e = self._engine
         key = (T, tree_capacity, batch)
         f = getattr(self, "_forest", None)
         if f is None or self._forest_key != key:
             self._forest = f = None                      # free the previous forest's slots first
-            f = ForestEngine(self.ctx, self.maze, self.start_node.state, self.goal_state, T, tree_capacity, action_horizon=e.A,
-                             pred_horizon=e.P, local_map_size=e.lm_n, local_map_scale=e.lm_scale, s_global=e.s_global,
-                             batch=batch, k_steps=e.k_steps, emulate_sticky_done=bool(e.sticky), norm=e.norm,
-                             early_exit=bool(e.early_exit), goal_scale=e.goal_scale, prop_duration=e.schedule)
+            if self.is_ant:
+                f = AntForestEngine(self.ctx, self.maze, self.start_node.state, self.goal_state, T, tree_capacity,
+                                    desired_goal=e.env_goal, norm=e.norm, edge_length=e.H, action_horizon=e.A, pred_horizon=e.P,
+                                    local_map_size=e.lm_n, local_map_scale=e.lm_scale, s_global=e.s_global, batch=batch,
+                                    k_steps=e.k_steps, early_exit=bool(e.early_exit), goal_scale=e.goal_scale,
+                                    dynamics=e.dynamics, model=e.model, ball_radius=e.ball_radius)
+                f.goal_radius = e.goal_radius
+            else:
+                f = ForestEngine(self.ctx, self.maze, self.start_node.state, self.goal_state, T, tree_capacity, action_horizon=e.A,
+                                 pred_horizon=e.P, local_map_size=e.lm_n, local_map_scale=e.lm_scale, s_global=e.s_global,
+                                 batch=batch, k_steps=e.k_steps, emulate_sticky_done=bool(e.sticky), norm=e.norm,
+                                 early_exit=bool(e.early_exit), goal_scale=e.goal_scale, prop_duration=e.schedule)
             self._forest, self._forest_key = f, key
         f.ddpm = e.ddpm
         f.update_maze(self.maze)
@@ -398,8 +407,16 @@ class RRT_Planner(BasePlanner):
         of its max_candidates) candidates; ``time_budget`` counts from a run's own start, so ``time`` is wall time inside a
         shared forest.  ``tree_capacity``: node slots per run (default: max_candidates + 1, at most ``capacity``).  The
         caller's ``random`` / ``np.random`` / torch generator states are left as they were; the summed collision-check count
-        is added to ``common.map_utils.cc_calls`` once.  Scope: the car, run_type 0, one rank, a network sampler or one with
-        ``sample_round`` (a plain callable draws from its own generator and cannot be split per run)."""
+        is added to ``common.map_utils.cc_calls`` once.  Scope: run_type 0, one rank, a network sampler or one with
+        ``sample_round`` (a plain callable draws from its own generator and cannot be split per run); the car, or the ant
+        (env_id 'antmaze') with ``ant_dynamics`` "model" or "tape".
+
+        The ant: the forest is an ``AntForestEngine``; ``ant_dynamics="host"`` is refused (the caller's simulator steps one
+        candidate at a time on the host, so it bounds such a run and a forest buys nothing).  ``reset()`` is called ONCE and
+        all runs share that reset's ``desired_goal``: equality with the sequential runs holds for an env whose ``reset``
+        returns the same ``desired_goal`` every time -- a gym env that adds position noise per reset gives one draw for all
+        runs here, a fresh one per run in the loop.  ``is_colliding_ant`` does not count its calls, so ant runs report
+        ``cc_calls`` 0 and leave ``common.map_utils.cc_calls`` as it is, as ``plan()`` does."""
         from ._runs import Job, check_forest_scope, run_jobs
         check_forest_scope(self, "plan_runs")
         seeds = [int(s) for s in seeds]
@@ -410,8 +427,12 @@ class RRT_Planner(BasePlanner):
             tree_capacity = self.capacity if self.max_candidates is None else min(self.capacity, int(self.max_candidates) + 1)
         eng = self._forest_engine(T, int(tree_capacity), T * self.batch)
         self.reset()                                        # env.reset(options) as before every sequential plan()
-        eng.reset(self.start_node.state, self.goal_state)
-        eng.env_goal = np.asarray(self.env.goal, dtype=np.float64)
+        if self.is_ant:
+            eng._desired_arg = self._engine.env_goal.copy()  # the desired_goal this reset left: one for all runs
+            eng.reset(self.start_node.state, self.goal_state)
+        else:
+            eng.reset(self.start_node.state, self.goal_state)
+            eng.env_goal = np.asarray(self.env.goal, dtype=np.float64)
         if hasattr(self.sampler, "ensure_bound"):
             self.sampler.ensure_bound(T * self.batch)
         results = [None] * len(seeds)
@@ -432,6 +453,9 @@ def _scene_settings(pl):
 def _check_scene_planners(planners):
     from ._runs import check_forest_scope
     for pl in planners:
+        if pl.is_ant:
+            raise NotImplementedError("plan_scenario_runs: the car (carmaze) only (an ant forest has one maze, start and goal: "
+                                      "RRT_Planner.plan_runs)")
         check_forest_scope(pl, "plan_scenario_runs")
     ref = _scene_settings(planners[0])
     for i, pl in enumerate(planners[1:], 1):

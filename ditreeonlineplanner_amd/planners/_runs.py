@@ -85,7 +85,12 @@ def run_jobs(eng, jobs, batch, device):
     ``draw_round`` on its own streams, and the noise of its own generator in ``plan()``'s order (start noise, then the DDPM
     step noise); ``time_budget`` counts from the run's own start.  Fills every job's slot with a ``plan_runs``-shaped dict,
     adds the summed collision-check count to ``common.map_utils.cc_calls`` once, leaves the caller's ``random`` /
-    ``np.random`` states as they were, and returns the dicts in job order."""
+    ``np.random`` states as they were, and returns the dicts in job order.
+
+    Ant jobs (``planner.is_ant``; an ``AntForestEngine``): with tape dynamics every run's
+    ``next_obs_tape_fn(the run's first candidate, n)`` rows, concatenated in tree order, go to ``expand_round``; and since
+    ``is_colliding_ant`` does not count its calls (``plan()`` adds nothing for the ant) the runs report ``cc_calls`` 0 and
+    ``common.map_utils.cc_calls`` stays as it is."""
     import torch
     from ..common import map_utils
     from ..engine import CNT_GOAL, CNT_ITERS
@@ -93,6 +98,8 @@ def run_jobs(eng, jobs, batch, device):
         return []
     T = eng.T
     network = hasattr(jobs[0].planner.sampler, "ensure_bound")
+    ant = bool(getattr(jobs[0].planner, "is_ant", False))
+    tape = ant and getattr(jobs[0].planner, "ant_dynamics", "host") == "tape"
     K = len(eng.ddpm[0]) if (network and eng.ddpm is not None) else 0
     results = [None] * len(jobs)
     queue = list(range(len(jobs)))[::-1]
@@ -118,7 +125,7 @@ def run_jobs(eng, jobs, batch, device):
         path = actions = None
         if node is not None:
             path, actions = eng.path_to(t, node)
-        cc = int(steps_dev[t].item())
+        cc = 0 if ant else int(steps_dev[t].item())          # is_colliding_ant does not count its calls (map_utils.py:126-136)
         total_cc += cc
         results[i] = job.slot[0][job.slot[1]] = {
             "seed": job.seed, "success": path is not None, "goal_reached": goal is not None, "iterations": int(row[CNT_ITERS]),
@@ -162,21 +169,30 @@ def run_jobs(eng, jobs, batch, device):
                     lo += sizes[t]
             else:
                 acts = torch.cat([pl._host_actions(slots[t][2], sizes[t]) for pl, t in zip(planners, active)])
-            cnt = eng.expand_round(s, c, noise=noise, inject_actions=acts, counts_per_tree=sizes, step_noise=step_noise)
-            tree_of = torch.as_tensor(np.repeat(np.arange(T), sizes), device=device)
-            steps_dev.index_add_(0, tree_of, eng.rb.chunk_steps[:B].sum(dim=1, dtype=torch.int64))
+            extra = {}                                          # the ant engine's own keyword arguments, for ant jobs only
+            if tape:
+                extra["next_obs_tape"] = torch.as_tensor(np.ascontiguousarray(np.concatenate(
+                    [pl._tape_fn(slots[t][2], sizes[t]) for pl, t in zip(planners, active)])), device=device)
+            cnt = eng.expand_round(s, c, noise=noise, inject_actions=acts, counts_per_tree=sizes, step_noise=step_noise, **extra)
+            if not ant:
+                tree_of = torch.as_tensor(np.repeat(np.arange(T), sizes), device=device)
+                steps_dev.index_add_(0, tree_of, eng.rb.chunk_steps[:B].sum(dim=1, dtype=torch.int64))
             for t in active:
                 slots[t][2] += sizes[t]
                 if int(cnt[t, CNT_GOAL]) >= 0:
                     finish(t, eng.goal_node(t))
-    map_utils.add_cc_calls(total_cc)            # the counter the drivers read (run_scenarios.py:338,343), once
+    if not ant:
+        map_utils.add_cc_calls(total_cc)        # the counter the drivers read (run_scenarios.py:338,343), once
     return results
 
 
 def check_forest_scope(pl, who):
     """What a planner must be to join a forest (``who``: the refusing function's name, for its messages)."""
     if pl.is_ant:
-        raise NotImplementedError(f"{who}: the car (carmaze) only")
+        if getattr(pl, "ant_dynamics", "host") not in ("model", "tape"):
+            raise NotImplementedError(f"{who}: the car (carmaze), or the ant with ant_dynamics 'model' or 'tape' -- with "
+                                      "ant_dynamics='host' the caller's simulator steps one candidate at a time on the host, "
+                                      "so it bounds such a run and a forest buys nothing there")
     if pl.run_type != 0:
         raise NotImplementedError(f"{who}: run_type 0 only (the online re-planning driver plans one run at a time)")
     if pl.world_size > 1:

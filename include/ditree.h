@@ -559,7 +559,8 @@ int32_t ditree_round_stats(ditree_ctx* ctx, int32_t* stats4);
  * layout of ditree_tree.counters, with the goal node in the global numbering and [7] the phantom candidate as a row of the round.
  * The candidates of one round are grouped by tree: tree t's are rows [off[t], off[t + 1]) (empty: no candidate this round),
  * in that run's own order.  All trees share the maze, the start and the goal (the goal test lives in the rollout).
- * The tree argument's own `counters` is not read by the forest calls. */
+ * The tree argument's own `counters` is not read by the forest calls.  The calls of this section take a car tree only; an
+ * ant tree (state_dim 29, action_dim 8, hist) has its own three calls, "ant forests" at the end of this header. */
 typedef struct {
   int32_t n_trees;               /* T >= 1 */
   int32_t tree_capacity;         /* C >= 1 node slots per tree; T * C <= tree->capacity */
@@ -677,6 +678,29 @@ int32_t ditree_ant_chunk_sample(ditree_ctx* ctx, const ditree_tree* tree, const 
                                 const ditree_ant_round_params* p, int32_t j, void* stream);
 int32_t ditree_ant_chunk_step(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round,
                               const ditree_ant_round_params* p, int32_t j, const double* next_obs, void* stream);
+
+/* ------------------------------------------------------------------ ant forests: many seeded antmaze runs in one round
+ * The benchmark loop (run_scenarios.py:336-343) for BASELINE config 3: a ditree_forest whose tree is an ANT tree (state_dim 29,
+ * action_dim 8, `hist` / `hist_n` present: 20.8 KB per node slot at edge length 48), run_type 0, one rank (no shards, no
+ * obstacle flags).  Layout, counter block and candidate offsets are ditree_forest's.  Each of the three calls validates the
+ * tree and the forest before anything is launched (DITREE_E_ARG with a message); the car's forest calls keep refusing an ant
+ * tree.  The host-stepped triple (ditree_ant_round_begin / _chunk_sample / _chunk_step) has no forest form. */
+/* ditree_expand_round_ant on a forest (planners/RRT.py:131-194 for the candidates of every run): each candidate's nearest node
+ * is searched in its own tree only (nodes [t * C, t * C + n_t), n_t from the tree's counter row on the device; p->n_nodes is
+ * not read), its state, last action, has_prev and -- from the global parent id -- its history rows are gathered; everything
+ * behind that is the single-tree ant round.  p->dynamics: DITREE_ANT_DYN_TAPE or DITREE_ANT_DYN_MODEL.  round->B = off[T]. */
+int32_t ditree_forest_expand_round_ant(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
+                                       const ditree_round* round, const ditree_ant_round_params* p, void* stream);
+/* ditree_accept (planners/RRT.py:195-217) per tree of an ant forest, without the sticky-done emulation (the ant env has no
+ * latched `done`): first goal, accepted prefix, iteration / candidate counts and overflow at the tree's own C in its counter
+ * row; global node ids from t * C + n_t; every appended node's hist / hist_n rows as the single-tree commit writes them (valid
+ * rows at the end of the three slots). */
+int32_t ditree_forest_accept_ant(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const ditree_round* round,
+                                 void* stream);
+/* ditree_forest_fallback (planners/RRT.py:227-254, run_type 0) on an ant forest's xy: goal_xy [host 2] -> out_node [dev] (T,)
+ * global ids; the norm as the key, first occurrence on ties, -1 for a tree that holds only its root. */
+int32_t ditree_forest_fallback_ant(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const double* goal_xy,
+                                   int32_t* out_node, void* stream);
 
 #ifdef __cplusplus
 }
