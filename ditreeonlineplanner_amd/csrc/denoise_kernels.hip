@@ -276,9 +276,46 @@ __device__ __forceinline__ void gemm_epilogue(const ConvGemmParams& p, f32x16_t 
 #pragma unroll
     for (int blk = 0; blk < 4; ++blk) slot[blk] = blk_b[blk] - tm * spt;
     const float inv_cnt = 1.0f / (float)(p.group_ch * p.L);
+    // One lane per group adds a row block's partial into its sample's cell.  Where several waves feed a cell with more than
+    // one add each (L >= 128: two or four wm waves; a 256-wide group at L = 32 / 64: both wn waves) the order the adds land
+    // in would reach the bits, so those levels are `ordered` as in gemm_epilogue16: a wave adds its row blocks of a sample
+    // in registers, writes a cell of its own, [wm][wn][group][sample of the wave (two at L = 32)], and the cells of a
+    // sample are added in index order after the barrier.  Cells that no wave writes stay 0.
+    const bool ordered = p.L >= 128 || (p.group_ch == 256 && p.L >= 32);
+    const bool adder = lane == 0 || (!wide && lane == 16);
+    const int ocell = ((wm * 2 + wn) * 4 + gi) * 2;
+    auto put = [&](float* cell, float (&t)[4]) {               // t: the wave's four row-block partials (reduced over the lanes)
+      if (ordered) {
+        if (p.L >= 64) { t[0] = (t[0] + t[1]) + (t[2] + t[3]); t[2] = 0.0f; }
+        else { t[0] += t[1]; t[2] += t[3]; }
+        if (adder) { cell[ocell] = t[0]; cell[ocell + 1] = t[2]; }
+      } else if (adder) {
+#pragma unroll
+        for (int blk = 0; blk < 4; ++blk) atomicAdd(&cell[slot[blk] * 4 + gi], t[blk]);
+      }
+    };
+    auto get = [&](const float* cell, float (&t)[4]) {
+      if (!ordered) {
+#pragma unroll
+        for (int blk = 0; blk < 4; ++blk) t[blk] = cell[slot[blk] * 4 + gi];
+        return;
+      }
+#pragma unroll
+      for (int blk = 0; blk < 4; blk += 2) {
+        const int r0 = slot[blk] * p.L;                          // the sample's first row in the tile
+        const int w0 = r0 >> 6, nw = p.L >= 64 ? p.L >> 6 : 1, sub = (r0 >> 5) & 1;
+        float v = 0.0f;
+        for (int w = w0; w < w0 + nw; ++w) {
+          v += cell[((w * 2 + 0) * 4 + gi) * 2 + sub];
+          v += cell[((w * 2 + 1) * 4 + gi) * 2 + sub];
+        }
+        t[blk] = v; t[blk + 1] = v;
+      }
+    };
     float mean[4], rstd[4];
     if constexpr (PREC != 1) {
       // one pass: sum and sum of squares (f32), var = E[x^2] - mean^2
+      float ps[4], pq[4];
 #pragma unroll
       for (int blk = 0; blk < 4; ++blk) {
         float s = 0.f, q = 0.f;
@@ -296,16 +333,17 @@ __device__ __forceinline__ void gemm_epilogue(const ConvGemmParams& p, f32x16_t 
         s += __shfl_xor(s, 8); q += __shfl_xor(q, 8);
         s += __shfl_xor(s, 32); q += __shfl_xor(q, 32);
         if (wide) { s += __shfl_xor(s, 16); q += __shfl_xor(q, 16); }
-        if (lane == 0 || (!wide && lane == 16)) {
-          atomicAdd(&s_sum[slot[blk] * 4 + gi], s);
-          atomicAdd(&s_sq[slot[blk] * 4 + gi], q);
-        }
+        ps[blk] = s; pq[blk] = q;
       }
+      put(s_sum, ps);
+      put(s_sq, pq);
       __syncthreads();
+      get(s_sum, ps);
+      get(s_sq, pq);
 #pragma unroll
       for (int blk = 0; blk < 4; ++blk) {
-        mean[blk] = s_sum[slot[blk] * 4 + gi] * inv_cnt;
-        const float var = fmaxf(s_sq[slot[blk] * 4 + gi] * inv_cnt - mean[blk] * mean[blk], 0.0f);
+        mean[blk] = ps[blk] * inv_cnt;
+        const float var = fmaxf(pq[blk] * inv_cnt - mean[blk] * mean[blk], 0.0f);
         rstd[blk] = rsqrtf(var + p.eps);
       }
     } else {
@@ -327,14 +365,17 @@ __device__ __forceinline__ void gemm_epilogue(const ConvGemmParams& p, f32x16_t 
         s += __shfl_xor(s, 1); s += __shfl_xor(s, 2); s += __shfl_xor(s, 4); s += __shfl_xor(s, 8);
         s += __shfl_xor(s, 32);
         if (wide) s += __shfl_xor(s, 16);
-        if (lane == 0 || (!wide && lane == 16)) atomicAdd(&s_sum[slot[blk] * 4 + gi], s);
+        ps[blk] = s;
       }
-    }
-    __syncthreads();
+      put(s_sum, ps);
+      __syncthreads();
+      get(s_sum, ps);
 #pragma unroll
-    for (int blk = 0; blk < 4; ++blk) mean[blk] = s_sum[slot[blk] * 4 + gi] * inv_cnt;
+      for (int blk = 0; blk < 4; ++blk) mean[blk] = ps[blk] * inv_cnt;
+    }
     // pass 2: centred squares
     {
+      float ps[4];
 #pragma unroll
       for (int blk = 0; blk < 4; ++blk) {
         float s = 0.f;
@@ -348,12 +389,14 @@ __device__ __forceinline__ void gemm_epilogue(const ConvGemmParams& p, f32x16_t 
         s += __shfl_xor(s, 1); s += __shfl_xor(s, 2); s += __shfl_xor(s, 4); s += __shfl_xor(s, 8);
         s += __shfl_xor(s, 32);
         if (wide) s += __shfl_xor(s, 16);
-        if (lane == 0 || (!wide && lane == 16)) atomicAdd(&s_sq[slot[blk] * 4 + gi], s);
+        ps[blk] = s;
       }
-    }
-    __syncthreads();
+      put(s_sq, ps);
+      __syncthreads();
+      get(s_sq, ps);
 #pragma unroll
-    for (int blk = 0; blk < 4; ++blk) rstd[blk] = rsqrtf(s_sq[slot[blk] * 4 + gi] * inv_cnt + p.eps);
+      for (int blk = 0; blk < 4; ++blk) rstd[blk] = rsqrtf(ps[blk] * inv_cnt + p.eps);
+    }
 
     }
 
@@ -800,9 +843,16 @@ __device__ __forceinline__ void gemm_epilogue16(const ConvGemmParams& p, f32x4_t
   // four rows h4 by two lane exchanges, and one lane per group adds into the sample's LDS cell.  For L <= 64 a cell is
   // fed by one wave (in program order) or by the two wn waves of a 256-wide group with one add each, so the sum does not
   // depend on the order the adds land in: results are reproducible bit for bit, whatever batch a sample is part of.
+  // That does not hold where several waves feed a cell with more than one add each: L >= 128 (a sample's rows span two or
+  // four wm waves with four row blocks each) and a 256-wide group at L = 32 / 64 (both wn waves, two / four row blocks each).
+  // Those levels are `ordered`: a wave adds its row blocks of a sample in registers and writes the sum to a cell of its
+  // own, [wm][wn][group][sample of the wave (two at L = 32)] = 64 cells (at most 2 x 4 x 4 of them are a sample's), and
+  // cell_sums() adds a sample's cells in index order after the barrier.  Cells that no wave writes stay 0.
+  const bool ordered = !short_l && (p.L >= 128 || (p.group_ch == 256 && p.L >= 32));
   // rows h4 of one sample: all four (16 | L), pairs (L = 8), each its own (L = 4)
   const int hsame = short_l ? (p.L == 8 ? 2 : 1) : 4;
   const bool adder = (r4 == 0 || (!wide && r4 == 8)) && (h4 & (hsame - 1)) == 0;
+  const int ocell = ((wm * 2 + wn) * 4 + gi) * 2;
   auto block_sums = [&](float (&s)[4], float* cell) {
 #pragma unroll
     for (int mb = 0; mb < 4; ++mb) s[mb] = dpp_add<0xB1>(s[mb]);           // quad_perm [1,0,3,2]
@@ -822,9 +872,32 @@ __device__ __forceinline__ void gemm_epilogue16(const ConvGemmParams& p, f32x4_t
 #pragma unroll
       for (int mb = 0; mb < 4; ++mb) s[mb] += __shfl_xor(s[mb], 32);
     }
-    if (adder) {
+    if (ordered) {
+      if (p.L >= 64) { s[0] = (s[0] + s[1]) + (s[2] + s[3]); s[2] = 0.0f; }
+      else { s[0] += s[1]; s[2] += s[3]; }                                   // L = 32: row blocks 0, 1 | 2, 3
+      if (adder) { cell[ocell] = s[0]; cell[ocell + 1] = s[2]; }
+    } else if (adder) {
 #pragma unroll
       for (int mb = 0; mb < 4; ++mb) atomicAdd(&cell[slot[mb]], s[mb]);
+    }
+  };
+  // the statistics of the samples of the four row blocks
+  auto cell_sums = [&](const float* cell, float (&t)[4]) {
+    if (!ordered) {
+#pragma unroll
+      for (int mb = 0; mb < 4; ++mb) t[mb] = cell[slot[mb]];
+      return;
+    }
+#pragma unroll
+    for (int mb = 0; mb < 4; mb += 2) {
+      const int r0 = (blk_b[mb] - tm * spt) * p.L;                           // the sample's first row in the tile
+      const int w0 = r0 >> 6, nw = p.L >= 64 ? p.L >> 6 : 1, sub = (r0 >> 5) & 1;
+      float v = 0.0f;
+      for (int w = w0; w < w0 + nw; ++w) {
+        v += cell[((w * 2 + 0) * 4 + gi) * 2 + sub];
+        v += cell[((w * 2 + 1) * 4 + gi) * 2 + sub];
+      }
+      t[mb] = v; t[mb + 1] = v;
     }
   };
   float mean_[4], rstd_[4];
@@ -849,10 +922,12 @@ __device__ __forceinline__ void gemm_epilogue16(const ConvGemmParams& p, f32x4_t
     block_sums(s, s_sum);
     block_sums(q, s_sq);
     __syncthreads();
+    cell_sums(s_sum, s);
+    cell_sums(s_sq, q);
 #pragma unroll
     for (int mb = 0; mb < 4; ++mb) {
-      mean_[mb] = s_sum[slot[mb]] * inv_cnt;
-      const float var = fmaxf(s_sq[slot[mb]] * inv_cnt - mean_[mb] * mean_[mb], 0.0f);
+      mean_[mb] = s[mb] * inv_cnt;
+      const float var = fmaxf(q[mb] * inv_cnt - mean_[mb] * mean_[mb], 0.0f);
       rstd_[mb] = rsqrtf(var + p.eps);
     }
   } else {
@@ -869,9 +944,10 @@ __device__ __forceinline__ void gemm_epilogue16(const ConvGemmParams& p, f32x4_t
     }
     block_sums(s, s_sum);
     __syncthreads();
+    cell_sums(s_sum, s);
 #pragma unroll
     for (int mb = 0; mb < 4; ++mb) {
-      mean_[mb] = s_sum[slot[mb]] * inv_cnt;
+      mean_[mb] = s[mb] * inv_cnt;
       f32x2_t q2 = {0.f, 0.f};
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
@@ -886,8 +962,9 @@ __device__ __forceinline__ void gemm_epilogue16(const ConvGemmParams& p, f32x4_t
     }
     block_sums(s, s_sq);
     __syncthreads();
+    cell_sums(s_sq, s);
 #pragma unroll
-    for (int mb = 0; mb < 4; ++mb) rstd_[mb] = rsqrtf(s_sq[slot[mb]] * inv_cnt + p.eps);
+    for (int mb = 0; mb < 4; ++mb) rstd_[mb] = rsqrtf(s[mb] * inv_cnt + p.eps);
   }
   // rows go through the arithmetic two at a time (rows 2ip, 2ip+1 of a block: the accumulator pairs above)
   const long long ostep = (long long)p.out_stride * p.ldc * 2;
