@@ -16,6 +16,7 @@ import os
 import re
 import subprocess
 import sys
+from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
@@ -31,7 +32,8 @@ UNITS = [
     ("ant_kernels.hip", ["-ffp-contract=off"]),
     ("mppi_ant_kernels.hip", ["-ffp-contract=off"]),
     ("ditree_api.hip", []),
-    ("denoise_kernels.hip", []),
+    ("conv_tiles.hip", []),
+    ("denoise_small_kernels.hip", []),
     ("encoder_kernels.hip", []),
     ("denoise_host.hip", []),
 ]
@@ -79,7 +81,7 @@ def _unit_hash(src: str, extra, build_id: str) -> str:
 def build(force: bool = False, verbose: bool = True) -> str:
     bid = source_id()
     objs = []
-    relink = force or library_id() != bid
+    stale = []
     for src, extra in UNITS:
         s = os.path.join(CSRC, src)
         o = os.path.join(CSRC, src.replace(".hip", ".o"))
@@ -89,14 +91,20 @@ def build(force: bool = False, verbose: bool = True) -> str:
         have = _read(side).decode().strip() if os.path.exists(side) and os.path.exists(o) else None
         if force or have != want:
             defs = [f'-DDITREE_BUILD_ID_STR="{bid}"'] if src == ID_UNIT else []
-            cmd = [HIPCC, *COMMON, *extra, *defs, "-c", s, "-o", o]
-            if verbose:
-                print(" ".join(cmd), flush=True)
-            subprocess.check_call(cmd)
-            with open(side, "w") as f:
-                f.write(want + "\n")
-            relink = True
-    if relink:
+            stale.append(([HIPCC, *COMMON, *extra, *defs, "-c", s, "-o", o], side, want))
+
+    def compile_unit(job):
+        cmd, side, want = job
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd)
+        with open(side, "w") as f:
+            f.write(want + "\n")
+
+    if stale:       # the stale units compile side by side; the first failing compile raises once all have ended
+        with ThreadPoolExecutor(max_workers=min(len(stale), int(os.environ.get("MAX_JOBS", 8)))) as pool:
+            list(pool.map(compile_unit, stale))
+    if stale or force or library_id() != bid:
         cmd = [HIPCC, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", LIB, *objs]
         if verbose:
             print(" ".join(cmd), flush=True)

@@ -23,182 +23,14 @@
 //  * epilogue fused in registers: bias, GroupNorm (two-pass statistics through LDS
 //    atomics; a tile always holds whole (sample, group) sets), Mish, FiLM scale/bias or
 //    residual add.
-#include <cstdlib>
 #include <type_traits>
 
-#include <stdexcept>
+#include "denoise_device.h"
 
-#include "denoise.h"
-
-// Plan validation (DenoiserState::build): every launcher runs its dispatch and shape contracts, but enqueues nothing while the
-// dry-run flag is set -- an unsupported layer shape fails at reserve time, and the validation leaves no launches in a profile.
+// The one definition of the dry-run flag (DN_LAUNCH, denoise_device.h, reads it through denoise_dry_run()).
 static thread_local bool g_dn_dry_run = false;
 void denoise_set_dry_run(bool on) { g_dn_dry_run = on; }
 bool denoise_dry_run() { return g_dn_dry_run; }
-#define DN_LAUNCH(...) do { if (!g_dn_dry_run) hipLaunchKernelGGL(__VA_ARGS__); } while (0)
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(8))) _Float16 half8_t;
-typedef __attribute__((ext_vector_type(8))) short short8_t;
-typedef __attribute__((ext_vector_type(4))) short short4_t;
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
-typedef __attribute__((ext_vector_type(2))) float f32x2_t;
-typedef __attribute__((ext_vector_type(2))) _Float16 half2_t;
-typedef __attribute__((ext_vector_type(2))) short short2_t;
-
-#define GLOBAL_AS __attribute__((address_space(1)))
-#define LDS_AS __attribute__((address_space(3)))
-
-__device__ __forceinline__ unsigned short f2bf(float f) {
-  __bf16 b = (__bf16)f;                       // v_cvt_pk_bf16_f32: RNE, NaN preserved
-  return __builtin_bit_cast(unsigned short, b);
-}
-__device__ __forceinline__ float bf2f(unsigned short u) {
-  unsigned int x = ((unsigned int)u) << 16;
-  return __builtin_bit_cast(float, x);
-}
-__device__ __forceinline__ unsigned short f2h(float f) {
-  // f16 has no headroom above 65504: saturate instead of producing inf (a NaN stays a NaN through v_med3)
-  _Float16 b = (_Float16)__builtin_amdgcn_fmed3f(f, -65504.0f, 65504.0f);
-  return __builtin_bit_cast(unsigned short, b);
-}
-__device__ __forceinline__ float h2f(unsigned short u) { return (float)__builtin_bit_cast(_Float16, u); }
-// f16 range guard.  The f16 instantiations saturate at +-65504 silently (v_med3 above / in the epilogues); so that a
-// checkpoint whose activations leave the f16 range is REPORTED instead of returning wrong actions with rc 0, every thread
-// that converts values to f16 keeps the largest magnitude it was handed (one v_max3_f32 with |.| source modifiers per two
-// values; a NaN drops out of the maximum, an infinity does not) and ORs 1 into the launch's flag word when it exceeds the
-// range.  The flag of each layer is read by ditree_denoise_status (denoise_host.hip).
-__device__ __forceinline__ void sat_see2(float& m, float a, float b) {
-  m = __builtin_fmaxf(__builtin_fmaxf(m, __builtin_fabsf(a)), __builtin_fabsf(b));
-}
-__device__ __forceinline__ void sat_see(float& m, float a) { m = __builtin_fmaxf(m, __builtin_fabsf(a)); }
-__device__ __forceinline__ void sat_flush(int* flag, float m) {
-  if (flag != nullptr && m > 65504.0f) atomicOr(flag, 1);
-}
-// The MFMA epilogues have no VGPR to spare for a running maximum (256 of 256 in use: carrying one spilled 70 registers,
-// and so did carrying the wave's compare mask): there the maximum of a ROW is formed in a transient register, compared once,
-// and the flag is written right away behind a wave-uniform branch that is never taken in a healthy network.
-__device__ __forceinline__ void sat_check_row(int* flag, const float (&v)[8]) {
-#ifdef DITREE_NO_RANGE_GUARD      // measurement build only: what the guard costs in the MFMA epilogues
-  return;
-#endif
-  float t = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(v[0]), __builtin_fabsf(v[1])), __builtin_fabsf(v[2]));
-  t = __builtin_fmaxf(__builtin_fmaxf(t, __builtin_fabsf(v[3])), __builtin_fabsf(v[4]));
-  t = __builtin_fmaxf(__builtin_fmaxf(t, __builtin_fabsf(v[5])), __builtin_fabsf(v[6]));
-  t = __builtin_fmaxf(t, __builtin_fabsf(v[7]));
-  if (__builtin_amdgcn_ballot_w64(t > 65504.0f) != 0ull) {
-    if (flag != nullptr && t > 65504.0f) atomicOr(flag, 1);
-  }
-}
-// 16-bit element types of the MFMA operands.  ET 0: bf16 (8 significand bits, f32 range), ET 1: f16 (11 bits, +-65504).
-// SPLIT instantiations carry every operand as two 16-bit planes hi + lo (lo = rnd(x - hi)) and form a product from
-// three MFMAs hi*hi + hi*lo + lo*hi with f32 accumulation: 16 (bf16) / 22 (f16) significand bits per operand at a
-// third of the 16-bit MFMA rate -- the f32-input MFMA runs at a sixteenth of it (MI355X_MICROARCH.md, Matrix cores).
-template <int ET> __device__ __forceinline__ unsigned short f2e(float f) { if constexpr (ET == 0) return f2bf(f); else return f2h(f); }
-template <int ET> __device__ __forceinline__ float e2f(unsigned short u) { if constexpr (ET == 0) return bf2f(u); else return h2f(u); }
-template <int ET>
-__device__ __forceinline__ f32x4_t mfma16(const short8_t& a, const short8_t& b, const f32x4_t& c) {
-  if constexpr (ET == 0)
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8_t, a), __builtin_bit_cast(half8_t, b), c, 0, 0, 0);
-}
-template <int ET>
-__device__ __forceinline__ f32x16_t mfma32(const short8_t& a, const short8_t& b, const f32x16_t& c) {
-  if constexpr (ET == 0)
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8_t, a), __builtin_bit_cast(half8_t, b), c, 0, 0, 0);
-}
-
-template <int PREC>
-__device__ __forceinline__ float mish_f(float x) {
-  // x * tanh(softplus(x)) = x * w / (w + 2), w = e^x (e^x + 2)
-  if constexpr (PREC == 0) {
-    // throughput path: x - 2x / (n (n + 2) + 2); n = inf (x > 88) gives rcp = 0 -> x, n = 0 gives 0,
-    // so torch's softplus threshold needs no branch.  5 VALU + exp + rcp.
-    const float n = __expf(x);
-    const float d = fmaf(n, n + 2.0f, 2.0f);
-    return fmaf(-2.0f * x, __builtin_amdgcn_rcpf(d), x);
-  } else if constexpr (PREC == 2) {
-    // f32-class at a third of the instructions of expf + IEEE division (the epilogue of the split kernels is VALU-bound):
-    // e^x = 2^t * (1 + r ln 2) with t = rnd(x log2 e) and r its exact residual (fma) plus the low part of the constant,
-    // 2^t by v_exp_f32 (1 ulp); 1 / (w + 2) by v_rcp_f32 and one Newton step.  Relative error ~1e-7, no branch.
-    const float L2E = 1.44269502162933349609375f, L2E_LO = 1.92596299112661746e-08f, LN2 = 0.693147182464599609375f;
-    const float t = x * L2E;
-    const float r = fmaf(x, L2E_LO, fmaf(x, L2E, -t));
-    const float e = __builtin_amdgcn_exp2f(t);
-    const float n = fmaf(e, r * LN2, e);
-    const float w = n * (n + 2.0f);
-    const float d = w + 2.0f;
-    float q = __builtin_amdgcn_rcpf(d);
-    q = fmaf(fmaf(-d, q, 1.0f), q, q);
-    const float y = x * (w * q);
-    return x > 20.0f ? x : y;                      // softplus threshold as torch (also keeps w finite)
-  } else {
-    if (x > 20.0f) return x;                       // softplus threshold as torch
-    const float n = expf(x);
-    const float w = n * (n + 2.0f);
-    return x * (w / (w + 2.0f));
-  }
-}
-
-// the same on a pair of values (two tile rows of one channel: adjacent accumulator registers, so the packed f32
-// instructions v_pk_fma / v_pk_mul / v_pk_add take them without register shuffles).  PREC 0: throughput, 2: f32-class.
-template <int PREC>
-__device__ __forceinline__ f32x2_t mish2(f32x2_t x) {
-  if constexpr (PREC == 0) {
-    const f32x2_t n = {__expf(x[0]), __expf(x[1])};
-    const f32x2_t d = __builtin_elementwise_fma(n, n + 2.0f, f32x2_t{2.0f, 2.0f});
-    const f32x2_t q = {__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
-    return __builtin_elementwise_fma(-2.0f * x, q, x);
-  } else {
-    const float L2E = 1.44269502162933349609375f, L2E_LO = 1.92596299112661746e-08f, LN2 = 0.693147182464599609375f;
-    // exponent of min(x, 20): above torch's softplus threshold w / (w + 2) rounds to 1 and x comes back (no select)
-    const f32x2_t xm = {__builtin_fminf(x[0], 20.0f), __builtin_fminf(x[1], 20.0f)};
-    const f32x2_t l2e = {L2E, L2E};
-    const f32x2_t t = xm * l2e;
-    f32x2_t r = __builtin_elementwise_fma(xm, l2e, -t);
-    r = __builtin_elementwise_fma(xm, f32x2_t{L2E_LO, L2E_LO}, r);
-    const f32x2_t e = {__builtin_amdgcn_exp2f(t[0]), __builtin_amdgcn_exp2f(t[1])};
-    const f32x2_t n = __builtin_elementwise_fma(e, r * LN2, e);
-    const f32x2_t w = n * (n + 2.0f);
-    const f32x2_t d = w + 2.0f;
-    f32x2_t q = {__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
-    q = __builtin_elementwise_fma(__builtin_elementwise_fma(-d, q, f32x2_t{1.0f, 1.0f}), q, q);
-    return x * (w * q);
-  }
-}
-
-// s + s of the lane that the row-local DPP control CTRL selects (a VALU add with a DPP operand: no LDS round trip)
-template <int CTRL>
-__device__ __forceinline__ float dpp_add(float s) {
-  return s + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s), CTRL, 0xf, 0xf, true));
-}
-
-// bijective XCD-aware tile remap (blocks b and b+8 share an XCD): each XCD gets a
-// contiguous range of tiles, so concurrently resident tiles share A / W panels in L2.
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-  int q = nwg >> 3, r = nwg & 7, x = bid & 7, k = bid >> 3;
-  int start = (x < r) ? x * (q + 1) : r * (q + 1) + (x - r) * q;
-  return start + k;
-}
-// The same with the walk INSIDE an XCD's range shaped for its L2: the 32 work-groups an XCD runs at a time (one per CU) stream
-// the A panels of their tile rows and the W panels of their tile columns together.  With 8 tile columns (C_out = 2048, W panel
-// 6.3 MB, A panel 2.1 MB at K = 6144) a group of 4 rows x 8 columns pulls 4 A + 8 W panels = 59 MB through the L2, a group of
-// 8 rows x 4 columns 8 A + 4 W = 42 MB: the range is walked in strips of four tile columns.  (Needs whole tile rows per XCD;
-// anything else keeps the plain order.)  DITREE_XCD_STRIPS=0 on the host passes strips = 0.
-__device__ __forceinline__ int xcd_remap_strips(int bid, int ntm, int ntn, int strips) {
-  const int nwg = ntm * ntn;
-  const int q = nwg >> 3, r = nwg & 7, x = bid & 7, k = bid >> 3;
-  const int start = (x < r) ? x * (q + 1) : r * (q + 1) + (x - r) * q;
-  if (strips && r == 0 && ntn >= 8 && (ntn & 3) == 0 && (q % ntn) == 0) {
-    const int per = (q / ntn) * 4, strip = k / per, kk = k - strip * per;
-    return start + (kk >> 2) * ntn + strip * 4 + (kk & 3);
-  }
-  return start + k;
-}
 
 // ---- shared epilogue: bias, GroupNorm + Mish (+ FiLM | + residual), store ------------------------
 // acc[mb][j][i] of lane (r5, h), wave (wm, wn) holds tile row wm*64 + mb*32 + (i&3) + 8*(i>>2) + 4*h,
@@ -1040,6 +872,19 @@ __device__ __forceinline__ void gemm_epilogue16(const ConvGemmParams& p, f32x4_t
   }
 }
 
+// ---- shared by the two halo kernels ------------------------------------------------------------------
+// 16 MFMAs of a 4 x 4 block in snake order: consecutive MFMAs always share one operand (A along a row, B at the turn)
+template <int ET>
+__device__ __forceinline__ void mm16_snake(f32x4_t (&acc)[4][8], const short8_t (&a)[4], const short8_t (&b)[4], int half) {
+#pragma unroll
+  for (int mb = 0; mb < 4; ++mb)
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) {
+      const int j = (mb & 1) ? 3 - jj : jj;
+      acc[mb][half * 4 + j] = mfma16<ET>(a[mb], b[j], acc[mb][half * 4 + j]);
+    }
+}
+
 #ifdef HALO16_STAMP   // diagnostic build only: in-kernel clock of the K loop (MI355X_MICROARCH.md, DVFS give-back (6))
 __device__ unsigned long long g_halo_stamp[8];
 extern "C" int ditree_debug_halo_stamp(unsigned long long* out) {
@@ -1061,7 +906,7 @@ extern "C" int ditree_debug_x3_stamp(unsigned long long* out, unsigned int* coun
   return rc;
 }
 #endif
-template <int ET, bool SPLIT>
+template <int ET>
 __global__ void __launch_bounds__(512, 2) conv3_halo16_kernel(ConvGemmParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int A_BUF = 40960, W_BUF = 32768, W_BASE = 2 * A_BUF;
@@ -1071,22 +916,17 @@ __global__ void __launch_bounds__(512, 2) conv3_halo16_kernel(ConvGemmParams p) 
   const int wm = w >> 1, wn = w & 1;
   const int ntn = (p.N + 255) >> 8;
   const int ntm = (p.M + 255) >> 8;
-  const int tile = xcd_remap_strips(blockIdx.x, ntm, ntn, p.dbg);
+  const int tile = xcd_remap_strips(blockIdx.x, ntm, ntn, p.xcd_strips);
   const int tm = tile / ntn, tn = tile - tm * ntn;
   const int L = p.L, Lp = p.in_Lp, S = 256 / L;
   const int a_rows = S * Lp;
-  const int nc = p.Cin >> 6;
-  // SPLIT: every 64-channel chunk is walked three times -- pass 0: A hi x W hi, 1: A hi x W lo, 2: A lo x W hi; `v` below is
-  // the virtual chunk 3 c + pass (the LDS double buffers and the barrier protocol only see its parity)
-  const int nv = SPLIT ? 3 * nc : nc;
-  const int a_plane = (int)p.a_plane, w_plane = (int)p.w_plane;
+  const int nc = p.Cin >> 6;                                         // 64-channel chunks
   const long long K = 3LL * p.Cin;
-  constexpr bool SNAKE = true;
 
   // ---- staging sources (buffer addressing, as conv3_halo_kernel) ------------------------------------
   // pieces 0..3 of the A block differ by 64 rows (a wave-uniform byte offset, folded into the scalar offset);
   // only piece 4 can run past the block and is clamped per lane
-  unsigned pa0, pa4, pbe, pbo;
+  unsigned pa0, pa4, pb;
   const char* const a_base = (const char*)p.A + ((long long)tm * S * Lp + p.in_off) * p.lda * 2;
   const char* const w_base = (const char*)p.W + ((long long)tn * 256) * K * 2;
   const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a_base, 0, 0x7fffffff, 0x00020000);
@@ -1102,14 +942,12 @@ __global__ void __launch_bounds__(512, 2) conv3_halo16_kernel(ConvGemmParams p) 
   const int a_piece = 64 * p.lda * 2;                                // bytes between pieces
   // W tile: LDS row r = (w*4 + q)*8 + (lane >> 3) holds channel c(r) = (r & 128) + 8*(r & 15) + ((r >> 4) & 7)
   // (row wn*128 + j*16 + r4 <- channel wn*128 + 8*r4 + j).  Per lane only 8*(lane >> 3) and the swizzled slot vary,
-  // and the slot depends on q through its parity alone: two lane offsets (q even / odd) + a wave-uniform row offset.
+  // and r & 7 = lane >> 3 for every piece q: one lane offset + a wave-uniform row offset.
   long long wq[4];
   {
     const int lr = lane >> 3;
-    const int slot0 = (lane & 7) ^ lr;                               // r & 7 = lr for every piece q
-    const int slot1 = slot0;
-    pbe = (unsigned)(((long long)(8 * lr) * K + slot0 * 8) * 2);
-    pbo = (unsigned)(((long long)(8 * lr) * K + slot1 * 8) * 2);
+    const int slot = (lane & 7) ^ lr;                                // r & 7 = lr for every piece q
+    pb = (unsigned)(((long long)(8 * lr) * K + slot * 8) * 2);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int r0 = (w * 4 + q) * 8;                                // row with lane >> 3 = 0
@@ -1118,17 +956,13 @@ __global__ void __launch_bounds__(512, 2) conv3_halo16_kernel(ConvGemmParams p) 
     }
   }
   const int w_tap = p.Cin * 2;
-  auto issue_a = [&](int v, int i) {
-    int c = v, po = 0;
-    if constexpr (SPLIT) { c = v / 3; po = (v - 3 * c == 2) ? a_plane : 0; }
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rsrc, (LDS_AS void*)(smem + (v & 1) * A_BUF + (w + 8 * i) * 1024), 16,
-                                             i < 4 ? pa0 : pa4, c * 128 + (i < 4 ? i * a_piece : 0) + po, 0, 0);
+  auto issue_a = [&](int c, int i) {
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rsrc, (LDS_AS void*)(smem + (c & 1) * A_BUF + (w + 8 * i) * 1024), 16,
+                                             i < 4 ? pa0 : pa4, c * 128 + (i < 4 ? i * a_piece : 0), 0, 0);
   };
-  auto issue_w = [&](int v, int t, int q) {
-    int c = v, po = 0;
-    if constexpr (SPLIT) { c = v / 3; po = (v - 3 * c == 1) ? w_plane : 0; }
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, (LDS_AS void*)(smem + W_BASE + ((v + t) & 1) * W_BUF + (w * 4 + q) * 1024),
-                                             16, (q & 1) ? pbo : pbe, (int)wq[q] + c * 128 + t * w_tap + po, 0, 0);
+  auto issue_w = [&](int c, int t, int q) {
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, (LDS_AS void*)(smem + W_BASE + ((c + t) & 1) * W_BUF + (w * 4 + q) * 1024),
+                                             16, pb, (int)wq[q] + c * 128 + t * w_tap, 0, 0);
   };
 
   // ---- fragment addressing ---------------------------------------------------------------------
@@ -1171,13 +1005,7 @@ __global__ void __launch_bounds__(512, 2) conv3_halo16_kernel(ConvGemmParams p) 
   auto mm = [&](int aset, int bset, int half, int mb, int jj) {
     acc[mb][half * 4 + jj] = mfma16<ET>(af[aset][mb], bq[bset][jj], acc[mb][half * 4 + jj]);
   };
-  // snake order: consecutive MFMAs always share one operand (A along a row of the 4 x 4 block, B at the turn)
-  auto mm16 = [&](int aset, int bset, int half) {
-#pragma unroll
-    for (int mb = 0; mb < 4; ++mb)
-#pragma unroll
-      for (int jj = 0; jj < 4; ++jj) mm(aset, bset, half, mb, SNAKE ? ((mb & 1) ? 3 - jj : jj) : jj);
-  };
+  auto mm16 = [&](int aset, int bset, int half) { mm16_snake<ET>(acc, af[aset], bq[bset], half); };
 
   // One K-step (chunk c, tap T); flags as in conv3_halo_kernel.  On entry af[0] = A(ks 0), bq[0] = B(ks 0, half 0).
   // Wave priorities and the placement of the LDS-DMA requests: see conv3_halo16x3_kernel (same scheme, four phases).
@@ -1238,7 +1066,7 @@ __global__ void __launch_bounds__(512, 2) conv3_halo16_kernel(ConvGemmParams p) 
     for (int mb = 0; mb < 4; ++mb)      // phase (1,1) + the weight pieces of step s+2
 #pragma unroll
       for (int jj = 0; jj < 4; ++jj) {
-        mm(1, 1, 1, mb, SNAKE ? ((mb & 1) ? 3 - jj : jj) : jj);
+        mm(1, 1, 1, mb, (mb & 1) ? 3 - jj : jj);
         const int i = mb * 4 + jj;
         // An LDS-DMA issue holds the wave's instruction stream for 60-180 cycles and both waves of a SIMD run this
         // phase together: one issue behind every second MFMA instead of all in a row leaves the partner wave MFMAs to
@@ -1278,36 +1106,36 @@ __global__ void __launch_bounds__(512, 2) conv3_halo16_kernel(ConvGemmParams p) 
 #endif
   // Issue order and counted waits as in conv3_halo16x3_kernel: vmcnt(3) at the barrier of T = 0 (the three activation
   // pieces requested in this step may stay in flight), vmcnt(2) at T = 1, vmcnt(0) at T = 2 (whole next activation stage).
-  for (int c = 0; c < nv - 2; ++c) {
+  for (int c = 0; c < nc - 2; ++c) {
     step(I0{}, Tt{}, Tt{}, Tt{}, I3{}, c);
     step(I1{}, Tt{}, Tt{}, Tt{}, I2{}, c);
     step(I2{}, Tt{}, Tt{}, Tt{}, I0{}, c);
   }
 #ifdef HALO16_STAMP
-  if (blockIdx.x == 100 && tid == 0 && nv >= 32) {
+  if (blockIdx.x == 100 && tid == 0 && nc >= 32) {
     g_halo_stamp[0] = __builtin_amdgcn_s_memtime() - st0;
     g_halo_stamp[1] = __builtin_amdgcn_s_memrealtime() - rt0;
-    g_halo_stamp[2] = (unsigned long long)(nv - 2) * 3;
+    g_halo_stamp[2] = (unsigned long long)(nc - 2) * 3;
   }
 #endif
   // The counted waits are only used inside the loop above, whose body holds no other vector-memory operation.  The two
   // tail chunks wait for everything: register spills the compiler may place here (scratch accesses count in vmcnt) must
   // not take part in a counted wait.
   {
-    const int c = nv - 2;
+    const int c = nc - 2;
     step(I0{}, Tt{}, Tt{}, Tt{}, I0{}, c);          // the activation stage of the last chunk
     step(I1{}, Tt{}, Tt{}, Tt{}, I0{}, c);
     step(I2{}, Tt{}, Tt{}, Ff{}, I0{}, c);
   }
   {
-    const int c = nv - 1;
+    const int c = nc - 1;
     step(I0{}, Tt{}, Tt{}, Ff{}, I0{}, c);
     step(I1{}, Tt{}, Ff{}, Ff{}, I0{}, c);
     step(I2{}, Ff{}, Ff{}, Ff{}, I0{}, c);
   }
   __builtin_amdgcn_s_setprio(0);
   __syncthreads();
-  gemm_epilogue16<ET, SPLIT>(p, acc, smem, tm, tn, tid, lane, r4, h4, wm, wn);
+  gemm_epilogue16<ET, false>(p, acc, smem, tm, tn, tid, lane, r4, h4, wm, wn);
 }
 
 // =================================================================================================
@@ -1339,7 +1167,7 @@ __global__ void __launch_bounds__(512, 2) conv3_halo16x3_kernel(ConvGemmParams p
   const int wm = w >> 1, wn = w & 1;
   const int ntn = (p.N + 255) >> 8;
   const int ntm = (p.M + 255) >> 8;
-  const int tile = xcd_remap_strips(blockIdx.x, ntm, ntn, p.dbg);
+  const int tile = xcd_remap_strips(blockIdx.x, ntm, ntn, p.xcd_strips);
   const int tm = tile / ntn, tn = tile - tm * ntn;
   const int L = p.L, Lp = p.in_Lp, S = 256 / L;
   const int a_rows = S * Lp;
@@ -1350,7 +1178,7 @@ __global__ void __launch_bounds__(512, 2) conv3_halo16x3_kernel(ConvGemmParams p
   const long long K = 3LL * p.Cin;
   const unsigned a_plane = (unsigned)p.a_plane, w_plane = (unsigned)p.w_plane;
 
-  unsigned pa0, pa4, pa5 = 0, pbe, pbo;
+  unsigned pa0, pa4, pa5 = 0, pb;
   const char* const a_base = (const char*)p.A + ((long long)tm * S * Lp + p.in_off) * p.lda * 2;
   const char* const w_base = (const char*)p.W + ((long long)tn * 256) * K * 2;
   const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a_base, 0, 0x7fffffff, 0x00020000);
@@ -1373,10 +1201,8 @@ __global__ void __launch_bounds__(512, 2) conv3_halo16x3_kernel(ConvGemmParams p
   long long wq[4];
   {
     const int lr = lane >> 3;
-    const int slot0 = (lane & 7) ^ lr;                               // r & 7 = lr for every piece q
-    const int slot1 = slot0;
-    pbe = (unsigned)(((long long)(8 * lr) * K + (slot0 & 3) * 8) * 2) + ((slot0 & 4) ? w_plane : 0u);
-    pbo = (unsigned)(((long long)(8 * lr) * K + (slot1 & 3) * 8) * 2) + ((slot1 & 4) ? w_plane : 0u);
+    const int slot = (lane & 7) ^ lr;                                // r & 7 = lr for every piece q
+    pb = (unsigned)(((long long)(8 * lr) * K + (slot & 3) * 8) * 2) + ((slot & 4) ? w_plane : 0u);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int r0 = (w * 4 + q) * 8;
@@ -1391,7 +1217,7 @@ __global__ void __launch_bounds__(512, 2) conv3_halo16x3_kernel(ConvGemmParams p
   };
   auto issue_w = [&](int v, int t, int q) {
     __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, (LDS_AS void*)(smem + W_BASE + ((v + t) & 1) * W_BUF + (w * 4 + q) * 1024),
-                                             16, (q & 1) ? pbo : pbe, (int)wq[q] + v * 64 + t * w_tap, 0, 0);
+                                             16, pb, (int)wq[q] + v * 64 + t * w_tap, 0, 0);
   };
 
   int lrow0;
@@ -1432,12 +1258,7 @@ __global__ void __launch_bounds__(512, 2) conv3_halo16x3_kernel(ConvGemmParams p
   auto mm = [&](int aset, int bset, int half, int mb, int jj) {
     acc[mb][half * 4 + jj] = mfma16<ET>(af[aset][mb], bq[bset][jj], acc[mb][half * 4 + jj]);
   };
-  auto mm16 = [&](int aset, int bset, int half) {
-#pragma unroll
-    for (int mb = 0; mb < 4; ++mb)
-#pragma unroll
-      for (int jj = 0; jj < 4; ++jj) mm(aset, bset, half, mb, (mb & 1) ? 3 - jj : jj);
-  };
+  auto mm16 = [&](int aset, int bset, int half) { mm16_snake<ET>(acc, af[aset], bq[bset], half); };
 
 #ifdef X3_PHASE_STAMP     // diagnostic build: issue time (core clock) of every phase of the last full K-steps, per tap
   unsigned pst[24];
@@ -1790,7 +1611,7 @@ __global__ void __launch_bounds__(512, 2) gemm16_kernel(ConvGemmParams p) {
   const int r4 = lane & 15, h4 = lane >> 4;
   const int wm = w >> 1, wn = w & 1;
   const int ntn = p.N >> 8, ntm = p.M >> 8;
-  const int tile = xcd_remap_strips(blockIdx.x, ntm, ntn, p.dbg);
+  const int tile = xcd_remap_strips(blockIdx.x, ntm, ntn, p.xcd_strips);
   const int tm = tile / ntn, tn = tile - tm * ntn;
   // SPLIT (hi + lo planes): a K-step is 32 channels of one tap, an LDS row holds [32 ch hi | the same 32 ch lo] (slots
   // 0..3 / 4..7, chosen by the per-lane source offset) and the step runs the three products A_hi W_lo, A_hi W_hi, A_lo W_hi
@@ -1896,6 +1717,7 @@ __global__ void __launch_bounds__(512, 2) gemm16_kernel(ConvGemmParams p) {
   auto mm = [&](int aset, int bset, int half, int mb, int jj) {
     acc[mb][half * 4 + jj] = mfma16<ET>(af[aset][mb], bq[bset][jj], acc[mb][half * 4 + jj]);
   };
+  // (not mm16_snake: through the shared helper the non-split instantiations of this kernel come out with other code)
   auto mm16 = [&](int aset, int bset, int half) {
 #pragma unroll
     for (int mb = 0; mb < 4; ++mb)
@@ -2025,32 +1847,98 @@ __global__ void __launch_bounds__(512, 2) gemm16_kernel(ConvGemmParams p) {
   __syncthreads();
   gemm_epilogue16<ET, SPLIT, SHORT>(p, acc, smem, tm, tn, tid, lane, r4, h4, wm, wn);
 }
+// ---- dispatch ---------------------------------------------------------------------------------
 // fmt = storage type | split << 2 (denoise.h).  The 16-bit tiles (halo, gemm16, small Conv2d) exist for bf16 and f16;
-// the hi/lo split forms only on the halo / gemm16 pipeline; f32 runs everything on conv_gemm_kernel<1>.
-static bool gemm16_eligible(const ConvGemmParams& p, int fmt) {
-  // L = 8 and 4 (the ant config's lower levels): a 16-row block of the epilogue spans 2 or 4 samples (per-lane sample indices)
-  const bool short_ok = p.L == 8 || p.L == 4;
-  return fmt_st(fmt) != ST_F32 && !p.c2d && (!p.out_f32 || p.mode == MODE_BIAS) && p.taps >= 1 && p.taps <= 3 && (p.M & 255) == 0 &&
-         (p.N & 255) == 0 && (p.Cin & 63) == 0 && ((p.L & 15) == 0 || short_ok) && p.M > 0 &&
-         (p.mode == MODE_BIAS || (256 % p.L) == 0);
+// the hi/lo split forms only on the halo / gemm16 / small-Conv2d tiles; f32 runs everything on conv_gemm_kernel<1>.
+//
+// Every tile kernel instantiation, once: the picker finds its entry here, the launcher takes kernel, LDS size and block from
+// it, and the LDS attribute is set from the same rows.
+enum { TILE_HALO, TILE_GEMM16, TILE_C2D_SMALL, TILE_GENERIC };
+enum { TV_SPLIT = 1,     // hi + lo planes
+       TV_SHORT = 2,     // L = 8 / 4: per-lane sample indices in the epilogue
+       TV_SPLITK = 4,    // latency mode of the split halo kernel: gridDim.y work-groups per tile
+       TV_NP6 = 8,       // L = 4 on the split halo kernel: six activation pieces, all 160 KB of LDS
+       TV_C2D = 16 };    // implicit Conv2d addressing
+struct TileVariant {
+  void (*kernel)(ConvGemmParams);
+  unsigned lds_bytes;    // dynamic LDS of a work-group
+  unsigned block;        // threads per work-group
+  int family, st;        // TILE_*, storage type ST_*
+  unsigned flags;        // TV_*
+  int kind;              // what conv_gemm_kind reports: 0 halo kernel, 1 gemm16 / generic, 2 implicit Conv2d
+};
+static const TileVariant k_tiles[] = {
+    {conv3_halo16_kernel<0>, 147456, 512, TILE_HALO, ST_BF16, 0, 0},
+    {conv3_halo16_kernel<1>, 147456, 512, TILE_HALO, ST_F16, 0, 0},
+    {conv3_halo16x3_kernel<0>, 147456, 512, TILE_HALO, ST_BF16, TV_SPLIT, 0},
+    {conv3_halo16x3_kernel<1>, 147456, 512, TILE_HALO, ST_F16, TV_SPLIT, 0},
+    {conv3_halo16x3_kernel<0, true>, 147456, 512, TILE_HALO, ST_BF16, TV_SPLIT | TV_SHORT, 0},
+    {conv3_halo16x3_kernel<1, true>, 147456, 512, TILE_HALO, ST_F16, TV_SPLIT | TV_SHORT, 0},
+    {conv3_halo16x3_kernel<0, false, true>, 147456, 512, TILE_HALO, ST_BF16, TV_SPLIT | TV_SPLITK, 0},
+    {conv3_halo16x3_kernel<1, false, true>, 147456, 512, TILE_HALO, ST_F16, TV_SPLIT | TV_SPLITK, 0},
+    {conv3_halo16x3_kernel<0, true, true>, 147456, 512, TILE_HALO, ST_BF16, TV_SPLIT | TV_SHORT | TV_SPLITK, 0},
+    {conv3_halo16x3_kernel<1, true, true>, 147456, 512, TILE_HALO, ST_F16, TV_SPLIT | TV_SHORT | TV_SPLITK, 0},
+    {conv3_halo16x3_kernel<0, true, false, 6>, 163840, 512, TILE_HALO, ST_BF16, TV_SPLIT | TV_SHORT | TV_NP6, 0},
+    {conv3_halo16x3_kernel<1, true, false, 6>, 163840, 512, TILE_HALO, ST_F16, TV_SPLIT | TV_SHORT | TV_NP6, 0},
+    {gemm16_kernel<0, false>, 131072, 512, TILE_GEMM16, ST_BF16, 0, 1},
+    {gemm16_kernel<1, false>, 131072, 512, TILE_GEMM16, ST_F16, 0, 1},
+    {gemm16_kernel<0, true>, 131072, 512, TILE_GEMM16, ST_BF16, TV_SPLIT, 1},
+    {gemm16_kernel<1, true>, 131072, 512, TILE_GEMM16, ST_F16, TV_SPLIT, 1},
+    {gemm16_kernel<0, false, true>, 131072, 512, TILE_GEMM16, ST_BF16, TV_SHORT, 1},
+    {gemm16_kernel<1, false, true>, 131072, 512, TILE_GEMM16, ST_F16, TV_SHORT, 1},
+    {gemm16_kernel<0, true, true>, 131072, 512, TILE_GEMM16, ST_BF16, TV_SPLIT | TV_SHORT, 1},
+    {gemm16_kernel<1, true, true>, 131072, 512, TILE_GEMM16, ST_F16, TV_SPLIT | TV_SHORT, 1},
+    {conv2d_small_kernel<0, false>, 3 * 16384, 256, TILE_C2D_SMALL, ST_BF16, TV_C2D, 2},
+    {conv2d_small_kernel<1, false>, 3 * 16384, 256, TILE_C2D_SMALL, ST_F16, TV_C2D, 2},
+    {conv2d_small_kernel<0, true>, 3 * 16384, 256, TILE_C2D_SMALL, ST_BF16, TV_C2D | TV_SPLIT, 2},
+    {conv2d_small_kernel<1, true>, 3 * 16384, 256, TILE_C2D_SMALL, ST_F16, TV_C2D | TV_SPLIT, 2},
+    {conv_gemm_kernel<0, false>, 131072, 512, TILE_GENERIC, ST_BF16, 0, 1},
+    {conv_gemm_kernel<1, false>, 131072, 512, TILE_GENERIC, ST_F32, 0, 1},
+    {conv_gemm_kernel<2, false>, 131072, 512, TILE_GENERIC, ST_F16, 0, 1},
+    {conv_gemm_kernel<0, true>, 131072, 512, TILE_GENERIC, ST_BF16, TV_C2D, 2},
+    {conv_gemm_kernel<1, true>, 131072, 512, TILE_GENERIC, ST_F32, TV_C2D, 2},
+    {conv_gemm_kernel<2, true>, 131072, 512, TILE_GENERIC, ST_F16, TV_C2D, 2},
+};
+// (pick_tile only asks for keys that have a row above; a key without one counts as "no tile fits")
+static const TileVariant* find_tile(int family, int st, unsigned flags) {
+  for (const TileVariant& v : k_tiles)
+    if (v.family == family && v.st == st && v.flags == flags) return &v;
+  return nullptr;
 }
-static bool halo_eligible(const ConvGemmParams& p, int fmt) {
-  // L = 8 (the ant network's middle level, split formats): a tile's 32 samples x 10 padded rows are exactly the 320 rows the
-  // five staging pieces hold; the fragment rows are per-lane offsets already (lrow0), the epilogue is the SHORT instantiation.
-  // L = 4: 64 samples x 6 padded rows = 384 staged rows, the six-piece instantiation (all 160 KB of LDS; no split-K form).
-  // DITREE_HALO_L8=0 / DITREE_HALO_L4=0 send these levels back to gemm16_kernel (A/B switches).
-  static const bool l8_off = [] { const char* e = getenv("DITREE_HALO_L8"); return e && atoi(e) == 0; }();
-  static const bool l4_off = [] { const char* e = getenv("DITREE_HALO_L4"); return e && atoi(e) == 0; }();
-  const bool l_ok = p.L >= 16 || (p.L == 8 && fmt_split(fmt) && !l8_off) || (p.L == 4 && fmt_split(fmt) && !l4_off && p.splitk <= 1);
-  return fmt_st(fmt) != ST_F32 && !p.c2d && p.taps == 3 && p.in_stride == 1 && p.in_Lp == p.L + 2 && (256 % p.L) == 0 &&
-         l_ok && (p.M & 255) == 0 && (p.N & 255) == 0 && (p.Cin & 63) == 0 && p.Cin >= 192;
+
+// The tile a GEMM runs on, or null where none fits (split formats only: the other formats fall back to conv_gemm_kernel).
+// The eligibility rules live here and nowhere else.
+static const TileVariant* pick_tile(const ConvGemmParams& p, int fmt) {
+  const int st = fmt_st(fmt);
+  const bool split = fmt_split(fmt);
+  const unsigned fsplit = split ? TV_SPLIT : 0;
+  const bool tile16 = st != ST_F32 && !p.c2d && (p.M & 255) == 0 && (p.N & 255) == 0 && (p.Cin & 63) == 0;
+  // halo tile.  L = 8 (the ant network's middle level, split formats): a tile's 32 samples x 10 padded rows are exactly the 320
+  // rows the five staging pieces hold; the fragment rows are per-lane offsets already (lrow0), the epilogue is the SHORT
+  // instantiation.  L = 4: 64 samples x 6 padded rows = 384 staged rows, the six-piece instantiation (no split-K form).
+  const bool l_ok = p.L >= 16 || (p.L == 8 && split) || (p.L == 4 && split && p.splitk <= 1);
+  if (tile16 && p.taps == 3 && p.in_stride == 1 && p.in_Lp == p.L + 2 && (256 % p.L) == 0 && l_ok && p.Cin >= 192) {
+    if (!split) return find_tile(TILE_HALO, st, 0);
+    const unsigned fshort = p.L <= 8 ? TV_SHORT : 0;
+    if (p.splitk > 1) return find_tile(TILE_HALO, st, TV_SPLIT | fshort | TV_SPLITK);   // latency mode (denoise.h)
+    return find_tile(TILE_HALO, st, TV_SPLIT | fshort | (p.L == 4 ? TV_NP6 : 0));
+  }
+  // gemm16 tile.  L = 8 and 4 (the ant config's lower levels): a 16-row block of the epilogue spans 2 or 4 samples
+  const bool short_l = p.L == 8 || p.L == 4;
+  if (tile16 && (!p.out_f32 || p.mode == MODE_BIAS) && p.taps >= 1 && p.taps <= 3 && ((p.L & 15) == 0 || short_l) && p.M > 0 &&
+      (p.mode == MODE_BIAS || (256 % p.L) == 0))
+    return find_tile(TILE_GEMM16, st, fsplit | ((p.L & 15) != 0 ? TV_SHORT : 0));
+  if (p.c2d && conv2d_small_eligible(fmt) && (p.N & 63) == 0 && (p.Cin & 63) == 0 && p.out_f32 && p.mode == MODE_BIAS)
+    return find_tile(TILE_C2D_SMALL, st, TV_C2D | fsplit);
+  if (split) return nullptr;
+  return find_tile(TILE_GENERIC, st, p.c2d ? TV_C2D : 0);
 }
 bool conv2d_small_eligible(int fmt) { return fmt_st(fmt) != ST_F32; }
-int conv_gemm_kind(const ConvGemmParams& p, int fmt) { return halo_eligible(p, fmt) ? 0 : (p.c2d ? 2 : 1); }
-bool conv_gemm_supported(const ConvGemmParams& p, int fmt) {
-  return !fmt_split(fmt) || halo_eligible(p, fmt) || gemm16_eligible(p, fmt) ||
-         (p.c2d && (p.N & 63) == 0 && (p.Cin & 63) == 0 && p.out_f32 && p.mode == MODE_BIAS);
+int conv_gemm_kind(const ConvGemmParams& p, int fmt) {
+  const TileVariant* v = pick_tile(p, fmt);
+  return v != nullptr ? v->kind : (p.c2d ? 2 : 1);
 }
+bool conv_gemm_supported(const ConvGemmParams& p, int fmt) { return pick_tile(p, fmt) != nullptr; }
 
 // > 64 KB of dynamic LDS needs the attribute once per kernel AND per device
 static void ensure_lds_attrs() {
@@ -2059,847 +1947,22 @@ static void ensure_lds_attrs() {
   hipGetDevice(&dev);
   if (dev < 0 || dev >= 64 || done[dev]) return;
   done[dev] = true;
-  const hipFuncAttribute at = hipFuncAttributeMaxDynamicSharedMemorySize;
-  hipFuncSetAttribute((const void*)conv_gemm_kernel<0, false>, at, 131072);
-  hipFuncSetAttribute((const void*)conv_gemm_kernel<1, false>, at, 131072);
-  hipFuncSetAttribute((const void*)conv_gemm_kernel<2, false>, at, 131072);
-  hipFuncSetAttribute((const void*)conv_gemm_kernel<0, true>, at, 131072);
-  hipFuncSetAttribute((const void*)conv_gemm_kernel<1, true>, at, 131072);
-  hipFuncSetAttribute((const void*)conv_gemm_kernel<2, true>, at, 131072);
-  hipFuncSetAttribute((const void*)conv3_halo16_kernel<0, false>, at, 147456);
-  hipFuncSetAttribute((const void*)conv3_halo16_kernel<1, false>, at, 147456);
-  hipFuncSetAttribute((const void*)conv3_halo16x3_kernel<0>, at, 147456);
-  hipFuncSetAttribute((const void*)conv3_halo16x3_kernel<1>, at, 147456);
-  hipFuncSetAttribute((const void*)conv3_halo16x3_kernel<0, true>, at, 147456);
-  hipFuncSetAttribute((const void*)conv3_halo16x3_kernel<1, true>, at, 147456);
-  hipFuncSetAttribute((const void*)conv3_halo16x3_kernel<0, false, true>, at, 147456);
-  hipFuncSetAttribute((const void*)conv3_halo16x3_kernel<1, false, true>, at, 147456);
-  hipFuncSetAttribute((const void*)conv3_halo16x3_kernel<0, true, true>, at, 147456);
-  hipFuncSetAttribute((const void*)conv3_halo16x3_kernel<1, true, true>, at, 147456);
-  hipFuncSetAttribute((const void*)conv3_halo16x3_kernel<0, true, false, 6>, at, 163840);
-  hipFuncSetAttribute((const void*)conv3_halo16x3_kernel<1, true, false, 6>, at, 163840);
-  hipFuncSetAttribute((const void*)gemm16_kernel<0, false>, at, 131072);
-  hipFuncSetAttribute((const void*)gemm16_kernel<1, false>, at, 131072);
-  hipFuncSetAttribute((const void*)gemm16_kernel<0, true>, at, 131072);
-  hipFuncSetAttribute((const void*)gemm16_kernel<1, true>, at, 131072);
-  hipFuncSetAttribute((const void*)gemm16_kernel<0, false, true>, at, 131072);
-  hipFuncSetAttribute((const void*)gemm16_kernel<1, false, true>, at, 131072);
-  hipFuncSetAttribute((const void*)gemm16_kernel<0, true, true>, at, 131072);
-  hipFuncSetAttribute((const void*)gemm16_kernel<1, true, true>, at, 131072);
+  for (const TileVariant& v : k_tiles)
+    if (v.lds_bytes > 65536) hipFuncSetAttribute((const void*)v.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v.lds_bytes);
 }
 
 void launch_conv_gemm(const ConvGemmParams& p, int fmt, hipStream_t s) {
   ensure_lds_attrs();
-  const int st = fmt_st(fmt);
-  const bool split = fmt_split(fmt), f16 = st == ST_F16;
-  const int ntn = (p.N + 255) >> 8, ntm = (p.M + 255) >> 8;
-  const dim3 grid(ntm * ntn), block(512);
-  if (halo_eligible(p, fmt)) {
-    if (split && p.splitk > 1) {                              // latency mode: gridDim.y work-groups per tile (denoise.h)
-      if (p.sk_ws == nullptr || p.sk_cnt == nullptr || ((p.Cin >> 5) % p.splitk) != 0 || (p.Cin >> 5) / p.splitk < 2)
-        throw std::runtime_error("conv_gemm: split-K of the halo kernel needs its workspace and splitk | Cin / 32, >= 2 chunks each");
-      const dim3 gsk(ntm * ntn, p.splitk);
-      if (p.L == 8) {
-        if (f16) DN_LAUNCH((conv3_halo16x3_kernel<1, true, true>), gsk, block, 147456, s, p);
-        else DN_LAUNCH((conv3_halo16x3_kernel<0, true, true>), gsk, block, 147456, s, p);
-      } else if (f16) DN_LAUNCH((conv3_halo16x3_kernel<1, false, true>), gsk, block, 147456, s, p);
-      else DN_LAUNCH((conv3_halo16x3_kernel<0, false, true>), gsk, block, 147456, s, p);
-      return;
-    }
-    if (split && p.L == 4) {                                  // six activation pieces: all 160 KB of LDS
-      if (f16) DN_LAUNCH((conv3_halo16x3_kernel<1, true, false, 6>), grid, block, 163840, s, p);
-      else DN_LAUNCH((conv3_halo16x3_kernel<0, true, false, 6>), grid, block, 163840, s, p);
-      return;
-    }
-    if (split) {
-      if (p.L == 8) {
-        if (f16) DN_LAUNCH((conv3_halo16x3_kernel<1, true>), grid, block, 147456, s, p);
-        else DN_LAUNCH((conv3_halo16x3_kernel<0, true>), grid, block, 147456, s, p);
-      } else if (f16) DN_LAUNCH(conv3_halo16x3_kernel<1>, grid, block, 147456, s, p);
-      else DN_LAUNCH(conv3_halo16x3_kernel<0>, grid, block, 147456, s, p);
-    } else {
-      if (f16) DN_LAUNCH((conv3_halo16_kernel<1, false>), grid, block, 147456, s, p);
-      else DN_LAUNCH((conv3_halo16_kernel<0, false>), grid, block, 147456, s, p);
-    }
-    return;
-  }
-  if (gemm16_eligible(p, fmt) && (p.L & 15) != 0) {          // L = 8, 4: per-lane sample indices in the epilogue
-    if (split) {
-      if (f16) DN_LAUNCH((gemm16_kernel<1, true, true>), grid, block, 131072, s, p);
-      else DN_LAUNCH((gemm16_kernel<0, true, true>), grid, block, 131072, s, p);
-    } else {
-      if (f16) DN_LAUNCH((gemm16_kernel<1, false, true>), grid, block, 131072, s, p);
-      else DN_LAUNCH((gemm16_kernel<0, false, true>), grid, block, 131072, s, p);
-    }
-    return;
-  }
-  if (gemm16_eligible(p, fmt)) {
-    if (split) {
-      if (f16) DN_LAUNCH((gemm16_kernel<1, true>), grid, block, 131072, s, p);
-      else DN_LAUNCH((gemm16_kernel<0, true>), grid, block, 131072, s, p);
-    } else {
-      if (f16) DN_LAUNCH((gemm16_kernel<1, false>), grid, block, 131072, s, p);
-      else DN_LAUNCH((gemm16_kernel<0, false>), grid, block, 131072, s, p);
-    }
-    return;
-  }
-  if (p.mode >= MODE_GN_MISH && (p.L & 15) != 0)
+  const TileVariant* v = pick_tile(p, fmt);
+  if (v != nullptr && (v->flags & TV_SPLITK) &&
+      (p.sk_ws == nullptr || p.sk_cnt == nullptr || ((p.Cin >> 5) % p.splitk) != 0 || (p.Cin >> 5) / p.splitk < 2))
+    throw std::runtime_error("conv_gemm: split-K of the halo kernel needs its workspace and splitk | Cin / 32, >= 2 chunks each");
+  if ((v == nullptr || v->family == TILE_GENERIC) && p.mode >= MODE_GN_MISH && (p.L & 15) != 0)
     throw std::runtime_error("conv_gemm: a fused GroupNorm epilogue at L = 8 / 4 exists on the gemm16 tile only (whole 256-row tiles)");
-  if (p.c2d && conv2d_small_eligible(fmt) && (p.N & 63) == 0 && (p.Cin & 63) == 0 && p.out_f32 && p.mode == MODE_BIAS) {
-    const dim3 g2(((p.M + 63) >> 6) * (p.N >> 6), p.splitk > 1 ? p.splitk : 1);
-    if (split) {
-      if (f16) DN_LAUNCH((conv2d_small_kernel<1, true>), g2, dim3(256), 3 * 16384, s, p);
-      else DN_LAUNCH((conv2d_small_kernel<0, true>), g2, dim3(256), 3 * 16384, s, p);
-    } else {
-      if (f16) DN_LAUNCH((conv2d_small_kernel<1, false>), g2, dim3(256), 3 * 16384, s, p);
-      else DN_LAUNCH((conv2d_small_kernel<0, false>), g2, dim3(256), 3 * 16384, s, p);
-    }
-    return;
-  }
-  if (split) throw std::runtime_error("conv_gemm: a split GEMM of this shape fits no tile (conv_gemm_supported is the contract)");
-  if (p.c2d) {
-    const dim3 grid2(ntm * ntn, p.splitk > 1 ? p.splitk : 1);
-    if (st == ST_F32) DN_LAUNCH((conv_gemm_kernel<1, true>), grid2, block, 131072, s, p);
-    else if (f16) DN_LAUNCH((conv_gemm_kernel<2, true>), grid2, block, 131072, s, p);
-    else DN_LAUNCH((conv_gemm_kernel<0, true>), grid2, block, 131072, s, p);
-    return;
-  }
-  if (st == ST_F32) DN_LAUNCH((conv_gemm_kernel<1, false>), grid, block, 131072, s, p);
-  else if (f16) DN_LAUNCH((conv_gemm_kernel<2, false>), grid, block, 131072, s, p);
-  else DN_LAUNCH((conv_gemm_kernel<0, false>), grid, block, 131072, s, p);
-}
-
-// ============================================================================= small kernels
-// FMT = storage type | split << 2 (denoise.h).  `plane` = bytes from the hi plane to the lo plane of a split buffer.
-template <int FMT>
-__device__ __forceinline__ void store_elem(void* base, long long idx, float v, long long plane = 0) {
-  constexpr int ST = FMT & 3;
-  if constexpr (ST == ST_F32) {
-    ((float*)base)[idx] = v;
-  } else {
-    constexpr int ET = ST == ST_F16 ? 1 : 0;
-    const unsigned short hi = f2e<ET>(v);
-    ((unsigned short*)base)[idx] = hi;
-    if constexpr ((FMT & 4) != 0) ((unsigned short*)((char*)base + plane))[idx] = f2e<ET>(v - e2f<ET>(hi));
-  }
-}
-// the same, feeding the f16 range guard of the calling thread
-template <int FMT>
-__device__ __forceinline__ void store_elem(void* base, long long idx, float v, long long plane, float& satm) {
-  if constexpr ((FMT & 3) == ST_F16) sat_see(satm, v);
-  store_elem<FMT>(base, idx, v, plane);
-}
-template <int FMT>
-__device__ __forceinline__ float load_elem(const void* base, long long idx, long long plane = 0) {
-  constexpr int ST = FMT & 3;
-  if constexpr (ST == ST_F32) {
-    return ((const float*)base)[idx];
-  } else {
-    constexpr int ET = ST == ST_F16 ? 1 : 0;
-    float v = e2f<ET>(((const unsigned short*)base)[idx]);
-    if constexpr ((FMT & 4) != 0) v += e2f<ET>(((const unsigned short*)((const char*)base + plane))[idx]);
-    return v;
-  }
-}
-// exact Mish for the f32 and the split (f32-class) formats, the fast form for plain 16-bit storage
-#define MISH_OF(FMT) mish_f<((FMT) == ST_BF16 || (FMT) == ST_F16) ? 0 : 1>
-// run CALL(FMT) with FMT a compile-time constant
-#define DISPATCH_FMT(fmt, CALL)                                   \
-  switch (fmt) {                                                  \
-    case 0: CALL(0); break;                                       \
-    case 1: CALL(1); break;                                       \
-    case 2: CALL(2); break;                                       \
-    case 4: CALL(4); break;                                       \
-    case 6: CALL(6); break;                                       \
-    default: throw std::runtime_error("denoiser kernels: unknown activation format"); \
-  }
-#define DISPATCH_ST(fmt, CALL)                                    \
-  switch (fmt) {                                                  \
-    case 0: CALL(0); break;                                       \
-    case 1: CALL(1); break;                                       \
-    case 2: CALL(2); break;                                       \
-    default: throw std::runtime_error("denoiser kernels: unknown activation format"); \
-  }
-
-// x (B, P, D) f32 -> A0 rows (b, l): [x[l-1,:], x[l,:], x[l+1,:], 0 ...] (K padded to 64): the
-// im2col of the first Conv1d(D -> C, 3) (conditional_unet1d.py:214-218 with dim_in = input_dim).
-// GroupNorm(8 groups) + Mish (+ FiLM | + residual) in place on a padded channels-last activation: the unfused form
-// of the GEMM epilogue, for channel counts whose groups do not map onto the 256-channel GEMM tiles (the reference's
-// denoiser sizes other than `large`: C/8 < 64 or > 256 channels per group).  conv1d_components.py:23-40,
-// conditional_unet1d.py:110-141.  One 256-thread work-group per (sample, group); a thread walks 8-channel vectors;
-// mean, then centred squares, then the update: three passes over at most 16 KB that stay in L2.
-template <int PREC>
-__global__ void __launch_bounds__(256) gn1d_kernel(void* __restrict__ x, int ld, int Lp, int row_off, int coff, int L, int C,
-                                                   const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
-                                                   int mode, const float* __restrict__ film, int film_ld, int film_off,
-                                                   const void* __restrict__ res, int ldres, int res_Lp, int res_off,
-                                                   long long x_plane, long long res_plane, int* __restrict__ sat) {
-  __shared__ float red[8];
-  float satm = 0.0f;
-  const int b = blockIdx.x >> 3, g = blockIdx.x & 7;
-  const int gc = C >> 3, vpr = gc >> 3, nvec = L * vpr;          // channels per group, 8-channel vectors per row
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  auto at = [&](int v, int& l, int& c) { l = v / vpr; c = g * gc + (v - l * vpr) * 8; };
-  auto load8 = [&](int l, int c, float (&o)[8]) {
-    const long long idx = ((long long)b * Lp + l + row_off) * ld + coff + c;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = load_elem<PREC>(x, idx + j, x_plane);
-  };
-  auto wg_sum = [&](float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    __syncthreads();
-    if (lane == 0) red[wv] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-  };
-  float s = 0.f;
-  for (int v = tid; v < nvec; v += 256) {
-    int l, c; at(v, l, c);
-    float o[8]; load8(l, c, o);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) s += o[j];
-  }
-  const float inv_n = 1.0f / (float)(L * gc);
-  const float mean = wg_sum(s) * inv_n;
-  float q = 0.f;
-  for (int v = tid; v < nvec; v += 256) {
-    int l, c; at(v, l, c);
-    float o[8]; load8(l, c, o);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { const float d = o[j] - mean; q = fmaf(d, d, q); }
-  }
-  const float rstd = rsqrtf(wg_sum(q) * inv_n + eps);
-  for (int v = tid; v < nvec; v += 256) {
-    int l, c; at(v, l, c);
-    float o[8]; load8(l, c, o);
-    const long long idx = ((long long)b * Lp + l + row_off) * ld + coff + c;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float y = MISH_OF(PREC)((o[j] - mean) * rstd * gamma[c + j] + beta[c + j]);
-      if (mode == MODE_GN_MISH_FILM) {
-        const float* fr = film + (long long)b * film_ld + film_off + c + j;
-        y = y * fr[0] + fr[C];
-      } else if (mode == MODE_GN_MISH_RES) {
-        y += load_elem<PREC>(res, ((long long)b * res_Lp + l + res_off) * ldres + c + j, res_plane);
-      }
-      store_elem<PREC>(x, idx + j, y, x_plane, satm);
-    }
-  }
-  if constexpr ((PREC & 3) == ST_F16) sat_flush(sat, satm);
-}
-// The same for short sequences in the 16-bit formats (the ant config's L = 8 and 4 levels: a (sample, group) is 128
-// 8-channel vectors): one WAVE per (sample, group), its vectors (up to four per lane) stay in registers -- one 16-byte load
-// per vector and plane, statistics by wave reductions, one 16-byte store per vector and plane; four (sample, group)s per
-// work-group.  Same arithmetic as gn1d_kernel (mean, then centred squares), so results are identical.
-template <int FMT>
-__global__ void __launch_bounds__(256) gn1d_short_kernel(void* __restrict__ x, int ld, int Lp, int row_off, int coff, int L, int C,
-                                                         const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                         float eps, int mode, const float* __restrict__ film, int film_ld,
-                                                         int film_off, const void* __restrict__ res, int ldres, int res_Lp,
-                                                         int res_off, long long x_plane, long long res_plane, int n_sg,
-                                                         int* __restrict__ sat) {
-  constexpr int ET = (FMT & 3) == ST_F16 ? 1 : 0;
-  constexpr bool SPL = (FMT & 4) != 0;
-  float satm = 0.0f;
-  const int lane = threadIdx.x & 63;
-  const int sg = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (sg >= n_sg) return;
-  const int b = sg >> 3, g = sg & 7;
-  const int gc = C >> 3, vpr = gc >> 3, nvec = L * vpr;
-  float v[4][8];
-  long long idx[4];
-  int cc[4], ll[4];
-  float s = 0.f;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int vi = lane + 64 * k;
-    if (vi < nvec) {
-      const int l = vi / vpr, c = g * gc + (vi - l * vpr) * 8;
-      ll[k] = l; cc[k] = c;
-      idx[k] = ((long long)b * Lp + l + row_off) * ld + coff + c;
-      const short8_t h = *(const short8_t*)((const char*)x + idx[k] * 2);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[k][j] = e2f<ET>((unsigned short)h[j]);
-      if constexpr (SPL) {
-        const short8_t lo = *(const short8_t*)((const char*)x + x_plane + idx[k] * 2);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[k][j] += e2f<ET>((unsigned short)lo[j]);
-      }
-#pragma unroll
-      for (int j = 0; j < 8; ++j) s += v[k][j];
-    }
-  }
-  auto wave_sum = [&](float t) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) t += __shfl_xor(t, m);
-    return t;
-  };
-  const float inv_n = 1.0f / (float)(L * gc);
-  const float mean = wave_sum(s) * inv_n;
-  float q = 0.f;
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-    if (lane + 64 * k < nvec) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { const float d = v[k][j] - mean; q = fmaf(d, d, q); }
-    }
-  const float rstd = rsqrtf(wave_sum(q) * inv_n + eps);
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-    if (lane + 64 * k < nvec) {
-      const int c = cc[k];
-      const f32x4_t g0 = *(const f32x4_t*)(gamma + c), g1 = *(const f32x4_t*)(gamma + c + 4);
-      const f32x4_t b0 = *(const f32x4_t*)(beta + c), b1 = *(const f32x4_t*)(beta + c + 4);
-      float y[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j)
-        y[j] = MISH_OF(FMT)((v[k][j] - mean) * rstd * (j < 4 ? g0[j & 3] : g1[j & 3]) + (j < 4 ? b0[j & 3] : b1[j & 3]));
-      if (mode == MODE_GN_MISH_FILM) {
-        const float* fr = film + (long long)b * film_ld + film_off + c;
-        const f32x4_t s0 = *(const f32x4_t*)fr, s1 = *(const f32x4_t*)(fr + 4);
-        const f32x4_t t0 = *(const f32x4_t*)(fr + C), t1 = *(const f32x4_t*)(fr + C + 4);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) y[j] = y[j] * (j < 4 ? s0[j & 3] : s1[j & 3]) + (j < 4 ? t0[j & 3] : t1[j & 3]);
-      } else if (mode == MODE_GN_MISH_RES) {
-        const long long ri = ((long long)b * res_Lp + ll[k] + res_off) * ldres + c;
-        const short8_t rh = *(const short8_t*)((const char*)res + ri * 2);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) y[j] += e2f<ET>((unsigned short)rh[j]);
-        if constexpr (SPL) {
-          const short8_t rl = *(const short8_t*)((const char*)res + res_plane + ri * 2);
-#pragma unroll
-          for (int j = 0; j < 8; ++j) y[j] += e2f<ET>((unsigned short)rl[j]);
-        }
-      }
-      short8_t oh, ol;
-      if constexpr (ET == 1) {
-#pragma unroll
-        for (int j = 0; j < 8; j += 2) sat_see2(satm, y[j], y[j + 1]);
-      }
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const unsigned short hh = f2e<ET>(y[j]);
-        oh[j] = (short)hh;
-        if constexpr (SPL) ol[j] = (short)f2e<ET>(y[j] - e2f<ET>(hh));
-      }
-      *(short8_t*)((char*)x + idx[k] * 2) = oh;
-      if constexpr (SPL) *(short8_t*)((char*)x + x_plane + idx[k] * 2) = ol;
-    }
-  if constexpr (ET == 1) sat_flush(sat, satm);
-}
-void launch_gn1d(void* x, int ld, int Lp, int row_off, int coff, int L, int C, const float* gamma, const float* beta, float eps,
-                 int mode, const float* film, int film_ld, int film_off, const void* res, int ldres, int res_Lp, int res_off,
-                 int B, int fmt, long long x_plane, long long res_plane, hipStream_t s, int* sat) {
-  // short (sample, group)s in a 16-bit format, 16-byte aligned vectors: the one-wave form
-  if (fmt_st(fmt) != ST_F32 && L * (C >> 6) <= 256 && (C & 63) == 0 && (ld & 7) == 0 && (coff & 7) == 0 &&
-      (mode != MODE_GN_MISH_RES || (ldres & 7) == 0) && (mode != MODE_GN_MISH_FILM || ((film_ld | film_off) & 3) == 0)) {
-    const int n_sg = B * 8;
-#define CALLS(F) DN_LAUNCH(gn1d_short_kernel<F>, dim3((n_sg + 3) / 4), dim3(256), 0, s, x, ld, Lp, row_off, coff, L, C, gamma, \
-                                    beta, eps, mode, film, film_ld, film_off, res, ldres, res_Lp, res_off, x_plane, res_plane, n_sg, sat)
-    switch (fmt) {
-      case 0: CALLS(0); break;
-      case 2: CALLS(2); break;
-      case 4: CALLS(4); break;
-      case 6: CALLS(6); break;
-      default: throw std::runtime_error("gn1d: unknown 16-bit format");
-    }
-#undef CALLS
-    return;
-  }
-#define CALL(F) DN_LAUNCH(gn1d_kernel<F>, dim3(B * 8), dim3(256), 0, s, x, ld, Lp, row_off, coff, L, C, gamma, beta, eps, \
-                                   mode, film, film_ld, film_off, res, ldres, res_Lp, res_off, x_plane, res_plane, sat)
-  DISPATCH_FMT(fmt, CALL)
-#undef CALL
-}
-
-// Encoder stem in one launch: Conv2d(1 -> 64, 7x7, stride 2, pad 3; the three identical input channels of
-// x.repeat(1,3,1,1) are folded into the weights) + GroupNorm(4 groups of 16 channels) + ReLU + MaxPool(3, 2, 1)
-// (local_map_encoder.py:101-122 through torchvision's resnet18 stem).  One 256-thread work-group per sample:
-// the padded 26 x 26 map and the 64 x 49 f32 weights sit in LDS / registers, thread (c = tid & 63, q = tid >> 6)
-// computes channel c at positions q, q+4, ... (25 of the 100), f32 FMA in (kh, kw) order; group statistics in two
-// passes over registers; the normalised 10 x 10 x 64 map goes through LDS to the 5 x 5 max-pool.
-// Replaces im2col + GEMM + GroupNorm + max-pool launches (and their 26 MB of intermediates per 1024 samples).
-template <int PREC, int N>
-__global__ void __launch_bounds__(256) encoder_stem_kernel(const float* __restrict__ lm /*[B][N][N]*/,
-                                                           const float* __restrict__ W /*[49][64]: tap-major, coalesced per lane*/,
-                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                           void* __restrict__ out /*[B][PH*PH][64]*/, float eps, long long plane,
-                                                           int* __restrict__ sat) {
-  // N = 20 (car): 26 x 26 padded map, 10 x 10 conv outputs, 5 x 5 after the pool;  N = 16 (ant): 22, 8 x 8, 4 x 4
-  constexpr int PD = N + 6, OH = N / 2, NP = OH * OH, J = NP / 4, PH = (OH - 1) / 2 + 1;
-  __shared__ float s_map[PD * PD];
-  __shared__ float s_act[NP * 64];
-  __shared__ float s_red[2][4][4];                    // [pass][position quarter][group]
-  float satm = 0.0f;
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const int c = tid & 63, q = tid >> 6, g = c >> 4;
-  for (int i = tid; i < PD * PD; i += 256) {
-    const int r = i / PD - 3, cc = i % PD - 3;
-    s_map[i] = (r >= 0 && r < N && cc >= 0 && cc < N) ? lm[(size_t)b * (N * N) + r * N + cc] : 0.0f;
-  }
-  float w[49];
-#pragma unroll
-  for (int k = 0; k < 49; ++k) w[k] = W[k * 64 + c];
-  __syncthreads();
-  float v[J];
-  float sum = 0.f;
-#pragma unroll
-  for (int j = 0; j < J; ++j) {
-    const int p = q + 4 * j, oh = p / OH, ow = p - oh * OH;
-    const float* m0 = s_map + (oh * 2) * PD + ow * 2;
-    float a = 0.f;
-#pragma unroll
-    for (int kh = 0; kh < 7; ++kh)
-#pragma unroll
-      for (int kw = 0; kw < 7; ++kw) a = fmaf(w[kh * 7 + kw], m0[kh * PD + kw], a);
-    v[j] = a;
-    sum += a;
-  }
-  // the 16 channels of a group are 16 adjacent lanes; the 4 position quarters are the 4 waves
-  sum += __shfl_xor(sum, 1); sum += __shfl_xor(sum, 2); sum += __shfl_xor(sum, 4); sum += __shfl_xor(sum, 8);
-  if ((c & 15) == 0) s_red[0][q][g] = sum;
-  __syncthreads();
-  constexpr float inv_n = 1.0f / (float)(NP * 16);
-  const float mean = ((s_red[0][0][g] + s_red[0][1][g]) + (s_red[0][2][g] + s_red[0][3][g])) * inv_n;
-  float sq = 0.f;
-#pragma unroll
-  for (int j = 0; j < J; ++j) { const float d = v[j] - mean; sq = fmaf(d, d, sq); }
-  sq += __shfl_xor(sq, 1); sq += __shfl_xor(sq, 2); sq += __shfl_xor(sq, 4); sq += __shfl_xor(sq, 8);
-  if ((c & 15) == 0) s_red[1][q][g] = sq;
-  __syncthreads();
-  const float var = ((s_red[1][0][g] + s_red[1][1][g]) + (s_red[1][2][g] + s_red[1][3][g])) * inv_n;
-  const float rstd = rsqrtf(var + eps);
-  const float ga = gamma[c] * rstd, be = beta[c] - mean * ga;
-#pragma unroll
-  for (int j = 0; j < J; ++j) {
-    float y = fmaf(v[j], ga, be);
-    y = y > 0.f ? y : 0.f;
-    if constexpr (PREC == ST_BF16) y = bf2f(f2bf(y));      // the activation is stored as bf16 before the pool in the layered path
-    if constexpr (PREC == ST_F16) y = h2f(f2h(y));         // (the split formats keep the f32 value: hi + lo carries it)
-    s_act[(q + 4 * j) * 64 + c] = y;
-  }
-  __syncthreads();
-  for (int o = tid; o < PH * PH * 64; o += 256) {
-    const int oc = o & 63, op = o >> 6, oh = op / PH, ow = op - oh * PH;
-    float best = -__builtin_huge_valf();
-#pragma unroll
-    for (int kh = 0; kh < 3; ++kh)
-#pragma unroll
-      for (int kw = 0; kw < 3; ++kw) {
-        const int ih = oh * 2 + kh - 1, iw = ow * 2 + kw - 1;
-        if (ih >= 0 && ih < OH && iw >= 0 && iw < OH) best = fmaxf(best, s_act[(ih * OH + iw) * 64 + oc]);
-      }
-    store_elem<PREC>(out, (long long)b * (PH * PH * 64) + o, best, plane, satm);
-  }
-  if constexpr ((PREC & 3) == ST_F16) sat_flush(sat, satm);
-}
-void launch_encoder_stem(const float* lm, int n, const float* W, const float* gamma, const float* beta, void* out, int B, float eps,
-                         int fmt, long long plane, hipStream_t s, int* sat) {
-  if (n != 20 && n != 16) throw std::runtime_error("encoder stem: local map must be 20 x 20 or 16 x 16");
-#define CALL(F)                                                                                                                    \
-  do {                                                                                                                             \
-    if (n == 20) DN_LAUNCH((encoder_stem_kernel<F, 20>), dim3(B), dim3(256), 0, s, lm, W, gamma, beta, out, eps, plane, sat);  \
-    else DN_LAUNCH((encoder_stem_kernel<F, 16>), dim3(B), dim3(256), 0, s, lm, W, gamma, beta, out, eps, plane, sat);          \
-  } while (0)
-  DISPATCH_FMT(fmt, CALL)
-#undef CALL
-}
-
-template <int PREC>
-__global__ void prep_sample_kernel(const float* __restrict__ x, void* __restrict__ A0, int B, int P, int D, long long plane,
-                                   int* __restrict__ sat) {
-  const long long row = blockIdx.x * (long long)(blockDim.x >> 6) + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (row >= (long long)B * P) return;
-  const int b = (int)(row / P), l = (int)(row - (long long)b * P);
-  float v = 0.f;
-  if (lane < 3 * D) {
-    const int t = lane / D, d = lane - t * D;
-    const int ls = l + t - 1;
-    if (ls >= 0 && ls < P) v = x[((long long)b * P + ls) * D + d];
-  }
-  float satm = 0.0f;
-  store_elem<PREC>(A0, row * 64 + lane, v, plane, satm);
-  if constexpr ((PREC & 3) == ST_F16) sat_flush(sat, satm);
-}
-void launch_prep_sample(const float* x, void* A0, int B, int P, int D, int fmt, long long plane, hipStream_t s, int* sat) {
-  long long rows = (long long)B * P;
-  dim3 grid((unsigned)((rows + 3) / 4)), block(256);
-#define CALL(F) DN_LAUNCH(prep_sample_kernel<F>, grid, block, 0, s, x, A0, B, P, D, plane, sat)
-  DISPATCH_FMT(fmt, CALL)
-#undef CALL
-}
-
-// Time embedding of one flow step: sinusoidal(256) -> Linear(256,1024) -> Mish -> Linear(1024,256)
-// (positional_embedding.py:10-17, conditional_unet1d.py:180-185).  Batch-invariant, f32.
-__global__ void __launch_bounds__(1024) time_embed_kernel(float t, const float* __restrict__ W1, const float* __restrict__ b1,
-                                                          const float* __restrict__ W2, const float* __restrict__ b2,
-                                                          float* __restrict__ out /*[256]*/) {
-  __shared__ float emb[256];
-  __shared__ float hid[1024];
-  const int tid = threadIdx.x;
-  if (tid < 256) {
-    const int half = 128;
-    const float wlog = logf(10000.0f) / (float)(half - 1);
-    const int k = tid & 127;
-    const float f = expf((float)k * -wlog);
-    const float a = t * f;
-    emb[tid] = (tid < 128) ? sinf(a) : cosf(a);
-  }
-  __syncthreads();
-  {
-    float s = b1[tid];
-    const float* wr = W1 + (long long)tid * 256;
-    for (int k = 0; k < 256; ++k) s += wr[k] * emb[k];
-    hid[tid] = mish_f<1>(s);
-  }
-  __syncthreads();
-  if (tid < 256) {
-    float s = b2[tid];
-    const float* wr = W2 + (long long)tid * 1024;
-    for (int k = 0; k < 1024; ++k) s += wr[k] * hid[k];
-    out[tid] = s;
-  }
-}
-void launch_time_embed(float t, const float* W1, const float* b1, const float* W2, const float* b2, float* out,
-                       hipStream_t s) {
-  DN_LAUNCH(time_embed_kernel, dim3(1), dim3(1024), 0, s, t, W1, b1, W2, b2, out);
-}
-
-// FiLM input: Mish(cat(time_emb 256, map_emb E, obs_cond G)) zero-padded to Kpad columns
-// (conditional_unet1d.py:59-64 cond_encoder = Mish -> Linear, :293 global_feature).
-template <int PREC>
-__global__ void prep_cond_kernel(const float* __restrict__ temb, const float* __restrict__ map_emb, int E, int E_ld,
-                                 const float* __restrict__ cond, int G, void* __restrict__ out, int B, int Kpad, long long plane,
-                                 int* __restrict__ sat) {
-  const int b = blockIdx.x;
-  float satm = 0.0f;
-  for (int k = threadIdx.x; k < Kpad; k += blockDim.x) {
-    float v = 0.f;
-    bool live = true;
-    if (k < 256) v = temb[k];
-    else if (k < 256 + E) v = map_emb[(long long)b * E_ld + (k - 256)];
-    else if (k < 256 + E + G) v = cond[(long long)b * G + (k - 256 - E)];
-    else live = false;
-    store_elem<PREC>(out, (long long)b * Kpad + k, live ? MISH_OF(PREC)(v) : 0.f, plane, satm);
-  }
-  if constexpr ((PREC & 3) == ST_F16) sat_flush(sat, satm);
-}
-void launch_prep_cond(const float* temb, const float* map_emb, int E, int E_ld, const float* cond, int G, void* out, int B,
-                      int Kpad, int fmt, long long plane, hipStream_t s, int* sat) {
-#define CALL(F) DN_LAUNCH(prep_cond_kernel<F>, dim3(B), dim3(256), 0, s, temb, map_emb, E, E_ld, cond, G, out, B, Kpad, plane, sat)
-  DISPATCH_FMT(fmt, CALL)
-#undef CALL
-}
-
-// Final Conv1d(C -> D, 1) + flow Euler step + un-normalise (conditional_unet1d.py:253-256,
-// policies/fm_policy.py:193,201-203).  One wave per position; Y is the padded channels-last
-// output of the last Conv1dBlock.
-struct ActNormArg { double mu[8], sg[8]; };
-template <int PREC, int D>
-__global__ void __launch_bounds__(256) final_proj_flow_kernel(const void* __restrict__ Y, int C, int Lp, long long plane,
-                                                              const float* __restrict__ W /*[D][C]*/,
-                                                              const float* __restrict__ bias,
-                                                              float* __restrict__ x /*[B][P][D] in/out*/, FlowStep fs,
-                                                              ActNormArg nm, double* __restrict__ actions, int B, int P) {
-  const long long pos = blockIdx.x * 4LL + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (pos >= (long long)B * P) return;
-  const int b = (int)(pos / P), l = (int)(pos - (long long)b * P);
-  const long long row = (long long)b * Lp + l + 1;
-  float s[D];
-#pragma unroll
-  for (int d = 0; d < D; ++d) s[d] = 0.f;
-  // a lane takes 8 consecutive channels per pass (16-B loads of 16-bit rows; C is a multiple of 8)
-  for (int c = lane * 8; c < C; c += 512) {
-    float y[8];
-    if constexpr ((PREC & 3) == ST_F32) {
-      const f32x4_t y0 = *(const f32x4_t*)((const float*)Y + row * C + c), y1 = *(const f32x4_t*)((const float*)Y + row * C + c + 4);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { y[j] = y0[j]; y[4 + j] = y1[j]; }
-    } else {
-      constexpr int ET = (PREC & 3) == ST_F16 ? 1 : 0;
-      const short8_t yv = *(const short8_t*)((const unsigned short*)Y + row * C + c);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) y[j] = e2f<ET>((unsigned short)yv[j]);
-      if constexpr ((PREC & 4) != 0) {
-        const short8_t yl = *(const short8_t*)((const unsigned short*)((const char*)Y + plane) + row * C + c);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) y[j] += e2f<ET>((unsigned short)yl[j]);
-      }
-    }
-#pragma unroll
-    for (int d = 0; d < D; ++d) {
-      const f32x4_t w0 = *(const f32x4_t*)(W + (long long)d * C + c), w1 = *(const f32x4_t*)(W + (long long)d * C + c + 4);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { s[d] = fmaf(y[j], w0[j], s[d]); }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { s[d] = fmaf(y[4 + j], w1[j], s[d]); }
-    }
-  }
-#pragma unroll
-  for (int d = 0; d < D; ++d) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) s[d] += __shfl_xor(s[d], m);
-  }
-  if (lane < D) {
-    float sv = s[0];
-    double sg = nm.sg[0], mu = nm.mu[0];
-#pragma unroll
-    for (int d = 1; d < D; ++d) if (lane == d) { sv = s[d]; sg = nm.sg[d]; mu = nm.mu[d]; }
-    const float v = sv + bias[lane];
-    const long long xi = pos * D + lane;
-    float xn;
-    if (fs.mode == 0) {
-      xn = x[xi] + v * fs.dt;                                 // naction + vel_pred * dt[k]
-    } else if (fs.mode == 1) {
-      xn = v;                                                 // raw: the network output itself
-    } else {                                                  // DDPM step, float32 as the scheduler's tensors
-      const float xc = x[xi];
-      float x0 = (xc - fs.sb * v) / fs.sa;
-      x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-      xn = fs.c0 * x0 + fs.c1 * xc;
-      if (fs.sigma != 0.0f) {
-        const long long zr = fs.z_idx ? (long long)fs.z_idx[b] : (long long)fs.z_row0 + b;
-        xn += fs.sigma * fs.z[zr * fs.z_row + (long long)l * D + lane];
-      }
-    }
-    x[xi] = xn;
-    if (actions != nullptr) actions[xi] = (double)xn * sg + mu;     // float32 * float64 -> float64 (:203)
-  }
-}
-// act_norm = [mu[0..D), sigma[0..D)] (host)
-void launch_final_proj_flow(const void* Y, int C, int Lp, long long plane, const float* W, const float* bias, int D, float* x,
-                            FlowStep fs, const double* act_norm, double* actions, int B, int P, int fmt, hipStream_t s) {
-  long long pos = (long long)B * P;
-  dim3 grid((unsigned)((pos + 3) / 4)), block(256);
-  ActNormArg nm{};
-  for (int d = 0; d < D && d < 8; ++d) { nm.mu[d] = act_norm[d]; nm.sg[d] = act_norm[D + d]; }
-#define CALLD(F, DD) DN_LAUNCH((final_proj_flow_kernel<F, DD>), grid, block, 0, s, Y, C, Lp, plane, W, bias, x, fs, nm, actions, B, P)
-#define CALL(F) do { if (D == 2) CALLD(F, 2); else if (D == 8) CALLD(F, 8); else throw std::runtime_error("final projection: action_dim must be 2 or 8"); } while (0)
-  DISPATCH_FMT(fmt, CALL)
-#undef CALL
-#undef CALLD
-}
-
-// ------------------------------------------------------------------------------- encoder helpers
-// im2col for Conv2d on NHWC activations: out row (b, oh, ow), column tap*C + c over the LIVE taps only
-// (a tap that falls into the zero padding for every output position is dropped from both the
-// columns and the packed weights -- exact, e.g. 3x3 convs on 1x1 maps keep the centre tap only),
-// zero padded to Kpad.  SRC_F32: the source is the f32 local map (B, H, W) with C = 1.
-template <int PREC, bool SRC_F32>
-__global__ void im2col2d_kernel(const void* __restrict__ in, void* __restrict__ out, int B, int H, int W, int C,
-                                TapList taps, int stride, int pad, int OH, int OW, int Kpad) {
-  const long long row = blockIdx.x;
-  const int ow = (int)(row % OW), oh = (int)((row / OW) % OH), b = (int)(row / ((long long)OW * OH));
-  const int K = taps.n * C;
-  for (int k = threadIdx.x; k < Kpad; k += blockDim.x) {
-    float v = 0.f;
-    if (k < K) {
-      const int c = k % C, kk = k / C;
-      const int ih = oh * stride + taps.kh[kk] - pad, iw = ow * stride + taps.kw[kk] - pad;
-      if (ih >= 0 && ih < H && iw >= 0 && iw < W) {
-        const long long idx = (((long long)b * H + ih) * W + iw) * C + c;
-        v = SRC_F32 ? ((const float*)in)[idx] : load_elem<PREC>(in, idx);
-      }
-    }
-    store_elem<PREC>(out, row * Kpad + k, v);
-  }
-}
-void launch_im2col2d(const void* in, bool src_f32, void* out, int B, int H, int W, int C, const TapList& taps, int stride,
-                     int pad, int OH, int OW, int Kpad, int fmt, hipStream_t s) {
-  dim3 grid((unsigned)((long long)B * OH * OW)), block(Kpad >= 256 ? 256 : 64);
-#define CALL(F) do { if (src_f32) DN_LAUNCH((im2col2d_kernel<F, true>), grid, block, 0, s, in, out, B, H, W, C, taps, stride, pad, OH, OW, Kpad); \
-                     else DN_LAUNCH((im2col2d_kernel<F, false>), grid, block, 0, s, in, out, B, H, W, C, taps, stride, pad, OH, OW, Kpad); } while (0)
-  DISPATCH_ST(fmt, CALL)
-#undef CALL
-}
-
-// GroupNorm (C/16 groups, local_map_encoder.py:63-76) on the f32 GEMM output [B][HW][C] (sum of the split-K
-// slabs), optional residual add and ReLU (torchvision BasicBlock), writes the activation type.
-// One 256-thread workgroup per sample: a thread owns 4 consecutive channels (16-B loads) of one position per
-// pass, T = C/4 threads span a position, 256/T positions per pass, <= GN2D_MAXP passes kept in registers;
-// a group is 4 adjacent threads x all positions: shuffle over the 4 threads, then 64 LDS partials
-// (positions-per-pass x groups) summed by every thread.  Mean first, then centred squares (two passes over
-// registers), as torch's GroupNorm.
-#define GN2D_MAXP 7
-template <int PREC>
-__global__ void __launch_bounds__(256) gn2d_kernel(const float* __restrict__ in, int nslab, long long slab_stride,
-                                                   const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                   const void* __restrict__ res, int relu, void* __restrict__ out, int HW,
-                                                   int C, float eps, long long res_plane, long long out_plane, int* __restrict__ sat) {
-  float satm = 0.0f;
-  __shared__ float red[2][64];
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const int T = C >> 2, PP = 256 / T, G = C >> 4;
-  const int tpos = tid / T, tc = tid - tpos * T, grp = tc >> 2;
-  const long long base = (long long)b * HW * C + 4 * tc;
-  f32x4_t v[GN2D_MAXP];
-  float s = 0.f;
-#pragma unroll
-  for (int k = 0; k < GN2D_MAXP; ++k) {
-    const int pos = k * PP + tpos;
-    f32x4_t x = {0.f, 0.f, 0.f, 0.f};
-    if (pos < HW) {
-      const float* src = in + base + (long long)pos * C;
-      for (int sl = 0; sl < nslab; ++sl) {
-        const f32x4_t t = *(const f32x4_t*)(src + sl * slab_stride);
-        x += t;
-      }
-      s += (x[0] + x[1]) + (x[2] + x[3]);
-    }
-    v[k] = x;
-  }
-  s += __shfl_xor(s, 1);
-  s += __shfl_xor(s, 2);
-  if ((tc & 3) == 0) red[0][tpos * G + grp] = s;
-  __syncthreads();
-  float tot = 0.f;
-  for (int q = 0; q < PP; ++q) tot += red[0][q * G + grp];
-  const float inv_n = 1.0f / (float)(HW * 16);
-  const float mean = tot * inv_n;
-  float q2 = 0.f;
-#pragma unroll
-  for (int k = 0; k < GN2D_MAXP; ++k) {
-    if (k * PP + tpos < HW) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { const float d = v[k][j] - mean; q2 = fmaf(d, d, q2); }
-    }
-  }
-  q2 += __shfl_xor(q2, 1);
-  q2 += __shfl_xor(q2, 2);
-  if ((tc & 3) == 0) red[1][tpos * G + grp] = q2;
-  __syncthreads();
-  float var = 0.f;
-  for (int q = 0; q < PP; ++q) var += red[1][q * G + grp];
-  const float rstd = rsqrtf(var * inv_n + eps);
-  const f32x4_t ga = *(const f32x4_t*)(gamma + 4 * tc), be = *(const f32x4_t*)(beta + 4 * tc);
-#pragma unroll
-  for (int k = 0; k < GN2D_MAXP; ++k) {
-    const int pos = k * PP + tpos;
-    if (pos >= HW) continue;
-    const long long idx = base + (long long)pos * C;
-    float y[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) y[j] = (v[k][j] - mean) * rstd * ga[j] + be[j];
-    constexpr int ET = (PREC & 3) == ST_F16 ? 1 : 0;
-    if (res != nullptr) {
-      if constexpr ((PREC & 3) == ST_F32) {
-        const f32x4_t r = *(const f32x4_t*)((const float*)res + idx);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) y[j] += r[j];
-      } else {
-        const short4_t r = *(const short4_t*)((const unsigned short*)res + idx);
-        if constexpr ((PREC & 4) != 0) {
-          const short4_t rl = *(const short4_t*)((const unsigned short*)((const char*)res + res_plane) + idx);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) y[j] += e2f<ET>((unsigned short)r[j]) + e2f<ET>((unsigned short)rl[j]);
-        } else {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) y[j] += e2f<ET>((unsigned short)r[j]);
-        }
-      }
-    }
-    if (relu) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) y[j] = y[j] > 0.f ? y[j] : 0.f;
-    }
-    if constexpr ((PREC & 3) == ST_F32) {
-      const f32x4_t o = {y[0], y[1], y[2], y[3]};
-      *(f32x4_t*)((float*)out + idx) = o;
-    } else {
-      short4_t o;
-      if constexpr (ET == 1) { sat_see2(satm, y[0], y[1]); sat_see2(satm, y[2], y[3]); }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) o[j] = (short)f2e<ET>(y[j]);
-      *(short4_t*)((unsigned short*)out + idx) = o;
-      if constexpr ((PREC & 4) != 0) {
-        short4_t o2;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o2[j] = (short)f2e<ET>(y[j] - e2f<ET>((unsigned short)o[j]));
-        *(short4_t*)((unsigned short*)((char*)out + out_plane) + idx) = o2;
-      }
-    }
-  }
-  if constexpr ((PREC & 3) == ST_F16) sat_flush(sat, satm);
-}
-void launch_gn2d(const float* in, int nslab, long long slab_stride, const float* gamma, const float* beta, const void* res,
-                 int relu, void* out, int B, int HW, int C, float eps, int fmt, long long res_plane, long long out_plane,
-                 hipStream_t s, int* sat) {
-  // host-side shape contract of the kernel (ResNet-18 stages on maps up to 10 x 10)
-  if (C < 64 || C > 1024 || (C & (C - 1)) != 0 || (HW + 256 / (C >> 2) - 1) / (256 / (C >> 2)) > GN2D_MAXP)
-    throw std::runtime_error("encoder GroupNorm: unsupported map shape");
-  dim3 grid((unsigned)B), block(256);
-#define CALL(F) DN_LAUNCH(gn2d_kernel<F>, grid, block, 0, s, in, nslab, slab_stride, gamma, beta, res, relu, out, HW, C, eps, \
-                                   res_plane, out_plane, sat)
-  DISPATCH_FMT(fmt, CALL)
-#undef CALL
-}
-
-// MaxPool2d(3, 2, 1) on NHWC.
-template <int PREC>
-__global__ void maxpool2d_kernel(const void* __restrict__ in, void* __restrict__ out, int B, int H, int W, int C, int OH,
-                                 int OW) {
-  const long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-  const long long total = (long long)B * OH * OW * C;
-  if (idx >= total) return;
-  const int c = (int)(idx % C);
-  const int ow = (int)((idx / C) % OW), oh = (int)((idx / ((long long)C * OW)) % OH), b = (int)(idx / ((long long)C * OW * OH));
-  float best = -__builtin_huge_valf();
-  for (int kh = 0; kh < 3; ++kh)
-    for (int kw = 0; kw < 3; ++kw) {
-      const int ih = oh * 2 + kh - 1, iw = ow * 2 + kw - 1;
-      if (ih >= 0 && ih < H && iw >= 0 && iw < W) {
-        float v = load_elem<PREC>(in, (((long long)b * H + ih) * W + iw) * C + c);
-        best = v > best ? v : best;
-      }
-    }
-  store_elem<PREC>(out, idx, best);
-}
-void launch_maxpool2d(const void* in, void* out, int B, int H, int W, int C, int OH, int OW, int fmt, hipStream_t s) {
-  long long total = (long long)B * OH * OW * C;
-  dim3 grid((unsigned)((total + 255) / 256)), block(256);
-#define CALL(F) DN_LAUNCH(maxpool2d_kernel<F>, grid, block, 0, s, in, out, B, H, W, C, OH, OW)
-  DISPATCH_ST(fmt, CALL)
-#undef CALL
-}
-
-// AdaptiveAvgPool2d(1) on NHWC -> [B][C].
-template <int PREC>
-__global__ void avgpool2d_kernel(const void* __restrict__ in, void* __restrict__ out, int B, int HW, int C, long long in_plane,
-                                 long long out_plane) {
-  const long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-  if (idx >= (long long)B * C) return;
-  const int c = (int)(idx % C), b = (int)(idx / C);
-  float s = 0.f;
-  for (int q = 0; q < HW; ++q) s += load_elem<PREC>(in, ((long long)b * HW + q) * C + c, in_plane);
-  store_elem<PREC>(out, idx, s / (float)HW, out_plane);
-}
-void launch_avgpool2d(const void* in, void* out, int B, int HW, int C, int fmt, long long in_plane, long long out_plane,
-                      hipStream_t s) {
-  long long total = (long long)B * C;
-  dim3 grid((unsigned)((total + 255) / 256)), block(256);
-#define CALL(F) DN_LAUNCH(avgpool2d_kernel<F>, grid, block, 0, s, in, out, B, HW, C, in_plane, out_plane)
-  DISPATCH_FMT(fmt, CALL)
-#undef CALL
-}
-
-// debug / test support: padded channels-last activation -> f32 [B][L][C]
-template <int PREC>
-__global__ void unpack_act_kernel(const void* __restrict__ in, int ld, int coff, int Lp, int roff, float* __restrict__ out,
-                                  int B, int L, int C, long long plane) {
-  const long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-  if (idx >= (long long)B * L * C) return;
-  const int c = (int)(idx % C);
-  const int l = (int)((idx / C) % L), b = (int)(idx / ((long long)C * L));
-  out[idx] = load_elem<PREC>(in, ((long long)b * Lp + l + roff) * ld + coff + c, plane);
-}
-void launch_unpack_act(const void* in, int ld, int coff, int Lp, int roff, float* out, int B, int L, int C, int fmt,
-                       long long plane, hipStream_t s) {
-  long long total = (long long)B * L * C;
-  dim3 grid((unsigned)((total + 255) / 256)), block(256);
-#define CALL(F) DN_LAUNCH(unpack_act_kernel<F>, grid, block, 0, s, in, ld, coff, Lp, roff, out, B, L, C, plane)
-  DISPATCH_FMT(fmt, CALL)
-#undef CALL
+  if (v == nullptr) throw std::runtime_error("conv_gemm: a split GEMM of this shape fits no tile (conv_gemm_supported is the contract)");
+  // 256 x 256 tiles, 64 x 64 on the small Conv2d kernel; gridDim.y = split-K work-groups where the variant has a split-K form
+  dim3 grid(((p.M + 255) >> 8) * ((p.N + 255) >> 8));
+  if (v->family == TILE_C2D_SMALL) grid.x = ((p.M + 63) >> 6) * (p.N >> 6);
+  if (v->flags & (TV_SPLITK | TV_C2D)) grid.y = p.splitk > 1 ? p.splitk : 1;
+  DN_LAUNCH(v->kernel, grid, dim3(v->block), v->lds_bytes, s, p);
 }

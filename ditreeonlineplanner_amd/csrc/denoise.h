@@ -14,7 +14,7 @@ static inline __host__ __device__ int fmt_st(int f) { return f & 3; }
 static inline __host__ __device__ bool fmt_split(int f) { return (f & 4) != 0; }
 static inline int fmt_es(int f) { return fmt_st(f) == ST_F32 ? 4 : 2; }
 
-// One implicit-GEMM launch (see denoise_kernels.hip).  All counts are in elements of the
+// One implicit-GEMM launch (see conv_tiles.hip).  All counts are in elements of the
 // activation type (bf16 or f32); pointers are device pointers.
 struct ConvGemmParams {
   const void* A;      // activations, channels contiguous
@@ -41,7 +41,7 @@ struct ConvGemmParams {
   const void* Res;    // residual, activation type
   int ldres, res_Lp, res_off;
   int out_f32;        // store f32 regardless of the activation type
-  int dbg;            // halo / gemm16 kernels: 1 = walk an XCD's tile range in strips of four tile columns (xcd_remap_strips)
+  int xcd_strips;     // halo / gemm16 kernels: 1 = walk an XCD's tile range in strips of four tile columns (xcd_remap_strips)
   // implicit Conv2d on NHWC activations (c2d != 0): GEMM row m = (b, oh, ow); K = live taps x Cin
   // (Cin a multiple of 64: one tap spans Cin/64 K-steps); A is the input activation (B, H, W, Cin);
   // taps that fall outside the map read `zero` (>= 128 zero bytes).

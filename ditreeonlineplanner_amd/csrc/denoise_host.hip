@@ -103,7 +103,7 @@ struct DenoiserState {
   Act final_h;                   // input of the final 1x1 projection
   const float* lm_ptr = nullptr; // caller's scaled local map of the current call
   void* zero_row = nullptr;      // 256 zero bytes: source of out-of-map taps in implicit Conv2d
-  // f16 range guard (denoise_kernels.hip sat_*): one device flag word per layer that stores f16 activations; a kernel ORs 1
+  // f16 range guard (denoise_device.h sat_*): one device flag word per layer that stores f16 activations; a kernel ORs 1
   // into its layer's word when it is handed a value beyond +-65504.  Sticky until ditree_denoise_status reads and clears.
   static constexpr int SAT_SLOTS = 256;
   int* sat_flags = nullptr;
@@ -164,8 +164,7 @@ struct DenoiserState {
   }
   void run_gemm(const ConvGemmParams& p_in, int fmt, hipStream_t s) {
     ConvGemmParams p = p_in;
-    static const int strips = [] { const char* e = getenv("DITREE_XCD_STRIPS"); return e ? atoi(e) : 1; }();
-    p.dbg = strips;                    // the halo / gemm16 kernels walk an XCD's tiles in strips of four tile columns (xcd_remap_strips)
+    p.xcd_strips = 1;                  // the halo / gemm16 kernels walk an XCD's tiles in strips of four tile columns (xcd_remap_strips)
     if (const int sk = pick_splitk(p, fmt); sk > 1) {
       if (sk_ws == nullptr) {
         sk_ws = (float*)dalloc((size_t)SK_MAX_SLABS * 65536 * sizeof(float), false);
@@ -371,6 +370,26 @@ struct DenoiserState {
   const char* aptr(const Act& a) const { return (const char*)a.p + (size_t)a.coff * es(); }
 
   // ------------------------------------------------------------------ GEMM op builders
+  // What the four builders below fill alike: operands and their row geometry, the weight, the f16 range-guard slot and the bias of
+  // layer `wname`; mode MODE_BIAS.  M follows per call (rows of the batch at hand).
+  ConvGemmParams gemm_params(const Act& in, const Act& out, const Packed& wp, int taps, int Cin, int Cout, int in_stride, int in_off,
+                             int out_stride, int out_off, int L, const std::string& wname) {
+    ConvGemmParams p{};
+    p.A = aptr(in); p.lda = in.ld; p.in_Lp = in.Lp(); p.in_stride = in_stride; p.in_off = in_off; p.taps = taps; p.Cin = Cin;
+    set_w(p, wp); set_in(p, in); set_out(p, out);
+    p.sat = sat_slot(wname, ufmt);
+    p.Out = (void*)aptr(out); p.ldc = out.ld; p.out_Lp = out.Lp(); p.out_stride = out_stride; p.out_off = out_off;
+    p.L = L; p.N = Cout; p.bias = vec(wname + ".bias"); p.mode = MODE_BIAS;
+    return p;
+  }
+  // a plain GEMM op: conv + bias on the Bp samples of a call
+  void push_gemm(std::vector<std::function<void(int, int, hipStream_t)>>& ops, const ConvGemmParams& p_in) {
+    const int uf = ufmt;
+    ops.push_back([this, p = p_in, uf](int, int Bp, hipStream_t s) mutable {
+      p.M = Bp * p.L;
+      run_gemm(p, uf, s);
+    });
+  }
   // Conv1d(k = 3, pad 1) [+ GroupNorm(8) + Mish (+ FiLM | + residual)] on padded activations.
   void add_conv3(std::vector<std::function<void(int, int, hipStream_t)>>& ops, const std::string& wname, const Act& in,
                  const Act& out, int mode, const std::string& gn, int film_off, const Act* res) {
@@ -378,12 +397,8 @@ struct DenoiserState {
     const int Cout = (int)w.dims[0], Cin = (int)w.dims[1];
     const float* wd = w.data;
     const Packed wp = pack(wname, ufmt, Cout, 3, Cin, [=](int n, int t, int ci) { return wd[((size_t)n * Cin + ci) * 3 + t]; });
-    ConvGemmParams p{};
-    p.A = aptr(in); p.lda = in.ld; p.in_Lp = in.Lp(); p.in_stride = 1; p.in_off = 0; p.taps = 3; p.Cin = Cin;
-    set_w(p, wp); set_in(p, in); set_out(p, out);
-    p.sat = sat_slot(wname, ufmt);
-    p.Out = (void*)aptr(out); p.ldc = out.ld; p.out_Lp = out.Lp(); p.out_stride = 1; p.out_off = 1; p.out_coff = 0;
-    p.L = in.L; p.N = Cout; p.bias = vec(wname + ".bias"); p.mode = mode; p.eps = 1e-5f;
+    ConvGemmParams p = gemm_params(in, out, wp, 3, Cin, Cout, 1, 0, 1, 1, in.L, wname);
+    p.mode = mode; p.eps = 1e-5f;
     if (mode >= MODE_GN_MISH) {
       p.gamma = vec(gn + ".weight"); p.beta = vec(gn + ".bias"); p.group_ch = Cout / 8;
     }
@@ -400,9 +415,8 @@ struct DenoiserState {
     const int Cout = p.N, mode = p.mode, uf = ufmt;
     const int gch = Cout / 8;
     // ... and a lane's four accumulator rows inside one sample: 16 | L, or L = 8 / 4 on the 16-bit tiles (the ant config's lower
-    // levels; DITREE_GN_SHORT_UNFUSED=1 keeps the round-3 two-launch form for A/B runs)
-    static const bool short_unfused = [] { const char* e = getenv("DITREE_GN_SHORT_UNFUSED"); return e && atoi(e) != 0; }();
-    const bool short_fusable = (L == 8 || L == 4) && fmt_st(uf) != ST_F32 && !short_unfused;
+    // levels)
+    const bool short_fusable = (L == 8 || L == 4) && fmt_st(uf) != ST_F32;
     const bool fused = mode < MODE_GN_MISH ||
                        ((Cout & 255) == 0 && (gch == 64 || gch == 128 || gch == 256) && ((L & 15) == 0 || short_fusable));
     // short levels fuse on the gemm16 tile only: whole 256-row tiles (always so for the split formats, batch by batch otherwise)
@@ -437,17 +451,7 @@ struct DenoiserState {
     const int Cout = (int)w.dims[0], Cin = (int)w.dims[1];
     const float* wd = w.data;
     const Packed wp = pack(wname, ufmt, Cout, 1, Cin, [=](int n, int, int ci) { return wd[(size_t)n * Cin + ci]; });
-    ConvGemmParams p{};
-    p.A = aptr(in); p.lda = in.ld; p.in_Lp = in.Lp(); p.in_stride = 1; p.in_off = 1; p.taps = 1; p.Cin = Cin;
-    set_w(p, wp); set_in(p, in); set_out(p, out);
-    p.sat = sat_slot(wname, ufmt);
-    p.Out = (void*)aptr(out); p.ldc = out.ld; p.out_Lp = out.Lp(); p.out_stride = 1; p.out_off = 1;
-    p.L = in.L; p.N = Cout; p.bias = vec(wname + ".bias"); p.mode = MODE_BIAS;
-    const int L = in.L, uf = ufmt;
-    ops.push_back([this, p, L, uf](int, int Bp, hipStream_t s) mutable {
-      p.M = Bp * L;
-      run_gemm(p, uf, s);
-    });
+    push_gemm(ops, gemm_params(in, out, wp, 1, Cin, Cout, 1, 1, 1, 1, in.L, wname));
   }
   // Downsample1d: Conv1d(C, C, 3, stride 2, pad 1)  (conv1d_components.py:7-13)
   void add_down(std::vector<std::function<void(int, int, hipStream_t)>>& ops, const std::string& wname, const Act& in,
@@ -456,17 +460,7 @@ struct DenoiserState {
     const int Cout = (int)w.dims[0], Cin = (int)w.dims[1];
     const float* wd = w.data;
     const Packed wp = pack(wname, ufmt, Cout, 3, Cin, [=](int n, int t, int ci) { return wd[((size_t)n * Cin + ci) * 3 + t]; });
-    ConvGemmParams p{};
-    p.A = aptr(in); p.lda = in.ld; p.in_Lp = in.Lp(); p.in_stride = 2; p.in_off = 0; p.taps = 3; p.Cin = Cin;
-    set_w(p, wp); set_in(p, in); set_out(p, out);
-    p.sat = sat_slot(wname, ufmt);
-    p.Out = (void*)aptr(out); p.ldc = out.ld; p.out_Lp = out.Lp(); p.out_stride = 1; p.out_off = 1;
-    p.L = out.L; p.N = Cout; p.bias = vec(wname + ".bias"); p.mode = MODE_BIAS;
-    const int L = out.L, uf = ufmt;
-    ops.push_back([this, p, L, uf](int, int Bp, hipStream_t s) mutable {
-      p.M = Bp * L;
-      run_gemm(p, uf, s);
-    });
+    push_gemm(ops, gemm_params(in, out, wp, 3, Cin, Cout, 2, 0, 1, 1, out.L, wname));
   }
   // Upsample1d: ConvTranspose1d(C, C, 4, 2, 1) as two 2-tap GEMMs (even / odd outputs)
   // out[2m] = W1^T x[m] + W3^T x[m-1];  out[2m+1] = W0^T x[m+1] + W2^T x[m]   (conv1d_components.py:15-21)
@@ -480,17 +474,7 @@ struct DenoiserState {
       const Packed wp = pack(wname + (par ? ".odd" : ".even"), ufmt, Cout, 2, Cin, [=](int n, int t, int ci) {
         return wd[((size_t)ci * Cout + n) * 4 + (t == 0 ? k0 : k1)];
       });
-      ConvGemmParams p{};
-      p.A = aptr(in); p.lda = in.ld; p.in_Lp = in.Lp(); p.in_stride = 1; p.in_off = par; p.taps = 2; p.Cin = Cin;
-      set_w(p, wp); set_in(p, in); set_out(p, out);
-      p.sat = sat_slot(wname, ufmt);
-      p.Out = (void*)aptr(out); p.ldc = out.ld; p.out_Lp = out.Lp(); p.out_stride = 2; p.out_off = 1 + par;
-      p.L = in.L; p.N = Cout; p.bias = vec(wname + ".bias"); p.mode = MODE_BIAS;
-      const int L = in.L, uf = ufmt;
-      ops.push_back([this, p, L, uf](int, int Bp, hipStream_t s) mutable {
-        p.M = Bp * L;
-        run_gemm(p, uf, s);
-      });
+      push_gemm(ops, gemm_params(in, out, wp, 2, Cin, Cout, 1, par, 2, 1 + par, in.L, wname));
     }
   }
 

@@ -1,4 +1,4 @@
-"""Issue time of the six MFMA phases of a K-step in the split halo kernel (diagnostic build: denoise_kernels.hip compiled
+"""Issue time of the six MFMA phases of a K-step in the split halo kernel (diagnostic build: conv_tiles.hip compiled
 with -DHALO16_STAMP -DX3_PHASE_STAMP).  Every wave of work-group 100 of a Cin = 2048 launch stamps s_memtime (core clock)
 at the head of each phase of its last three in-loop K-steps (taps 0, 1, 2 of one channel chunk):
     0 P1  1 P2  2 P3  3 P4  4 P5  5 wait+barrier  6 reads + P6 (LDS-DMA issue)  7 end

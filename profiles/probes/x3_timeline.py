@@ -1,6 +1,6 @@
-"""In-kernel timeline of the split halo kernel (diagnostic build: denoise_kernels.hip compiled with -DHALO16_STAMP).
+"""In-kernel timeline of the split halo kernel (diagnostic build: conv_tiles.hip compiled with -DHALO16_STAMP).
 
-    hipcc ... -DHALO16_STAMP -c denoise_kernels.hip && python -m ditreeonlineplanner_amd.build
+    hipcc ... -DHALO16_STAMP -c conv_tiles.hip && python -m ditreeonlineplanner_amd.build
     python profiles/probes/x3_timeline.py [B] [out.json]            (on the GPU box)
 
 Every work-group of conv3_halo16x3_kernel records {start, loop start, epilogue start, end} on the 100 MHz real-time

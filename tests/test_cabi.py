@@ -43,7 +43,7 @@ def test_halo_kernel_loop_has_no_scratch_traffic(tmp_path):
     there (scratch_* counts in vmcnt) would change what the count means.  Guard the generated code, not the source."""
     import re
     import subprocess
-    src = os.path.join(REPO, "ditreeonlineplanner_amd", "csrc", "denoise_kernels.hip")
+    src = os.path.join(REPO, "ditreeonlineplanner_amd", "csrc", "conv_tiles.hip")
     out = tmp_path / "dk.s"
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     subprocess.run([hipcc, "-S", "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", src, "-o", str(out)],
@@ -58,7 +58,7 @@ def test_halo_kernel_loop_has_no_scratch_traffic(tmp_path):
     cases += [(et, 1, "ELb1ELb0ELi6", mf) for et, mf in ((0, "bf16"), (1, "f16"))]      # six activation pieces (L = 4)
     for et, split, extra, mfma in cases:
         name = (f"_Z21conv3_halo16x3_kernelILi{et}{extra}EEv14ConvGemmParams:" if split
-                else f"_Z19conv3_halo16_kernelILi{et}ELb0EEv14ConvGemmParams:")
+                else f"_Z19conv3_halo16_kernelILi{et}EEv14ConvGemmParams:")
         start = text.index(name)
         body = text[start:text.index(".Lfunc_end", start)].splitlines()
         headers = [n for n, l in enumerate(body) if "Loop Header" in l]
