@@ -35,6 +35,7 @@ UNITS = [
     ("conv_tiles.hip", []),
     ("denoise_small_kernels.hip", []),
     ("encoder_kernels.hip", []),
+    ("denoise_plan.hip", []),
     ("denoise_host.hip", []),
 ]
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",

@@ -95,21 +95,14 @@ struct FlowStep {
 void launch_final_proj_flow(const void* Y, int C, int Lp, long long plane, const float* W, const float* bias, int D, float* x,
                             FlowStep fs, const double* act_norm /*[mu[D], sigma[D]]*/, double* actions, int B, int P, int fmt,
                             hipStream_t s);
-struct TapList {          // live (kh, kw) taps of a Conv2d on a small map
-  int n;
-  signed char kh[49], kw[49];
-};
 void launch_gn1d(void* x, int ld, int Lp, int row_off, int coff, int L, int C, const float* gamma, const float* beta, float eps,
                  int mode, const float* film, int film_ld, int film_off, const void* res, int ldres, int res_Lp, int res_off,
                  int B, int fmt, long long x_plane, long long res_plane, hipStream_t s, int* sat = nullptr);
 void launch_encoder_stem(const float* lm, int n, const float* W, const float* gamma, const float* beta, void* out, int B, float eps,
                          int fmt, long long plane, hipStream_t s, int* sat = nullptr);
-void launch_im2col2d(const void* in, bool src_f32, void* out, int B, int H, int W, int C, const TapList& taps, int stride,
-                     int pad, int OH, int OW, int Kpad, int fmt, hipStream_t s);
 void launch_gn2d(const float* in, int nslab, long long slab_stride, const float* gamma, const float* beta, const void* res,
                  int relu, void* out, int B, int HW, int C, float eps, int fmt, long long res_plane, long long out_plane,
                  hipStream_t s, int* sat = nullptr);
-void launch_maxpool2d(const void* in, void* out, int B, int H, int W, int C, int OH, int OW, int fmt, hipStream_t s);
 void launch_avgpool2d(const void* in, void* out, int B, int HW, int C, int fmt, long long in_plane, long long out_plane,
                       hipStream_t s);
 void launch_unpack_act(const void* in, int ld, int coff, int Lp, int roff, float* out, int B, int L, int C, int fmt,

@@ -203,10 +203,3 @@ __device__ __forceinline__ float load_elem(const void* base, long long idx, long
     case 6: CALL(6); break;                                       \
     default: throw std::runtime_error("denoiser kernels: unknown activation format"); \
   }
-#define DISPATCH_ST(fmt, CALL)                                    \
-  switch (fmt) {                                                  \
-    case 0: CALL(0); break;                                       \
-    case 1: CALL(1); break;                                       \
-    case 2: CALL(2); break;                                       \
-    default: throw std::runtime_error("denoiser kernels: unknown activation format"); \
-  }

@@ -465,38 +465,6 @@ void launch_final_proj_flow(const void* Y, int C, int Lp, long long plane, const
 }
 
 // ------------------------------------------------------------------------------- encoder helpers
-// im2col for Conv2d on NHWC activations: out row (b, oh, ow), column tap*C + c over the LIVE taps only
-// (a tap that falls into the zero padding for every output position is dropped from both the
-// columns and the packed weights -- exact, e.g. 3x3 convs on 1x1 maps keep the centre tap only),
-// zero padded to Kpad.  SRC_F32: the source is the f32 local map (B, H, W) with C = 1.
-template <int PREC, bool SRC_F32>
-__global__ void im2col2d_kernel(const void* __restrict__ in, void* __restrict__ out, int B, int H, int W, int C,
-                                TapList taps, int stride, int pad, int OH, int OW, int Kpad) {
-  const long long row = blockIdx.x;
-  const int ow = (int)(row % OW), oh = (int)((row / OW) % OH), b = (int)(row / ((long long)OW * OH));
-  const int K = taps.n * C;
-  for (int k = threadIdx.x; k < Kpad; k += blockDim.x) {
-    float v = 0.f;
-    if (k < K) {
-      const int c = k % C, kk = k / C;
-      const int ih = oh * stride + taps.kh[kk] - pad, iw = ow * stride + taps.kw[kk] - pad;
-      if (ih >= 0 && ih < H && iw >= 0 && iw < W) {
-        const long long idx = (((long long)b * H + ih) * W + iw) * C + c;
-        v = SRC_F32 ? ((const float*)in)[idx] : load_elem<PREC>(in, idx);
-      }
-    }
-    store_elem<PREC>(out, row * Kpad + k, v);
-  }
-}
-void launch_im2col2d(const void* in, bool src_f32, void* out, int B, int H, int W, int C, const TapList& taps, int stride,
-                     int pad, int OH, int OW, int Kpad, int fmt, hipStream_t s) {
-  dim3 grid((unsigned)((long long)B * OH * OW)), block(Kpad >= 256 ? 256 : 64);
-#define CALL(F) do { if (src_f32) DN_LAUNCH((im2col2d_kernel<F, true>), grid, block, 0, s, in, out, B, H, W, C, taps, stride, pad, OH, OW, Kpad); \
-                     else DN_LAUNCH((im2col2d_kernel<F, false>), grid, block, 0, s, in, out, B, H, W, C, taps, stride, pad, OH, OW, Kpad); } while (0)
-  DISPATCH_ST(fmt, CALL)
-#undef CALL
-}
-
 // GroupNorm (C/16 groups, local_map_encoder.py:63-76) on the f32 GEMM output [B][HW][C] (sum of the split-K
 // slabs), optional residual add and ReLU (torchvision BasicBlock), writes the activation type.
 // One 256-thread workgroup per sample: a thread owns 4 consecutive channels (16-B loads) of one position per
@@ -615,34 +583,6 @@ void launch_gn2d(const float* in, int nslab, long long slab_stride, const float*
 #define CALL(F) DN_LAUNCH(gn2d_kernel<F>, grid, block, 0, s, in, nslab, slab_stride, gamma, beta, res, relu, out, HW, C, eps, \
                                    res_plane, out_plane, sat)
   DISPATCH_FMT(fmt, CALL)
-#undef CALL
-}
-
-// MaxPool2d(3, 2, 1) on NHWC.
-template <int PREC>
-__global__ void maxpool2d_kernel(const void* __restrict__ in, void* __restrict__ out, int B, int H, int W, int C, int OH,
-                                 int OW) {
-  const long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-  const long long total = (long long)B * OH * OW * C;
-  if (idx >= total) return;
-  const int c = (int)(idx % C);
-  const int ow = (int)((idx / C) % OW), oh = (int)((idx / ((long long)C * OW)) % OH), b = (int)(idx / ((long long)C * OW * OH));
-  float best = -__builtin_huge_valf();
-  for (int kh = 0; kh < 3; ++kh)
-    for (int kw = 0; kw < 3; ++kw) {
-      const int ih = oh * 2 + kh - 1, iw = ow * 2 + kw - 1;
-      if (ih >= 0 && ih < H && iw >= 0 && iw < W) {
-        float v = load_elem<PREC>(in, (((long long)b * H + ih) * W + iw) * C + c);
-        best = v > best ? v : best;
-      }
-    }
-  store_elem<PREC>(out, idx, best);
-}
-void launch_maxpool2d(const void* in, void* out, int B, int H, int W, int C, int OH, int OW, int fmt, hipStream_t s) {
-  long long total = (long long)B * OH * OW * C;
-  dim3 grid((unsigned)((total + 255) / 256)), block(256);
-#define CALL(F) DN_LAUNCH(maxpool2d_kernel<F>, grid, block, 0, s, in, out, B, H, W, C, OH, OW)
-  DISPATCH_ST(fmt, CALL)
 #undef CALL
 }
 

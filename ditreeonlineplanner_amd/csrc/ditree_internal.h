@@ -22,7 +22,7 @@ struct AntNormArg {
   double obs_mean[27], obs_std[27], act_mean[8], act_std[8];
 };
 
-struct DenoiserState;   // denoise_host.hip
+struct DenoiserState;   // denoise_state.h
 
 // One scene of a scene table (ditree_upload_scenes): its maze at atlas[offset], rows x cols, and its goal.
 struct SceneRec {

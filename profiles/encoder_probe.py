@@ -26,8 +26,7 @@ B = 1024
 ENCODERS = (("resnet", 400), ("identity", 400), ("mlp", 400), ("max", 9), ("grid", 144), ("cnn", 576))
 OWN = {"identity": ("enc_identity_kernel",), "mlp": ("enc_mlp_kernel",), "max": ("enc_max_kernel",),
        "grid": ("enc_conv_kernel<0>",), "cnn": ("enc_conv_kernel<1>",),
-       "resnet": ("encoder_stem_kernel", "conv2d_small_kernel", "gn2d_kernel", "avgpool2d_kernel", "maxpool2d_kernel",
-                  "im2col2d_kernel")}
+       "resnet": ("encoder_stem_kernel", "conv2d_small_kernel", "gn2d_kernel", "avgpool2d_kernel")}
 
 
 def run(calls, warmup):

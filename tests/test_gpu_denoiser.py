@@ -280,15 +280,19 @@ def test_actions_and_multi_step(ctx, oracle_net, inputs, prec):
     assert rel(a.cpu().numpy(), a_ref) < 2 * TOL[prec]["l2"]
 
 
-def test_batch_sizes_agree(ctx, oracle_net, inputs):
-    """Rows are independent: a sub-batch gives the same rows (ragged B, padding rows inert)."""
+@pytest.mark.parametrize("prec", [0, 1, 2])
+def test_batch_sizes_agree(ctx, oracle_net, inputs, prec):
+    """Rows are independent: a sub-batch gives the same rows and the same map embedding, bit for bit (ragged B, padding rows
+    inert).  The full call fills the whole reservation: the encoder's one scratch region end to end."""
     noise, lm, cond = inputs
-    _bind(ctx, oracle_net, 0, 24)
+    _bind(ctx, oracle_net, prec, 24)
     full = ctx.denoise(noise.cuda(), lm.cuda(), cond.cuda(), want_actions=False).cpu().numpy()
+    full_emb = ctx.debug_read("map_emb", 24).cpu().numpy()
     for b in (1, 5, 17):
         part = ctx.denoise(noise[:b].cuda().contiguous(), lm[:b].cuda().contiguous(), cond[:b].cuda().contiguous(),
                            want_actions=False).cpu().numpy()
         assert np.array_equal(part, full[:b]), b
+        assert np.array_equal(ctx.debug_read("map_emb", b).cpu().numpy(), full_emb[:b]), b
 
 
 class _ToyScheduler:
