@@ -186,6 +186,9 @@ SIGNATURES = {
                                               _vp]),
     "ditree_forest_accept_ant": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), C.POINTER(Round), _vp]),
     "ditree_forest_fallback_ant": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), _pd, _vp, _vp]),
+    "ditree_forest_expand_round_ant_scenes": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), C.POINTER(ForestScenes),
+                                                     C.POINTER(Round), C.POINTER(AntRoundParams), _vp]),
+    "ditree_forest_fallback_goals_ant": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), _pd, _vp, _vp]),
 }
 
 _LIB = None

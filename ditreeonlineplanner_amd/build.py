@@ -30,6 +30,7 @@ UNITS = [
     ("geom_kernels.hip", ["-ffp-contract=off"]),
     ("mppi_kernels.hip", ["-ffp-contract=off"]),
     ("ant_kernels.hip", ["-ffp-contract=off"]),
+    ("ant_scene_kernels.hip", ["-ffp-contract=off"]),
     ("mppi_ant_kernels.hip", ["-ffp-contract=off"]),
     ("ditree_api.hip", []),
     ("conv_tiles.hip", []),

@@ -586,16 +586,18 @@ static int ensure_scratch(ditree_ctx* ctx, int B, int lm_n, int P) {
 }
 
 // ---- BASELINE config 3: the ant round (include/ditree.h "One expansion round of the ANT").
+// scenes (an ant scene forest, validated by the caller): each row's maze and desired goal come from the scene table, so neither
+// an uploaded single maze nor p->desired_goal is required.
 static int check_ant_round(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round, const ditree_ant_round_params* p,
-                           int need_sampler, int* P_out) {
+                           int need_sampler, int* P_out, bool scenes = false) {
   int rc = check_tree(ctx, tree);
   if (rc) return rc;
   rc = check_round(ctx, round);
   if (rc) return rc;
-  if (!ctx->maze) return set_err(ctx, DITREE_E_STATE, "expand_round_ant: no maze uploaded");
+  if (!scenes && !ctx->maze) return set_err(ctx, DITREE_E_STATE, "expand_round_ant: no maze uploaded");
   if (tree->state_dim != ANT_S || tree->action_dim != ANT_D || !tree->hist)
     return set_err(ctx, DITREE_E_ARG, "expand_round_ant: the tree must have state_dim 29, action_dim 8 and hist / hist_n");
-  if (!p || !p->cond_goal || !p->norm || !p->desired_goal || !p->axis || !(p->s_global > 0.0) || p->P < tree->A)
+  if (!p || !p->cond_goal || !p->norm || (!scenes && !p->desired_goal) || !p->axis || !(p->s_global > 0.0) || p->P < tree->A)
     return set_err(ctx, DITREE_E_ARG, "expand_round_ant: bad parameters");
   if (need_sampler) {
     if (!p->noise && !p->inject_actions) return set_err(ctx, DITREE_E_ARG, "expand_round_ant: neither noise nor inject_actions");
@@ -640,10 +642,10 @@ static int ensure_ant_scratch(ditree_ctx* ctx, int B, int P, int lm) {
 // The begin step of an ant round on one tree, or (f != NULL, validated by the caller) on a forest: only the nearest-node search
 // differs -- the first p->n_nodes nodes, or each candidate's own tree up to its counter row's node count.
 static int ant_round_begin_impl(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* f, const ditree_round* round,
-                                const ditree_ant_round_params* p, void* stream) {
+                                const ditree_ant_round_params* p, void* stream, bool scenes = false) {
   if (!ctx) return DITREE_E_ARG;
   int P = 0;
-  int rc = check_ant_round(ctx, tree, round, p, 0, &P);
+  int rc = check_ant_round(ctx, tree, round, p, 0, &P, scenes);
   if (rc) return rc;
   if (!p->samples || (!f && (p->n_nodes <= 0 || p->n_nodes > tree->capacity)))
     return set_err(ctx, DITREE_E_ARG, "ant_round_begin: samples / n_nodes");
@@ -673,11 +675,12 @@ int32_t ditree_ant_round_begin(ditree_ctx* ctx, const ditree_tree* tree, const d
   return ant_round_begin_impl(ctx, tree, nullptr, round, p, stream);
 }
 
-int32_t ditree_ant_chunk_sample(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round,
-                                const ditree_ant_round_params* p, int32_t j, void* stream) {
+// The sample half of chunk j; scp != NULL (an ant scene forest): the local map is cut from each row's own scene.
+static int ant_chunk_sample_impl(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round,
+                                 const ditree_ant_round_params* p, int32_t j, void* stream, const SceneArg* scp) {
   if (!ctx) return DITREE_E_ARG;
   int P = 0;
-  int rc = check_ant_round(ctx, tree, round, p, 1, &P);
+  int rc = check_ant_round(ctx, tree, round, p, 1, &P, scp != nullptr);
   if (rc) return rc;
   const int B = round->B, nC = tree->n_chunks, A = tree->A;
   if (j < 0 || j >= nC) return set_err(ctx, DITREE_E_ARG, "ant_chunk_sample: chunk index out of range");
@@ -712,8 +715,11 @@ int32_t ditree_ant_chunk_sample(ditree_ctx* ctx, const ditree_tree* tree, const 
   AntNormArg nm;
   fill_ant_norm(p->norm, &nm);
   // RRT.py:158-166: the local map is cut at the chunk's start state (x, y, element 2)
-  launch_local_map(ctx->maze, ctx->rows, ctx->cols, round->end_state, round->status, idx, n_run, p->lm_n, ax, p->s_global, 1,
-                   ctx->ant_lmap, s, ANT_S);
+  if (scp)
+    launch_local_map_scenes(*scp, round->end_state, round->status, idx, n_run, p->lm_n, ax, p->s_global, ctx->ant_lmap, s, ANT_S);
+  else
+    launch_local_map(ctx->maze, ctx->rows, ctx->cols, round->end_state, round->status, idx, n_run, p->lm_n, ax, p->s_global, 1,
+                     ctx->ant_lmap, s, ANT_S);
   launch_cond_vector_ant(ctx->ant_hist, 3, ctx->ant_hist_n, ctx->ant_prev, ctx->ant_hasprev, p->cond_goal, idx, n_run, nm,
                          p->lm_size, ctx->ant_cond, s);
   if (p->cond_out) {
@@ -735,8 +741,14 @@ int32_t ditree_ant_chunk_sample(ditree_ctx* ctx, const ditree_tree* tree, const 
   return DITREE_OK;
 }
 
+int32_t ditree_ant_chunk_sample(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round,
+                                const ditree_ant_round_params* p, int32_t j, void* stream) {
+  return ant_chunk_sample_impl(ctx, tree, round, p, j, stream, nullptr);
+}
+
 static int ant_chunk_step_impl(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round, const ditree_ant_round_params* p,
-                               int j, const double* obs, int64_t obs_stride, const AntModelArg* model, hipStream_t s) {
+                               int j, const double* obs, int64_t obs_stride, const AntModelArg* model, hipStream_t s,
+                               const SceneArg* scp = nullptr) {
   const int B = round->B, nC = tree->n_chunks, A = tree->A, P = p->P;
   const int n_run = ctx->ant_n_run;
   if (n_run == 0) return DITREE_OK;
@@ -753,12 +765,13 @@ static int ant_chunk_step_impl(ditree_ctx* ctx, const ditree_tree* tree, const d
     act_dense = 1;
   }
   const int64_t st_stride = (int64_t)nC * (A + 1) * ANT_S, ac_stride = (int64_t)nC * A * ANT_D;
+  const double gx = scp ? 0.0 : p->desired_goal[0], gy = scp ? 0.0 : p->desired_goal[1];   // scenes: each row's own goal
   launch_ant_rollout(ctx->maze, ctx->rows, ctx->cols, model, round->end_state, acts, act_stride, obs, obs_stride, round->status,
-                     n_run, A, p->desired_goal[0], p->desired_goal[1], p->goal_radius, p->ball_radius, p->s_global,
+                     n_run, A, gx, gy, p->goal_radius, p->ball_radius, p->s_global,
                      round->states + (size_t)j * (A + 1) * ANT_S, ditree_strides{st_stride, ANT_S, 1},
                      round->actions + (size_t)j * A * ANT_D, ditree_strides{ac_stride, ANT_D, 1}, round->chunk_steps + j, nC,
                      round->chunks_run, ctx->ant_prev, ctx->ant_hasprev, ctx->ant_hist, ctx->ant_hist_n, ctx->ant_run_idx, act_dense,
-                     s);
+                     s, 0, AntChunkStrides{0, 0, 0, 0}, scp);
   (void)B;
   HIP_TRY(ctx, hipGetLastError());
   return DITREE_OK;
@@ -777,12 +790,15 @@ int32_t ditree_ant_chunk_step(ditree_ctx* ctx, const ditree_tree* tree, const di
   return ant_chunk_step_impl(ctx, tree, round, p, j, next_obs, (int64_t)tree->A * ANT_S, nullptr, (hipStream_t)stream);
 }
 
-// The ant round of one tree, or (f != NULL, validated by the caller) of a forest: only the begin step differs.
+static int ensure_row_scene(ditree_ctx* ctx, int B, hipStream_t s);
+
+// The ant round of one tree, or (f != NULL, validated by the caller) of a forest: only the begin step differs.  An ant scene
+// forest (tree_scene != NULL, validated by the caller) reads each row's maze and desired goal from the scene table instead.
 static int expand_round_ant_impl(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* f, const ditree_round* round,
-                                 const ditree_ant_round_params* p, void* stream) {
+                                 const ditree_ant_round_params* p, void* stream, const int32_t* tree_scene = nullptr) {
   if (!ctx) return DITREE_E_ARG;
   int P = 0;
-  int rc = check_ant_round(ctx, tree, round, p, 1, &P);
+  int rc = check_ant_round(ctx, tree, round, p, 1, &P, tree_scene != nullptr);
   if (rc) return rc;
   AntModelArg ma;
   const AntModelArg* model = nullptr;
@@ -796,13 +812,26 @@ static int expand_round_ant_impl(ditree_ctx* ctx, const ditree_tree* tree, const
   } else {
     return set_err(ctx, DITREE_E_ARG, "expand_round_ant: dynamics must be DITREE_ANT_DYN_TAPE or DITREE_ANT_DYN_MODEL");
   }
-  rc = ant_round_begin_impl(ctx, tree, f, round, p, stream);
+  SceneArg sc{};
+  const SceneArg* scp = nullptr;
+  if (p->early_exit && round->B > 0 && p->cond_out)
+    return set_err(ctx, DITREE_E_ARG, "expand_round_ant: cond_out is a test output of rounds without early_exit");
+  if (tree_scene) {
+    sc = SceneArg{ctx->scene_tab, ctx->atlas_cells, ctx->max_scene_cells};
+    scp = &sc;
+    if (round->B > 0) {
+      rc = ensure_row_scene(ctx, round->B, (hipStream_t)stream);
+      if (rc) return rc;
+      launch_row_scene(f->off, f->n_trees, tree_scene, round->B, ctx->row_scene, (hipStream_t)stream);
+    }
+  }
+  const double gx = scp ? 0.0 : p->desired_goal[0], gy = scp ? 0.0 : p->desired_goal[1];   // scenes: each row's own goal
+  rc = ant_round_begin_impl(ctx, tree, f, round, p, stream, scp != nullptr);
   if (rc) return rc;
   const int nC = tree->n_chunks, A = tree->A;
   if (p->early_exit && round->B > 0) {
     // the pool-scheduled form of the car round's early exit (ditree_expand_round): calls packed to whole tile-waves (2048
     // candidates for the ant network) from the ready list, rows of one launch at different chunks of their edges
-    if (p->cond_out) return set_err(ctx, DITREE_E_ARG, "expand_round_ant: cond_out is a test output of rounds without early_exit");
     hipStream_t s = (hipStream_t)stream;
     const int quantum = p->inject_actions ? 64 : denoise_wave_quantum(ctx);
     AxisArg ax;
@@ -821,8 +850,12 @@ static int expand_round_ant_impl(ditree_ctx* ctx, const ditree_tree* tree, const
         act_stride = (int64_t)nC * P * ANT_D;
         act_dense = 0;
       } else {
-        launch_local_map(ctx->maze, ctx->rows, ctx->cols, round->end_state, round->status, ctx->ant_idx, take, p->lm_n, ax, p->s_global,
-                         1, ctx->ant_lmap, s, ANT_S);
+        if (scp)
+          launch_local_map_scenes(sc, round->end_state, round->status, ctx->ant_idx, take, p->lm_n, ax, p->s_global, ctx->ant_lmap, s,
+                                  ANT_S);
+        else
+          launch_local_map(ctx->maze, ctx->rows, ctx->cols, round->end_state, round->status, ctx->ant_idx, take, p->lm_n, ax,
+                           p->s_global, 1, ctx->ant_lmap, s, ANT_S);
         launch_cond_vector_ant(ctx->ant_hist, 3, ctx->ant_hist_n, ctx->ant_prev, ctx->ant_hasprev, p->cond_goal, ctx->ant_idx, take, nm,
                                p->lm_size, ctx->ant_cond, s);
         const int src = round_sampler(ctx, p->noise, (int64_t)P * ANT_D, ctx->ant_nrow, ctx->ant_lmap, ctx->ant_cond, take, p->K, p->t0,
@@ -833,10 +866,10 @@ static int expand_round_ant_impl(ditree_ctx* ctx, const ditree_tree* tree, const
         act_stride = (int64_t)P * ANT_D;
       }
       launch_ant_rollout(ctx->maze, ctx->rows, ctx->cols, model, round->end_state, acts, act_stride, p->next_obs_tape,
-                         (int64_t)nC * A * ANT_S, round->status, take, A, p->desired_goal[0], p->desired_goal[1], p->goal_radius,
+                         (int64_t)nC * A * ANT_S, round->status, take, A, gx, gy, p->goal_radius,
                          p->ball_radius, p->s_global, round->states, ditree_strides{st_stride, ANT_S, 1}, round->actions,
                          ditree_strides{ac_stride, ANT_D, 1}, round->chunk_steps, nC, round->chunks_run, ctx->ant_prev, ctx->ant_hasprev,
-                         ctx->ant_hist, ctx->ant_hist_n, ctx->ant_idx, act_dense, s, 1, cs);
+                         ctx->ant_hist, ctx->ant_hist_n, ctx->ant_idx, act_dense, s, 1, cs, scp);
       return DITREE_OK;
     });
     if (rc) return rc;
@@ -844,11 +877,11 @@ static int expand_round_ant_impl(ditree_ctx* ctx, const ditree_tree* tree, const
     return DITREE_OK;
   }
   for (int j = 0; j < nC; ++j) {
-    rc = ditree_ant_chunk_sample(ctx, tree, round, p, j, stream);
+    rc = ant_chunk_sample_impl(ctx, tree, round, p, j, stream, scp);
     if (rc) return rc;
     if (ctx->ant_n_run == 0) break;
     const double* obs = model ? nullptr : p->next_obs_tape + (size_t)j * A * ANT_S;
-    rc = ant_chunk_step_impl(ctx, tree, round, p, j, obs, (int64_t)nC * A * ANT_S, model, (hipStream_t)stream);
+    rc = ant_chunk_step_impl(ctx, tree, round, p, j, obs, (int64_t)nC * A * ANT_S, model, (hipStream_t)stream, scp);
     if (rc) return rc;
   }
   return DITREE_OK;
@@ -973,7 +1006,7 @@ static int expand_round_impl(ditree_ctx* ctx, const ditree_tree* tree, const dit
       act_dense = 0;
     } else {
       if (scp)
-        launch_local_map_scenes(sc, ctx->cur_state, round->status, idx, n, p->lm_n, ax, p->s_global, ctx->lmap, s);
+        launch_local_map_scenes(sc, ctx->cur_state, round->status, idx, n, p->lm_n, ax, p->s_global, ctx->lmap, s, 6);
       else
         launch_local_map(ctx->maze, ctx->rows, ctx->cols, ctx->cur_state, round->status, idx, n, p->lm_n, ax, p->s_global, 1,
                          ctx->lmap, s);
@@ -1276,6 +1309,28 @@ int32_t ditree_forest_fallback_ant(ditree_ctx* ctx, const ditree_tree* tree, con
   std::vector<double> q((size_t)forest->n_trees * 2);   // T copies of the goal as the queries
   for (int t = 0; t < forest->n_trees; ++t) { q[(size_t)t * 2] = goal_xy[0]; q[(size_t)t * 2 + 1] = goal_xy[1]; }
   return forest_fallback_impl(ctx, tree, forest, q.data(), out_node, (hipStream_t)stream);
+}
+
+// ---- ant scene forests (include/ditree.h "ant scene forests")
+int32_t ditree_forest_expand_round_ant_scenes(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
+                                              const ditree_forest_scenes* scenes, const ditree_round* round,
+                                              const ditree_ant_round_params* p, void* stream) {
+  if (!ctx) return DITREE_E_ARG;
+  int rc = check_ant_forest(ctx, tree, forest, round, "forest_expand_round_ant_scenes");
+  if (rc) return rc;
+  rc = check_scenes(ctx, forest, scenes, "forest_expand_round_ant_scenes");
+  if (rc) return rc;
+  return expand_round_ant_impl(ctx, tree, forest, round, p, stream, scenes->tree_scene);
+}
+
+int32_t ditree_forest_fallback_goals_ant(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const double* goal_xy,
+                                         int32_t* out_node, void* stream) {
+  if (!ctx) return DITREE_E_ARG;
+  const int rc = check_ant_forest(ctx, tree, forest, nullptr, "forest_fallback_goals_ant");
+  if (rc) return rc;
+  if (!goal_xy) return set_err(ctx, DITREE_E_ARG, "forest_fallback_goals_ant: goals array (T, 2) missing");
+  if (!out_node) return set_err(ctx, DITREE_E_ARG, "forest_fallback_goals_ant: out_node missing");
+  return forest_fallback_impl(ctx, tree, forest, goal_xy, out_node, (hipStream_t)stream);
 }
 
 }  // extern "C"

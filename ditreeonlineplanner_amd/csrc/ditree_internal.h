@@ -120,7 +120,7 @@ void launch_nn_forest(const double* queries, int q_stride, int B, const double* 
 void launch_forest_fallback(const double* goals, int T, const double* node_xy, const int32_t* counters, int C, int32_t* out_idx,
                             hipStream_t s);
 void launch_local_map_scenes(const SceneArg& sc, const double* state, const int32_t* active, const int32_t* idx, int B, int n,
-                             const AxisArg& axis, double s_global, float* out, hipStream_t s);
+                             const AxisArg& axis, double s_global, float* out, hipStream_t s, int state_stride);
 void launch_row_scene(const int32_t* off, int T, const int32_t* tree_scene, int B, int32_t* row_scene, hipStream_t s);
 void launch_local_map(const unsigned char* maze, int rows, int cols, const double* state,
                       const int32_t* active, const int32_t* idx, int B, int n, const AxisArg& axis,
@@ -148,7 +148,7 @@ void launch_ant_rollout(const unsigned char* maze, int rows, int cols, const Ant
                         ditree_strides sl, double* actions_out, ditree_strides al, int32_t* steps_out, int64_t steps_stride,
                         int32_t* chunks_run, double* prev_action_io, uint8_t* has_prev_io, double* hist_out, int32_t* hist_n,
                         const int32_t* idx, int act_dense, hipStream_t s, int chunk_from_counter = 0,
-                        AntChunkStrides cs = AntChunkStrides{0, 0, 0, 0});
+                        AntChunkStrides cs = AntChunkStrides{0, 0, 0, 0}, const SceneArg* scenes = nullptr);
 // per-chunk strides (doubles) of the round's row outputs / the injected action tape, for launches whose rows sit at different chunks
 struct ChunkStrides { int64_t states, actions_out, actions_in; };
 void launch_compact_ready(const int32_t* status, const int32_t* chunks_run, const int32_t* budget, int n_chunks, int B,

@@ -253,9 +253,9 @@ void launch_local_map(const unsigned char* maze, int rows, int cols, const doubl
                      s_global, scaled, out);
 }
 void launch_local_map_scenes(const SceneArg& sc, const double* state, const int32_t* active, const int32_t* idx, int B, int n,
-                             const AxisArg& axis, double s_global, float* out, hipStream_t s) {
+                             const AxisArg& axis, double s_global, float* out, hipStream_t s, int state_stride) {
   const size_t lds = ((size_t)sc.max_cells + 15) & ~(size_t)15;
-  hipLaunchKernelGGL(local_map_kernel<true>, dim3(B), dim3(256), lds, s, (const unsigned char*)sc.table, 0, 0, state, 6, active,
+  hipLaunchKernelGGL(local_map_kernel<true>, dim3(B), dim3(256), lds, s, (const unsigned char*)sc.table, 0, 0, state, state_stride, active,
                      idx, n, axis, s_global, 1, out);
 }
 // The scene of every candidate row: tree_scene[t] for the tree whose range [off[t], off[t+1]) holds the row (the last tree

@@ -205,6 +205,16 @@ def env_goal_of(maze, goal_state):
     return np.array([(gj + 0.5) * 1.0 - W / 2, H / 2 - (gi + 0.5) * 1.0])
 
 
+def ant_cell_centre(maze, goal_state, s_global):
+    """The centre of the cell ``goal_state[:2]`` lies in, in the map scaled by ``s_global``: an ant env's ``desired_goal``
+    without its position noise."""
+    H, W = np.asarray(maze).shape
+    sg = float(s_global)
+    gi = np.floor((H / 2 * sg - goal_state[1]) / sg)
+    gj = np.floor((goal_state[0] + W / 2 * sg) / sg)
+    return np.array([(gj + 0.5) * sg - W / 2 * sg, H / 2 * sg - (gi + 0.5) * sg])
+
+
 def tree_path(tr, node, n_nodes, base=0, edge_rows=None):
     """planners/base_planner.py:342-363 on a ``DeviceTree``: float32 path (edge states + node states) and actions from the
     root to ``node``.  The tree is the ``n_nodes`` slots from ``base`` (a forest's tree; ``node`` is local to it, the stored
@@ -592,11 +602,7 @@ class AntExpansionEngine(ExpansionEngine):
         if self._desired_arg is not None:
             self.env_goal = self._desired_arg.copy()
             return
-        H, W = self.maze.shape
-        sg = float(self.s_global)
-        gi = np.floor((H / 2 * sg - self.goal_state[1]) / sg)
-        gj = np.floor((self.goal_state[0] + W / 2 * sg) / sg)
-        self.env_goal = np.array([(gj + 0.5) * sg - W / 2 * sg, H / 2 * sg - (gi + 0.5) * sg])
+        self.env_goal = ant_cell_centre(self.maze, self.goal_state, self.s_global)
 
     def _params(self, samples, cond_goal, noise, inject_actions, lo, hi, next_obs_tape=None, cond_out=None, step_noise=None):
         n = hi - lo

@@ -11,8 +11,10 @@ the batch, so each tree grows exactly as it would in its own ``ExpansionEngine``
 
 Scope: run_type 0, one GPU.  The car: one maze / start / goal for every tree -- or, in a ``SceneForestEngine``, each tree on
 its own scene (maze, start, goal) of a scenario set (run_scenarios.py:203-250), the mazes in one scene table on the device.
-The ant (BASELINE config 3): ``AntForestEngine``, one maze / start / goal, tape or model dynamics (a host-stepped simulator
-steps one candidate at a time and has no forest form).  ``ForestTrees`` holds what both share.
+The ant (BASELINE config 3): ``AntForestEngine``, one maze / start / goal -- or, in an ``AntSceneForestEngine``, each tree on its
+own scene of the ant scenario set (run_scenarios.py:202-233) -- tape or model dynamics (a host-stepped simulator steps one
+candidate at a time and has no forest form).  ``ForestTrees`` holds what the forests share, ``SceneTrees`` what the two scene
+forests share.
 """
 from __future__ import annotations
 
@@ -22,7 +24,8 @@ import numpy as np
 import torch
 
 from ._lib import MAX_ATLAS_CELLS, MAX_SCENES, Forest, ForestScenes, RoundParams, check, lib
-from .engine import CNT_GOAL, CNT_NODES, CNT_PHANTOM, AntExpansionEngine, ExpansionEngine, env_goal_of, tree_path
+from .engine import (CNT_GOAL, CNT_NODES, CNT_PHANTOM, AntExpansionEngine, ExpansionEngine, ant_cell_centre, env_goal_of,
+                     tree_path)
 from .ops import CAR_NORM, Context, _dbl
 
 
@@ -284,13 +287,14 @@ class AntForestEngine(ForestTrees, AntExpansionEngine):
         self._check_round_shapes(B, samples, cond_goal, noise, inject_actions, next_obs_tape)
         self.ensure_maze()
         rp, keep = self._params(samples, cond_goal, noise, inject_actions, 0, B, next_obs_tape, cond_out, step_noise)
-        rd = self.rb.desc(0, B)
-        h = self.ctx._h
-        check(h, lib().ditree_forest_expand_round_ant(h, C.byref(self.tree.desc), C.byref(self.fdesc), C.byref(rd), C.byref(rp),
-                                                      self.ctx.stream), "forest_expand_round_ant")
+        self._launch_round(self.rb.desc(0, B), rp)
         del keep
         return self._end_round(B, noise is not None, accept)
 
+    def _launch_round(self, rd, rp):
+        h = self.ctx._h
+        check(h, lib().ditree_forest_expand_round_ant(h, C.byref(self.tree.desc), C.byref(self.fdesc), C.byref(rd), C.byref(rp),
+                                                      self.ctx.stream), "forest_expand_round_ant")
 
 
 # ---------------------------------------------------------------------- scene forests
@@ -318,14 +322,16 @@ def atlas_layout(mazes):
     return np.array(offsets, dtype=np.int64), np.array(dims, dtype=np.int64).reshape(-1, 2), used
 
 
-class SceneForestEngine(ForestEngine):
-    """A forest whose trees belong to different scenes of a scenario set.  ``scenes``: a list of ``(maze, start_state,
-    goal_state, env_goal)`` (env_goal None: the goal cell's centre, as env.reset sets it).  Tree t grows on scene
-    ``tree_scene(t)``: its root is that scene's start, its local map, collision and goal tests use that scene's maze and goal,
-    and its fallback is the node nearest to that scene's goal -- exactly as its own ``ExpansionEngine`` on that scene.  All
-    mazes sit in one scene table on the device (include/ditree.h "scene forests"); no single maze is read."""
+class SceneTrees:
+    """The scene bookkeeping of a scene forest, mixed in over a forest engine (``ForestEngine`` for the car, ``AntForestEngine``
+    for the ant): the scene lists, the atlas and the scene table's upload, the scene id of every tree, ``reset`` /
+    ``reset_tree(t, scene)`` and the per-tree fallback goals.  ``scenes``: a list of ``(maze, start_state, goal_state, goal)``;
+    ``goal`` is what the scene table's goal column holds -- what the rollout's goal test reads: the car's ``env.goal``, the
+    ant's ``desired_goal`` -- and the engine class derives it when it is None or left out (``_scene_goal``).  The engine class
+    names its fallback entry point: ``_FALLBACK_GOALS`` = (symbol, what)."""
 
-    def __init__(self, ctx: Context, scenes, n_trees, tree_capacity, **kw):
+    def _init_scenes(self, ctx, scenes, n_trees):
+        """Before the forest's own constructor (which ends in ``reset``)."""
         scenes = list(scenes)
         if not 1 <= len(scenes) <= MAX_SCENES:
             raise ValueError(f"a scene forest holds 1..{MAX_SCENES} scenes, got {len(scenes)}")
@@ -338,7 +344,7 @@ class SceneForestEngine(ForestEngine):
             self.scene_mazes.append(maze)
             self.scene_starts.append(np.asarray(start, dtype=np.float64).copy())
             self.scene_goals.append(goal)
-            self.scene_env_goals.append(np.asarray(env_goal_of(maze, goal) if env_goal is None else env_goal, dtype=np.float64)[:2].copy())
+            self.scene_env_goals.append(np.asarray(self._scene_goal(maze, goal) if env_goal is None else env_goal, dtype=np.float64)[:2].copy())
         cells = sum(m.size for m in self.scene_mazes)
         if cells > MAX_ATLAS_CELLS:
             raise ValueError(f"the scenes' mazes hold {cells} cells, more than the atlas's {MAX_ATLAS_CELLS}")
@@ -349,7 +355,6 @@ class SceneForestEngine(ForestEngine):
         self.sdesc = ForestScenes(self.tree_scene_dev.data_ptr(), self.tree_scene_host)
         self.ctx = ctx
         self.upload_scenes()
-        super().__init__(ctx, self.scene_mazes[0], self.scene_starts[0], self.scene_goals[0], n_trees, tree_capacity, **kw)
 
     def upload_scenes(self):
         self.ctx.upload_scenes(self.scene_mazes, np.stack(self.scene_env_goals), owner=self)
@@ -376,7 +381,8 @@ class SceneForestEngine(ForestEngine):
         self.generation = getattr(self, "generation", 0) + 1
 
     def reset_tree(self, t, scene=None):
-        """Tree t back to a root: the start of ``scene`` (default: the tree's current scene), which the tree then grows on."""
+        """Tree t back to a root: the start of ``scene`` (default: the tree's current scene), which the tree then grows on
+        (the ant: with the root's history rows restored from that start, as ``ForestTrees.reset_tree`` leaves them)."""
         t = self._tree_index(t)
         scene = int(self.tree_scene_host[t] if scene is None else scene)
         if not 0 <= scene < self.n_scenes:
@@ -388,12 +394,57 @@ class SceneForestEngine(ForestEngine):
     def tree_scene(self, t):
         return int(self.tree_scene_host[self._tree_index(t)])
 
+    def fallback_nodes(self):
+        """planners/RRT.py:227-254 (run_type 0) for every tree, each against its own scene's goal_state[:2]."""
+        goals = np.stack([self.scene_goals[self.tree_scene(t)][:2] for t in range(self.T)])
+        entry, what = self._FALLBACK_GOALS
+        return self._fallback_launch(getattr(lib(), entry), what, goals)
+
+
+class SceneForestEngine(SceneTrees, ForestEngine):
+    """A forest whose trees belong to different scenes of a scenario set.  ``scenes``: a list of ``(maze, start_state,
+    goal_state, env_goal)`` (env_goal None: the goal cell's centre, as env.reset sets it).  Tree t grows on scene
+    ``tree_scene(t)``: its root is that scene's start, its local map, collision and goal tests use that scene's maze and goal,
+    and its fallback is the node nearest to that scene's goal -- exactly as its own ``ExpansionEngine`` on that scene.  All
+    mazes sit in one scene table on the device (include/ditree.h "scene forests"); no single maze is read.  The scene
+    bookkeeping is ``SceneTrees``'."""
+    _FALLBACK_GOALS = ("ditree_forest_fallback_goals", "forest_fallback_goals")
+    _scene_goal = staticmethod(env_goal_of)
+
+    def __init__(self, ctx: Context, scenes, n_trees, tree_capacity, **kw):
+        self._init_scenes(ctx, scenes, n_trees)
+        super().__init__(ctx, self.scene_mazes[0], self.scene_starts[0], self.scene_goals[0], n_trees, tree_capacity, **kw)
+
     def _launch_round(self, rd, rp):
         h = self.ctx._h
         check(h, lib().ditree_forest_expand_round_scenes(h, C.byref(self.tree.desc), C.byref(self.fdesc), C.byref(self.sdesc),
                                                          C.byref(rd), C.byref(rp), self.ctx.stream), "forest_expand_round_scenes")
 
-    def fallback_nodes(self):
-        """planners/RRT.py:227-254 (run_type 0) for every tree, each against its own scene's goal_state[:2]."""
-        goals = np.stack([self.scene_goals[self.tree_scene(t)][:2] for t in range(self.T)])
-        return self._fallback_launch(lib().ditree_forest_fallback_goals, "forest_fallback_goals", goals)
+
+class AntSceneForestEngine(SceneTrees, AntForestEngine):
+    """An ant forest whose trees belong to different scenes of the antmaze scenario set (run_scenarios.py:202-233).
+    ``scenes``: a list of ``(maze, start_state (29,), goal_state (29,), desired_goal (2,))`` (desired_goal None: the goal cell's
+    centre); ``**ant_kw``: ``AntForestEngine``'s keyword arguments.  Tree t grows on scene ``tree_scene(t)``: its root (state and
+    history rows) is that scene's start, its local map, collision test and goal test use that scene's maze and
+    ``desired_goal`` -- the scene table's goal column -- and its fallback is the node nearest to that scene's
+    ``goal_state[:2]``: exactly as its own ``AntExpansionEngine`` on that scene.  ``goal_radius``, ``ball_radius`` and
+    ``s_global`` hold for all scenes.  All mazes sit in one scene table on the device (include/ditree.h "ant scene forests");
+    no single maze is read."""
+    _FALLBACK_GOALS = ("ditree_forest_fallback_goals_ant", "forest_fallback_goals_ant")
+
+    def __init__(self, ctx: Context, scenes, n_trees, tree_capacity, **ant_kw):
+        if "desired_goal" in ant_kw:
+            raise TypeError("AntSceneForestEngine: every scene carries its own desired_goal")
+        self._scene_s_global = float(ant_kw.get("s_global", 4.0))
+        self._init_scenes(ctx, scenes, n_trees)
+        super().__init__(ctx, self.scene_mazes[0], self.scene_starts[0], self.scene_goals[0], n_trees, tree_capacity,
+                         desired_goal=self.scene_env_goals[0], **ant_kw)
+
+    def _scene_goal(self, maze, goal_state):
+        return ant_cell_centre(maze, goal_state, self._scene_s_global)
+
+    def _launch_round(self, rd, rp):
+        h = self.ctx._h
+        check(h, lib().ditree_forest_expand_round_ant_scenes(h, C.byref(self.tree.desc), C.byref(self.fdesc), C.byref(self.sdesc),
+                                                             C.byref(rd), C.byref(rp), self.ctx.stream),
+              "forest_expand_round_ant_scenes")

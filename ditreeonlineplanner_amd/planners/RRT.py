@@ -454,15 +454,19 @@ def _check_scene_planners(planners):
     from ._runs import check_forest_scope
     for pl in planners:
         if pl.is_ant:
-            raise NotImplementedError("plan_scenario_runs: the car (carmaze) only (an ant forest has one maze, start and goal: "
-                                      "RRT_Planner.plan_runs)")
+            raise NotImplementedError("plan_scenario_runs: the car (carmaze) only (antmaze planners: plan_ant_scenario_runs)")
         check_forest_scope(pl, "plan_scenario_runs")
-    ref = _scene_settings(planners[0])
+    _check_shared_settings(planners, _scene_settings, "plan_scenario_runs")
+
+
+def _check_shared_settings(planners, settings, who):
+    """ValueError naming the first entry of ``settings(planner)`` in which a planner differs from planner 0."""
+    ref = settings(planners[0])
     for i, pl in enumerate(planners[1:], 1):
-        for (name, a), (_, b) in zip(ref, _scene_settings(pl)):
+        for (name, a), (_, b) in zip(ref, settings(pl)):
             same = a is b if name in ("ctx", "sampler") else a == b
             if not same:
-                raise ValueError(f"plan_scenario_runs: planner {i} differs from planner 0 in {name}"
+                raise ValueError(f"{who}: planner {i} differs from planner 0 in {name}"
                                  + ("" if name in ("ctx", "sampler") else f" ({b!r} != {a!r})")
                                  + ("; all planners must share one object" if name in ("ctx", "sampler") else ""))
 
@@ -511,6 +515,77 @@ def plan_scenario_runs(planners, seeds, concurrent=None, tree_capacity=None):
                             goal_scale=e.goal_scale, prop_duration=e.schedule)
     eng.ddpm = e.ddpm
     if network:
+        sampler.ensure_bound(T * batch)
+    run_jobs(eng, jobs, batch, ctx.device)
+    return results
+
+
+# ---------------------------------------------------------------------- an antmaze scenario set at once
+def _ant_scene_settings(pl):
+    """What every planner of one ant scene forest must share (one round program, one goal_radius / ball_radius / s_global)."""
+    e = pl._engine
+    return [("ctx", pl.ctx), ("sampler", pl.sampler), ("edge_length", e.H), ("action_horizon", e.A), ("pred_horizon", e.P),
+            ("local map size", e.lm_n), ("local map scale", float(e.lm_scale)), ("s_global", float(e.s_global)),
+            ("k_steps", e.k_steps), ("norm", e.norm.tobytes()), ("early_exit", e.early_exit), ("batch", pl.batch),
+            ("ant_dynamics", pl.ant_dynamics), ("ant_model", bytes(e.model)), ("ball_radius", float(e.ball_radius)),
+            ("goal_radius", float(e.goal_radius))]
+
+
+def _check_ant_scene_planners(planners):
+    from ._runs import check_forest_scope
+    for pl in planners:
+        if not pl.is_ant:
+            raise NotImplementedError("plan_ant_scenario_runs: antmaze planners only (the car: plan_scenario_runs)")
+        check_forest_scope(pl, "plan_ant_scenario_runs")
+    _check_shared_settings(planners, _ant_scene_settings, "plan_ant_scenario_runs")
+
+
+def plan_ant_scenario_runs(planners, seeds, concurrent=None, tree_capacity=None):
+    """``plan_scenario_runs`` for ``env_id='antmaze'`` planners: the seeded runs of several ant scenarios (one ``RRT_Planner``
+    each: its own maze, start, goal and ``desired_goal``) expanded together as one ant scene forest
+    (forest.AntSceneForestEngine) on one GPU -- the ant benchmark loop of run_scenarios.py:202-233,336-343 as one stream of
+    rounds.
+
+    ``seeds``: one list per planner.  Returns one list per planner of ``plan_runs``-shaped dicts: run (i, s) is what
+    ``random.seed(s); np.random.seed(s); torch.manual_seed(s); planners[i].reset(); planners[i].plan()`` leaves.  Queueing,
+    ``concurrent``, ``tree_capacity``, the per-run streams and budgets and the caller's generator states are
+    ``plan_scenario_runs``'; ant runs report ``cc_calls`` 0 (``is_colliding_ant`` does not count its calls).  Each planner's
+    ``reset()`` is called ONCE and scene i's ``desired_goal`` is what that reset left, for all of its runs: as in ``plan_runs``,
+    equality with the sequential runs holds for an env whose ``reset`` returns the same ``desired_goal`` every time -- a gym env
+    that adds position noise per reset gives one draw per scenario here, a fresh one per run in the loop.  Scope: run_type 0,
+    one rank, ``ant_dynamics`` "model" or "tape", a network sampler or one with ``sample_round``.  All planners must share one
+    ctx and one sampler object and agree on the round settings, the dynamics and its model, ``ball_radius`` and
+    ``goal_radius`` (ValueError names the first difference)."""
+    from ..forest import AntSceneForestEngine
+    from ._runs import Job, run_jobs
+    planners = list(planners)
+    if not planners:
+        return []
+    if len(seeds) != len(planners):
+        raise ValueError(f"seeds: one list per planner ({len(planners)}), got {len(seeds)}")
+    _check_ant_scene_planners(planners)
+    seeds = [[int(s) for s in ss] for ss in seeds]
+    results = [[None] * len(ss) for ss in seeds]
+    jobs = [Job(planners[i], s, (results[i], k), (i,)) for i, ss in enumerate(seeds) for k, s in enumerate(ss)]
+    if not jobs:
+        return results
+    p0 = planners[0]
+    ctx, sampler, batch = p0.ctx, p0.sampler, p0.batch
+    T = len(jobs) if concurrent is None else max(1, min(int(concurrent), len(jobs)))
+    if tree_capacity is None:
+        caps = [pl.capacity if pl.max_candidates is None else min(pl.capacity, int(pl.max_candidates) + 1) for pl in planners]
+        tree_capacity = max(caps)
+    for pl in planners:
+        pl.reset()                                           # env.reset(options) as before every sequential plan()
+    scenes = [(pl.maze, pl.start_node.state, pl.goal_state, pl._engine.env_goal.copy()) for pl in planners]
+    e = p0._engine
+    eng = AntSceneForestEngine(ctx, scenes, T, int(tree_capacity), norm=e.norm, edge_length=e.H, action_horizon=e.A,
+                               pred_horizon=e.P, local_map_size=e.lm_n, local_map_scale=e.lm_scale, s_global=e.s_global,
+                               batch=T * batch, k_steps=e.k_steps, early_exit=bool(e.early_exit), goal_scale=e.goal_scale,
+                               dynamics=e.dynamics, model=e.model, ball_radius=e.ball_radius)
+    eng.goal_radius = e.goal_radius
+    eng.ddpm = e.ddpm
+    if hasattr(sampler, "ensure_bound"):
         sampler.ensure_bound(T * batch)
     run_jobs(eng, jobs, batch, ctx.device)
     return results

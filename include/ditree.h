@@ -702,6 +702,24 @@ int32_t ditree_forest_accept_ant(ditree_ctx* ctx, const ditree_tree* tree, const
 int32_t ditree_forest_fallback_ant(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const double* goal_xy,
                                    int32_t* out_node, void* stream);
 
+/* ------------------------------------------------------------------ ant scene forests: an antmaze scenario set in one round
+ * The ant benchmark is a scenario set too (run_scenarios.py:202-233: one maze, start and goal cell per row of
+ * experiments/test_scenarios_ant.csv).  An ant scene forest is an ant forest plus a scene id per tree (ditree_forest_scenes) on
+ * the scene table of ditree_upload_scenes, whose goal column holds each scene's obs['desired_goal'] (base_planner.py:296).  The
+ * accept step is ditree_forest_accept_ant.  Both calls validate everything on the host before anything is launched. */
+/* ditree_forest_expand_round_ant with each tree's own scene: every row's local map, collision tests and goal test use its
+ * tree's maze and desired goal.  p->desired_goal is not read and no single maze is needed; p->goal_radius, p->ball_radius and
+ * p->s_global hold for all scenes.  DITREE_E_STATE without an uploaded scene table; DITREE_E_ARG for a car tree, a sharded
+ * round, an incomplete forest or scene descriptor, a scene id outside [0, n uploaded), or p->dynamics that is neither
+ * DITREE_ANT_DYN_TAPE nor DITREE_ANT_DYN_MODEL.  Each candidate's arithmetic is the single-maze ant round's on its scene's bytes,
+ * dims and goal. */
+int32_t ditree_forest_expand_round_ant_scenes(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
+                                              const ditree_forest_scenes* scenes, const ditree_round* round,
+                                              const ditree_ant_round_params* p, void* stream);
+/* ditree_forest_fallback_ant with one goal per tree: goal_xy [host] (T, 2) (ditree_forest_fallback_goals refuses an ant tree). */
+int32_t ditree_forest_fallback_goals_ant(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
+                                         const double* goal_xy, int32_t* out_node, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
