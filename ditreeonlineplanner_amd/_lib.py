@@ -155,6 +155,8 @@ SIGNATURES = {
     "ditree_allgather_nodes": (_i32, [_vp, _vp, _vp, _i64, _vp]),
     "ditree_comm_destroy": (_i32, [_vp]),
     "ditree_mppi_step": (_i32, [_vp, C.POINTER(MppiParams), _vp, _vp, _vp, _i32, _pd, _vp, C.c_uint64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ditree_mppi_missions": (_i32, [_vp, C.POINTER(MppiParams), _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32,
+                                    _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "ditree_mppi_step_ant": (_i32, [_vp, C.POINTER(MppiAntParams), _vp, _vp, _vp, _i32, _pd, _vp, C.c_uint64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ditree_load_weights": (_i32, [_vp, _vp, _i64, C.c_char_p, _vp]),
     "ditree_denoise_reserve": (_i32, [_vp, _i32, _i32]),

@@ -29,6 +29,7 @@ ARCH = "gfx950"
 UNITS = [
     ("geom_kernels.hip", ["-ffp-contract=off"]),
     ("mppi_kernels.hip", ["-ffp-contract=off"]),
+    ("mppi_mission_kernels.hip", ["-ffp-contract=off"]),
     ("ant_kernels.hip", ["-ffp-contract=off"]),
     ("ant_scene_kernels.hip", ["-ffp-contract=off"]),
     ("mppi_ant_kernels.hip", ["-ffp-contract=off"]),

@@ -6,7 +6,8 @@ and in-place numpy semantics, so the reference's driver loop runs unchanged on t
 the driver's inner ``while`` (one Python iteration + one lidar scan every 11th step in the reference) by a single
 launch of the fused kernel: dynamics, goal / collision tests, periodic scans, maze updates and the path-crossing
 check stay on the GPU until the first event, and the engine's device copy of the known maze is refreshed in the
-same launch (no re-upload before the next plan).
+same launch (no re-upload before the next plan).  ``follow_reference`` does the same for the MPPI driver's loop
+(run_scenarios_with_lidar_MPPI.py:417-452) on an ``MPPI`` controller.
 """
 from __future__ import annotations
 
@@ -82,3 +83,18 @@ def follow_plan(planner, curr_state, main_actions, action_idx, main_path_array, 
     planner.env.set_state(new_state)
     planner.adopt_maze(maze_data)
     return new_state, nxt, executed.cpu().numpy(), event, obstacle
+
+
+def follow_reference(mppi_controller, curr_state, maze_data, maze_data_with_obstacle, scanned_maze, max_steps,
+                     allowed_trials=1, action_time_count=0.0, trials=0):
+    """run_scenarios_with_lidar_MPPI.py:417-452 as one fused launch: the MPPI driver's ``while`` (``mppi_controller.step``,
+    the ALLOWED_TRIALS collision retries, ``env.set_state``, the executed path / actions, and every ``scan_time`` a
+    ``scan_and_update_maze(mppi_controller, ...)``) for up to ``max_steps`` controller calls from ``curr_state``.
+
+    ``maze_data`` / ``scanned_maze`` are updated in place like the reference's arrays, and the controller takes the new
+    known maze (``mppi_controller.maze``, ``env.maze_map``), ``env.state`` and ``env.done``.  Returns
+    ``(curr_state, executed_states (n, 6), executed_actions (n, 2), event, info)`` with ``event`` one of
+    ``mppi.MEV_STEPS_DONE / MEV_GOAL / MEV_TRIALS`` and ``info["action_time_count"]`` / ``info["trials"]`` the driver's two
+    loop variables, to be handed back in when the loop is resumed."""
+    return mppi_controller.follow(curr_state, maze_data, maze_data_with_obstacle, scanned_maze, max_steps,
+                                  allowed_trials=allowed_trials, action_time_count=action_time_count, trials=trials)

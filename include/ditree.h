@@ -375,6 +375,49 @@ int32_t ditree_mppi_step(ditree_ctx* ctx, const ditree_mppi_params* p, double* s
                          int32_t P, const double* goal_xy, const double* noise, uint64_t counter, int32_t stages,
                          double* costs, double* weights, int32_t* flags, double* sums, double* result, void* stream);
 
+/* MPPI missions: the MPPI driver's control loop (run_scenarios_with_lidar_MPPI.py:417-452: mppi_controller.step, the
+ * ALLOWED_TRIALS collision retries, the executed path / actions, and every scan_time a scan_and_update_maze of the controller)
+ * for M independent missions (a fleet) in ONE launch -- the controller-side counterpart of ditree_follow_plan.  One work-group
+ * of 256 threads owns one mission from its first controller step to its terminating event; work-groups share nothing, so any
+ * M runs.  With c counting the controller calls of this launch:
+ *   input state inside the goal radius: event GOAL, nothing executed;
+ *   for c in [0, max_steps): one controller step (noise counter counter0 + c) = rollouts, beta, weights and sums, U update, one
+ *     executed step against the KNOWN maze.  Collided: the state stays, U <- 0, trials += 1, event TRIALS once trials >=
+ *     allowed_trials.  Else trials = 0, the new state and the executed action are appended to the mission's trace, t_acc += dt;
+ *     t_acc > scan_time: lidar scan of the TRUE maze from the pose, ray end cells -> 1 in known and scanned, visited cells -> 2
+ *     in scanned (ditree_follow_plan's scan), t_acc = 0; then inside the goal radius: event GOAL (after the scan, as the
+ *     driver's loop body ends before is_done is tested again);
+ *   event STEPS_DONE when the loop runs out.
+ * BIT-EXACT against the stepwise form: a mission leaves exactly what the same sequence of ditree_mppi_step(DITREE_MPPI_ALL),
+ * ditree_lidar_scan and ditree_upload_maze calls leaves (K <= 256 is that path's one-slice case; every sum takes its order).
+ *   p: shared by the fleet (T <= 64, K <= 256, lambda, sigma, weights, windows; p->seed and p->lanes are not read, k_offset = 0).
+ *   Per mission, [dev] arrays of M rows: seed, counter0 u64; state_io (M, 6), U_io (M, T, 2) f64 in/out; path_xy packed
+ *   (sum P, 2) f64 with path_off / path_len (M) i32, every length <= P_max <= 4096; goal_xy (M, 2) f64; known_maze / scanned_maze
+ *   (M, rows, cols) f32 in/out, true_maze (M, rows, cols) f32, rows * cols <= 13104; max_steps (M) i32, each <= trace_steps <=
+ *   DITREE_MPPI_MISSION_MAX_STEPS (longer missions take further launches); allowed_trials (M) i32; dt, scan_time (M) f64;
+ *   t_acc_io (M) f64 and trials_io (M) i32 in/out carry the scan cadence and the trial count across launches.
+ *   Out: executed_states (M, trace_steps, 6), executed_actions (M, trace_steps, 2) f64, rows [0, steps executed) written;
+ *   result (M, DITREE_MPPI_MISSION_RESULT) f64: event (DITREE_MEV_*), controller calls made, steps executed, scans, then the
+ *   last controller call's beta, eta, nearest path index, collided rollouts and effective sample size (zero without a call).
+ *   A mission whose path_len or max_steps breaks its bound runs nothing and reports DITREE_MEV_REFUSED.
+ *   refresh_mission >= 0: that mission's final known-maze codes also replace the ctx's own maze copy (which must have the same
+ *   shape), as ditree_follow_plan does; -1: the ctx's maze is not touched.
+ * DITREE_E_ARG, each naming its limit, for K > 256, T > 64, P_max > 4096, rows * cols > 13104, k_offset != 0, a null pointer,
+ * M < 1, trace_steps above the launch bound. */
+#define DITREE_MEV_REFUSED (-1)
+#define DITREE_MEV_STEPS_DONE 0
+#define DITREE_MEV_GOAL 1
+#define DITREE_MEV_TRIALS 2
+#define DITREE_MPPI_MISSION_RESULT 16
+#define DITREE_MPPI_MISSION_MAX_STEPS 2048
+int32_t ditree_mppi_missions(ditree_ctx* ctx, const ditree_mppi_params* p, int32_t M, const uint64_t* seed,
+                             const uint64_t* counter0, double* state_io, double* U_io, const double* path_xy,
+                             const int32_t* path_off, const int32_t* path_len, int32_t P_max, const double* goal_xy,
+                             float* known_maze, const float* true_maze, float* scanned_maze, int32_t rows, int32_t cols,
+                             const int32_t* max_steps, int32_t trace_steps, const int32_t* allowed_trials, const double* dt,
+                             const double* scan_time, double* t_acc_io, int32_t* trials_io, double* executed_states,
+                             double* executed_actions, double* result, int32_t refresh_mission, void* stream);
+
 /* The same controller on the higher-DoF rollout slot -- BASELINE config 5 as written ("MPPI antmaze, 65 536 rollouts"): 29-d
  * state, 8-d controls U (T, 8) with noise eps ~ N(0, diag(sigma^2)), every rollout step one env step of the build's STAND-IN
  * model (ditree_ant_model; NOT MuJoCo), the reference's ant collision test (ditree_ant_collision) and goal radius, the same
