@@ -115,6 +115,24 @@ class MppiAntParams(C.Structure):
                 ("ball_radius", C.c_double), ("s_global", C.c_double), ("model", AntModel)]
 
 
+class PolicyBatch(C.Structure):
+    """include/ditree.h ditree_policy_batch: N car episodes of a policy roll-out, every array on the device."""
+    _fields_ = [("N", C.c_int32), ("A", C.c_int32), ("max_steps", C.c_int32), ("scene", C.c_void_p),
+                ("scene_host", C.POINTER(C.c_int32)), ("state", C.c_void_p), ("rows", C.c_void_p), ("n_steps", C.c_void_p),
+                ("success_step", C.c_void_p), ("collided", C.c_void_p), ("status", C.c_void_p), ("best_dist", C.c_void_p),
+                ("last_action", C.c_void_p), ("has_prev", C.c_void_p), ("goal_xy", C.c_void_p), ("idx", C.c_void_p)]
+
+
+class PolicyParams(C.Structure):
+    """include/ditree.h ditree_policy_params: one chunk of a policy roll-out."""
+    _fields_ = [("step_limit", C.c_int32), ("noise", C.c_void_p), ("tape", C.c_void_p), ("P", C.c_int32), ("K", C.c_int32),
+                ("t0", C.POINTER(C.c_float)), ("dt", C.POINTER(C.c_float)), ("norm", C.POINTER(C.c_double)),
+                ("axis", C.POINTER(C.c_double)), ("lm_n", C.c_int32), ("lm_size", C.c_double), ("s_global", C.c_double),
+                ("ddpm_coef", C.POINTER(C.c_float)), ("step_noise", C.c_void_p)]
+
+
+EP_RUNNING, EP_SUCCESS, EP_COLLIDED, EP_OUT_OF_STEPS = 0, 1, 2, 3
+
 MPPI_ROLLOUTS, MPPI_MIN, MPPI_SUMS, MPPI_APPLY, MPPI_EXECUTE, MPPI_ALL = 1, 2, 4, 8, 16, 31
 
 
@@ -191,6 +209,8 @@ SIGNATURES = {
     "ditree_forest_expand_round_ant_scenes": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), C.POINTER(ForestScenes),
                                                      C.POINTER(Round), C.POINTER(AntRoundParams), _vp]),
     "ditree_forest_fallback_goals_ant": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), _pd, _vp, _vp]),
+    "ditree_policy_begin": (_i32, [_vp, C.POINTER(PolicyBatch), _vp]),
+    "ditree_policy_chunk": (_i32, [_vp, C.POINTER(PolicyBatch), C.POINTER(PolicyParams), C.POINTER(_i32), _vp]),
 }
 
 _LIB = None

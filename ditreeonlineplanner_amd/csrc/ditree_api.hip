@@ -1333,4 +1333,108 @@ int32_t ditree_forest_fallback_goals_ant(ditree_ctx* ctx, const ditree_tree* tre
   return forest_fallback_impl(ctx, tree, forest, goal_xy, out_node, (hipStream_t)stream);
 }
 
+// ---- policy roll-outs (include/ditree.h "policy roll-outs"): every check runs on the host before anything is launched
+static int check_policy_batch(ditree_ctx* ctx, const ditree_policy_batch* b, const char* what) {
+  const std::string w(what);
+  if (ctx->n_scenes < 1) return set_err(ctx, DITREE_E_STATE, w + ": no scene table uploaded (ditree_upload_scenes)");
+  if (!b || b->N < 1 || !b->scene || !b->scene_host || !b->state || !b->rows || !b->n_steps || !b->success_step || !b->collided ||
+      !b->status || !b->best_dist || !b->last_action || !b->has_prev || !b->goal_xy || !b->idx)
+    return set_err(ctx, DITREE_E_ARG, w + ": batch descriptor incomplete (N >= 1 and every array)");
+  if (b->A < 1 || b->A > 64 || b->max_steps < 1)
+    return set_err(ctx, DITREE_E_ARG, w + ": need 1 <= A <= 64, A <= P and 1 <= step_limit <= max_steps (A " + std::to_string(b->A) +
+                   ", max_steps " + std::to_string(b->max_steps) + ")");
+  for (int i = 0; i < b->N; ++i)
+    if (b->scene_host[i] < 0 || b->scene_host[i] >= ctx->n_scenes)
+      return set_err(ctx, DITREE_E_ARG, w + ": episode " + std::to_string(i) + " has scene id " + std::to_string(b->scene_host[i]) +
+                     ", out of range [0, " + std::to_string(ctx->n_scenes) + ")");
+  return DITREE_OK;
+}
+
+int32_t ditree_policy_begin(ditree_ctx* ctx, const ditree_policy_batch* batch, void* stream) {
+  if (!ctx) return DITREE_E_ARG;
+  const int rc = check_policy_batch(ctx, batch, "policy_begin");
+  if (rc) return rc;
+  ctx->policy_key = nullptr;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  launch_policy_begin(SceneArg{ctx->scene_tab, ctx->atlas_cells, ctx->max_scene_cells}, *batch, (hipStream_t)stream);
+  HIP_TRY(ctx, hipGetLastError());
+  ctx->policy_key = batch->idx;
+  ctx->policy_n = batch->N;
+  return DITREE_OK;
+}
+
+int32_t ditree_policy_chunk(ditree_ctx* ctx, const ditree_policy_batch* batch, const ditree_policy_params* p,
+                            int32_t* n_active_out, void* stream) {
+  if (!ctx) return DITREE_E_ARG;
+  int rc = check_policy_batch(ctx, batch, "policy_chunk");
+  if (rc) return rc;
+  if (!p || !n_active_out) return set_err(ctx, DITREE_E_ARG, "policy_chunk: parameters and n_active_out are required");
+  const int N = batch->N, A = batch->A, P = p->P;
+  if (A > P || p->step_limit < 1 || p->step_limit > batch->max_steps)
+    return set_err(ctx, DITREE_E_ARG, "policy_chunk: need 1 <= A <= 64, A <= P and 1 <= step_limit <= max_steps (A " + std::to_string(A) +
+                   ", P " + std::to_string(P) + ", step_limit " + std::to_string(p->step_limit) + ", max_steps " +
+                   std::to_string(batch->max_steps) + ")");
+  if (!p->noise && !p->tape) return set_err(ctx, DITREE_E_ARG, "policy_chunk: neither noise nor an action tape");
+  if (!p->tape) {
+    if (!p->norm || !p->axis || !(p->s_global > 0.0))
+      return set_err(ctx, DITREE_E_ARG, "policy_chunk: norm, axis and s_global > 0 are required with the network");
+    if (!p->t0 || (!p->dt && !p->ddpm_coef) || p->K < 1) return set_err(ctx, DITREE_E_ARG, "policy_chunk: flow schedule missing");
+    if (p->ddpm_coef && !p->step_noise && p->K > 1)
+      return set_err(ctx, DITREE_E_ARG, "policy_chunk: the DDPM branch needs step_noise (N, K, P, 2)");
+    int32_t d5[5];
+    if (ditree_denoise_dims(ctx, d5) != DITREE_OK) return DITREE_E_STATE;
+    if (P != d5[0] || p->lm_n != d5[2] || d5[1] != 2 || d5[3] != 7)
+      return set_err(ctx, DITREE_E_ARG, "policy_chunk: pred_horizon " + std::to_string(P) + " / local map " + std::to_string(p->lm_n) +
+                     " do not match the loaded denoiser (P " + std::to_string(d5[0]) + ", action_dim " + std::to_string(d5[1]) +
+                     ", map " + std::to_string(d5[2]) + ", cond " + std::to_string(d5[3]) + "; the car's is action_dim 2, cond 7)");
+  }
+  if (ctx->policy_key != batch->idx || ctx->policy_n < 0 || ctx->policy_n > N)
+    return set_err(ctx, DITREE_E_STATE, "policy_chunk: call ditree_policy_begin on this batch first");
+  const int n = ctx->policy_n;
+  *n_active_out = n;
+  if (n == 0) return DITREE_OK;
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  rc = ensure_scratch(ctx, N, p->tape ? 1 : p->lm_n, p->tape ? 1 : P);
+  if (rc) return rc;
+  const SceneArg sc{ctx->scene_tab, ctx->atlas_cells, ctx->max_scene_cells};
+  const double* acts = p->tape;
+  int64_t act_stride = (int64_t)P * 2;
+  int act_dense = 0;
+  if (!p->tape) {
+    AxisArg ax;
+    rc = fill_axis(ctx, p->axis, p->lm_n, &ax);
+    if (rc) return rc;
+    NormArg nm;
+    fill_norm(p->norm, &nm);
+    // the local-map kernel reads a row's scene through the table's row -> scene scratch: rows are episodes here
+    rc = ensure_row_scene(ctx, N, s);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->row_scene, batch->scene, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    launch_local_map_scenes(sc, batch->state, batch->status, batch->idx, n, p->lm_n, ax, p->s_global, ctx->lmap, s, 6);
+    launch_cond_vector(batch->state, batch->last_action, batch->has_prev, batch->goal_xy, batch->idx, n, nm, p->lm_size, ctx->cond, s);
+    double an[4] = {p->norm[12], p->norm[13], p->norm[14], p->norm[15]};
+    rc = round_sampler(ctx, p->noise, (int64_t)P * 2, batch->idx, ctx->lmap, ctx->cond, n, p->K, p->t0, p->dt, p->ddpm_coef,
+                       p->step_noise, (int64_t)p->K * P * 2, (int64_t)P * 2, an, ctx->act64, s);
+    if (rc) { ctx->policy_key = nullptr; return rc; }
+    acts = ctx->act64;
+    act_dense = 1;
+  }
+  ctx->policy_key = nullptr;                         // until the new list and its length are known
+  launch_policy_episode(sc, *batch, n, acts, act_stride, act_dense, p->step_limit, ctx->alive_cnt, s);
+  launch_compact_alive(batch->status, N, batch->idx, ctx->alive_cnt + 1, s);
+  HIP_TRY(ctx, hipGetLastError());
+  // [0] the kernel's count of the episodes still running, [1] the length of the rebuilt list: one copy, and they must agree
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->alive_cnt_host, ctx->alive_cnt, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(ctx, hipStreamSynchronize(s));
+  const int left = ctx->alive_cnt_host[0];
+  if (left < 0 || left > n || left != ctx->alive_cnt_host[1])
+    return set_err(ctx, DITREE_E_STATE, "policy_chunk: the running count (" + std::to_string(left) + ") and the running list (" +
+                   std::to_string(ctx->alive_cnt_host[1]) + ") disagree");
+  ctx->policy_key = batch->idx;
+  ctx->policy_n = left;
+  *n_active_out = left;
+  return DITREE_OK;
+}
+
 }  // extern "C"

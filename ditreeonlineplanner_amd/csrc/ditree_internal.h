@@ -93,6 +93,9 @@ struct ditree_ctx {
   int n_scenes = 0, atlas_cells = 0, max_scene_cells = 0;
   int32_t* row_scene = nullptr;
   int row_scene_cap = 0;
+  // policy roll-outs (ditree_policy_begin / _chunk): the batch whose running list is current (its idx array) and its length
+  const void* policy_key = nullptr;
+  int policy_n = 0;
   // optional RCCL communicator (ditree_comm_*): librccl opened at run time
   void* rccl_lib = nullptr;
   void* comm = nullptr;
@@ -174,6 +177,10 @@ void launch_round_chunk_end(const int32_t* chunk_status_in, int32_t* status, int
 void launch_round_pack(const ditree_tree& t, const ditree_round& r, double* rec, hipStream_t s);
 void launch_round_unpack(const ditree_tree& t, const ditree_round& r, const double* rec, hipStream_t s);
 int record_doubles(const ditree_tree& t);
+// policy_rollout_kernels.hip
+void launch_policy_begin(const SceneArg& sc, const ditree_policy_batch& b, hipStream_t s);
+void launch_policy_episode(const SceneArg& sc, const ditree_policy_batch& b, int n_run, const double* actions, int64_t act_stride,
+                           int act_dense, int step_limit, int32_t* count, hipStream_t s);
 struct AheadArg { double t[30]; };
 void launch_accept(const ditree_tree& t, const ditree_round& r, int emulate_sticky, const unsigned char* maze, int rows,
                    int cols, const AheadArg& ts, hipStream_t s);

@@ -20,8 +20,9 @@ DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data")
 
 
 def car_scenarios(csv_path=None, mazes_dir=None):
-    """-> list of dicts ``name``, ``maze_name``, ``maze`` (float64 map as np.loadtxt reads it), ``start`` (6,), ``goal`` (6,), in
-    file order.  A row whose maze file is missing is skipped, as the reference skips it."""
+    """-> list of dicts ``name``, ``maze_name``, ``maze`` (float64 map as np.loadtxt reads it), ``start`` (6,), ``goal`` (6,),
+    ``start_cell`` / ``goal_cell`` (row, col), in file order.  A row whose maze file is missing is skipped, as the reference
+    skips it."""
     from .car_env import CarEnv
     csv_path = os.path.join(DATA, "test_scenarios_car.csv") if csv_path is None else csv_path
     mazes_dir = DATA if mazes_dir is None else mazes_dir
@@ -44,7 +45,8 @@ def car_scenarios(csv_path=None, mazes_dir=None):
             goal_xy = env.cell_rowcol_to_xy(np.array([int(goal_row), int(goal_col)]))
             out.append(dict(name=name, maze_name=maze_name, maze=maze.copy(),
                             start=np.array([start_xy[0], start_xy[1], np.deg2rad(float(start_deg)), 0.0, 0.0, 0.0]),
-                            goal=np.array([goal_xy[0], goal_xy[1], 0.0, 0.0, 0.0, 0.0])))
+                            goal=np.array([goal_xy[0], goal_xy[1], 0.0, 0.0, 0.0, 0.0]),
+                            start_cell=(int(start_row), int(start_col)), goal_cell=(int(goal_row), int(goal_col))))
     return out
 
 

@@ -763,6 +763,75 @@ int32_t ditree_forest_expand_round_ant_scenes(ditree_ctx* ctx, const ditree_tree
 int32_t ditree_forest_fallback_goals_ant(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
                                          const double* goal_xy, int32_t* out_node, void* stream);
 
+/* ------------------------------------------------------------------ policy roll-outs: validation episodes as one batch
+ * The closed-loop roll-out of rollout_manager.py:545-838 (what train_diffusion_policy.py:354,481,604 runs on every row of
+ * experiments/validation_scenarios_car.csv) for the car: N = S scenes x E episodes, each car driven by the sampler alone --
+ * local map at its pose -> conditioning vector (previous action = the last executed one, none before the first step; the
+ * goal = its scene's goal) -> sampler -> up to A env steps (car_env.py:371-390) each followed by success = ||xy - goal|| < 0.5
+ * (car_env.py:341-350) and is_colliding_car (car_env.py:267-268) -- until it succeeds, collides or has run `step_limit` steps.
+ * Mazes and goals come from the scene table of ditree_upload_scenes; episode i lives in scene batch->scene[i].
+ * Departures from the reference loop, PARITY UNPINNED: (a) stable-baselines3's DummyVecEnv (not in the
+ * reference tree) re-resets a terminated env and hands observations back in its buffer dtype -- here a terminated episode is
+ * frozen, `collided` is 0 or 1 and every quantity comes from the float64 env state; (b) terminated episodes are left out of
+ * later sampler calls (the denoiser is batch-invariant: nobody else's result changes); (c) best_dist takes the success test's
+ * norm, sqrt(fma(dy, dy, dx * dx)), where rollout_manager.py:800 adds the two squares unfused.
+ * All arrays [dev], caller-owned, N rows. */
+#define DITREE_EP_RUNNING 0         /* = DITREE_ST_OK */
+#define DITREE_EP_SUCCESS 1         /* = DITREE_ST_GOAL */
+#define DITREE_EP_COLLIDED 2        /* = DITREE_ST_COLLIDED; | DITREE_ST_FLAG_GOAL_AT_COLLISION when the same step also succeeded */
+#define DITREE_EP_OUT_OF_STEPS 3    /* n_steps reached step_limit */
+typedef struct {
+  int32_t N;                     /* episodes */
+  int32_t A;                     /* action_horizon: env steps per chunk, 1 .. 64 */
+  int32_t max_steps;             /* rows per episode in `rows` */
+  const int32_t* scene;          /* (N,) the scene of every episode */
+  const int32_t* scene_host;     /* [host] (N,) the same ids: each in [0, n uploaded), validated before anything is launched */
+  double* state;                 /* (N, 6) in: start states (ditree_policy_begin does not touch them); live env state */
+  double* rows;                  /* (N, max_steps, 8): row t = [state before step t (6) | the action as sampled (2)] */
+  int32_t* n_steps;              /* (N,) env steps executed */
+  int32_t* success_step;         /* (N,) index of the first successful step, -1 = never */
+  int32_t* collided;             /* (N,) 0 / 1 */
+  int32_t* status;               /* (N,) DITREE_EP_* */
+  double* best_dist;             /* (N,) min over executed steps of the distance to the goal after the step; +inf before */
+  double* last_action;           /* (N, 2) the last executed action (as sampled) */
+  uint8_t* has_prev;             /* (N,) a step has been executed */
+  double* goal_xy;               /* (N, 2) out of ditree_policy_begin: each episode's goal = its scene's (the sampler's goal input) */
+  int32_t* idx;                  /* (N,) scratch: the running episodes, in episode order */
+} ditree_policy_batch;
+typedef struct {
+  int32_t step_limit;            /* max_episode_steps: an episode stops in the middle of a chunk when it is reached; <= max_steps */
+  const float* noise;            /* (N, P, 2) f32: the chunk's start noise for the WHOLE batch (fm_policy.py:158), or NULL with tape */
+  const double* tape;            /* (N, P, 2) f64 or NULL: the chunk's actions given from outside -- no map, conditioning, sampler */
+  int32_t P;                     /* pred_horizon >= A */
+  int32_t K;                     /* flow / DDPM steps */
+  const float* t0;               /* [host] K */
+  const float* dt;               /* [host] K */
+  const double* norm;            /* [host] 16 doubles, see ditree_cond_vector */
+  const double* axis;            /* [host] local-map axis, lm_n doubles */
+  int32_t lm_n;                  /* local_map_size */
+  double lm_size;                /* the divisor of the goal conditioning */
+  double s_global;
+  const float* ddpm_coef;        /* [host] (K, 5) or NULL, as ditree_round_params */
+  const float* step_noise;       /* (N, K, P, 2) f32 with ddpm_coef */
+} ditree_policy_params;
+/* Start a batch of episodes: n_steps = 0, success_step = -1, collided = 0, status = RUNNING, best_dist = +inf, has_prev = 0,
+ * last_action = 0, goal_xy = the scene's goal, idx = 0 .. N - 1.  The ctx remembers the batch (by its idx array) and its running
+ * count.  Validated like ditree_policy_chunk ("policy_begin: ..."); needs the scene table. */
+int32_t ditree_policy_begin(ditree_ctx* ctx, const ditree_policy_batch* batch, void* stream);
+/* One chunk of the loop (rollout_manager.py:706-807) for the running episodes: [local maps -> conditioning -> sampler (flow
+ * steps, or the DDPM loop with p->ddpm_coef) ->] up to A env steps with the bookkeeping above, then the list of the episodes
+ * still running is rebuilt; its length and the kernel's own count of running episodes are read back (one 8-byte D2H per chunk;
+ * they must agree) -> *n_active_out [host].  With p->tape the bracketed steps are skipped.  A ctx follows ONE batch at a time:
+ * a chunk on another batch than the one last begun (or chunked) is DITREE_E_STATE.  A chunk on a batch with no running episode
+ * launches nothing and returns 0.
+ * Everything is validated before anything is launched: DITREE_E_STATE "policy_chunk: no scene table uploaded" / "policy_chunk:
+ * call ditree_policy_begin on this batch first"; DITREE_E_ARG "policy_chunk: batch descriptor incomplete", "policy_chunk: need
+ * 1 <= A <= 64, A <= P and 1 <= step_limit <= max_steps", "policy_chunk: episode i has scene id k, out of range [0, n)",
+ * "policy_chunk: neither noise nor an action tape", "policy_chunk: flow schedule missing", "policy_chunk: the DDPM branch needs
+ * step_noise", "policy_chunk: ... do not match the loaded denoiser (...; the car's is action_dim 2, cond 7)". */
+int32_t ditree_policy_chunk(ditree_ctx* ctx, const ditree_policy_batch* batch, const ditree_policy_params* p,
+                            int32_t* n_active_out /*[host]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
