@@ -1144,8 +1144,10 @@ __global__ void __launch_bounds__(512, 2) conv3_halo16_kernel(ConvGemmParams p) 
 // Same tile, wave geometry, LDS image sizes, double buffers, barrier protocol and epilogue as conv3_halo16_kernel.  What
 // differs is what a 128-byte LDS row holds and how many MFMAs a K-step runs on it: a row is [32 channels of the hi plane |
 // the same 32 channels of the lo plane] (the 16-byte staging slots 0..3 come from the hi plane, 4..7 from the lo plane --
-// only the per-lane source offset knows), so fragment read "ks = 0" is the hi and "ks = 1" the lo fragment of the SAME 32
-// channels, for activations and weights alike.  One K-step (32 channels of one tap) then forms all three products
+// only the per-lane source offset knows; the weights are stored chunk-interleaved, so a weight row's eight slots are one
+// 128-byte line: ConvGemmParams::w_row / w_step / w_plane), so fragment read "ks = 0" is the hi and "ks = 1" the lo
+// fragment of the SAME 32 channels, for activations and weights alike.  One K-step (32 channels of one tap) then forms all
+// three products
 //      A_hi x W_lo,  A_hi x W_hi,  A_lo x W_hi            (A_lo x W_lo, 2^-22 of the result, is dropped)
 // = 96 MFMAs per wave on the bytes a plain K-step stages for 64: against walking the planes as three separate passes
 // (what the first version did: 14.7 k candidates/s) a third fewer barriers and LDS-DMA issues per MFMA.
@@ -1175,12 +1177,14 @@ __global__ void __launch_bounds__(512, 2) conv3_halo16x3_kernel(ConvGemmParams p
   // SPLITK (latency mode): this work-group walks chunks [v_lo, nv) of the layer's nv_all (host: splitk | nv_all, >= 2 each)
   const int v_lo = SPLITK ? (int)blockIdx.y * (nv_all / p.splitk) : 0;
   const int nv = SPLITK ? v_lo + nv_all / p.splitk : nv_all;
-  const long long K = 3LL * p.Cin;
+  // weight layout (denoise.h): bytes per row, between 32-channel chunks of a row, and from a chunk's hi to its lo half
+  const long long w_row = p.w_row;
+  const int w_step = p.w_step;
   const unsigned a_plane = (unsigned)p.a_plane, w_plane = (unsigned)p.w_plane;
 
   unsigned pa0, pa4, pa5 = 0, pb;
   const char* const a_base = (const char*)p.A + ((long long)tm * S * Lp + p.in_off) * p.lda * 2;
-  const char* const w_base = (const char*)p.W + ((long long)tn * 256) * K * 2;
+  const char* const w_base = (const char*)p.W + ((long long)tn * 256) * w_row;
   const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a_base, 0, 0x7fffffff, 0x00020000);
   const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)w_base, 0, 0x7fffffff, 0x00020000);
   {
@@ -1202,22 +1206,22 @@ __global__ void __launch_bounds__(512, 2) conv3_halo16x3_kernel(ConvGemmParams p
   {
     const int lr = lane >> 3;
     const int slot = (lane & 7) ^ lr;                                // r & 7 = lr for every piece q
-    pb = (unsigned)(((long long)(8 * lr) * K + (slot & 3) * 8) * 2) + ((slot & 4) ? w_plane : 0u);
+    pb = (unsigned)((long long)(8 * lr) * w_row + (slot & 3) * 16) + ((slot & 4) ? w_plane : 0u);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int r0 = (w * 4 + q) * 8;
       const int cu = (r0 & 128) + 8 * (r0 & 8) + ((r0 >> 4) & 7);
-      wq[q] = (long long)cu * K * 2;
+      wq[q] = (long long)cu * w_row;
     }
   }
-  const int w_tap = p.Cin * 2;
+  const int w_tap = (p.Cin >> 5) * w_step;                            // one tap = Cin / 32 chunks further
   auto issue_a = [&](int v, int i) {
     __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rsrc, (LDS_AS void*)(smem + (v & 1) * A_BUF + (w + 8 * i) * 1024), 16,
                                              i < 4 ? pa0 : (i == 4 ? pa4 : pa5), v * 64 + (i < 4 ? i * a_piece : 0), 0, 0);
   };
   auto issue_w = [&](int v, int t, int q) {
     __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, (LDS_AS void*)(smem + W_BASE + ((v + t) & 1) * W_BUF + (w * 4 + q) * 1024),
-                                             16, pb, (int)wq[q] + v * 64 + t * w_tap, 0, 0);
+                                             16, pb, (int)wq[q] + v * w_step + t * w_tap, 0, 0);
   };
 
   int lrow0;
@@ -1519,7 +1523,7 @@ __global__ void __launch_bounds__(256) conv2d_small_kernel(ConvGemmParams p) {
     a_base[q] = (const char*)p.A + (long long)b * p.c2_H * p.c2_W * p.Cin * 2;
     ih0[q] = oh * p.c2_stride - p.c2_pad;
     iw0[q] = ow * p.c2_stride - p.c2_pad;
-    w_src[q] = (const char*)p.W + ((long long)(tn * 64 + r) * K) * 2 + slot_b[q] + plane_w;
+    w_src[q] = (const char*)p.W + (long long)(tn * 64 + r) * (SPLIT ? (long long)p.w_row : K * 2) + slot_b[q] + plane_w;
   }
   auto issue = [&](int kl) {                                         // local K-step kl -> ring slot kl % 3
     const int k = k0 + kl;
@@ -1535,7 +1539,7 @@ __global__ void __launch_bounds__(256) conv2d_small_kernel(ConvGemmParams p) {
     }
 #pragma unroll
     for (int q = 0; q < 2; ++q)
-      __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)(w_src[q] + (long long)k * (CK * 2)),
+      __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)(w_src[q] + (long long)k * (SPLIT ? p.w_step : 128)),
                                        (LDS_AS void*)(st + 8192 + (2 * w + q) * 1024), 16, 0, 0);
   };
 
@@ -1631,8 +1635,11 @@ __global__ void __launch_bounds__(512, 2) gemm16_kernel(ConvGemmParams p) {
   }
   const __amdgpu_buffer_rsrc_t a_rsrc =
       __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)p.A + a_tile0), 0, 0x7fffffff, 0x00020000);
+  // weights (denoise.h): split rows are w_row bytes, their 32-channel chunks w_step apart, a chunk's lo half w_plane behind hi
+  const long long w_row = SPLIT ? (long long)p.w_row : K * 2;
+  const int w_step = SPLIT ? p.w_step : 128;
   const __amdgpu_buffer_rsrc_t w_rsrc =
-      __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)p.W + ((long long)tn * 256) * K * 2), 0, 0x7fffffff, 0x00020000);
+      __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)p.W + ((long long)tn * 256) * w_row), 0, 0x7fffffff, 0x00020000);
   unsigned pae, pao, pbe, pbo;
   int aq[4], wq[4];
   {
@@ -1644,8 +1651,8 @@ __global__ void __launch_bounds__(512, 2) gemm16_kernel(ConvGemmParams p) {
     if constexpr (SPLIT) {
       pae = (unsigned)((lro * p.lda + (slot0 & 3) * 8) * 2) + ((slot0 & 4) ? a_plane : 0u);
       pao = (unsigned)((lro * p.lda + (slot1 & 3) * 8) * 2) + ((slot1 & 4) ? a_plane : 0u);
-      pbe = (unsigned)(((long long)(8 * lr) * K + (slot0 & 3) * 8) * 2) + ((slot0 & 4) ? w_plane : 0u);
-      pbo = (unsigned)(((long long)(8 * lr) * K + (slot1 & 3) * 8) * 2) + ((slot1 & 4) ? w_plane : 0u);
+      pbe = (unsigned)((long long)(8 * lr) * w_row + (slot0 & 3) * 16) + ((slot0 & 4) ? w_plane : 0u);
+      pbo = (unsigned)((long long)(8 * lr) * w_row + (slot1 & 3) * 16) + ((slot1 & 4) ? w_plane : 0u);
     } else {
       pae = (unsigned)((lro * p.lda + slot0 * 8) * 2);
       pao = (unsigned)((lro * p.lda + slot1 * 8) * 2);
@@ -1659,7 +1666,7 @@ __global__ void __launch_bounds__(512, 2) gemm16_kernel(ConvGemmParams p) {
       const int b = m / p.L, l = m - b * p.L;
       aq[q] = (int)((((long long)b * p.in_Lp + (long long)l * p.in_stride + p.in_off) * p.lda) * 2 - a_tile0);
       const int cu = (r0 & 128) + 8 * (r0 & 8) + ((r0 >> 4) & 7);    // W: LDS row wn*128 + j*16 + r4 <- channel wn*128 + 8*r4 + j
-      wq[q] = (int)((long long)cu * K * 2);
+      wq[q] = (int)((long long)cu * w_row);
     }
   }
   const int tap_bytes = p.lda * 2;                                   // one activation row further per tap
@@ -1667,7 +1674,7 @@ __global__ void __launch_bounds__(512, 2) gemm16_kernel(ConvGemmParams p) {
   auto src_off = [&](int k, int& ao, int& wo) {
     const int t = k / nc, c = k - t * nc;
     ao = t * tap_bytes + c * KB;
-    wo = k * KB;
+    wo = k * w_step;
   };
   auto issue = [&](int kv) {                                         // K-step kv -> buffers kv & 1
     int ao, wo;

@@ -48,8 +48,9 @@ struct ConvGemmParams {
   int c2d, c2_H, c2_W, c2_OW, c2_OHW, c2_stride, c2_pad;
   signed char c2_kh[12], c2_kw[12];
   const void* zero;
-  // split formats: bytes from the hi plane to the lo plane of each operand; f16 weights are stored multiplied by a power
-  // of two (the range of f16 is narrow) and `w_scale` = its reciprocal is applied to the accumulator
+  // split formats: bytes from the hi plane to the lo plane of each operand (the weights: from an element's hi half to its lo
+  // half, see w_row / w_step below); f16 weights are stored multiplied by a power of two (the range of f16 is narrow) and
+  // `w_scale` = its reciprocal is applied to the accumulator
   long long a_plane, w_plane, out_plane, res_plane;
   float w_scale;
   // split-K (implicit Conv2d mode only): gridDim.y = splitk blocks share a tile, block y handles a
@@ -64,6 +65,11 @@ struct ConvGemmParams {
   // f16 range guard: device flag word of this layer (set to 1 by any thread that stores a value beyond +-65504; null = off).
   // Only the f16 instantiations look at it.
   int* sat;
+  // split weights, where element (row n, K index k = tap * Cin + ci) lives: n * w_row + (k >> 5) * w_step + (k & 31) * 2 bytes,
+  // its lo half w_plane bytes further.  Chunk-interleaved (the default): a 32-channel chunk is one 128-byte unit [32 hi | 32 lo],
+  // w_step = 128, w_plane = 64, w_row = 4 K.  Planar (DITREE_SPLIT_PLANAR=1): w_step = 64, w_plane = the plane distance,
+  // w_row = 2 K.  The non-split formats do not read these.
+  int w_row, w_step;
 };
 
 void denoise_set_dry_run(bool on);   // launchers check their contracts but enqueue nothing (plan validation at reserve time)

@@ -143,8 +143,11 @@ float* DenoiserState::vec(const std::string& name) {
 }
 
 // Pack a GEMM weight [Npad][T*Cin_pad] in format `fmt` from get(n, t, ci): f32, or 16-bit elements -- for a split
-// format two planes hi = rnd16(w) and lo = rnd16(w - hi).  f16 has a narrow range: the matrix is stored multiplied by a
-// power of two that puts its largest magnitude in [2^13, 2^14); the kernels multiply the accumulator by 1 / that.
+// format hi = rnd16(w) and lo = rnd16(w - hi), chunk-interleaved: the 32 channels of a K-step are one 128-byte unit
+// [32 hi | 32 lo], so that the tile kernels stage an LDS row from ONE 128-byte line (rows of 4 K bytes); with
+// `split_planar` as two planes [Npad][K] (rows of 2 K bytes), the A/B arm of that layout.  f16 has a narrow range: the
+// matrix is stored multiplied by a power of two that puts its largest magnitude in [2^13, 2^14); the kernels multiply the
+// accumulator by 1 / that.
 template <class F>
 Packed DenoiserState::pack(const std::string& key, int fmt, int N, int T, int Cin_pad, F get) {
   auto it = dev_w.find(key);
@@ -153,6 +156,11 @@ Packed DenoiserState::pack(const std::string& key, int fmt, int N, int T, int Ci
   const size_t K = (size_t)T * Cin_pad, total = (size_t)Npad * K;
   const int st = fmt_st(fmt), e = fmt_es(fmt), npl = fmt_split(fmt) ? 2 : 1;
   std::vector<uint8_t> host(total * e * npl, 0);
+  const bool inter = npl == 2 && !split_planar;
+  const size_t row_bytes = K * e * (inter ? 2 : 1), lo_off = inter ? 64 : total * e;
+  // the tile kernels reach a tile's 256 rows, and a lo half, through 32-bit buffer offsets from the tile's first row
+  if (npl == 2 && ((K & 31) != 0 || 256 * row_bytes + lo_off >= 0x7f000000ull))
+    throw std::runtime_error("split weight " + key + ": K must be a multiple of 32 and a 256-row tile span less than 2 GiB");
   const int nthreads = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
   float mul = 1.0f;
   if (st == ST_F16) {
@@ -183,14 +191,15 @@ Packed DenoiserState::pack(const std::string& key, int fmt, int N, int T, int Ci
             const float v = get(n, t, ci) * mul;
             const size_t idx = (size_t)n * K + (size_t)t * Cin_pad + ci;
             if (st == ST_F32) { ((float*)host.data())[idx] = v; continue; }
-            uint16_t* hi = (uint16_t*)host.data();
-            uint16_t* lo = hi + total;
+            const size_t k = (size_t)t * Cin_pad + ci;
+            uint16_t* hi = (uint16_t*)(host.data() + (inter ? (size_t)n * row_bytes + (k >> 5) * 128 + (k & 31) * 2 : idx * 2));
+            uint16_t* lo = (uint16_t*)((uint8_t*)hi + lo_off);
             if (st == ST_BF16) {
-              hi[idx] = f2bf_host(v);
-              if (npl == 2) lo[idx] = f2bf_host(v - bf2f_host(hi[idx]));
+              *hi = f2bf_host(v);
+              if (npl == 2) *lo = f2bf_host(v - bf2f_host(*hi));
             } else {
-              hi[idx] = f2h_host(v);
-              if (npl == 2) lo[idx] = f2h_host(v - h2f_host(hi[idx]));
+              *hi = f2h_host(v);
+              if (npl == 2) *lo = f2h_host(v - h2f_host(*hi));
             }
           }
       }
@@ -199,7 +208,9 @@ Packed DenoiserState::pack(const std::string& key, int fmt, int N, int T, int Ci
   for (auto& t : th) t.join();
   Packed pk;
   pk.p = dalloc(total * e * npl, false);
-  pk.plane = npl == 2 ? (long long)(total * e) : 0;
+  pk.plane = npl == 2 ? (long long)lo_off : 0;
+  pk.row_bytes = (int)row_bytes;
+  pk.chunk_step = inter ? 128 : 64;
   pk.scale = 1.0f / mul;
   if (hipMemcpy(pk.p, host.data(), total * e * npl, hipMemcpyHostToDevice) != hipSuccess) throw std::runtime_error("memcpy");
   dev_w[key] = pk;
@@ -228,7 +239,7 @@ ConvGemmParams DenoiserState::gemm_params(const Act& in, const Act& out, const P
                                           int in_off, int out_stride, int out_off, int L, const float* bias, int* sat) {
   ConvGemmParams p{};
   p.A = aptr(in); p.lda = in.ld; p.in_Lp = in.Lp(); p.in_stride = in_stride; p.in_off = in_off; p.taps = taps; p.Cin = Cin;
-  p.W = wp.p; p.w_plane = wp.plane; p.w_scale = wp.scale;
+  p.W = wp.p; p.w_plane = wp.plane; p.w_row = wp.row_bytes; p.w_step = wp.chunk_step; p.w_scale = wp.scale;
   p.a_plane = in.plane; p.out_plane = out.plane;
   p.sat = sat;
   p.Out = (void*)aptr(out); p.ldc = out.ld; p.out_Lp = out.Lp(); p.out_stride = out_stride; p.out_off = out_off;
@@ -356,6 +367,10 @@ void DenoiserState::add_crb(const std::string& pre, const Act& in, const Act& ou
 void DenoiserState::build(int prec_, int Bmax_) {
   free_workspace();
   prec = prec_;
+  {
+    const char* e = getenv("DITREE_SPLIT_PLANAR");          // A/B switch of the split weight layout
+    split_planar = e != nullptr && atoi(e) != 0;
+  }
   // DITREE_PREC_*  ->  formats of the U-Net and of the encoder (the split instantiations run the encoder split as well: its
   // stem is the fused kernel for both map sizes, 20 x 20 and 16 x 16).
   switch (prec) {

@@ -29,7 +29,9 @@ struct Act {             // channels-last activation view
 
 struct Packed {          // a GEMM weight in the MFMA layout
   void* p = nullptr;
-  long long plane = 0;   // split formats: bytes to the lo plane
+  long long plane = 0;   // split formats: bytes from an element's hi half to its lo half
+  int row_bytes = 0;     // split formats: bytes per weight row, and between the 32-channel chunks of a row
+  int chunk_step = 0;    //   (ConvGemmParams::w_row / w_step: chunk-interleaved or planar)
   float scale = 1.0f;    // f16: the stored values are w / scale (scale a power of two)
 };
 
@@ -60,6 +62,7 @@ struct DenoiserState {
   int Buser = 0;               // samples the caller reserved for: calls up to this size are served in sub-batches of <= Bmax
   int bgran = 16;              // batch rows are padded to a multiple of this
   int ufmt = 0, efmt = 0;      // formats (denoise.h) of the U-Net activations / GEMMs and of the encoder
+  bool split_planar = false;   // DITREE_SPLIT_PLANAR=1 (read by build): split weights as two planes instead of chunk-interleaved
   std::vector<void*> allocs;
   std::map<std::string, Act> named;
   std::map<std::string, Packed> dev_w;      // packed GEMM weights by name
