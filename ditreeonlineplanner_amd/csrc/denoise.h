@@ -78,11 +78,12 @@ void launch_conv_gemm(const ConvGemmParams& p, int fmt, hipStream_t s);
 bool conv2d_small_eligible(int fmt);                    // implicit Conv2d layers run on the 64 x 64-tile kernel
 int conv_gemm_kind(const ConvGemmParams& p, int fmt);   // 0 halo kernel, 1 gemm16 / generic, 2 implicit Conv2d
 bool conv_gemm_supported(const ConvGemmParams& p, int fmt);   // split formats: only shapes of the halo / gemm16 tiles
-void launch_prep_sample(const float* x, void* A0, int B, int P, int D, int fmt, long long plane, hipStream_t s, int* sat = nullptr);
+// (prep_sample / prep_cond: rows B .. Bp-1, the padding up to the batch granule, are written as zeros)
+void launch_prep_sample(const float* x, void* A0, int B, int Bp, int P, int D, int fmt, long long plane, hipStream_t s, int* sat = nullptr);
 void launch_time_embed(float t, const float* W1, const float* b1, const float* W2, const float* b2, float* out,
                        hipStream_t s);
 void launch_prep_cond(const float* temb, const float* map_emb, int E, int E_ld, const float* cond, int G, void* out, int B,
-                      int Kpad, int fmt, long long plane, hipStream_t s, int* sat = nullptr);
+                      int Bp, int Kpad, int fmt, long long plane, hipStream_t s, int* sat = nullptr);
 // What the last projection does with the network output v of a sampler step:
 //   FLOW  x += v * dt                     (policies/fm_policy.py:183-196)
 //   RAW   x  = v                          (one raw network evaluation)

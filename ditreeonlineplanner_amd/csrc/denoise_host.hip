@@ -177,11 +177,11 @@ static int denoise_core_one(ditree_ctx* ctx, const float* noise, int64_t noise_s
       st->temb_t = K == 1 ? t : -1.0f;                                  // several steps share one buffer: recompute
     }
     st->prof.note_other();
-    launch_prep_cond(st->temb, st->map_emb, st->E, st->E_ld, cond, st->G, st->condA, B, st->condK, uf, st->cond_plane, s,
+    launch_prep_cond(st->temb, st->map_emb, st->E, st->E_ld, cond, st->G, st->condA, B, Bp, st->condK, uf, st->cond_plane, s,
                      st->sat_cond);
     st->film_op(B, Bp, s);
     st->prof.note_other();
-    launch_prep_sample(st->x_cur, st->named["a0"].p, Bp, st->P, st->D, uf, st->named["a0"].plane, s,
+    launch_prep_sample(st->x_cur, st->named["a0"].p, B, Bp, st->P, st->D, uf, st->named["a0"].plane, s,
                        st->sat_sample);
     for (auto& op : st->unet_ops) op(B, Bp, s);
     const bool last = (k == K - 1);

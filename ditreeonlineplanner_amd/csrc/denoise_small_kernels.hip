@@ -257,7 +257,10 @@ __global__ void __launch_bounds__(256) encoder_stem_kernel(const float* __restri
     float y = fmaf(v[j], ga, be);
     y = y > 0.f ? y : 0.f;
     if constexpr (PREC == ST_BF16) y = bf2f(f2bf(y));      // the activation is stored as bf16 before the pool in the layered path
-    if constexpr (PREC == ST_F16) y = h2f(f2h(y));         // (the split formats keep the f32 value: hi + lo carries it)
+    if constexpr (PREC == ST_F16) {                        // (the split formats keep the f32 value: hi + lo carries it)
+      sat_see(satm, y);                                    // the range guard looks HERE: f2h clamps, the pool sees no more than 65504
+      y = h2f(f2h(y));
+    }
     s_act[(q + 4 * j) * 64 + c] = y;
   }
   __syncthreads();
@@ -288,14 +291,15 @@ void launch_encoder_stem(const float* lm, int n, const float* W, const float* ga
 }
 
 template <int PREC>
-__global__ void prep_sample_kernel(const float* __restrict__ x, void* __restrict__ A0, int B, int P, int D, long long plane,
+__global__ void prep_sample_kernel(const float* __restrict__ x, void* __restrict__ A0, int B, int Bp, int P, int D, long long plane,
                                    int* __restrict__ sat) {
   const long long row = blockIdx.x * (long long)(blockDim.x >> 6) + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
-  if (row >= (long long)B * P) return;
+  if (row >= (long long)Bp * P) return;
   const int b = (int)(row / P), l = (int)(row - (long long)b * P);
   float v = 0.f;
-  if (lane < 3 * D) {
+  // rows B .. Bp-1 pad the batch to whole work units: zeros, not what an earlier call left in x (the guard would see it)
+  if (b < B && lane < 3 * D) {
     const int t = lane / D, d = lane - t * D;
     const int ls = l + t - 1;
     if (ls >= 0 && ls < P) v = x[((long long)b * P + ls) * D + d];
@@ -304,10 +308,10 @@ __global__ void prep_sample_kernel(const float* __restrict__ x, void* __restrict
   store_elem<PREC>(A0, row * 64 + lane, v, plane, satm);
   if constexpr ((PREC & 3) == ST_F16) sat_flush(sat, satm);
 }
-void launch_prep_sample(const float* x, void* A0, int B, int P, int D, int fmt, long long plane, hipStream_t s, int* sat) {
-  long long rows = (long long)B * P;
+void launch_prep_sample(const float* x, void* A0, int B, int Bp, int P, int D, int fmt, long long plane, hipStream_t s, int* sat) {
+  long long rows = (long long)Bp * P;
   dim3 grid((unsigned)((rows + 3) / 4)), block(256);
-#define CALL(F) DN_LAUNCH(prep_sample_kernel<F>, grid, block, 0, s, x, A0, B, P, D, plane, sat)
+#define CALL(F) DN_LAUNCH(prep_sample_kernel<F>, grid, block, 0, s, x, A0, B, Bp, P, D, plane, sat)
   DISPATCH_FMT(fmt, CALL)
 #undef CALL
 }
@@ -359,7 +363,8 @@ __global__ void prep_cond_kernel(const float* __restrict__ temb, const float* __
   for (int k = threadIdx.x; k < Kpad; k += blockDim.x) {
     float v = 0.f;
     bool live = true;
-    if (k < 256) v = temb[k];
+    if (b >= B) live = false;          // blocks B .. Bp-1 pad the batch to whole work units: zeros, not an earlier call's rows
+    else if (k < 256) v = temb[k];
     else if (k < 256 + E) v = map_emb[(long long)b * E_ld + (k - 256)];
     else if (k < 256 + E + G) v = cond[(long long)b * G + (k - 256 - E)];
     else live = false;
@@ -368,8 +373,8 @@ __global__ void prep_cond_kernel(const float* __restrict__ temb, const float* __
   if constexpr ((PREC & 3) == ST_F16) sat_flush(sat, satm);
 }
 void launch_prep_cond(const float* temb, const float* map_emb, int E, int E_ld, const float* cond, int G, void* out, int B,
-                      int Kpad, int fmt, long long plane, hipStream_t s, int* sat) {
-#define CALL(F) DN_LAUNCH(prep_cond_kernel<F>, dim3(B), dim3(256), 0, s, temb, map_emb, E, E_ld, cond, G, out, B, Kpad, plane, sat)
+                      int Bp, int Kpad, int fmt, long long plane, hipStream_t s, int* sat) {
+#define CALL(F) DN_LAUNCH(prep_cond_kernel<F>, dim3(Bp), dim3(256), 0, s, temb, map_emb, E, E_ld, cond, G, out, B, Kpad, plane, sat)
   DISPATCH_FMT(fmt, CALL)
 #undef CALL
 }

@@ -366,6 +366,9 @@ def _ctx_check_range(self):
 
 
 def _ctx_raise_range_error(self, layers):
+    # the library lists the U-Net's layers before the encoder's; the encoder runs first, and the message (which names six layers)
+    # must show the layer that left the range, not the ones its clamped output saturated afterwards
+    layers = [n for n in layers if n.startswith("encoder.")] + [n for n in layers if not n.startswith("encoder.")]
     if True:
         raise _lib.DitreeError(
             "f16 range guard: activations beyond +-65504 were clamped in " + ", ".join(layers[:6]) +
