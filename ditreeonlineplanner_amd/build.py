@@ -32,7 +32,6 @@ UNITS = [
     ("mppi_mission_kernels.hip", ["-ffp-contract=off"]),
     ("ant_kernels.hip", ["-ffp-contract=off"]),
     ("ant_scene_kernels.hip", ["-ffp-contract=off"]),
-    ("mppi_ant_kernels.hip", ["-ffp-contract=off"]),
     ("policy_rollout_kernels.hip", ["-ffp-contract=off"]),
     ("ditree_api.hip", []),
     ("conv_tiles.hip", []),

@@ -66,6 +66,19 @@ static int run_ready_pool(ditree_ctx* ctx, const char* who, const ditree_round* 
   return DITREE_OK;
 }
 
+// checked copy of the caller's ant model into the kernels' argument block (also mppi_kernels.hip)
+int fill_ant_model(ditree_ctx* ctx, const ditree_ant_model* m, AntModelArg* a) {
+  if (!(m->h > 0.0) || !(m->frame_skip >= 1.0) || m->frame_skip > 64.0 || m->frame_skip != (double)(int)m->frame_skip)
+    return set_err(ctx, DITREE_E_ARG, "ant model: need h > 0 and an integral frame_skip in 1..64");
+  a->h = m->h; a->frame_skip = (int)m->frame_skip;
+  a->k_act = m->k_act; a->k_spr = m->k_spr; a->k_dmp = m->k_dmp; a->k_lim = m->k_lim; a->hip_lim = m->hip_lim;
+  a->ank_lo = m->ank_lo; a->ank_hi = m->ank_hi; a->ank_rest = m->ank_rest; a->contact_gain = m->contact_gain;
+  a->leg_r = m->leg_r; a->k_push = m->k_push; a->c_lin = m->c_lin; a->z0 = m->z0; a->z_gain = m->z_gain; a->k_z = m->k_z;
+  a->c_z = m->c_z; a->k_lift = m->k_lift; a->c_ang = m->c_ang; a->k_up = m->k_up; a->k_yaw = m->k_yaw; a->cphi = m->cphi;
+  a->sphi = m->sphi;
+  return DITREE_OK;
+}
+
 extern "C" {
 
 int32_t ditree_version(void) { return DITREE_VERSION; }
@@ -108,7 +121,6 @@ void ditree_ctx_destroy(ditree_ctx* ctx) {
   if (ctx->alive_cnt_host) hipHostFree(ctx->alive_cnt_host);
   if (ctx->path_dev) hipFree(ctx->path_dev);
   if (ctx->mppi_partial) hipFree(ctx->mppi_partial);
-  if (ctx->mppi_ant_partial) hipFree(ctx->mppi_ant_partial);
   if (ctx->mppi_minkey) hipFree(ctx->mppi_minkey);
   if (ctx->scene_tab) hipFree(ctx->scene_tab);
   if (ctx->row_scene) hipFree(ctx->row_scene);
@@ -275,18 +287,6 @@ int32_t ditree_ant_collision(ditree_ctx* ctx, const double* state, int32_t strid
     return set_err(ctx, DITREE_E_ARG, "ant_collision: bad argument (stride >= 7, s_global > 0)");
   launch_ant_collision(ctx->maze, ctx->rows, ctx->cols, state, stride, B, ball_radius, s_global, out, (hipStream_t)stream);
   HIP_TRY(ctx, hipGetLastError());
-  return DITREE_OK;
-}
-
-static int fill_ant_model(ditree_ctx* ctx, const ditree_ant_model* m, AntModelArg* a) {
-  if (!(m->h > 0.0) || !(m->frame_skip >= 1.0) || m->frame_skip > 64.0 || m->frame_skip != (double)(int)m->frame_skip)
-    return set_err(ctx, DITREE_E_ARG, "ant model: need h > 0 and an integral frame_skip in 1..64");
-  a->h = m->h; a->frame_skip = (int)m->frame_skip;
-  a->k_act = m->k_act; a->k_spr = m->k_spr; a->k_dmp = m->k_dmp; a->k_lim = m->k_lim; a->hip_lim = m->hip_lim;
-  a->ank_lo = m->ank_lo; a->ank_hi = m->ank_hi; a->ank_rest = m->ank_rest; a->contact_gain = m->contact_gain;
-  a->leg_r = m->leg_r; a->k_push = m->k_push; a->c_lin = m->c_lin; a->z0 = m->z0; a->z_gain = m->z_gain; a->k_z = m->k_z;
-  a->c_z = m->c_z; a->k_lift = m->k_lift; a->c_ang = m->c_ang; a->k_up = m->k_up; a->k_yaw = m->k_yaw; a->cphi = m->cphi;
-  a->sphi = m->sphi;
   return DITREE_OK;
 }
 

@@ -84,8 +84,7 @@ struct ditree_ctx {
   float* ant_lmap = nullptr;
   double* ant_act = nullptr;
   int ant_P = 0, ant_lm = 0;
-  double* mppi_partial = nullptr;   // partial sums of the MPPI update (ditree_mppi_step)
-  double* mppi_ant_partial = nullptr;   // the same for ditree_mppi_step_ant (3 + 8 T per slice)
+  double* mppi_partial = nullptr;   // partial sums of the MPPI update, sized for the ant (256 slices of 3 + 8 * 64 doubles)
   unsigned long long* mppi_minkey = nullptr;   // running minimum of the rollout costs (order-preserving integer image)
   DenoiserState* dn = nullptr;
   // scene table (ditree_upload_scenes): atlas of u8 cell codes, (n_scenes,) records, and a (row_scene_cap,) row -> scene scratch
@@ -138,6 +137,7 @@ void launch_path_after_obstacle(const float* path, int stride, int P, double cx,
                                 int rows, int cols, int32_t* out, hipStream_t s);
 // ant_kernels.hip
 struct AntModelArg;
+int fill_ant_model(ditree_ctx* ctx, const ditree_ant_model* m, AntModelArg* a);      // ditree_api.hip: checked copy
 struct AntChunkStrides { int64_t states, actions_out, actions_in, tape; };
 void launch_ant_collision(const unsigned char* maze, int rows, int cols, const double* state, int stride, int B, double ball_radius,
                           double s_global, uint8_t* out, hipStream_t s);

@@ -6,29 +6,21 @@
 //
 // Compiled with -ffp-contract=off like mppi_kernels.hip and geom_kernels.hip.  BIT-EXACTNESS IS THE CONTRACT: a mission equals
 // the same number of ditree_mppi_step / lidar scan / ditree_upload_maze calls bit for bit (tests/test_gpu_mppi_mission.py holds
-// it to np.array_equal).  K <= 256 is the stepwise controller's one-slice case, and every sum below takes that case's order:
-//   rollouts   thread k runs rollout k with the G = 1 body of mppi_rollout_kernel (block-cooperative nearest index i0 with ties
-//              to the lowest index, car_collides, nearest_in_window<1>, the cost expression term by term);
-//   beta       an exact minimum (order-independent);
-//   sums       mppi_partial_kernel for lo = 0: the 64-lane butterfly v += shfl_xor(v, o), o = 32 .. 1, lane 0 adding into its
-//              wave's (zeroed) row, (r0 + r1) + (r2 + r3), then mppi_finish_kernel's acc = 0.0; acc += partial[0];
-//   noise      regenerated per (k, t) with mppi_noise (mppi_device.h);
-//   execute    mppi_finish_kernel's clip, collision restart and shift with the last control held;
-//   scan       follow_plan_kernel's scan block (lidar_ray of lidar_device.h, end cells -> known / scanned, visited = 2).
+// it to np.array_equal).  K <= 256 is the stepwise controller's one-slice case, and a controller step below is the calls the
+// stepwise kernels make into mppi_device.h, in their order, with thread k on rollout k, one lane per rollout, a one-slice
+// `partial` in LDS and k0 = 0; beta is an exact minimum (order-independent).  The scan is follow_plan_kernel's scan block
+// (lidar_ray of lidar_device.h, end cells -> known / scanned, visited = 2).
 // Every loop bound and every branch that contains a barrier is uniform over the work-group (flags in LDS, as
 // follow_plan_kernel); the step count of a launch is bounded on the host (DITREE_MPPI_MISSION_MAX_STEPS).
-#include "car_device.h"
 #include "ditree_internal.h"
 #include "lidar_device.h"
 #include "mppi_device.h"
 
 namespace {
 
-constexpr int MISSION_MAX_T = 64;
 constexpr int MISSION_MAX_K = 256;
-constexpr int MISSION_MAX_P = 4096;
 constexpr int MISSION_MAX_CELLS = 13104;                 // five byte maps of 13 104 cells = 64 KB, as follow_plan_kernel
-constexpr int MISSION_NACC = 3 + 2 * MISSION_MAX_T;
+constexpr int MISSION_NACC = 3 + 2 * MPPI_MAX_T;
 
 struct MissionArgs {
   const unsigned long long* seed;      // (M)
@@ -55,13 +47,7 @@ struct MissionArgs {
   int rows, cols, P_max, trace_steps, refresh_mission;
 };
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-__global__ void __launch_bounds__(256) mppi_mission_kernel(MissionArgs g, MppiArgs a) {
+__global__ void __launch_bounds__(256) mppi_mission_kernel(MissionArgs g, MppiArgs a, CarTail cm) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   const int m = blockIdx.x, tid = threadIdx.x;
   const int rows = g.rows, cols = g.cols, ncell = rows * cols, pad = (ncell + 15) & ~15;
@@ -76,9 +62,11 @@ __global__ void __launch_bounds__(256) mppi_mission_kernel(MissionArgs g, MppiAr
   __shared__ double s_amin[4];                                           // block argmin of i0: distance, index per wave
   __shared__ int s_aidx[4];
   __shared__ double s_wmin[4];                                           // per-wave minimum of the costs
-  __shared__ double s_rows[4][MISSION_NACC];                             // per-wave sums (mppi_partial_kernel's red rows)
+  __shared__ double s_rows[4][MISSION_NACC];                             // per-wave rows of the sums
+  __shared__ double s_partial[MISSION_NACC];                             // the one slice
   __shared__ double s_sums[MISSION_NACC];                                // eta, sum w^2, collided rollouts, sum_k w_k eps[k, t, d]
-  __shared__ double s_last[5];                                           // beta, eta, i0, collided rollouts, effective samples
+  __shared__ double s_res[8];                                            // the last step's result [3..8): beta, eta, i0, collided
+                                                                         // rollouts, effective samples
   __shared__ int sh_scan, sh_stop;
 
   a.P = g.path_len[m];
@@ -111,7 +99,7 @@ __global__ void __launch_bounds__(256) mppi_mission_kernel(MissionArgs g, MppiAr
     dirty[i] = 0;
   }
   if (tid < 6) s_x[tid] = g.state_io[(size_t)m * 6 + tid];
-  if (tid < 5) s_last[tid] = 0.0;
+  if (tid < 8) s_res[tid] = 0.0;
   if (tid == 0) { sh_scan = 0; sh_stop = 0; }
   __syncthreads();
 
@@ -135,112 +123,44 @@ __global__ void __launch_bounds__(256) mppi_mission_kernel(MissionArgs g, MppiAr
     double x0[6];
 #pragma unroll
     for (int j = 0; j < 6; ++j) x0[j] = s_x[j];
-    // ---- rollouts (mppi_rollout_kernel<1>): i0 = nearest path point of the state over the whole path
-    int i0;
-    {
-      double best = __builtin_huge_val();
-      int bi = 0x7fffffff;
-      for (int i = tid; i < a.P; i += 256) {
-        const double dx = s_path[i].x - x0[0], dy = s_path[i].y - x0[1];
-        const double d = dx * dx + dy * dy;
-        if (d < best) { best = d; bi = i; }
-      }
-#pragma unroll
-      for (int o = 32; o >= 1; o >>= 1) {
-        const double ob = __shfl_xor(best, o);
-        const int oi = __shfl_xor(bi, o);
-        if (ob < best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-      }
-      if (lane0) { s_amin[wv] = best; s_aidx[wv] = bi; }
-      __syncthreads();
-      best = s_amin[0]; bi = s_aidx[0];
-      for (int w = 1; w < 4; ++w)
-        if (s_amin[w] < best || (s_amin[w] == best && s_aidx[w] < bi)) { best = s_amin[w]; bi = s_aidx[w]; }
-      i0 = bi;
-    }
+    // ---- rollouts: thread k runs rollout k against the KNOWN maze
+    const int i0 = block_nearest_index(s_path, a.P, x0[0], x0[1], 256, s_amin, s_aidx);
     const int k = tid;
     const bool live = k < a.K;
-    double s[6];
-#pragma unroll
-    for (int j = 0; j < 6; ++j) s[j] = x0[j];
-    double cost = 0.0;
-    int ip = i0;
-    int flag = 0;                                        // 1 = reached the goal, 2 = collided
-    for (int t = 0; live && t < a.T; ++t) {
-      double e0 = 0.0, e1 = 0.0;
-      if (k > 0) mppi_noise(a.seed, a.counter, k, t, a.s0, a.s1, e0, e1);        // rollout 0 is the noise-free nominal sequence
-      const double u0 = s_U[2 * t], u1 = s_U[2 * t + 1];
-      car_euler_step(s, u0 + e0, u1 + e1);
-      const bool coll = car_collides(s[0], s[1], s[2], kn, rows, cols);
-      const double ex = s[0] - a.gx, ey = s[1] - a.gy;
-      const bool reached = sqrt(fma(ey, ey, ex * ex)) < 0.5;
-      const int lo = max(ip - a.wback, 0), hi = min(ip + a.wfwd, a.P - 1);
-      double d2;
-      nearest_in_window<1>(s_path, lo, hi, s[0], s[1], 0, ip, d2);
-      cost = cost + a.w_track * d2;
-      cost = cost + a.lambda * ((u0 * e0) / (a.s0 * a.s0) + (u1 * e1) / (a.s1 * a.s1));
-      if (coll) { cost = cost + a.w_collision; flag = 2; break; }
-      if (reached) { cost = cost - a.w_goal; flag = 1; break; }
-    }
-    cost = cost + a.w_progress * (double)(a.P - 1 - ip);
+    double cost;
+    int flag;
+    car_rollout<1>(a, cm, s_path, s_U, kn, rows, cols, x0, i0, nullptr, k, 0, live, cost, flag);
     // ---- beta = min_k S_k
-    double mn = live ? cost : __builtin_huge_val();
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) mn = fmin(mn, __shfl_xor(mn, o));
+    const double mn = wave_min(live ? cost : __builtin_huge_val());
     if (lane0) s_wmin[wv] = mn;
     __syncthreads();
     const double beta = fmin(fmin(s_wmin[0], s_wmin[1]), fmin(s_wmin[2], s_wmin[3]));
-    // ---- weights and sums (mppi_partial_kernel, one slice, lo = 0; mppi_finish_kernel's ordered sum of that one slice)
-    const double w = live ? exp(-(cost - beta) / a.lambda) : 0.0;
-    {
-      const double sw = wave_sum(w), sw2 = wave_sum(w * w);
-      const double scn = wave_sum((live && flag == 2) ? 1.0 : 0.0);
-      if (lane0) {
-        double r0 = 0.0, r1 = 0.0, r2 = 0.0;
-        r0 += sw; r1 += sw2; r2 += scn;
-        s_rows[wv][0] = r0; s_rows[wv][1] = r1; s_rows[wv][2] = r2;
-      }
-    }
+    // ---- weights and sums: one trip of one slice per step t, the wave's row in registers until lane 0 stores it
+    const double w = live ? mppi_weight(cost, beta, a.lambda) : 0.0;
     for (int t = 0; t < a.T; ++t) {
-      double e0 = 0.0, e1 = 0.0;
-      if (live && k > 0) mppi_noise(a.seed, a.counter, k, t, a.s0, a.s1, e0, e1);
-      const double v0 = wave_sum(w * e0), v1 = wave_sum(w * e1);
+      double row[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+      if (t == 0) mppi_accumulate_scalars(w, live && flag == 2, row);
+      double e[2] = {0.0, 0.0};
+      if (live && k > 0) CarModel::noise(a, cm, k, t, e);
+      mppi_accumulate_noise<2>(w, e, row);
       if (lane0) {
-        double r3 = 0.0, r4 = 0.0;
-        r3 += v0; r4 += v1;
-        s_rows[wv][3 + 2 * t] = r3; s_rows[wv][4 + 2 * t] = r4;
+        if (t == 0) { s_rows[wv][0] = row[0]; s_rows[wv][1] = row[1]; s_rows[wv][2] = row[2]; }
+        s_rows[wv][3 + 2 * t] = row[3]; s_rows[wv][4 + 2 * t] = row[4];
       }
     }
     __syncthreads();
-    if (tid < nacc) {
-      const double partial = (s_rows[0][tid] + s_rows[1][tid]) + (s_rows[2][tid] + s_rows[3][tid]);
-      double acc = 0.0;
-      acc += partial;
-      s_sums[tid] = acc;
-    }
+    if (tid < nacc) s_partial[tid] = mppi_row_tree(&s_rows[0][0], MISSION_NACC, tid);
     __syncthreads();
-    // ---- apply (mppi_finish_kernel): U += sums[3..] / eta
-    const double eta = s_sums[0];
-    if (tid < 2 * a.T) s_U[tid] = s_U[tid] + s_sums[3 + tid] / eta;
-    __syncthreads();
+    mppi_sum_slices(s_partial, 1, nacc, s_sums);
+    if (tid == 0) { s_res[3] = beta; s_res[5] = (double)i0; }
+    mppi_apply(s_sums, 2 * a.T, s_U, s_res);
     // ---- execute: one env step with the first control against the KNOWN maze, then the driver's books
     if (tid == 0) {
-      s_last[0] = beta;
-      s_last[1] = eta;
-      s_last[2] = (double)i0;
-      s_last[3] = s_sums[2];
-      s_last[4] = (eta * eta) / s_sums[1];
       ++calls;
-      double st[6];
-      for (int j = 0; j < 6; ++j) st[j] = s_x[j];
-      const double a0 = fmin(fmax(s_U[0], -10.0), 10.0), a1 = fmin(fmax(s_U[1], -2.0), 2.0);
-      car_euler_step(st, a0, a1);
-      const double ex = st[0] - a.gx, ey = st[1] - a.gy;
-      const bool reached = sqrt(fma(ey, ey, ex * ex)) < 0.5;
-      const bool coll = car_collides(st[0], st[1], st[2], kn, rows, cols);
+      double act[2], st[6];
+      const int status = mppi_execute<CarModel>(a, cm, kn, rows, cols, s_x, st, s_U, act);
       int scan = 0, stop = 0;
-      if (coll) {                                        // the state stays; the nominal sequence restarts from rest
-        for (int j = 0; j < 2 * a.T; ++j) s_U[j] = 0.0;
+      if (status == 2) {
         ++trials;
         if (trials >= allowed) { event = DITREE_MEV_TRIALS; stop = 1; }
       } else {
@@ -248,12 +168,11 @@ __global__ void __launch_bounds__(256) mppi_mission_kernel(MissionArgs g, MppiAr
         double* eo = g.ex_states + ((size_t)m * g.trace_steps + n_exec) * 6;
         double* ao = g.ex_actions + ((size_t)m * g.trace_steps + n_exec) * 2;
         for (int j = 0; j < 6; ++j) { s_x[j] = st[j]; eo[j] = st[j]; }
-        ao[0] = a0; ao[1] = a1;
+        ao[0] = act[0]; ao[1] = act[1];
         ++n_exec;
-        for (int t = 0; t + 1 < a.T; ++t) { s_U[2 * t] = s_U[2 * t + 2]; s_U[2 * t + 1] = s_U[2 * t + 3]; }   // last control held
         t_acc += dt;
         if (t_acc > scan_time) { scan = 1; t_acc = 0.0; ++n_scans; }
-        if (reached) { event = DITREE_MEV_GOAL; stop = 1; }      // after the scan: the driver's loop body ends before is_done
+        if (status == 1) { event = DITREE_MEV_GOAL; stop = 1; }      // after the scan: the driver's loop body ends before is_done
       }
       sh_scan = scan;
       sh_stop = stop;
@@ -301,7 +220,7 @@ __global__ void __launch_bounds__(256) mppi_mission_kernel(MissionArgs g, MppiAr
     res[1] = (double)calls;
     res[2] = (double)n_exec;
     res[3] = (double)n_scans;
-    for (int j = 0; j < 5; ++j) res[4 + j] = s_last[j];
+    for (int j = 0; j < 5; ++j) res[4 + j] = s_res[3 + j];
     for (int j = 9; j < DITREE_MPPI_MISSION_RESULT; ++j) res[j] = 0.0;
   }
 }
@@ -325,8 +244,8 @@ extern "C" int32_t ditree_mppi_missions(ditree_ctx* ctx, const ditree_mppi_param
   if (p->K < 1 || p->K > MISSION_MAX_K)
     return set_err(ctx, DITREE_E_ARG, "mppi_missions: 1 <= K <= 256 (one rollout per thread of the mission's work-group; larger "
                                       "controllers keep ditree_mppi_step)");
-  if (p->T < 1 || p->T > MISSION_MAX_T) return set_err(ctx, DITREE_E_ARG, "mppi_missions: 1 <= T <= 64");
-  if (P_max < 1 || P_max > MISSION_MAX_P)
+  if (p->T < 1 || p->T > MPPI_MAX_T) return set_err(ctx, DITREE_E_ARG, "mppi_missions: 1 <= T <= 64");
+  if (P_max < 1 || P_max > MPPI_MAX_P)
     return set_err(ctx, DITREE_E_ARG, "mppi_missions: 1 <= P <= 4096 (the reference path is staged in LDS)");
   if (rows < 1 || cols < 1 || (int64_t)rows * cols > MISSION_MAX_CELLS)
     return set_err(ctx, DITREE_E_ARG, "mppi_missions: rows * cols <= 13104 (five byte maps of the maze stay in LDS)");
@@ -342,12 +261,13 @@ extern "C" int32_t ditree_mppi_missions(ditree_ctx* ctx, const ditree_mppi_param
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   MppiArgs a;
   a.T = p->T; a.K = p->K; a.P = 0;
-  a.lambda = p->lambda; a.s0 = p->sigma[0]; a.s1 = p->sigma[1];
+  a.lambda = p->lambda;
   a.w_track = p->w_track; a.w_progress = p->w_progress; a.w_collision = p->w_collision; a.w_goal = p->w_goal;
   a.seed = 0; a.counter = 0;
   a.wback = p->window_back; a.wfwd = p->window_fwd;
   a.gx = 0.0; a.gy = 0.0;
   a.k0 = 0;
+  const CarTail cm{{p->sigma[0], p->sigma[1]}};
   MissionArgs g;
   g.seed = (const unsigned long long*)seed; g.counter0 = (const unsigned long long*)counter0;
   g.state_io = state_io; g.U_io = U_io;
@@ -365,7 +285,7 @@ extern "C" int32_t ditree_mppi_missions(ditree_ctx* ctx, const ditree_mppi_param
     HIP_TRY(ctx, hipFuncSetAttribute((const void*)mppi_mission_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
     if (ctx->device < 64) attr_done[ctx->device] = true;
   }
-  hipLaunchKernelGGL(mppi_mission_kernel, dim3(M), dim3(256), lds, s, g, a);
+  hipLaunchKernelGGL(mppi_mission_kernel, dim3(M), dim3(256), lds, s, g, a, cm);
   HIP_TRY(ctx, hipGetLastError());
   return DITREE_OK;
 }

@@ -37,6 +37,10 @@ class MPPI:
             return super().__new__(AntMPPI)
         return super().__new__(cls)
 
+    NX, NU = 6, 2                                    # state / action widths
+    N_RESULT, ACTION_AT, STATE_AT = 16, 0, 8         # the result block (include/ditree.h): its length, where action and state stand
+    ENTRY = "ditree_mppi_step"
+
     def __init__(self, maze_data=None, T=16, K=1024, nx=6, nu=2, lam=1.0, sigma=(3.0, 0.6), w_track=20.0, w_progress=0.5,
                  w_collision=1.0e3, w_goal=50.0, window_back=8, window_fwd=56, seed=0, lanes=0, ctx=None, env=None,
                  rank=None, world_size=None, process_group=None, **kw):
@@ -44,9 +48,18 @@ class MPPI:
             raise ValueError("MPPI needs the known maze (maze_data)")
         if nx != 6 or nu != 2:
             raise NotImplementedError("the controller drives the car model: nx = 6 (x, y, psi, v, D, delta), nu = 2 (dD, ddelta)")
+        self._set_up(maze_data, T, K, ctx, rank, world_size, process_group)
+        self.env = env if env is not None else CarEnv(maze_map=np.asarray(maze_data), collision_checking=False, ctx=self.ctx)
+        self.params = _lib.MppiParams(self.T, self.K_local, float(lam), (C.c_double * 2)(float(sigma[0]), float(sigma[1])),
+                                      float(w_track), float(w_progress), float(w_collision), float(w_goal), int(seed),
+                                      int(window_back), int(window_fwd), int(lanes), int(self.k_lo))
+        self.ctx.upload_maze(self.maze, owner=self)
+
+    def _set_up(self, maze_data, T, K, ctx, rank, world_size, process_group):
+        """What every model's controller holds: sizes, its shard of the rollouts, the context, the device buffers."""
         if not (1 <= int(T) <= 64) or int(K) < 1:
             raise ValueError("1 <= T <= 64, K >= 1")
-        self.T, self.K, self.nx, self.nu = int(T), int(K), nx, nu
+        self.T, self.K, self.nx, self.nu = int(T), int(K), self.NX, self.NU
         # K is the GLOBAL number of rollouts; with world_size > 1 (one process per GPU) every rank runs a contiguous block
         from .engine import default_shard
         d_rank, d_world, d_pg = default_shard()
@@ -59,26 +72,21 @@ class MPPI:
         if self.K_local < 1:
             raise ValueError("fewer rollouts than ranks")
         self.ctx = ctx or default_context()
-        self.env = env if env is not None else CarEnv(maze_map=np.asarray(maze_data), collision_checking=False, ctx=self.ctx)
         self.maze = np.float32(maze_data)
-        self.params = _lib.MppiParams(self.T, self.K_local, float(lam), (C.c_double * 2)(float(sigma[0]), float(sigma[1])),
-                                      float(w_track), float(w_progress), float(w_collision), float(w_goal), int(seed),
-                                      int(window_back), int(window_fwd), int(lanes), int(self.k_lo))
         dev = self.ctx.device
         f64 = torch.float64
-        self._state = torch.zeros(6, dtype=f64, device=dev)
-        self._U = torch.zeros(self.T, 2, dtype=f64, device=dev)
+        self._state = torch.zeros(self.NX, dtype=f64, device=dev)
+        self._U = torch.zeros(self.T, self.NU, dtype=f64, device=dev)
         self._costs = torch.zeros(self.K_local, dtype=f64, device=dev)
         self._flags = torch.zeros(self.K_local, dtype=torch.int32, device=dev)
-        self._result = torch.zeros(16, dtype=f64, device=dev)
+        self._result = torch.zeros(self.N_RESULT, dtype=f64, device=dev)
         self._state_host = None            # the state the device holds (skip the upload when the driver hands it back)
-        self._sums = torch.zeros(3 + 2 * self.T, dtype=f64, device=dev)
+        self._sums = torch.zeros(3 + self.NU * self.T, dtype=f64, device=dev)
         self._path = None
         self.reference_path = None
         self.goal_state = None
         self.counter = 0                   # one noise stream per step() call (also the retried ones)
         self.last = {}
-        self.ctx.upload_maze(self.maze, owner=self)
 
     # ------------------------------------------------------------------ the surface the driver uses
     def reset(self, start_state=None, goal_state=None):
@@ -112,7 +120,7 @@ class MPPI:
         return self.env.is_done(state)
 
     def step(self, state, noise=None):
-        """One controller step from `state` (6,): -> (next_state (6,) f64, action (2,) f64, done in {False, True, None})."""
+        """One controller step from `state` (NX,): -> (next_state (NX,) f64, action (NU,) f64, done in {False, True, None})."""
         if self._path is None:
             raise _lib.DitreeError("MPPI.step: set_ref_path(path) first")
         if self.ctx.maze_owner is not self:
@@ -126,9 +134,9 @@ class MPPI:
         status = int(res[2])
         self.last = {"beta": float(res[3]), "eta": float(res[4]), "nearest_path_index": int(res[5]),
                      "collided_rollouts": int(res[6]), "effective_samples": float(res[7])}
-        nxt = res[8:14].copy()
+        nxt = res[self.STATE_AT:self.STATE_AT + self.NX].copy()
         self._state_host = nxt.copy()
-        action = res[:2].copy()
+        action = res[self.ACTION_AT:self.ACTION_AT + self.NU].copy()
         if status == 2:
             return nxt, action, None
         self.env.set_state(nxt.copy())
@@ -138,7 +146,7 @@ class MPPI:
 
     def controller_step(self, noise=None, weights=None):
         """One controller step on the device state / controls.  One rank: a single C-ABI call.  Sharded: rollouts + local
-        minimum, all-reduce(MIN) of beta, weighted sums, all-reduce(SUM) of 3 + 2T doubles, then the (replicated) update and
+        minimum, all-reduce(MIN) of beta, weighted sums, all-reduce(SUM) of 3 + NU T doubles, then the (replicated) update and
         executed step -- every rank ends with the same state and controls."""
         if self.world <= 1:
             return self.launch(_lib.MPPI_ALL, noise=noise, weights=weights)
@@ -177,11 +185,11 @@ class MPPI:
     # ------------------------------------------------------------------ one C-ABI call (stages: _lib.MPPI_*)
     def launch(self, stages, noise=None, weights=None):
         goal = (C.c_double * 2)(float(self.env.goal[0]), float(self.env.goal[1]))
-        _lib.check(self.ctx._h, _lib.lib().ditree_mppi_step(
+        _lib.check(self.ctx._h, getattr(_lib.lib(), self.ENTRY)(
             self.ctx._h, C.byref(self.params), self._state.data_ptr(), self._U.data_ptr(), self._path.data_ptr(),
             int(self._path.shape[0]), goal, None if noise is None else noise.data_ptr(), self.counter, int(stages),
             self._costs.data_ptr(), None if weights is None else weights.data_ptr(), self._flags.data_ptr(),
-            self._sums.data_ptr(), self._result.data_ptr(), self.ctx.stream), "mppi_step")
+            self._sums.data_ptr(), self._result.data_ptr(), self.ctx.stream), self.ENTRY[len("ditree_"):])
 
 
 MEV_STEPS_DONE, MEV_GOAL, MEV_TRIALS = 0, 1, 2     # include/ditree.h DITREE_MEV_*
@@ -397,6 +405,10 @@ class AntMPPI(MPPI):
     126-219) and goal radius (planners/base_planner.py:296-297).  The reference has neither an MPPI module nor the ant's
     physics in its repository: PARITY UNPINNED BY CONSTRUCTION; held to oracle/mppi.py (tests/test_gpu_mppi.py)."""
 
+    NX, NU = 29, 8
+    N_RESULT, ACTION_AT, STATE_AT = 64, 16, 24
+    ENTRY = "ditree_mppi_step_ant"
+
     def __init__(self, maze_data=None, T=16, K=1024, nx=29, nu=8, lam=1.0, sigma=0.5, w_track=2.0, w_progress=0.5, w_collision=1.0e3,
                  w_goal=50.0, window_back=8, window_fwd=56, seed=0, ctx=None, s_global=4.0, ball_radius=1.2, model=None,
                  rank=None, world_size=None, process_group=None, **kw):
@@ -404,42 +416,14 @@ class AntMPPI(MPPI):
             raise ValueError("MPPI needs the known maze (maze_data)")
         if (nx, nu) != (29, 8):
             raise NotImplementedError("AntMPPI: nx = 29, nu = 8")
-        if not (1 <= int(T) <= 64) or int(K) < 1:
-            raise ValueError("1 <= T <= 64, K >= 1")
-        self.T, self.K, self.nx, self.nu = int(T), int(K), 29, 8
-        from .engine import default_shard
-        d_rank, d_world, d_pg = default_shard()
-        self.world = int(d_world if world_size is None else world_size)
-        self.rank = int((d_rank if self.world == d_world else 0) if rank is None else rank)
-        self.pg = d_pg if process_group is None else process_group
-        per = (self.K + self.world - 1) // self.world
-        self.k_lo = min(self.rank * per, self.K)
-        self.K_local = max(min(self.k_lo + per, self.K) - self.k_lo, 0)
-        if self.K_local < 1:
-            raise ValueError("fewer rollouts than ranks")
-        self.ctx = ctx or default_context()
+        self._set_up(maze_data, T, K, ctx, rank, world_size, process_group)
         self.s_global = float(s_global)
         self.env = _AntGoalEnv(maze_data, s_global)
-        self.maze = np.float32(maze_data)
         sg = np.broadcast_to(np.asarray(sigma, dtype=np.float64), (8,))
         self.params = _lib.MppiAntParams(self.T, self.K_local, float(lam), (C.c_double * 8)(*[float(v) for v in sg]), float(w_track),
                                          float(w_progress), float(w_collision), float(w_goal), int(seed), int(window_back),
                                          int(window_fwd), int(self.k_lo), 0.45 * float(s_global), float(ball_radius), float(s_global),
                                          _lib.AntModel.default() if model is None else model)
-        dev = self.ctx.device
-        f64 = torch.float64
-        self._state = torch.zeros(29, dtype=f64, device=dev)
-        self._U = torch.zeros(self.T, 8, dtype=f64, device=dev)
-        self._costs = torch.zeros(self.K_local, dtype=f64, device=dev)
-        self._flags = torch.zeros(self.K_local, dtype=torch.int32, device=dev)
-        self._result = torch.zeros(64, dtype=f64, device=dev)
-        self._state_host = None
-        self._sums = torch.zeros(3 + 8 * self.T, dtype=f64, device=dev)
-        self._path = None
-        self.reference_path = None
-        self.goal_state = None
-        self.counter = 0
-        self.last = {}
         self.ctx.upload_maze(self.maze, owner=self)
 
     def reset(self, start_state=None, goal_state=None, desired_goal=None):
@@ -456,39 +440,6 @@ class AntMPPI(MPPI):
         self.env.maze_map = np.asarray(new_maze)
         self.ctx.upload_maze(self.maze, owner=self)
 
-    def step(self, state, noise=None):
-        """One controller step from `state` (29,): -> (next_state (29,), action (8,), done in {False, True, None})."""
-        if self._path is None:
-            raise _lib.DitreeError("MPPI.step: set_ref_path(path) first")
-        if self.ctx.maze_owner is not self:
-            self.ctx.upload_maze(self.maze, owner=self)
-        state = np.asarray(state, dtype=np.float64)
-        if self._state_host is None or not np.array_equal(state, self._state_host):
-            self._state.copy_(torch.as_tensor(state))
-        self.controller_step(noise=noise)
-        res = self._result.cpu().numpy()
-        self.counter += 1
-        status = int(res[2])
-        self.last = {"beta": float(res[3]), "eta": float(res[4]), "nearest_path_index": int(res[5]),
-                     "collided_rollouts": int(res[6]), "effective_samples": float(res[7])}
-        nxt = res[24:53].copy()
-        self._state_host = nxt.copy()
-        action = res[16:24].copy()
-        if status == 2:
-            return nxt, action, None
-        self.env.set_state(nxt.copy())
-        if status == 1:
-            self.env.done = True
-        return nxt, action, status == 1
-
     def follow(self, *a, **kw):
         raise NotImplementedError("AntMPPI has no mission form: the reference has no ant mission driver and the ant slot has no "
                                   "lidar; drive it with step()")
-
-    def launch(self, stages, noise=None, weights=None):
-        goal = (C.c_double * 2)(float(self.env.goal[0]), float(self.env.goal[1]))
-        _lib.check(self.ctx._h, _lib.lib().ditree_mppi_step_ant(
-            self.ctx._h, C.byref(self.params), self._state.data_ptr(), self._U.data_ptr(), self._path.data_ptr(),
-            int(self._path.shape[0]), goal, None if noise is None else noise.data_ptr(), self.counter, int(stages),
-            self._costs.data_ptr(), None if weights is None else weights.data_ptr(), self._flags.data_ptr(),
-            self._sums.data_ptr(), self._result.data_ptr(), self.ctx.stream), "mppi_step_ant")

@@ -364,3 +364,138 @@ def test_ant_mppi_matches_the_numpy_restatement(ctx):
         st, a, done = m2.step(st)
         assert done is False and np.isfinite(st).all() and np.abs(a).max() <= 1.0
     assert m2.last["effective_samples"] > 1.0
+
+
+# ------------------------------------------------------------------------------------------ the shared controller core, both models
+STAGED = (1 | 2, 4, 8 | 16)                  # what the sharded controller issues: rollouts + min, sums, apply + execute
+
+
+def ant_state_by_the_wall(path, start, dy):
+    """`dy` below the corridor centre at path[400]: -0.7 is 0.1 from touching the bottom wall, -1.0 overlaps it."""
+    state = start.copy()
+    state[:2] = path[400] + np.array([0.0, dy])
+    return state
+
+
+def test_ant_noise_tape_at_ragged_sizes_matches_the_restatement(ctx):
+    """K = 257 (a second slice of one rollout), T = 5 (odd), noise from a tape: costs / beta / eta / controls / weights 1e-9
+    against oracle/mppi.py, flags exact, with rollouts that collide and rollouts that do not."""
+    K, T = 257, 5
+    m, maze, path, start = make_ant(ctx, K, T)
+    state = ant_state_by_the_wall(path, start, -0.7)
+    state[15:18] = [0.8, -1.2, 0.0]                          # drifting towards the wall
+    U = np.random.default_rng(6).uniform(-0.5, 0.5, (T, 8))
+    noise = torch.randn(K, T, 8, generator=torch.Generator().manual_seed(21), dtype=torch.float64) * 0.5
+    m._state.copy_(torch.as_tensor(state))
+    m._U.copy_(torch.as_tensor(U))
+    w = torch.zeros(K, dtype=torch.float64, device=ctx.device)
+    m.launch(UPD, noise=noise.to(ctx.device), weights=w)
+    kw = kw_ant(m)
+    rc, rf, i0 = OM.rollout_costs_ant(maze, state, U, path, m.env.goal, noise.numpy(), **kw)
+    Un, wn, beta, eta, ess = OM.update_ant(U, rc, noise.numpy(), kw["lam"])
+    res = m._result.cpu().numpy()
+    flags = m._flags.cpu().numpy()
+    assert int(res[5]) == i0
+    assert np.array_equal(flags, rf), (np.bincount(flags, minlength=3), np.bincount(rf, minlength=3))
+    assert (rf == 2).sum() > 0 and (rf != 2).sum() > 0 and int(res[6]) == int((rf == 2).sum())
+    assert np.abs(m._costs.cpu().numpy() - rc).max() < 1e-9 * max(1.0, np.abs(rc).max())
+    assert abs(res[3] - beta) < 1e-9 * max(1.0, abs(beta)) and abs(res[4] - eta) < 1e-9 * eta and abs(res[7] - ess) < 1e-7 * ess
+    assert np.abs(m._U.cpu().numpy() - Un).max() < 1e-9
+    wg = w.cpu().numpy()
+    assert abs(wg.sum() - 1.0) < 1e-10 and np.abs(wg - wn).max() < 1e-9
+
+
+def test_ant_collision_of_the_executed_step_restarts_the_controls(ctx):
+    """The ball overlaps the wall: the executed step collides whatever the controls are -- status 2, the state stays, the
+    controls restart from rest, the action is the clipped first control (oracle/mppi.py execute_ant)."""
+    T = 5
+    m, maze, path, start = make_ant(ctx, 64, T)
+    state = ant_state_by_the_wall(path, start, -1.0)
+    U = np.random.default_rng(7).uniform(-1.4, 1.4, (T, 8))
+    U[0, :2] = [3.0, -3.0]                                   # clipped whatever the update adds (sigma = 0.5)
+    m._state.copy_(torch.as_tensor(state))
+    m._U.copy_(torch.as_tensor(U))
+    m.launch(UPD)
+    U_upd = m._U.cpu().numpy().copy()
+    m.launch(16)                                             # DITREE_MPPI_EXECUTE alone, on the updated controls
+    res = m._result.cpu().numpy()
+    x_ref, a_ref, status, U_ref = OM.execute_ant(maze, state, U_upd, m.env.goal)
+    assert status == 2 and res[2] == 2.0
+    assert np.array_equal(res[24:53], state) and np.array_equal(m._state.cpu().numpy(), state) and np.array_equal(x_ref, state)
+    assert np.array_equal(res[16:24], a_ref) and np.array_equal(a_ref, np.clip(U_upd[0], -1.0, 1.0)) and np.abs(a_ref).max() == 1.0
+    assert (m._U.cpu().numpy() == 0).all() and (U_ref == 0).all()
+    m._U.copy_(torch.as_tensor(U))
+    nxt, action, done = m.step(state)                        # the facade: None, the state handed back
+    assert done is None and np.array_equal(nxt, state) and (m._U.cpu().numpy() == 0).all()
+
+
+def core_case(ctx, model, K=600, lanes=2):
+    """-> (controller, state, U) at T = 5: the car heading at the bottom wall, the ant 0.1 from touching it."""
+    T = 5
+    if model == "car":
+        m, maze, path, start = make(ctx, K, T, lanes=lanes, seed=9)
+        state = np.array([path[250, 0], path[250, 1] - 0.15, -0.35, 2.8, 0.5, 0.02])
+        U = np.tile(np.array([1.0, 0.2]), (T, 1))
+    else:
+        m, maze, path, start = make_ant(ctx, K, T, seed=9)
+        state = ant_state_by_the_wall(path, start, -0.7)
+        U = np.random.default_rng(8).uniform(-0.5, 0.5, (T, 8))
+    return m, state, U
+
+
+@pytest.mark.parametrize("model", ["car", "ant"])
+def test_staged_launches_equal_the_fused_step_bit_for_bit(ctx, model):
+    """One rank issuing the sharded controller's three launches leaves what one DITREE_MPPI_ALL launch leaves."""
+    m, state, U = core_case(ctx, model)
+    got = []
+    for stages in ((31,), STAGED):
+        m.counter = 4
+        m._state.copy_(torch.as_tensor(state))
+        m._U.copy_(torch.as_tensor(U))
+        w = torch.zeros(m.K, dtype=torch.float64, device=ctx.device)
+        for s in stages:
+            m.launch(s, weights=w)
+        got.append([t.cpu().numpy().copy() for t in (m._U, m._sums, m._result, w, m._state)])
+    for a, b in zip(*got):
+        assert np.array_equal(a, b)
+    assert abs(got[0][3].sum() - 1.0) < 1e-12                                 # the weights both forms normalised
+
+
+@pytest.mark.parametrize("model,lanes", [("car", 1), ("car", 2), ("car", 4), ("ant", 0)])
+def test_a_shard_draws_the_noise_of_the_whole(ctx, model, lanes):
+    """costs / flags of K = 300 at k_offset = 300 are rows 300..599 of K = 600 at k_offset = 0, bit for bit."""
+    got = []
+    for K, k0 in ((600, 0), (300, 300)):
+        m, state, U = core_case(ctx, model, K, lanes)
+        m.params.k_offset = k0
+        m.counter = 4
+        m._state.copy_(torch.as_tensor(state))
+        m._U.copy_(torch.as_tensor(U))
+        m.launch(ROLL)
+        got.append((m._costs.cpu().numpy(), m._flags.cpu().numpy()))
+    assert np.array_equal(got[0][0][300:], got[1][0]) and np.array_equal(got[0][1][300:], got[1][1])
+    assert len(np.unique(got[1][0])) > 250                                    # noisy rollouts, not 300 copies of the nominal one
+
+
+def test_car_slices_of_two_trips_match_the_restatement(ctx):
+    """K = 65 836 = 256 slices of 258 rollouts: every slice makes two trips of the 256 threads, the second with two rollouts."""
+    K, T = 65836, 2
+    m, maze, path, start = make(ctx, K, T, seed=4242)
+    state = np.array([path[250, 0], path[250, 1] - 0.15, -0.35, 2.8, 0.5, 0.02])
+    U = np.array([[0.8, -0.2], [0.3, 0.1]])
+    m.counter = 3
+    m._state.copy_(torch.as_tensor(state))
+    m._U.copy_(torch.as_tensor(U))
+    w = torch.zeros(K, dtype=torch.float64, device=ctx.device)
+    m.launch(UPD, weights=w)
+    kw = kw_of(m)
+    eps = OM.device_noise(4242, 3, K, T, kw["sigma"])
+    rc, rf, i0 = OM.rollout_costs(maze, state, U, path, m.env.goal, eps, **kw)
+    Un, wn, beta, eta, ess = OM.update(U, rc, eps, kw["lam"])
+    res = m._result.cpu().numpy()
+    assert int(res[5]) == i0 and np.array_equal(m._flags.cpu().numpy(), rf) and int(res[6]) == int((rf == 2).sum())
+    assert np.abs(m._costs.cpu().numpy() - rc).max() < 1e-9 * max(1.0, np.abs(rc).max())
+    assert abs(res[3] - beta) < 1e-9 * max(1.0, abs(beta)) and abs(res[4] - eta) < 1e-9 * eta and abs(res[7] - ess) < 1e-7 * ess
+    assert np.abs(m._U.cpu().numpy() - Un).max() < 1e-9
+    wg = w.cpu().numpy()
+    assert abs(wg.sum() - 1.0) < 1e-10 and np.abs(wg - wn).max() < 1e-9
