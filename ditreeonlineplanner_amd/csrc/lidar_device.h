@@ -32,8 +32,10 @@ __device__ __forceinline__ bool border_solve(double rx, double ry, double dx, do
 __device__ __forceinline__ void lidar_ray(double x0, double y0, double yaw, int ray, const unsigned char* mz, int rows,
                                           int cols, unsigned char* vis, double* d_out, double* ex_out, double* ey_out,
                                           bool* hit_out) {
-  // maze_width, maze_height = maze_data.shape (sic, :51): "width" = rows
-  const double mw = (double)rows, mh = (double)cols;
+  // x runs along columns, y along rows: width = cols, height = rows.  The reference unpacks maze_data.shape the other
+  // way round (:51), which is the same arithmetic on a square map and raises on any other; there this is the build's own
+  // definition.
+  const double mw = (double)cols, mh = (double)rows;
   const double angle = -180.0 + 2.0 * (double)ray;                 // np.arange(-180, 182, 2)
   const double ang = (yaw + angle) * (M_PI / 180.0);               // np.deg2rad(yaw + angle) (:53-54)
   double rx, ry;
@@ -67,18 +69,16 @@ __device__ __forceinline__ void lidar_ray(double x0, double y0, double yaw, int 
     double t = (double)i * step;                                     // arange value start + i*delta
     double px = x0 + t * vx, py = y0 + t * vy;                       // :86
     double fx = floor(px), fy = floor(py);
-    int qx = fx >= 0.0 ? (fx < mw ? (int)fx : rows - 1) : 0;         // clip to [0, maze_width-1]  (:89)
-    int qy = fy >= 0.0 ? (fy < mh ? (int)fy : cols - 1) : 0;         // clip to [0, maze_height-1]
-    // maze_data[q_y, q_x] (:91): q_y indexes rows.  On non-square maps the reference's swapped
-    // clip bounds can index past the array (IndexError); clamp so the device never faults.
-    int rr = min(qy, rows - 1), cc = min(qx, cols - 1);
-    if (mz[rr * cols + cc] == 1) {
+    int qx = fx >= 0.0 ? (fx < mw ? (int)fx : cols - 1) : 0;         // clip to [0, maze_width-1]  (:89)
+    int qy = fy >= 0.0 ? (fy < mh ? (int)fy : rows - 1) : 0;         // clip to [0, maze_height-1]
+    // maze_data[q_y, q_x] (:91): q_y indexes rows, q_x columns; both are inside the map after the clip
+    if (mz[qy * cols + qx] == 1) {
       h = true;
       ox = px;
       oy = py;
       break;
     }
-    vis[rr * cols + cc] = 1;                                         // benign race: all writers store 1
+    vis[qy * cols + qx] = 1;                                         // benign race: all writers store 1
   }
   double ex = ox - x0, ey = oy - y0;
   double d = sqrt(fma(ey, ey, ex * ex));                             // :96

@@ -6,6 +6,11 @@ Returned ``visited_points`` are the *set* of cells (x, y) a ray sample touched b
 (the reference returns the same cells as a ragged, duplicated list in ray order; the drivers only
 use them as an index set, run_scenarios_with_lidar_DiTree.py:121).  ``scan_batch`` scans many poses
 in one launch.  Gaussian range noise (noise_std > 0) is added on the host like lidar_2d_sim.py:30-33.
+
+Extents on a rows x cols map: x runs along columns (0 .. cols), y along rows (0 .. rows).  On a square map this is the
+reference bit for bit.  On any other map the reference raises (it unpacks ``maze_width, maze_height = maze_data.shape``,
+:51), so there the definition is this build's own, parity unpinned by construction.  A pose outside the map returns
+distance 0 and no visited cell for every ray (the reference raises TypeError).
 """
 from __future__ import annotations
 

@@ -189,6 +189,10 @@ int32_t ditree_ant_rollout(ditree_ctx* ctx, const ditree_ant_model* model, doubl
 /* lidar_sim/lidar_2d_sim.py:18-98 Lidar2DSim.scan for B poses (pose = x_col, y_row, yaw
  * in cell units) against `maze` [dev] (rows, cols) f32 (the *true* world, which may
  * differ from the uploaded known maze).  181 rays, arange(-180, 182, 2) degrees.
+ * Extents: x runs along columns (0 .. cols), y along rows (0 .. rows).  On a square map this is the reference bit for bit;
+ * on any other map the reference raises (it unpacks the shape as width = rows, :51), so there this is the build's own
+ * definition, parity unpinned by construction.  A pose outside the map finds no border: d = 0, no hit, nothing visited
+ * (the reference raises TypeError).
  *   dist [dev] (B,181) f64; endpoints [dev] (B,181,2) f64; hit [dev] (B,181) u8;
  *   visited [dev] (B, rows*cols) u8 or NULL: 1 where a ray sample fell before its hit. */
 int32_t ditree_lidar_scan(ditree_ctx* ctx, const double* poses, int32_t B, const float* maze,
@@ -315,7 +319,8 @@ int32_t ditree_fallback_select(ditree_ctx* ctx, const ditree_tree* tree, int32_t
  *   expansion round); goal_xy [host] 2; executed [dev] (n_actions - action_idx, 6) f64: state after every
  *   executed action; result [dev] 4 x i32: event (DITREE_EV_*), next action index, first blocked path index
  *   or -1, number of scans.  Ray end cells outside the map (only possible without border walls, where the
- *   reference raises IndexError) are dropped.  rows * cols <= 13104 (five byte maps of the maze stay in LDS). */
+ *   reference raises IndexError) are dropped.  rows * cols <= 13104 (five byte maps of the maze stay in LDS).
+ *   The scan is ditree_lidar_scan's: x along columns, y along rows, on non-square maps the build's own definition. */
 #define DITREE_EV_ACTIONS_DONE 0
 #define DITREE_EV_GOAL 1
 #define DITREE_EV_COLLISION 2
@@ -385,7 +390,8 @@ int32_t ditree_mppi_step(ditree_ctx* ctx, const ditree_mppi_params* p, double* s
  *     executed step against the KNOWN maze.  Collided: the state stays, U <- 0, trials += 1, event TRIALS once trials >=
  *     allowed_trials.  Else trials = 0, the new state and the executed action are appended to the mission's trace, t_acc += dt;
  *     t_acc > scan_time: lidar scan of the TRUE maze from the pose, ray end cells -> 1 in known and scanned, visited cells -> 2
- *     in scanned (ditree_follow_plan's scan), t_acc = 0; then inside the goal radius: event GOAL (after the scan, as the
+ *     in scanned (ditree_follow_plan's scan: x along columns, y along rows, on non-square maps the build's own definition),
+ *     t_acc = 0; then inside the goal radius: event GOAL (after the scan, as the
  *     driver's loop body ends before is_done is tested again);
  *   event STEPS_DONE when the loop runs out.
  * BIT-EXACT against the stepwise form: a mission leaves exactly what the same sequence of ditree_mppi_step(DITREE_MPPI_ALL),

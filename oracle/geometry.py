@@ -274,16 +274,25 @@ def check_obstacle_ahead(state, maze):
 LIDAR_ANGLES_DEG = np.arange(-360 / 2, 360 / 2 + 2.0, 2.0)      # lidar_2d_sim.py:14-16 (181)
 
 
-def lidar_cast_ray(pose, maze, angle_deg):
+def lidar_cast_ray(pose, maze, angle_deg, extents="reference"):
     """lidar_sim/lidar_2d_sim.py:47-98, one ray.  pose = (x_col, y_row, yaw) in cells.
 
     Keeps the reference quirks: yaw (radians) is added to the angle in degrees (:53),
     ``maze_width, maze_height = maze.shape`` (:51), first admissible border in the
     order Left/Right/Bottom/Top (:57-82).
+    ``extents="reference"`` is that swap (width = rows): invisible on a square map, and on any other map the
+    reference raises (IndexError past the array, TypeError when no border is found).  ``extents="map"`` is the
+    build's own definition, which the device implements: x runs along columns (extent cols), y along rows
+    (extent rows); on a square map the two are the same arithmetic.
     Returns (distance, endpoint(2,), visited cells (k, 2) int [x, y], hit flag).
     """
     x0, y0, yaw = pose
-    mw, mh = maze.shape
+    if extents == "reference":
+        mw, mh = maze.shape
+    elif extents == "map":
+        mh, mw = maze.shape
+    else:
+        raise ValueError(f"extents = {extents!r}: 'reference' or 'map'")
     ang = np.deg2rad(yaw + angle_deg)
     rv = np.array([np.cos(ang), np.sin(ang)])
     p = np.array([x0, y0], dtype=np.float64)
@@ -315,8 +324,8 @@ def lidar_cast_ray(pose, maze, angle_deg):
     return float(np.linalg.norm(obstacle - p)), obstacle, q[:first], hit
 
 
-def lidar_scan(pose, maze):
-    """lidar_sim/lidar_2d_sim.py:18-45 with noise_std = 0 (the default, :6).
+def lidar_scan(pose, maze, extents="reference"):
+    """lidar_sim/lidar_2d_sim.py:18-45 with noise_std = 0 (the default, :6); ``extents`` as in lidar_cast_ray.
 
     Returns distances (181,), endpoints (181, 2), visited (k, 2), hits (181,) bool.
     The endpoint is re-derived from the distance as in :30-40.
@@ -325,7 +334,7 @@ def lidar_scan(pose, maze):
     yaw = pose[-1]
     dists, ends, visited, hits = [], [], [], []
     for ang in LIDAR_ANGLES_DEG:
-        d, _, cells, hit = lidar_cast_ray(pose, maze, ang)
+        d, _, cells, hit = lidar_cast_ray(pose, maze, ang, extents)
         visited.extend(cells)
         a = np.deg2rad(yaw + ang)
         d = float(np.clip(d, 0, 300))

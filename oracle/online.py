@@ -23,11 +23,12 @@ def lidar_pose(state, maze):
     return np.array([rc[1], rc[0], float(state[2])])
 
 
-def scan_and_update_maze(state, maze_known, maze_true, scanned):
+def scan_and_update_maze(state, maze_known, maze_true, scanned, extents="reference"):
     """:112-127.  Scans the TRUE maze from the robot pose and writes the ray end cells as occupied into
-    the known maze and the scanned maze (visited cells = 2, end cells = 1); both are updated in place."""
+    the known maze and the scanned maze (visited cells = 2, end cells = 1); both are updated in place.
+    ``extents``: geometry.lidar_cast_ray."""
     pose = lidar_pose(state, maze_known)
-    _, ends, visited, _ = G.lidar_scan(pose, maze_true)
+    _, ends, visited, _ = G.lidar_scan(pose, maze_true, extents)
     cells = np.floor(ends).astype(int)
     maze_known[cells[:, 1], cells[:, 0]] = 1
     if len(visited):
@@ -50,7 +51,8 @@ def check_no_obstacles_in_path(scanned, path_xy):
     return -1
 
 
-def follow_plan(state, actions, action_idx, path_xy, maze_known, maze_true, scanned, goal_xy, dt=0.02, scan_time=0.2):
+def follow_plan(state, actions, action_idx, path_xy, maze_known, maze_true, scanned, goal_xy, dt=0.02, scan_time=0.2,
+                extents="reference"):
     """:470-506 for run_type < 4: execute ``actions[action_idx:]`` one env step at a time
     (propagate_action_sequence_env: step, goal test, collision test on the KNOWN maze), scanning every
     time the accumulated step time exceeds ``scan_time`` and stopping at the first event.
@@ -73,7 +75,7 @@ def follow_plan(state, actions, action_idx, path_xy, maze_known, maze_true, scan
         action_idx += 1
         t_acc += dt
         if t_acc > scan_time:
-            scan_and_update_maze(state, maze_known, maze_true, scanned)
+            scan_and_update_maze(state, maze_known, maze_true, scanned, extents)
             obstacle = check_no_obstacles_in_path(scanned, path_xy)
             t_acc = 0
         if r["status"][0] == G.STATUS_GOAL:

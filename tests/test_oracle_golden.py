@@ -48,6 +48,39 @@ def test_lidar_matches_reference():
         assert np.array_equal(vis, vis_all[i])
 
 
+def test_lidar_on_every_bundled_maze_fails_where_the_reference_fails():
+    """tests/golden/lidar_nonsquare.json (make_lidar_nonsquare.py): what the reference's Lidar2DSim did at 8 free poses of
+    every bundled car maze, "ok" or the exception type it raised.  The oracle's default extents fail in the same way at the
+    same poses (on every non-square maze, never on a square one); extents="map" scans every pose, every ray ends on a wall
+    and every visited cell lies inside the map."""
+    with open(os.path.join(os.path.dirname(__file__), "golden", "lidar_nonsquare.json")) as f:
+        rec = json.load(f)["mazes"]
+    assert {"Race_Track", "narrow_short", "random_large", "shapes", "boxes"} <= set(rec)
+    raised = set()
+    for name, r in rec.items():
+        maze = load_maze(name)
+        assert list(maze.shape) == r["shape"] and len(r["poses"]) == len(r["result"]) == 8
+        square = maze.shape[0] == maze.shape[1]
+        for pose, exp in zip(r["poses"], r["result"]):
+            assert maze[int(pose[1]), int(pose[0])] == 0
+            try:
+                G.lidar_scan(pose, maze)
+                got = "ok"
+            except Exception as e:                                   # noqa: BLE001 -- the type is what is compared
+                got = type(e).__name__
+            assert got == exp, (name, pose, got, exp)
+            assert (exp == "ok") == square, (name, pose, exp)
+            raised.add(exp)
+            d, e, v, h = G.lidar_scan(pose, maze, extents="map")
+            assert h.all() and (d > 0).all(), (name, pose)
+            assert (v[:, 0] >= 0).all() and (v[:, 0] < maze.shape[1]).all(), (name, pose)
+            assert (v[:, 1] >= 0).all() and (v[:, 1] < maze.shape[0]).all(), (name, pose)
+            if square:
+                d0, e0, v0, h0 = G.lidar_scan(pose, maze)
+                assert np.array_equal(d, d0) and np.array_equal(e, e0) and np.array_equal(v, v0) and np.array_equal(h, h0)
+    assert raised == {"ok", "IndexError", "TypeError"}
+
+
 def test_kdtree_matches_scipy():
     g = golden("geometry")
     for n in (1, 17, 1000):
