@@ -165,6 +165,7 @@ SIGNATURES = {
     "ditree_fallback_select": (_i32, [_vp, C.POINTER(Tree), _i32, _pd, _pd, _i32, _vp, _vp]),
     "ditree_follow_plan": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _pd, _f64, _f64, _vp, _vp, _vp]),
     "ditree_accept": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Round), _i32, _vp]),
+    "ditree_accept_best": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Round), _vp, _vp]),
     "ditree_round_pack": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Round), _vp, _vp]),
     "ditree_round_unpack": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Round), _vp, _vp]),
     "ditree_record_doubles": (_i32, [C.POINTER(Tree)]),
@@ -194,6 +195,7 @@ SIGNATURES = {
     "ditree_expand_round": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Round), C.POINTER(RoundParams), _vp]),
     "ditree_forest_expand_round": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), C.POINTER(Round), C.POINTER(RoundParams), _vp]),
     "ditree_forest_accept": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), C.POINTER(Round), _i32, _vp]),
+    "ditree_forest_accept_best": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), C.POINTER(Round), _vp, _vp]),
     "ditree_forest_chunk_budget": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), _vp, _i32, C.POINTER(_i32), _i32, _vp, _vp,
                                           _vp]),
     "ditree_forest_nn_argmin": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), _vp, _i32, _i32, _vp, _vp]),

@@ -444,6 +444,29 @@ int32_t ditree_accept(ditree_ctx* ctx, const ditree_tree* tree, const ditree_rou
   return DITREE_OK;
 }
 
+// What ditree_accept_best and ditree_forest_accept_best refuse by name before anything is launched.
+static int check_accept_best(ditree_ctx* ctx, const ditree_round* round, const int32_t* cost) {
+  if (!cost) return set_err(ctx, DITREE_E_ARG, "accept_best: cost array missing");
+  if (round->shard != 0) return set_err(ctx, DITREE_E_ARG, "accept_best: one rank (round->shard must be 0)");
+  return DITREE_OK;
+}
+
+int32_t ditree_accept_best(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round, int32_t* cost, void* stream) {
+  if (!ctx) return DITREE_E_ARG;
+  int rc = check_tree(ctx, tree);
+  if (rc) return rc;
+  rc = check_round(ctx, round);
+  if (rc) return rc;
+  rc = check_accept_best(ctx, round, cost);
+  if (rc) return rc;
+  if (round->B == 0) return DITREE_OK;
+  if (tree->obstacle_ahead && !ctx->maze) return set_err(ctx, DITREE_E_STATE, "accept_best: obstacle-ahead flags need the maze");
+  const AheadArg ts = ahead_samples();
+  launch_accept_best(*tree, *round, cost, ctx->maze, ctx->rows, ctx->cols, ts, (hipStream_t)stream);
+  HIP_TRY(ctx, hipGetLastError());
+  return DITREE_OK;
+}
+
 int32_t ditree_round_pack(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round, double* records_out,
                           void* stream) {
   if (!ctx) return DITREE_E_ARG;
@@ -1109,6 +1132,25 @@ int32_t ditree_forest_accept(ditree_ctx* ctx, const ditree_tree* tree, const dit
   const AheadArg ts = ahead_samples();
   launch_forest_accept(*tree, *round, forest->off, forest->counters, forest->n_trees, forest->tree_capacity, emulate_sticky,
                        ctx->maze, ctx->rows, ctx->cols, ts, (hipStream_t)stream);
+  HIP_TRY(ctx, hipGetLastError());
+  return DITREE_OK;
+}
+
+int32_t ditree_forest_accept_best(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const ditree_round* round,
+                                  int32_t* cost, void* stream) {
+  if (!ctx) return DITREE_E_ARG;
+  int rc = check_round(ctx, round);
+  if (rc) return rc;
+  rc = check_forest(ctx, tree, forest, round->B, "forest_accept_best");
+  if (rc) return rc;
+  rc = check_accept_best(ctx, round, cost);
+  if (rc) return rc;
+  if (tree->obstacle_ahead || tree->hist)
+    return set_err(ctx, DITREE_E_ARG, "forest_accept_best: a forest is one rank's run_type-0 car tree (no obstacle flags or hist)");
+  if (round->B == 0) return DITREE_OK;
+  const AheadArg ts = ahead_samples();
+  launch_forest_accept_best(*tree, *round, forest->off, forest->counters, forest->n_trees, forest->tree_capacity, cost, ctx->maze,
+                            ctx->rows, ctx->cols, ts, (hipStream_t)stream);
   HIP_TRY(ctx, hipGetLastError());
   return DITREE_OK;
 }

@@ -186,6 +186,10 @@ void launch_accept(const ditree_tree& t, const ditree_round& r, int emulate_stic
                    int cols, const AheadArg& ts, hipStream_t s);
 void launch_forest_accept(const ditree_tree& t, const ditree_round& r, const int32_t* off, int32_t* counters, int T, int C,
                           int emulate_sticky, const unsigned char* maze, int rows, int cols, const AheadArg& ts, hipStream_t s);
+void launch_accept_best(const ditree_tree& t, const ditree_round& r, int32_t* cost, const unsigned char* maze, int rows, int cols,
+                        const AheadArg& ts, hipStream_t s);
+void launch_forest_accept_best(const ditree_tree& t, const ditree_round& r, const int32_t* off, int32_t* counters, int T, int C,
+                               int32_t* cost, const unsigned char* maze, int rows, int cols, const AheadArg& ts, hipStream_t s);
 void launch_obstacle_ahead(const unsigned char* maze, int rows, int cols, const double* state, int stride, int B,
                            const AheadArg& ts, uint8_t* out, hipStream_t s);
 void launch_fallback_select(const ditree_tree& t, int n_nodes, double gx, double gy, const double* path_dev, int P,

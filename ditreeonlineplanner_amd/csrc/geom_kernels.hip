@@ -1220,9 +1220,110 @@ __device__ __forceinline__ void accept_scan_tree(int32_t* __restrict__ counters,
     counters[7] = phantom < 0 ? -1 : cand_base + phantom;
   }
 }
+// The scan of ditree_accept_best: every candidate of the round in index order, nothing cut at a goal and no sticky-done
+// phantom.  A candidate gets a node slot iff it did not collide; the goal node is chosen after the commit (accept_pick_tree),
+// so counters[1], [2] and [5] are not touched here.  Arguments as accept_scan_tree's.
+__device__ __forceinline__ void accept_best_scan_tree(int32_t* __restrict__ counters, int32_t* __restrict__ num_visit,
+                                                      const int32_t* __restrict__ status, const int32_t* __restrict__ chunks_run,
+                                                      const int32_t* __restrict__ parent, int32_t* __restrict__ node_id, int B,
+                                                      int node_base, int cap) {
+  __shared__ int s_iters;
+  __shared__ int s_wave_sum[16];
+  const int tid = threadIdx.x;
+  if (tid == 0) s_iters = 0;
+  __syncthreads();
+  const int n0 = counters[0];
+  // ordered prefix sum of accepted flags over all B candidates, 1024 at a time
+  int base = 0;
+  for (int start = 0; start < B; start += blockDim.x) {
+    const int b = start + tid;
+    int acc = 0, it = 0;
+    if (b < B) {
+      acc = (status[b] & 0xff) != DITREE_ST_COLLIDED;
+      it = chunks_run[b];
+      atomicAdd(&num_visit[parent[b]], 1);
+    }
+    int v = acc;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      int o = __shfl_up(v, d);
+      if ((tid & 63) >= d) v += o;
+    }
+    int itw = it;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) itw += __shfl_xor(itw, m);
+    if ((tid & 63) == 63) s_wave_sum[tid >> 6] = v;
+    if ((tid & 63) == 0) atomicAdd(&s_iters, itw);
+    __syncthreads();
+    int woff = 0;
+    for (int w = 0; w < (tid >> 6); ++w) woff += s_wave_sum[w];
+    int chunk_total = 0;
+    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) chunk_total += s_wave_sum[w];
+    if (b < B) {
+      int id = acc ? (n0 + base + woff + v - acc) : -1;   // n0 + exclusive rank
+      if (id >= cap) id = -1;
+      node_id[b] = id < 0 ? -1 : node_base + id;
+    }
+    base += chunk_total;
+    __syncthreads();
+  }
+  if (tid == 0) {
+    int n1 = n0 + base;
+    if (n1 > cap) { n1 = cap; counters[6] = 1; }
+    counters[0] = n1;
+    counters[3] += s_iters;
+    counters[4] += B;
+    counters[7] = -1;
+  }
+}
+// The pick of ditree_accept_best, after the commit: among the round's goal candidates that got a node slot, the smallest
+// (cost[node], candidate index); it replaces the incumbent counters[1] only when there is none or its cost is strictly smaller.
+__device__ __forceinline__ void accept_pick_tree(int32_t* __restrict__ counters, const int32_t* __restrict__ status,
+                                                 const int32_t* __restrict__ node_id, const int32_t* __restrict__ cost, int B) {
+  __shared__ unsigned long long s_best;
+  const int tid = threadIdx.x;
+  if (tid == 0) s_best = ~0ull;
+  __syncthreads();
+  for (int b = tid; b < B; b += blockDim.x) {
+    const int id = node_id[b];
+    if ((status[b] & 0xff) == DITREE_ST_GOAL && id >= 0)  // a collided candidate's goal-at-collision flag is not a goal
+      atomicMin(&s_best, ((unsigned long long)(unsigned)cost[id] << 32) | (unsigned)b);
+  }
+  __syncthreads();
+  if (tid == 0 && s_best != ~0ull) {
+    const int c = (int)(s_best >> 32), b = (int)(s_best & 0xffffffffull);
+    const int inc = counters[1];
+    if (inc < 0 || c < cost[inc]) counters[1] = node_id[b];
+  }
+}
 __global__ void __launch_bounds__(1024)
 accept_scan_kernel(ditree_tree t, ditree_round r, int emulate_sticky) {
   accept_scan_tree(t.counters, t.num_visit, r.status, r.chunks_run, r.parent, r.node_id, r.B, 0, t.capacity, 0, emulate_sticky);
+}
+__global__ void __launch_bounds__(1024)
+accept_best_scan_kernel(ditree_tree t, ditree_round r) {
+  accept_best_scan_tree(t.counters, t.num_visit, r.status, r.chunks_run, r.parent, r.node_id, r.B, 0, t.capacity);
+}
+__global__ void __launch_bounds__(1024)
+accept_pick_kernel(ditree_tree t, ditree_round r, const int32_t* __restrict__ cost) {
+  accept_pick_tree(t.counters, r.status, r.node_id, cost, r.B);
+}
+__global__ void __launch_bounds__(1024)
+forest_accept_best_scan_kernel(ditree_tree t, ditree_round r, const int32_t* __restrict__ off, int32_t* __restrict__ counters, int C) {
+  const int tr = blockIdx.x;
+  const int lo = off[tr], n = off[tr + 1] - lo;
+  if (n <= 0) return;
+  accept_best_scan_tree(counters + (size_t)tr * 8, t.num_visit, r.status + lo, r.chunks_run + lo, r.parent + lo, r.node_id + lo, n,
+                        tr * C, C);
+}
+__global__ void __launch_bounds__(1024)
+forest_accept_pick_kernel(ditree_round r, const int32_t* __restrict__ off, int32_t* __restrict__ counters,
+                          const int32_t* __restrict__ cost) {
+  const int tr = blockIdx.x;
+  const int lo = off[tr], n = off[tr + 1] - lo;
+  if (n <= 0) return;
+  // candidate indices are compared within the tree: the offset lo is common to all of them
+  accept_pick_tree(counters + (size_t)tr * 8, r.status + lo, r.node_id + lo, cost, n);
 }
 // A forest: one work-group per tree over its candidate range [off[t], off[t+1]); trees run in parallel.  An empty range leaves
 // the tree untouched (as ditree_accept does for an empty round).
@@ -1240,10 +1341,12 @@ forest_accept_scan_kernel(ditree_tree t, ditree_round r, const int32_t* __restri
 // all-zero rows (RRT.py:196-199).  State / action width S / D at run time (car 6 / 2, ant 29 / 8; S, D <= 64: a lane per
 // component, the zero-row test is one ballot).
 // FOREST: the phantom candidate is the one in the counter row of the node's own tree (id / C of the forest's counters).
+// cost != NULL (ditree_accept_best): cost[id] = rows of the path to the node = cost[parent] + kept edge states + 1; the
+// parent is a node of an earlier round, so its cost is final.
 template <bool FOREST>
 __global__ void __launch_bounds__(64)
 accept_commit_kernel(ditree_tree t, ditree_round r, const unsigned char* __restrict__ maze, int rows, int cols,
-                     AheadArg ts, const int32_t* __restrict__ forest_counters, int C) {
+                     AheadArg ts, const int32_t* __restrict__ forest_counters, int C, int32_t* __restrict__ cost) {
   const int b = blockIdx.x;
   const int id = r.node_id[b];
   if (id < 0) return;
@@ -1311,6 +1414,7 @@ accept_commit_kernel(ditree_tree t, ditree_round r, const unsigned char* __restr
     t.num_visit[id] = 0;
     t.edge_nstates[id] = ns;
     t.edge_nactions[id] = na;
+    if (cost != nullptr) cost[id] = cost[par] + ns + 1;
     if (t.edge_owner != nullptr) t.edge_owner[id] = owner;
     if (t.obstacle_ahead != nullptr)                                   // RRT.py:202-205 (run_type > 0)
       t.obstacle_ahead[id] = obstacle_ahead_dev(ex, ey, psi, maze, rows, cols, ts) ? 1 : 0;
@@ -1408,10 +1512,22 @@ void launch_round_unpack(const ditree_tree& t, const ditree_round& r, const doub
 void launch_accept(const ditree_tree& t, const ditree_round& r, int emulate_sticky, const unsigned char* maze, int rows,
                    int cols, const AheadArg& ts, hipStream_t s) {
   hipLaunchKernelGGL(accept_scan_kernel, dim3(1), dim3(1024), 0, s, t, r, emulate_sticky);
-  hipLaunchKernelGGL(accept_commit_kernel<false>, dim3(r.B), dim3(64), 0, s, t, r, maze, rows, cols, ts, nullptr, 0);
+  hipLaunchKernelGGL(accept_commit_kernel<false>, dim3(r.B), dim3(64), 0, s, t, r, maze, rows, cols, ts, nullptr, 0, nullptr);
+}
+void launch_accept_best(const ditree_tree& t, const ditree_round& r, int32_t* cost, const unsigned char* maze, int rows, int cols,
+                        const AheadArg& ts, hipStream_t s) {
+  hipLaunchKernelGGL(accept_best_scan_kernel, dim3(1), dim3(1024), 0, s, t, r);
+  hipLaunchKernelGGL(accept_commit_kernel<false>, dim3(r.B), dim3(64), 0, s, t, r, maze, rows, cols, ts, nullptr, 0, cost);
+  hipLaunchKernelGGL(accept_pick_kernel, dim3(1), dim3(1024), 0, s, t, r, cost);
 }
 void launch_forest_accept(const ditree_tree& t, const ditree_round& r, const int32_t* off, int32_t* counters, int T, int C,
                           int emulate_sticky, const unsigned char* maze, int rows, int cols, const AheadArg& ts, hipStream_t s) {
   hipLaunchKernelGGL(forest_accept_scan_kernel, dim3(T), dim3(1024), 0, s, t, r, off, counters, C, emulate_sticky);
-  hipLaunchKernelGGL(accept_commit_kernel<true>, dim3(r.B), dim3(64), 0, s, t, r, maze, rows, cols, ts, counters, C);
+  hipLaunchKernelGGL(accept_commit_kernel<true>, dim3(r.B), dim3(64), 0, s, t, r, maze, rows, cols, ts, counters, C, nullptr);
+}
+void launch_forest_accept_best(const ditree_tree& t, const ditree_round& r, const int32_t* off, int32_t* counters, int T, int C,
+                               int32_t* cost, const unsigned char* maze, int rows, int cols, const AheadArg& ts, hipStream_t s) {
+  hipLaunchKernelGGL(forest_accept_best_scan_kernel, dim3(T), dim3(1024), 0, s, t, r, off, counters, C);
+  hipLaunchKernelGGL(accept_commit_kernel<true>, dim3(r.B), dim3(64), 0, s, t, r, maze, rows, cols, ts, counters, C, cost);
+  hipLaunchKernelGGL(forest_accept_pick_kernel, dim3(T), dim3(1024), 0, s, r, off, counters, cost);
 }

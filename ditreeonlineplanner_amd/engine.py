@@ -27,10 +27,11 @@ CNT_NODES, CNT_GOAL, CNT_LATCH, CNT_ITERS, CNT_CANDS, CNT_STICKY, CNT_OVERFLOW, 
 class DeviceTree:
     """planners/base_planner.py:24-34 ``Node`` as a struct of arrays in HBM (include/ditree.h ditree_tree).  ``state_dim`` /
     ``action_dim``: 6 / 2 for the car, 29 / 8 for the ant; ``hist``: keep the last three rows of every node's edge (what the
-    first sampler call of a child sees with obs_history 3 -- the ant)."""
+    first sampler call of a child sees with obs_history 3 -- the ant); ``cost``: keep every node's path cost (the rows
+    ``tree_path`` returns for it), which the ``solution`` modes other than "first" rank goal nodes by."""
 
     def __init__(self, ctx: Context, capacity: int, n_chunks: int, A: int, track_obstacle_ahead: bool = False,
-                 state_dim: int = 6, action_dim: int = 2, hist: bool = False):
+                 state_dim: int = 6, action_dim: int = 2, hist: bool = False, cost: bool = False):
         dev = ctx.device
         self.capacity, self.n_chunks, self.A = capacity, n_chunks, A
         self.S, self.D = S, D = int(state_dim), int(action_dim)
@@ -52,6 +53,7 @@ class DeviceTree:
         self.edge_owner = torch.full((capacity,), -1, dtype=i32, device=dev)
         self.hist = torch.zeros(capacity, 3, S, dtype=f64, device=dev) if hist else None
         self.hist_n = torch.zeros(capacity, dtype=i32, device=dev) if hist else None
+        self.cost = torch.zeros(capacity, dtype=i32, device=dev) if cost else None      # not part of the descriptor
         self.desc = Tree(capacity, n_chunks, A, S, D, *[None if t is None else t.data_ptr() for t in (
             self.state, self.xy, self.parent, self.last_action, self.has_prev, self.num_visit,
             self.edge_states, self.edge_actions, self.edge_nstates, self.edge_nactions, self.obstacle_ahead,
@@ -75,6 +77,8 @@ class DeviceTree:
             self.hist[0].zero_()
             self.hist[0, 2] = s
             self.hist_n[0] = 1
+        if self.cost is not None:
+            self.cost[0] = 1                            # the root's path is its own state row
         self.counters.zero_()
         self.counters[CNT_NODES] = 1
         self.counters[CNT_GOAL] = -1
@@ -244,14 +248,38 @@ def tree_path(tr, node, n_nodes, base=0, edge_rows=None):
     return path, actions
 
 
+SOLUTIONS = ("first", "best_of_round", "anytime")
+
+
+def check_solution(solution, emulate_sticky_done, world_size=1, run_type=0):
+    """The scope of the ``solution`` modes other than "first" (ditree_accept_best): one rank, run_type 0, no sticky-done
+    emulation (its phantom candidate belongs to the first-goal rule)."""
+    if solution not in SOLUTIONS:
+        raise ValueError(f"solution must be one of {SOLUTIONS}, got {solution!r}")
+    if solution == "first":
+        return
+    if emulate_sticky_done:
+        raise ValueError(f"solution={solution!r} needs emulate_sticky_done=False (the sticky-done emulation ends a plan at its "
+                         "first goal)")
+    if world_size > 1:
+        raise NotImplementedError(f"solution={solution!r}: one rank (world_size {world_size})")
+    if run_type != 0:
+        raise NotImplementedError(f"solution={solution!r}: run_type 0 only (got {run_type})")
+
+
 class ExpansionEngine:
-    """Batched RRT expansion on one GPU (optionally one shard of a multi-GPU round)."""
+    """Batched RRT expansion on one GPU (optionally one shard of a multi-GPU round).  ``solution``: which goal-reaching
+    candidate becomes the goal node -- "first" (the reference's: the lowest index, the rest of the round dropped), or, through
+    ditree_accept_best, the cheapest one ("best_of_round", "anytime": every non-collided candidate of the round is appended
+    and ``goal_node`` is the incumbent, which later rounds may replace)."""
     STATE_DIM, ACTION_DIM, HIST = 6, 2, False
 
     def __init__(self, ctx: Context, maze, start_state, goal_state, edge_length=64, action_horizon=8,
                  pred_horizon=64, local_map_size=20, local_map_scale=0.2, s_global=1.0, batch=1024,
                  capacity=65536, k_steps=1, emulate_sticky_done=True, norm=CAR_NORM, rank=0, world_size=1,
-                 process_group=None, early_exit=False, run_type=0, goal_scale=None, prop_duration=None):
+                 process_group=None, early_exit=False, run_type=0, goal_scale=None, prop_duration=None, solution="first"):
+        check_solution(solution, emulate_sticky_done, world_size, run_type)
+        self.solution = solution
         self.ctx = ctx
         self.maze = np.asarray(maze, dtype=np.float32)
         # planners/RRT.py:26,149-152: per-visit edge lengths; the tree's edge capacity is the longest entry
@@ -276,7 +304,8 @@ class ExpansionEngine:
         self.run_type = int(run_type)
         self.init_main_path = None          # (P, >=2) reference path of an earlier plan (run_type > 0)
         self.tree = DeviceTree(ctx, capacity, self.n_chunks, self.A, track_obstacle_ahead=self.run_type > 0,
-                               state_dim=self.STATE_DIM, action_dim=self.ACTION_DIM, hist=self.HIST)
+                               state_dim=self.STATE_DIM, action_dim=self.ACTION_DIM, hist=self.HIST,
+                               cost=solution != "first")
         # sharded rounds exchange ceil(batch / world) fixed slots per rank: size the round buffers for whole slots, so a batch
         # that does not divide by the rank count is fine (the last rank's tail slots stay unused)
         per = (batch + world_size - 1) // world_size
@@ -481,8 +510,12 @@ class ExpansionEngine:
             rd = self.rb.desc(0, B, own=(lo, hi - lo), shard=per)
         else:
             rd = self.rb.desc(0, B)
-        check(self.ctx._h, lib().ditree_accept(self.ctx._h, C.byref(self.tree.desc), C.byref(rd), self.sticky,
-                                                self.ctx.stream), "accept")
+        if self.solution == "first":
+            check(self.ctx._h, lib().ditree_accept(self.ctx._h, C.byref(self.tree.desc), C.byref(rd), self.sticky,
+                                                    self.ctx.stream), "accept")
+        else:
+            check(self.ctx._h, lib().ditree_accept_best(self.ctx._h, C.byref(self.tree.desc), C.byref(rd),
+                                                         self.tree.cost.data_ptr(), self.ctx.stream), "accept_best")
         cnt = self.tree.read_counters()           # one small D2H per round: n_nodes / goal
         self._range_guard()
         return cnt
@@ -503,8 +536,14 @@ class ExpansionEngine:
             self.ctx.raise_range_error(layers)
 
     # ------------------------------------------------------------------ results
+    def round_solutions(self, B):
+        """Device scalar: how many of the last round's first B candidates are goal nodes of the tree now."""
+        rb = self.rb
+        return (((rb.status[:B] & 0xFF) == _lib.ST_GOAL) & (rb.node_id[:B] >= 0)).sum()
+
     @property
     def goal_node(self):
+        """counters[1]: the first goal node, or -- ``solution`` other than "first" -- the incumbent."""
         g = int(self.tree.counters[CNT_GOAL].item())
         return None if g < 0 else g
 

@@ -23,7 +23,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import MAX_ATLAS_CELLS, MAX_SCENES, Forest, ForestScenes, RoundParams, check, lib
+from ._lib import MAX_ATLAS_CELLS, MAX_SCENES, ST_GOAL, Forest, ForestScenes, RoundParams, check, lib
 from .engine import (CNT_GOAL, CNT_NODES, CNT_PHANTOM, AntExpansionEngine, ExpansionEngine, ant_cell_centre, env_goal_of,
                      tree_path)
 from .ops import CAR_NORM, Context, _dbl
@@ -89,6 +89,8 @@ class ForestTrees:
             tr.hist[r].zero_()
             tr.hist[r, 2] = s
             tr.hist_n[r] = 1
+        if tr.cost is not None:
+            tr.cost[r] = 1
         self.fcounters[t] = self._root_row
         self.cnt_host[t] = self._ROOT
         self.n_nodes_host[t] = 1
@@ -146,9 +148,12 @@ class ForestTrees:
         B = self._B if B is None else int(B)
         self.ensure_maze()
         rd = self.rb.desc(0, B)
-        entry, what = self._ACCEPT
+        if self.solution == "first":
+            entry, what, args = *self._ACCEPT, self._accept_args()
+        else:                                         # car forests only (ExpansionEngine's ``solution``)
+            entry, what, args = "ditree_forest_accept_best", "forest_accept_best", (self.tree.cost.data_ptr(),)
         check(self.ctx._h, getattr(lib(), entry)(self.ctx._h, C.byref(self.tree.desc), C.byref(self.fdesc), C.byref(rd),
-                                                 *self._accept_args(), self.ctx.stream), what)
+                                                 *args, self.ctx.stream), what)
         cnt = self.read_counters().copy()             # one small D2H per round: every tree's row
         self._range_guard()
         return cnt
@@ -164,9 +169,17 @@ class ForestTrees:
         return self.cnt_host[self._tree_index(t)].copy()
 
     def goal_node(self, t):
+        """Tree t's goal node (``solution`` other than "first": its incumbent) as of the last accept, local to the tree."""
         t = self._tree_index(t)
         g = int(self.cnt_host[t, CNT_GOAL])
         return None if g < 0 else g - t * self.C
+
+    def round_solutions(self, B):
+        """Device (T,) int64: how many of the last round's B candidates are goal nodes of each tree now."""
+        rb = self.rb
+        is_goal = ((rb.status[:B] & 0xFF) == ST_GOAL) & (rb.node_id[:B] >= 0)
+        tree_of = torch.div(rb.node_id[:B].clamp(min=0), self.C, rounding_mode="floor").long()
+        return torch.zeros(self.T, dtype=torch.int64, device=is_goal.device).index_add_(0, tree_of, is_goal.long())
 
     def phantom(self, t):
         """The round row of tree t's sticky-done phantom in the last round, or None."""
@@ -214,13 +227,13 @@ class ForestEngine(ForestTrees, ExpansionEngine):
 
     def __init__(self, ctx: Context, maze, start_state, goal_state, n_trees, tree_capacity, edge_length=64, action_horizon=8,
                  pred_horizon=64, local_map_size=20, local_map_scale=0.2, s_global=1.0, batch=1024, k_steps=1,
-                 emulate_sticky_done=True, norm=CAR_NORM, early_exit=False, goal_scale=None, prop_duration=None):
+                 emulate_sticky_done=True, norm=CAR_NORM, early_exit=False, goal_scale=None, prop_duration=None, solution="first"):
         capacity = self._init_forest(ctx, n_trees, tree_capacity)
         super().__init__(ctx, maze, start_state, goal_state, edge_length=edge_length, action_horizon=action_horizon,
                          pred_horizon=pred_horizon, local_map_size=local_map_size, local_map_scale=local_map_scale,
                          s_global=s_global, batch=batch, capacity=capacity, k_steps=k_steps,
                          emulate_sticky_done=emulate_sticky_done, norm=norm, early_exit=early_exit, run_type=0,
-                         goal_scale=goal_scale, prop_duration=prop_duration)
+                         goal_scale=goal_scale, prop_duration=prop_duration, solution=solution)
 
     def expand_round(self, samples, cond_goal, noise=None, inject_actions=None, counts_per_tree=None, step_noise=None,
                      accept=True):

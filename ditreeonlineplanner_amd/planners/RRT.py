@@ -14,6 +14,15 @@ Constructor kwargs, ``plan() -> (path f32 (P,6)|None, actions f32 (A,2)|None)``,
                        the initialised default group, i.e. what `torch.distributed.run` set up; one rank otherwise).  All
                        ranks must draw the same samples and noise -- the reference's scripts seed every RNG with 42
                        (run_scenarios.py:86-90) -- and all ranks return the same path.
+  ``solution``         which goal-reaching candidate a plan returns.  "first" (default): the lowest-index one of the first
+                       goal-reaching round, the rest of that round dropped -- the reference's loop.  "best_of_round": the plan
+                       still ends with that round, but every non-collided candidate of it is appended and the goal node is the
+                       one with the shortest path (rows of ``path``; ties to the lowest index).  "anytime": rounds go on until
+                       ``time_budget`` / ``max_candidates`` ends and the shortest goal path found is returned (a later node
+                       replaces the incumbent only when strictly shorter).  The two new modes need
+                       ``emulate_sticky_done=False`` (its default then) and cover the car, one rank, run_type 0.
+                       ``results`` gains ``solutions`` (goal nodes appended) and ``first_solution_candidates`` (candidates
+                       processed up to and including the first goal-reaching round, or None).
 All of the reference's ``run_type`` values: 0 "Original"; 1 "Original+Ref" (obstacle-ahead flags per node, sampling
 biased to the part of ``init_main_path`` behind the obstacle, furthest-along-path fallback); 2 "OM+Ref" (sample
 positions drawn from the EDT prior); 3 "OM+LB+Ref" (prior log-blended with the start -> goal Gaussian, refreshed at
@@ -59,6 +68,9 @@ class RRT_Planner(BasePlanner):
         self.batch = int(kwargs.get("batch", 512))
         self.max_candidates = kwargs.get("max_candidates", None)
         self.capacity = int(kwargs.get("capacity", 65536))
+        self.solution = kwargs.get("solution", "first")
+        self._check_solution(kwargs)
+        sticky = kwargs.get("emulate_sticky_done", self.solution == "first")
         lm = self.local_map_size if isinstance(self.local_map_size, (int, float)) else self.local_map_size[0]
         d_rank, d_world, d_pg = default_shard()
         self.world_size = int(kwargs.get("world_size", d_world))
@@ -74,13 +86,32 @@ class RRT_Planner(BasePlanner):
             local_map_size=int(lm), local_map_scale=self.local_map_scale, s_global=self.s_global, batch=self.batch,
             capacity=self.capacity, k_steps=getattr(sampler, "num_diffusion_iters", 1),
             norm=getattr(sampler, "norm", None) if getattr(sampler, "norm", None) is not None else None,
-            emulate_sticky_done=kwargs.get("emulate_sticky_done", True), early_exit=kwargs.get("early_exit", True),
+            emulate_sticky_done=sticky, early_exit=kwargs.get("early_exit", True),
             run_type=self.run_type, goal_scale=getattr(sampler, "local_map_size", None),
-            rank=self.rank, world_size=self.world_size, process_group=self.process_group)
+            rank=self.rank, world_size=self.world_size, process_group=self.process_group, solution=self.solution)
         self._engine.env_goal = np.asarray(self.env.goal, dtype=np.float64)
         self._engine.ddpm = self._ddpm
         from concurrent.futures import ThreadPoolExecutor
         self._draw_pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="ditree-draw")
+
+    def _check_solution(self, kwargs):
+        """The ``solution`` modes other than "first": refused by name where they are not built, before the device is touched."""
+        from ..engine import SOLUTIONS
+        sol = self.solution
+        if sol not in SOLUTIONS:
+            raise ValueError(f"solution must be one of {SOLUTIONS}, got {sol!r}")
+        if sol == "first":
+            return
+        if kwargs.get("emulate_sticky_done", False):
+            raise ValueError(f"solution={sol!r} and emulate_sticky_done=True do not go together: the sticky-done emulation ends "
+                             "a plan at its first goal")
+        if self.is_ant:
+            raise NotImplementedError(f"solution={sol!r}: the car only (env_id='antmaze' keeps solution='first')")
+        world = int(kwargs.get("world_size", default_shard()[1]))
+        if world > 1:
+            raise NotImplementedError(f"solution={sol!r}: one rank (world_size {world}; a sharded round keeps solution='first')")
+        if self.run_type != 0:
+            raise NotImplementedError(f"solution={sol!r}: run_type 0 only (run_type {self.run_type} keeps solution='first')")
 
     # ------------------------------------------------------------------ ant (BASELINE config 3)
     def _init_ant_engine(self, sampler, kwargs):
@@ -150,7 +181,8 @@ class RRT_Planner(BasePlanner):
                 self.options["reset_deg"] = np.rad2deg(start_state[2])
             self.options["goal_cell"] = to_rc(goal_state[:2])
         self.failed_node_list = []
-        self.results = {"iterations": 0, "time": 0, "path": None, "actions": None, "number_of_nodes": 0}
+        self.results = {"iterations": 0, "time": 0, "path": None, "actions": None, "number_of_nodes": 0, "solutions": 0,
+                        "first_solution_candidates": None}
         out = self.env.reset(options=self.options)
         if self.is_ant:
             if isinstance(out, tuple) and isinstance(out[0], dict) and "desired_goal" in out[0]:
@@ -319,6 +351,9 @@ class RRT_Planner(BasePlanner):
         pending = rng_before = None
         cnt = None
         steps_dev = torch.zeros((), dtype=torch.int64, device=dev)     # env steps = two-ball collision tests (cc_calls)
+        first = self.solution == "first"
+        solutions_dev = None if first else torch.zeros((), dtype=torch.int64, device=dev)
+        first_at = None                                                # candidates drawn when the first goal node appeared
         while eng.agree((time.time() - start_time) < self.time_budget):
             if self.max_candidates is not None and drawn >= self.max_candidates:
                 break
@@ -347,9 +382,14 @@ class RRT_Planner(BasePlanner):
             drawn += B
             lo, hi, _ = eng.shard(B)
             steps_dev += eng.rb.chunk_steps[lo:hi].sum()
-            goal = int(cnt[CNT_GOAL]) if int(cnt[CNT_GOAL]) >= 0 else None
+            if not first:
+                solutions_dev += eng.round_solutions(B)
+            goal = int(cnt[CNT_GOAL]) if int(cnt[CNT_GOAL]) >= 0 else None      # the incumbent, for the modes that keep one
             if goal is not None:
-                break
+                if first_at is None:
+                    first_at = drawn
+                if self.solution != "anytime":
+                    break
         if pending is not None:
             pending.result()                     # never leave the helper running on the global RNGs
             random.setstate(rng_before[0])       # the pre-drawn round is dropped: un-draw it
@@ -360,6 +400,8 @@ class RRT_Planner(BasePlanner):
             _mu.add_cc_calls(eng.sum_over_ranks(int(steps_dev.item())))   # the counter the drivers read (run_scenarios.py:338,343)
         if has_pm:
             self.env.prob_map = orig_prob_map
+        self.results["solutions"] = (0 if goal is None else 1) if first else int(solutions_dev.item())
+        self.results["first_solution_candidates"] = first_at
         if goal is not None:
             if not self.is_ant:
                 self.env.done = True
@@ -390,7 +432,8 @@ class RRT_Planner(BasePlanner):
                 f = ForestEngine(self.ctx, self.maze, self.start_node.state, self.goal_state, T, tree_capacity, action_horizon=e.A,
                                  pred_horizon=e.P, local_map_size=e.lm_n, local_map_scale=e.lm_scale, s_global=e.s_global,
                                  batch=batch, k_steps=e.k_steps, emulate_sticky_done=bool(e.sticky), norm=e.norm,
-                                 early_exit=bool(e.early_exit), goal_scale=e.goal_scale, prop_duration=e.schedule)
+                                 early_exit=bool(e.early_exit), goal_scale=e.goal_scale, prop_duration=e.schedule,
+                                 solution=self.solution)
             self._forest, self._forest_key = f, key
         f.ddpm = e.ddpm
         f.update_maze(self.maze)
@@ -447,7 +490,7 @@ def _scene_settings(pl):
     return [("ctx", pl.ctx), ("sampler", pl.sampler), ("action_horizon", e.A), ("pred_horizon", e.P), ("local map size", e.lm_n),
             ("local map scale", float(e.lm_scale)), ("s_global", float(e.s_global)), ("k_steps", e.k_steps),
             ("norm", e.norm.tobytes()), ("emulate_sticky_done", e.sticky), ("early_exit", e.early_exit),
-            ("prop_duration", tuple(e.schedule)), ("batch", pl.batch)]
+            ("prop_duration", tuple(e.schedule)), ("batch", pl.batch), ("solution", getattr(pl, "solution", "first"))]
 
 
 def _check_scene_planners(planners):
@@ -512,7 +555,7 @@ def plan_scenario_runs(planners, seeds, concurrent=None, tree_capacity=None):
     eng = SceneForestEngine(ctx, scenes, T, int(tree_capacity), action_horizon=e.A, pred_horizon=e.P, local_map_size=e.lm_n,
                             local_map_scale=e.lm_scale, s_global=e.s_global, batch=T * batch, k_steps=e.k_steps,
                             emulate_sticky_done=bool(e.sticky), norm=e.norm, early_exit=bool(e.early_exit),
-                            goal_scale=e.goal_scale, prop_duration=e.schedule)
+                            goal_scale=e.goal_scale, prop_duration=e.schedule, solution=p0.solution)
     eng.ddpm = e.ddpm
     if network:
         sampler.ensure_bound(T * batch)

@@ -90,7 +90,12 @@ def run_jobs(eng, jobs, batch, device):
     Ant jobs (``planner.is_ant``; an ``AntForestEngine``): with tape dynamics every run's
     ``next_obs_tape_fn(the run's first candidate, n)`` rows, concatenated in tree order, go to ``expand_round``; and since
     ``is_colliding_ant`` does not count its calls (``plan()`` adds nothing for the ant) the runs report ``cc_calls`` 0 and
-    ``common.map_utils.cc_calls`` stays as it is."""
+    ``common.map_utils.cc_calls`` stays as it is.
+
+    ``planner.solution`` (one value for all jobs): with "first" and "best_of_round" a run finishes with its first goal-reaching
+    round, with "anytime" on its own budgets only; a finished run's node is its tree's goal node -- for the two new modes the
+    incumbent -- else the fallback.  Every dict carries ``solutions`` (goal nodes appended) and ``first_solution_candidates``
+    (the run's candidates up to and including its first goal-reaching round, or None)."""
     import torch
     from ..common import map_utils
     from ..engine import CNT_GOAL, CNT_ITERS
@@ -101,10 +106,13 @@ def run_jobs(eng, jobs, batch, device):
     ant = bool(getattr(jobs[0].planner, "is_ant", False))
     tape = ant and getattr(jobs[0].planner, "ant_dynamics", "host") == "tape"
     K = len(eng.ddpm[0]) if (network and eng.ddpm is not None) else 0
+    solution = getattr(jobs[0].planner, "solution", "first")
+    first = solution == "first"
     results = [None] * len(jobs)
     queue = list(range(len(jobs)))[::-1]
-    slots = [None] * T                                      # per tree: [job index, RunStreams, drawn, start time]
+    slots = [None] * T                    # per tree: [job index, RunStreams, drawn, start time, first_solution_candidates]
     steps_dev = torch.zeros(T, dtype=torch.int64, device=device)
+    solutions_dev = None if first else torch.zeros(T, dtype=torch.int64, device=device)
     total_cc = 0
 
     def start(t):
@@ -113,11 +121,13 @@ def run_jobs(eng, jobs, batch, device):
             i = queue.pop()
             eng.reset_tree(t, *jobs[i].reset_args)
             steps_dev[t] = 0
-            slots[t] = [i, RunStreams(jobs[i].seed, device), 0, time.time()]
+            if not first:
+                solutions_dev[t] = 0
+            slots[t] = [i, RunStreams(jobs[i].seed, device), 0, time.time(), None]
 
     def finish(t, goal):
         nonlocal total_cc
-        i, _, _, t0 = slots[t]
+        i, _, _, t0, first_at = slots[t]
         job = jobs[i]
         row = eng.counters(t)
         node = goal if goal is not None else eng.fallback_node(t)          # RRT.py:227-254
@@ -130,7 +140,9 @@ def run_jobs(eng, jobs, batch, device):
         results[i] = job.slot[0][job.slot[1]] = {
             "seed": job.seed, "success": path is not None, "goal_reached": goal is not None, "iterations": int(row[CNT_ITERS]),
             "time": elapsed, "path": path, "actions": actions, "number_of_nodes": int(eng.n_nodes_host[t]),
-            "path_time": None if path is None else len(path) * job.planner.env_dt, "cc_calls": cc}
+            "path_time": None if path is None else len(path) * job.planner.env_dt, "cc_calls": cc,
+            "solutions": (0 if goal is None else 1) if first else int(solutions_dev[t].item()),
+            "first_solution_candidates": first_at}
         start(t)
 
     with caller_states_kept():
@@ -141,12 +153,12 @@ def run_jobs(eng, jobs, batch, device):
             sizes = [0] * T
             for t in range(T):
                 while slots[t] is not None:
-                    i, _, drawn, t0 = slots[t]
+                    i, _, drawn, t0, _ = slots[t]
                     pl = jobs[i].planner
                     if (time.time() - t0) < pl.time_budget and (pl.max_candidates is None or drawn < pl.max_candidates):
                         sizes[t] = batch if pl.max_candidates is None else min(batch, pl.max_candidates - drawn)
                         break
-                    finish(t, None)
+                    finish(t, None if first else eng.goal_node(t))          # the budgets ended: an anytime run's incumbent
             if not any(sizes):
                 break
             active = [t for t in range(T) if sizes[t] > 0]
@@ -177,10 +189,15 @@ def run_jobs(eng, jobs, batch, device):
             if not ant:
                 tree_of = torch.as_tensor(np.repeat(np.arange(T), sizes), device=device)
                 steps_dev.index_add_(0, tree_of, eng.rb.chunk_steps[:B].sum(dim=1, dtype=torch.int64))
+            if not first:
+                solutions_dev += eng.round_solutions(B)
             for t in active:
                 slots[t][2] += sizes[t]
                 if int(cnt[t, CNT_GOAL]) >= 0:
-                    finish(t, eng.goal_node(t))
+                    if slots[t][4] is None:
+                        slots[t][4] = slots[t][2]
+                    if solution != "anytime":
+                        finish(t, eng.goal_node(t))
     if not ant:
         map_utils.add_cc_calls(total_cc)        # the counter the drivers read (run_scenarios.py:338,343), once
     return results

@@ -281,6 +281,23 @@ int32_t ditree_comm_destroy(ditree_ctx* ctx);
 int32_t ditree_accept(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round,
                       int32_t emulate_sticky, void* stream);
 
+/* The accept step of the planner's `solution` modes "best_of_round" and "anytime": the round keeps every solution it holds
+ * and the goal node is the cheapest one, not the first drawn.
+ *   cost [dev] (capacity,) int32, kept by the caller next to the tree: cost[n] = rows of the path from the root to node n
+ *   (edge states + node states, as base_planner.py:342-363 strings them) -- cost[root] = 1, set by the caller at reset;
+ *   cost[n] = cost[parent[n]] + edge_nstates[n] + 1, written here for every node the round appends.
+ * Scan: candidates 0 .. B-1 in index order, nothing is cut at a goal; a candidate is accepted iff
+ * (status & 0xff) != DITREE_ST_COLLIDED; node ids run from counters[0], an id at or past the capacity becomes -1 and sets
+ * counters[6]; num_visit[parent[b]] += 1 for every candidate; counters[3] += sum of chunks_run, counters[4] += B;
+ * counters[2] and [5] are untouched (no sticky-done phantom here) and counters[7] = -1.  Commit: as ditree_accept's.
+ * Pick: among the candidates with status DITREE_ST_GOAL and a node id, the smallest (cost[node_id], b) is written to
+ * counters[1] when counters[1] < 0 or its cost is strictly below cost[counters[1]] -- the incumbent wins a tie, within a round
+ * the lowest index does.  A collided candidate with DITREE_ST_FLAG_GOAL_AT_COLLISION is not a goal, and a goal candidate that
+ * lost its slot to the capacity is not eligible.
+ * DITREE_E_ARG before anything is launched: "accept_best: cost array missing",
+ * "accept_best: one rank (round->shard must be 0)". */
+int32_t ditree_accept_best(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round, int32_t* cost, void* stream);
+
 /* planners/RRT.py:61-81 check_obstacle_ahead on the uploaded maze: 30 samples over 1.5 cells ahead of the
  * heading in (col, row) space, int-truncated and clipped, any occupied.
  *   state [dev] (B, stride) f64 (x, y, psi used); out [dev] (B,) u8.  The sample offsets are
@@ -627,6 +644,12 @@ int32_t ditree_forest_expand_round(ditree_ctx* ctx, const ditree_tree* tree, con
  * iteration / candidate counts, overflow at the tree's own C) to its counter row and writes global node ids from t * C + n_t. */
 int32_t ditree_forest_accept(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const ditree_round* round,
                              int32_t emulate_sticky, void* stream);
+/* ditree_accept_best per tree: one work-group per tree scans its candidate range (ids from t * C + n_t, overflow at the tree's
+ * own C), and after the commit one work-group per tree picks its goal node into its counter row.  cost [dev] (tree->capacity,)
+ * is indexed by the global node id; the caller sets cost[t * C] = 1 when it resets tree t.  An empty range leaves the tree
+ * untouched.  The same two DITREE_E_ARG messages, before anything is launched. */
+int32_t ditree_forest_accept_best(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const ditree_round* round,
+                                  int32_t* cost, void* stream);
 /* ditree_chunk_budget on a forest: samples [dev] (off[T], 6), nearest nodes searched per tree; B = off[T]. */
 int32_t ditree_forest_chunk_budget(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const double* samples,
                                    int32_t B, const int32_t* schedule_chunks, int32_t n_schedule, int32_t* parent_scratch,
