@@ -51,6 +51,13 @@ class Forest(C.Structure):
                 ("off_host", C.POINTER(C.c_int32))]
 
 
+class Bound(C.Structure):
+    """include/ditree.h ditree_bound: cost and key columns, per-tree goals, goal radius, reach and the (T, 4) stats rows of the
+    "anytime_pruned" mode."""
+    _fields_ = [("cost", C.c_void_p), ("key", C.c_void_p), ("goal_xy", C.c_void_p), ("goal_radius", C.c_double),
+                ("reach", C.c_double), ("stats", C.c_void_p)]
+
+
 class ForestScenes(C.Structure):
     """include/ditree.h ditree_forest_scenes: the scene id of every tree of a scene forest."""
     _fields_ = [("tree_scene", C.c_void_p), ("tree_scene_host", C.POINTER(C.c_int32))]
@@ -203,6 +210,15 @@ SIGNATURES = {
     "ditree_upload_scenes": (_i32, [_vp, _i32, C.POINTER(C.c_float), C.POINTER(_i32), C.POINTER(_i32), _pd, _vp]),
     "ditree_forest_expand_round_scenes": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), C.POINTER(ForestScenes), C.POINTER(Round),
                                                  C.POINTER(RoundParams), _vp]),
+    "ditree_bound_keys": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Bound), _i32, _i32, _i32, _vp]),
+    "ditree_nn_argmin_bounded": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Bound), _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "ditree_forest_nn_argmin_bounded": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), C.POINTER(Bound), _vp, _i32, _i32, _vp, _vp,
+                                               _vp, _vp, _vp]),
+    "ditree_expand_round_bounded": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Round), C.POINTER(RoundParams), C.POINTER(Bound), _vp]),
+    "ditree_forest_expand_round_bounded": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), C.POINTER(ForestScenes), C.POINTER(Round),
+                                                  C.POINTER(RoundParams), C.POINTER(Bound), _vp]),
+    "ditree_accept_bounded": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Round), C.POINTER(Bound), _vp]),
+    "ditree_forest_accept_bounded": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), C.POINTER(Round), C.POINTER(Bound), _vp]),
     "ditree_forest_fallback_goals": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), _pd, _vp, _vp]),
     "ditree_forest_expand_round_ant": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), C.POINTER(Round), C.POINTER(AntRoundParams),
                                               _vp]),

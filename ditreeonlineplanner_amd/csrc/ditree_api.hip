@@ -3,6 +3,7 @@
 #include <dlfcn.h>
 
 #include <algorithm>
+#include <cmath>
 
 #include <cstdio>
 #include <cstring>
@@ -960,8 +961,10 @@ static int ensure_row_scene(ditree_ctx* ctx, int B, hipStream_t s) {
 
 // The car round of one tree, or (f != NULL, validated by the caller) of a forest: only the nearest-node step differs.  A scene
 // forest (tree_scene != NULL, validated by the caller) reads each row's maze and goal from the scene table instead.
+// bd != NULL (validated by the caller): the masked nearest-node search of the "anytime_pruned" mode.
 static int expand_round_impl(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* f, const ditree_round* round,
-                             const ditree_round_params* p, void* stream, const int32_t* tree_scene = nullptr) {
+                             const ditree_round_params* p, void* stream, const int32_t* tree_scene = nullptr,
+                             const ditree_bound* bd = nullptr) {
   if (!ctx) return DITREE_E_ARG;
   int rc = check_tree(ctx, tree);
   if (rc) return rc;
@@ -1007,7 +1010,14 @@ static int expand_round_impl(ditree_ctx* ctx, const ditree_tree* tree, const dit
   }
   const double gx = tree_scene ? 0.0 : p->goal_xy[0], gy = tree_scene ? 0.0 : p->goal_xy[1];   // scenes: each row's own goal
   launch_round_begin(round->status, round->chunks_run, round->chunk_steps, B, nC, s);
-  if (f)
+  if (f && bd)
+    launch_nn_forest_bounded(p->samples, 6, B, tree->xy, f->off, f->n_trees, f->counters, f->tree_capacity, round->parent,
+                             tree->state, tree->last_action, tree->has_prev, ctx->cur_state, ctx->prev_action, ctx->has_prev,
+                             bd->key, bd->cost, s);
+  else if (bd)
+    launch_nn_argmin_bounded(p->samples, 6, B, tree->xy, p->n_nodes, round->parent, tree->state, tree->last_action,
+                             tree->has_prev, ctx->cur_state, ctx->prev_action, ctx->has_prev, bd->key, bd->cost, tree->counters, s);
+  else if (f)
     launch_nn_forest(p->samples, 6, B, tree->xy, f->off, f->n_trees, f->counters, f->tree_capacity, 0, round->parent, tree->state,
                      tree->last_action, tree->has_prev, ctx->cur_state, ctx->prev_action, ctx->has_prev, s);
   else
@@ -1292,6 +1302,145 @@ int32_t ditree_forest_expand_round_scenes(ditree_ctx* ctx, const ditree_tree* tr
   rc = check_scenes(ctx, forest, scenes, "forest_expand_round_scenes");
   if (rc) return rc;
   return expand_round_impl(ctx, tree, forest, round, p, stream, scenes->tree_scene);
+}
+
+// ---- branch and bound (include/ditree.h "branch and bound"): what every call of the section refuses by name before anything
+// is launched.  round: the calls that take one (NULL otherwise); search: the nearest-node calls read key, cost and counters only.
+static int check_bound(ditree_ctx* ctx, const ditree_bound* bd, const ditree_round* round, bool search = false) {
+  if (!bd) return set_err(ctx, DITREE_E_ARG, "bound: descriptor missing");
+  if (!bd->cost) return set_err(ctx, DITREE_E_ARG, "bound: cost array missing");
+  if (!bd->key) return set_err(ctx, DITREE_E_ARG, "bound: key column missing");
+  if (round && round->shard != 0) return set_err(ctx, DITREE_E_ARG, "bound: one rank (round->shard must be 0)");
+  if (search) return DITREE_OK;
+  if (!bd->goal_xy) return set_err(ctx, DITREE_E_ARG, "bound: goal_xy missing");
+  if (!bd->stats) return set_err(ctx, DITREE_E_ARG, "bound: stats rows missing");
+  if (!(bd->reach > 0.0) || !std::isfinite(bd->reach)) return set_err(ctx, DITREE_E_ARG, "bound: reach must be > 0");
+  if (!(bd->goal_radius >= 0.0) || !std::isfinite(bd->goal_radius))
+    return set_err(ctx, DITREE_E_ARG, "bound: goal_radius must be >= 0 and finite");
+  return DITREE_OK;
+}
+
+int32_t ditree_bound_keys(ditree_ctx* ctx, const ditree_tree* tree, const ditree_bound* bound, int32_t first, int32_t n,
+                          int32_t tree_capacity, void* stream) {
+  if (!ctx) return DITREE_E_ARG;
+  int rc = check_tree(ctx, tree);
+  if (rc) return rc;
+  rc = check_bound(ctx, bound, nullptr);
+  if (rc) return rc;
+  if (first < 0 || n < 0 || tree_capacity < 0 || (int64_t)first + n > tree->capacity)
+    return set_err(ctx, DITREE_E_ARG, "bound_keys: nodes [first, first + n) must lie in the tree; tree_capacity >= 0");
+  if (n == 0) return DITREE_OK;
+  launch_bound_keys(tree->xy, first, n, tree_capacity, *bound, (hipStream_t)stream);
+  HIP_TRY(ctx, hipGetLastError());
+  return DITREE_OK;
+}
+
+int32_t ditree_nn_argmin_bounded(ditree_ctx* ctx, const ditree_tree* tree, const ditree_bound* bound, const double* queries,
+                                 int32_t q_stride, int32_t B, int32_t n_nodes, int32_t* out_idx, double* out_state,
+                                 double* out_prev_action, uint8_t* out_has_prev, void* stream) {
+  if (!ctx) return DITREE_E_ARG;
+  int rc = check_tree(ctx, tree);
+  if (rc) return rc;
+  rc = check_bound(ctx, bound, nullptr, true);
+  if (rc) return rc;
+  if (B == 0) return DITREE_OK;
+  const bool gather = out_state || out_prev_action || out_has_prev;
+  if (!queries || !out_idx || B < 0 || q_stride < 2 || n_nodes <= 0 || n_nodes > tree->capacity ||
+      (gather && (!out_state || !out_prev_action || !out_has_prev)))
+    return set_err(ctx, DITREE_E_ARG, "nn_argmin_bounded: bad argument (the three gather outputs come together)");
+  launch_nn_argmin_bounded(queries, q_stride, B, tree->xy, n_nodes, out_idx, gather ? tree->state : nullptr, tree->last_action,
+                           tree->has_prev, out_state, out_prev_action, out_has_prev, bound->key, bound->cost, tree->counters,
+                           (hipStream_t)stream, tree->state_dim, tree->action_dim);
+  HIP_TRY(ctx, hipGetLastError());
+  return DITREE_OK;
+}
+
+int32_t ditree_forest_nn_argmin_bounded(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
+                                        const ditree_bound* bound, const double* queries, int32_t q_stride, int32_t B,
+                                        int32_t* out_idx, double* out_state, double* out_prev_action, uint8_t* out_has_prev,
+                                        void* stream) {
+  if (!ctx) return DITREE_E_ARG;
+  int rc = check_forest(ctx, tree, forest, B, "forest_nn_argmin_bounded");
+  if (rc) return rc;
+  rc = check_bound(ctx, bound, nullptr, true);
+  if (rc) return rc;
+  if (B == 0) return DITREE_OK;
+  const bool gather = out_state || out_prev_action || out_has_prev;
+  if (!queries || !out_idx || q_stride < 2 || (gather && (!out_state || !out_prev_action || !out_has_prev)))
+    return set_err(ctx, DITREE_E_ARG, "forest_nn_argmin_bounded: bad argument (the three gather outputs come together)");
+  launch_nn_forest_bounded(queries, q_stride, B, tree->xy, forest->off, forest->n_trees, forest->counters, forest->tree_capacity,
+                           out_idx, gather ? tree->state : nullptr, tree->last_action, tree->has_prev, out_state, out_prev_action,
+                           out_has_prev, bound->key, bound->cost, (hipStream_t)stream, tree->state_dim, tree->action_dim);
+  HIP_TRY(ctx, hipGetLastError());
+  return DITREE_OK;
+}
+
+int32_t ditree_expand_round_bounded(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round,
+                                    const ditree_round_params* p, const ditree_bound* bound, void* stream) {
+  if (!ctx) return DITREE_E_ARG;
+  int rc = check_round(ctx, round);
+  if (rc) return rc;
+  rc = check_bound(ctx, bound, round);
+  if (rc) return rc;
+  if (p && p->chunk_budget)
+    return set_err(ctx, DITREE_E_ARG, "expand_round_bounded: chunk budgets are not built (p->chunk_budget must be NULL)");
+  return expand_round_impl(ctx, tree, nullptr, round, p, stream, nullptr, bound);
+}
+
+int32_t ditree_forest_expand_round_bounded(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
+                                           const ditree_forest_scenes* scenes, const ditree_round* round,
+                                           const ditree_round_params* p, const ditree_bound* bound, void* stream) {
+  if (!ctx) return DITREE_E_ARG;
+  int rc = check_round(ctx, round);
+  if (rc) return rc;
+  rc = check_forest(ctx, tree, forest, round->B, "forest_expand_round_bounded");
+  if (rc) return rc;
+  if (scenes) {
+    rc = check_scenes(ctx, forest, scenes, "forest_expand_round_bounded");
+    if (rc) return rc;
+  }
+  rc = check_bound(ctx, bound, round);
+  if (rc) return rc;
+  if (p && p->chunk_budget)
+    return set_err(ctx, DITREE_E_ARG, "expand_round_bounded: chunk budgets are not built (p->chunk_budget must be NULL)");
+  return expand_round_impl(ctx, tree, forest, round, p, stream, scenes ? scenes->tree_scene : nullptr, bound);
+}
+
+int32_t ditree_accept_bounded(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round, const ditree_bound* bound,
+                              void* stream) {
+  if (!ctx) return DITREE_E_ARG;
+  int rc = check_tree(ctx, tree);
+  if (rc) return rc;
+  rc = check_round(ctx, round);
+  if (rc) return rc;
+  rc = check_bound(ctx, bound, round);
+  if (rc) return rc;
+  if (tree->obstacle_ahead || tree->hist)
+    return set_err(ctx, DITREE_E_ARG, "accept_bounded: a run_type-0 car tree (no obstacle flags or hist)");
+  if (round->B == 0) return DITREE_OK;
+  const AheadArg ts = ahead_samples();
+  launch_accept_bounded(*tree, *round, *bound, ctx->maze, ctx->rows, ctx->cols, ts, (hipStream_t)stream);
+  HIP_TRY(ctx, hipGetLastError());
+  return DITREE_OK;
+}
+
+int32_t ditree_forest_accept_bounded(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
+                                     const ditree_round* round, const ditree_bound* bound, void* stream) {
+  if (!ctx) return DITREE_E_ARG;
+  int rc = check_round(ctx, round);
+  if (rc) return rc;
+  rc = check_forest(ctx, tree, forest, round->B, "forest_accept_bounded");
+  if (rc) return rc;
+  rc = check_bound(ctx, bound, round);
+  if (rc) return rc;
+  if (tree->obstacle_ahead || tree->hist)
+    return set_err(ctx, DITREE_E_ARG, "forest_accept_bounded: a forest is one rank's run_type-0 car tree (no obstacle flags or hist)");
+  if (round->B == 0) return DITREE_OK;
+  const AheadArg ts = ahead_samples();
+  launch_forest_accept_bounded(*tree, *round, forest->off, forest->counters, forest->n_trees, forest->tree_capacity, *bound,
+                               ctx->maze, ctx->rows, ctx->cols, ts, (hipStream_t)stream);
+  HIP_TRY(ctx, hipGetLastError());
+  return DITREE_OK;
 }
 
 int32_t ditree_forest_fallback_goals(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const double* goal_xy,

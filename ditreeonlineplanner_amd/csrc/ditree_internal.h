@@ -121,6 +121,18 @@ void launch_nn_forest(const double* queries, int q_stride, int B, const double* 
                       uint8_t* out_has_prev, hipStream_t s, int S = 6, int D = 2);
 void launch_forest_fallback(const double* goals, int T, const double* node_xy, const int32_t* counters, int C, int32_t* out_idx,
                             hipStream_t s);
+// the bound of the "anytime_pruned" rounds travels to the kernels as the public descriptor (include/ditree.h ditree_bound)
+using BoundArg = ditree_bound;
+void launch_nn_argmin_bounded(const double* queries, int q_stride, int B, const double* node_xy, int N, int32_t* out_idx,
+                              const double* node_state, const double* node_last_action, const uint8_t* node_has_prev,
+                              double* out_state, double* out_prev_action, uint8_t* out_has_prev, const int32_t* key,
+                              const int32_t* cost, const int32_t* counters, hipStream_t s, int S = 6, int D = 2);
+void launch_nn_forest_bounded(const double* queries, int q_stride, int B, const double* node_xy, const int32_t* off, int T,
+                              const int32_t* counters, int C, int32_t* out_idx, const double* node_state,
+                              const double* node_last_action, const uint8_t* node_has_prev, double* out_state,
+                              double* out_prev_action, uint8_t* out_has_prev, const int32_t* key, const int32_t* cost,
+                              hipStream_t s, int S = 6, int D = 2);
+void launch_bound_keys(const double* xy, int first, int n, int C, const BoundArg& bd, hipStream_t s);
 void launch_local_map_scenes(const SceneArg& sc, const double* state, const int32_t* active, const int32_t* idx, int B, int n,
                              const AxisArg& axis, double s_global, float* out, hipStream_t s, int state_stride);
 void launch_row_scene(const int32_t* off, int T, const int32_t* tree_scene, int B, int32_t* row_scene, hipStream_t s);
@@ -190,6 +202,11 @@ void launch_accept_best(const ditree_tree& t, const ditree_round& r, int32_t* co
                         const AheadArg& ts, hipStream_t s);
 void launch_forest_accept_best(const ditree_tree& t, const ditree_round& r, const int32_t* off, int32_t* counters, int T, int C,
                                int32_t* cost, const unsigned char* maze, int rows, int cols, const AheadArg& ts, hipStream_t s);
+void launch_accept_bounded(const ditree_tree& t, const ditree_round& r, const BoundArg& bd, const unsigned char* maze, int rows,
+                           int cols, const AheadArg& ts, hipStream_t s);
+void launch_forest_accept_bounded(const ditree_tree& t, const ditree_round& r, const int32_t* off, int32_t* counters, int T, int C,
+                                  const BoundArg& bd, const unsigned char* maze, int rows, int cols, const AheadArg& ts,
+                                  hipStream_t s);
 void launch_obstacle_ahead(const unsigned char* maze, int rows, int cols, const double* state, int stride, int B,
                            const AheadArg& ts, uint8_t* out, hipStream_t s);
 void launch_fallback_select(const ditree_tree& t, int n_nodes, double gx, double gy, const double* path_dev, int P,

@@ -42,16 +42,43 @@ __device__ __forceinline__ void stage_maze(unsigned char* lds, const unsigned ch
 // One wave per group of QPW queries; lanes stride the node array (coalesced 16-B loads),
 // then a 64-lane arg-min reduction carrying (distance, index); ties -> lowest index.
 #define NN_QPW 4
+// The bound of a branch-and-bound round (include/ditree.h ditree_bound): U = cost[incumbent] as the tree's counter row names
+// it, INT32_MAX without one.  The counter row is not written between a round's nearest-node search and its accept's pick, so
+// every kernel of the round reads the same value.
+__device__ __forceinline__ int bound_of(const int32_t* __restrict__ counters, const int32_t* __restrict__ cost) {
+  const int inc = counters[1];
+  return inc < 0 ? 0x7fffffff : cost[inc];
+}
+// The rows a path from (x, y) still needs at best to reach the goal disc, at `reach` metres per row: the norm is
+// fallback_select_kernel's, sqrt(fma(dy, dy, dx*dx)); 0 inside the disc and for a NaN distance, at most 2^30.  The one place
+// where the mode's heuristic is computed (keys of new nodes, keys of roots, the accept's pre-pass).
+__device__ __forceinline__ int bound_h(double x, double y, double gx, double gy, double goal_radius, double reach) {
+  const double dx = x - gx, dy = y - gy;
+  const double d = sqrt(fma(dy, dy, dx * dx));
+  const double q = (d - goal_radius) / reach;
+  if (!(q > 0.0)) return 0;
+  const double c = ceil(q);
+  return c < 1073741824.0 ? (int)c : 1073741824;
+}
+// MASK (the planner's "anytime_pruned" mode, ditree_nn_argmin_bounded): only open nodes, key[n] < U, take part in the compare
+// -- eight more independent coalesced i32 loads per trip beside the eight double2 loads; a closed node is masked exactly as an
+// index past N is.  Scan order, strict '<' and the reduction are unchanged, so with U = INT32_MAX the result is the unmasked
+// kernel's, and a scan without an open node ends as an all-NaN scan does (node 0).  MASK = false is the kernel as it was before
+// the flag: the three trailing arguments are not read.
+template <bool MASK>
 __global__ void __launch_bounds__(256)
 nn_argmin_kernel(const double* __restrict__ queries, int q_stride, int B, const double2* __restrict__ node_xy,
                  int N, int32_t* __restrict__ out_idx, const double* __restrict__ node_state,
                  const double* __restrict__ node_last_action, const uint8_t* __restrict__ node_has_prev,
                  double* __restrict__ out_state, double* __restrict__ out_prev_action,
-                 uint8_t* __restrict__ out_has_prev, int S, int D) {
+                 uint8_t* __restrict__ out_has_prev, int S, int D, const int32_t* __restrict__ key,
+                 const int32_t* __restrict__ cost, const int32_t* __restrict__ counters) {
   const int lane = threadIdx.x & 63;
   const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int q0 = wave * NN_QPW;
   if (q0 >= B) return;
+  int U = 0x7fffffff;
+  if constexpr (MASK) U = bound_of(counters, cost);
   double qx[NN_QPW], qy[NN_QPW], best[NN_QPW];
   int bidx[NN_QPW];
 #pragma unroll
@@ -69,10 +96,17 @@ nn_argmin_kernel(const double* __restrict__ queries, int q_stride, int B, const 
     double2 p[8];
 #pragma unroll
     for (int u = 0; u < 8; ++u) p[u] = node_xy[min(i + u * WAVE, N - 1)];
+    int kk[8];
+    if constexpr (MASK) {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) kk[u] = key[min(i + u * WAVE, N - 1)];
+    }
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
       const int iu = i + u * WAVE;
-      if (iu < N) {
+      bool in = iu < N;
+      if constexpr (MASK) in = in && kk[u] < U;
+      if (in) {
 #pragma unroll
         for (int k = 0; k < NN_QPW; ++k) {
           double dx = qx[k] - p[u].x, dy = qy[k] - p[u].y;
@@ -110,9 +144,19 @@ void launch_nn_argmin(const double* queries, int q_stride, int B, const double* 
                       double* out_state, double* out_prev_action, uint8_t* out_has_prev, hipStream_t s, int S, int D) {
   int waves = (B + NN_QPW - 1) / NN_QPW;
   int blocks = (waves + 3) / 4;
-  hipLaunchKernelGGL(nn_argmin_kernel, dim3(blocks), dim3(256), 0, s, queries, q_stride, B,
+  hipLaunchKernelGGL(nn_argmin_kernel<false>, dim3(blocks), dim3(256), 0, s, queries, q_stride, B,
                      (const double2*)node_xy, N, out_idx, node_state, node_last_action, node_has_prev, out_state,
-                     out_prev_action, out_has_prev, S, D);
+                     out_prev_action, out_has_prev, S, D, nullptr, nullptr, nullptr);
+}
+void launch_nn_argmin_bounded(const double* queries, int q_stride, int B, const double* node_xy, int N, int32_t* out_idx,
+                              const double* node_state, const double* node_last_action, const uint8_t* node_has_prev,
+                              double* out_state, double* out_prev_action, uint8_t* out_has_prev, const int32_t* key,
+                              const int32_t* cost, const int32_t* counters, hipStream_t s, int S, int D) {
+  int waves = (B + NN_QPW - 1) / NN_QPW;
+  int blocks = (waves + 3) / 4;
+  hipLaunchKernelGGL(nn_argmin_kernel<true>, dim3(blocks), dim3(256), 0, s, queries, q_stride, B,
+                     (const double2*)node_xy, N, out_idx, node_state, node_last_action, node_has_prev, out_state,
+                     out_prev_action, out_has_prev, S, D, key, cost, counters);
 }
 
 // Segmented nearest node of a forest (include/ditree.h ditree_forest): query q belongs to tree t -- the t whose candidate range
@@ -126,14 +170,17 @@ void launch_nn_argmin(const double* queries, int q_stride, int B, const double* 
 // neighbouring doubles, so two nodes whose squares differ in the last place can have equal norms; the reference then returns
 // the lower index, which the square's strict '<' would not.  The expansion search (NORM = false) keeps the squared distance:
 // it is pinned bit for bit to the KDTree goldens, and its instantiation is the kernel as it was before the flag.
-template <bool NORM>
+// MASK: nn_argmin_kernel's, with each tree's own bound U read from its counter row; key and cost are indexed by the global slot.
+// MASK = false leaves the two instantiations as they were before the flag: the two trailing arguments are not read.
+template <bool NORM, bool MASK = false>
 __global__ void __launch_bounds__(256)
 nn_forest_kernel(const double* __restrict__ queries, int q_stride, int B, const double2* __restrict__ node_xy,
                  const int32_t* __restrict__ off, int T, const int32_t* __restrict__ counters, int C, int skip,
                  int32_t* __restrict__ out_idx, const double* __restrict__ node_state,
                  const double* __restrict__ node_last_action, const uint8_t* __restrict__ node_has_prev,
                  double* __restrict__ out_state, double* __restrict__ out_prev_action,
-                 uint8_t* __restrict__ out_has_prev, int S, int D) {
+                 uint8_t* __restrict__ out_has_prev, int S, int D, const int32_t* __restrict__ key,
+                 const int32_t* __restrict__ cost) {
   const int lane = threadIdx.x & 63;
   const int q = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   if (q >= B) return;
@@ -152,14 +199,23 @@ nn_forest_kernel(const double* __restrict__ queries, int q_stride, int B, const 
   const double qx = queries[(size_t)q * q_stride + 0], qy = queries[(size_t)q * q_stride + 1];
   double best = __builtin_huge_val();
   int bidx = 0x7fffffff;
+  int U = 0x7fffffff;
+  if constexpr (MASK) U = bound_of(counters + (size_t)t * 8, cost);
   for (int i = lane; i < n; i += 8 * WAVE) {
     double2 p[8];
 #pragma unroll
     for (int u = 0; u < 8; ++u) p[u] = node_xy[base + min(i + u * WAVE, n - 1)];
+    int kk[8];
+    if constexpr (MASK) {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) kk[u] = key[base + min(i + u * WAVE, n - 1)];
+    }
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
       const int iu = i + u * WAVE;
-      if (iu < n) {
+      bool in = iu < n;
+      if constexpr (MASK) in = in && kk[u] < U;
+      if (in) {
         double dx = qx - p[u].x, dy = qy - p[u].y;
         double d;
         if constexpr (NORM) d = sqrt(fma(dy, dy, dx * dx));
@@ -193,14 +249,23 @@ void launch_nn_forest(const double* queries, int q_stride, int B, const double* 
                       uint8_t* out_has_prev, hipStream_t s, int S, int D) {
   hipLaunchKernelGGL(nn_forest_kernel<false>, dim3((B + 3) / 4), dim3(256), 0, s, queries, q_stride, B, (const double2*)node_xy,
                      off, T, counters, C, skip, out_idx, node_state, node_last_action, node_has_prev, out_state, out_prev_action,
-                     out_has_prev, S, D);
+                     out_has_prev, S, D, nullptr, nullptr);
+}
+void launch_nn_forest_bounded(const double* queries, int q_stride, int B, const double* node_xy, const int32_t* off, int T,
+                              const int32_t* counters, int C, int32_t* out_idx, const double* node_state,
+                              const double* node_last_action, const uint8_t* node_has_prev, double* out_state,
+                              double* out_prev_action, uint8_t* out_has_prev, const int32_t* key, const int32_t* cost,
+                              hipStream_t s, int S, int D) {
+  hipLaunchKernelGGL((nn_forest_kernel<false, true>), dim3((B + 3) / 4), dim3(256), 0, s, queries, q_stride, B,
+                     (const double2*)node_xy, off, T, counters, C, 0, out_idx, node_state, node_last_action, node_has_prev,
+                     out_state, out_prev_action, out_has_prev, S, D, key, cost);
 }
 // The fallback choice of every tree (planners/RRT.py:233-237): query t is tree t's goal, the scan covers its nodes 1.. with the
 // norm as the key.
 void launch_forest_fallback(const double* goals, int T, const double* node_xy, const int32_t* counters, int C, int32_t* out_idx,
                             hipStream_t s) {
   hipLaunchKernelGGL(nn_forest_kernel<true>, dim3((T + 3) / 4), dim3(256), 0, s, goals, 2, T, (const double2*)node_xy, nullptr, T,
-                     counters, C, 1, out_idx, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 6, 2);
+                     counters, C, 1, out_idx, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 6, 2, nullptr, nullptr);
 }
 
 // ------------------------------------------------------------------------- local map
@@ -1223,16 +1288,28 @@ __device__ __forceinline__ void accept_scan_tree(int32_t* __restrict__ counters,
 // The scan of ditree_accept_best: every candidate of the round in index order, nothing cut at a goal and no sticky-done
 // phantom.  A candidate gets a node slot iff it did not collide; the goal node is chosen after the commit (accept_pick_tree),
 // so counters[1], [2] and [5] are not touched here.  Arguments as accept_scan_tree's.
+// BOUND (ditree_accept_bounded): on entry node_id[b] holds f = cost + h of candidate b (accept_cost_kernel); a candidate that
+// did not collide gets a slot only if f < U, U the tree's bound as of the round's start, else it is pruned: node id -1, counted
+// in stats[1] (since the tree's reset) and stats[3] (this round).  The overflow flag is raised by unpruned rows alone, because
+// only they are ranked.  Every candidate still counts, adds its chunks and visits its parent.
+template <bool BOUND = false>
 __device__ __forceinline__ void accept_best_scan_tree(int32_t* __restrict__ counters, int32_t* __restrict__ num_visit,
                                                       const int32_t* __restrict__ status, const int32_t* __restrict__ chunks_run,
                                                       const int32_t* __restrict__ parent, int32_t* __restrict__ node_id, int B,
-                                                      int node_base, int cap) {
+                                                      int node_base, int cap, const int32_t* __restrict__ cost = nullptr,
+                                                      int32_t* __restrict__ stats = nullptr) {
   __shared__ int s_iters;
+  __shared__ int s_pruned;
   __shared__ int s_wave_sum[16];
   const int tid = threadIdx.x;
   if (tid == 0) s_iters = 0;
+  if constexpr (BOUND) {
+    if (tid == 0) s_pruned = 0;
+  }
   __syncthreads();
   const int n0 = counters[0];
+  int U = 0x7fffffff;
+  if constexpr (BOUND) U = bound_of(counters, cost);
   // ordered prefix sum of accepted flags over all B candidates, 1024 at a time
   int base = 0;
   for (int start = 0; start < B; start += blockDim.x) {
@@ -1240,6 +1317,9 @@ __device__ __forceinline__ void accept_best_scan_tree(int32_t* __restrict__ coun
     int acc = 0, it = 0;
     if (b < B) {
       acc = (status[b] & 0xff) != DITREE_ST_COLLIDED;
+      if constexpr (BOUND) {
+        if (acc && !(node_id[b] < U)) { acc = 0; atomicAdd(&s_pruned, 1); }
+      }
       it = chunks_run[b];
       atomicAdd(&num_visit[parent[b]], 1);
     }
@@ -1274,6 +1354,7 @@ __device__ __forceinline__ void accept_best_scan_tree(int32_t* __restrict__ coun
     counters[3] += s_iters;
     counters[4] += B;
     counters[7] = -1;
+    if constexpr (BOUND) { stats[1] += s_pruned; stats[3] = s_pruned; }
   }
 }
 // The pick of ditree_accept_best, after the commit: among the round's goal candidates that got a node slot, the smallest
@@ -1296,6 +1377,17 @@ __device__ __forceinline__ void accept_pick_tree(int32_t* __restrict__ counters,
     if (inc < 0 || c < cost[inc]) counters[1] = node_id[b];
   }
 }
+// The tail of a bounded pick (thread 0, which also wrote the incumbent just above): the bound the next round will use and
+// whether any node can still be open -- key[root] is the smallest key a tree can hold below its root, so key[root] >= U closes
+// the whole tree.  stats: [0] U, [1] candidates pruned since the reset, [2] exhausted, [3] candidates pruned this round.
+__device__ __forceinline__ void bound_stats_tree(const int32_t* __restrict__ counters, const int32_t* __restrict__ cost,
+                                                 const int32_t* __restrict__ key, int root, int32_t* __restrict__ stats) {
+  if (threadIdx.x == 0) {
+    const int U = bound_of(counters, cost);
+    stats[0] = U;
+    stats[2] = key[root] >= U ? 1 : 0;
+  }
+}
 __global__ void __launch_bounds__(1024)
 accept_scan_kernel(ditree_tree t, ditree_round r, int emulate_sticky) {
   accept_scan_tree(t.counters, t.num_visit, r.status, r.chunks_run, r.parent, r.node_id, r.B, 0, t.capacity, 0, emulate_sticky);
@@ -1307,6 +1399,70 @@ accept_best_scan_kernel(ditree_tree t, ditree_round r) {
 __global__ void __launch_bounds__(1024)
 accept_pick_kernel(ditree_tree t, ditree_round r, const int32_t* __restrict__ cost) {
   accept_pick_tree(t.counters, r.status, r.node_id, cost, r.B);
+}
+__global__ void __launch_bounds__(1024)
+accept_bounded_scan_kernel(ditree_tree t, ditree_round r, BoundArg bd) {
+  accept_best_scan_tree<true>(t.counters, t.num_visit, r.status, r.chunks_run, r.parent, r.node_id, r.B, 0, t.capacity, bd.cost,
+                              bd.stats);
+}
+__global__ void __launch_bounds__(1024)
+accept_bounded_pick_kernel(ditree_tree t, ditree_round r, BoundArg bd) {
+  accept_pick_tree(t.counters, r.status, r.node_id, bd.cost, r.B);
+  bound_stats_tree(t.counters, bd.cost, bd.key, 0, bd.stats);
+}
+__global__ void __launch_bounds__(1024)
+forest_accept_bounded_scan_kernel(ditree_tree t, ditree_round r, const int32_t* __restrict__ off, int32_t* __restrict__ counters,
+                                  int C, BoundArg bd) {
+  const int tr = blockIdx.x;
+  const int lo = off[tr], n = off[tr + 1] - lo;
+  if (n <= 0) return;
+  accept_best_scan_tree<true>(counters + (size_t)tr * 8, t.num_visit, r.status + lo, r.chunks_run + lo, r.parent + lo,
+                              r.node_id + lo, n, tr * C, C, bd.cost, bd.stats + (size_t)tr * 4);
+}
+__global__ void __launch_bounds__(1024)
+forest_accept_bounded_pick_kernel(ditree_round r, const int32_t* __restrict__ off, int32_t* __restrict__ counters, int C,
+                                  BoundArg bd) {
+  const int tr = blockIdx.x;
+  const int lo = off[tr], n = off[tr + 1] - lo;
+  if (n <= 0) return;
+  accept_pick_tree(counters + (size_t)tr * 8, r.status + lo, r.node_id + lo, bd.cost, n);
+  bound_stats_tree(counters + (size_t)tr * 8, bd.cost, bd.key, tr * C, bd.stats + (size_t)tr * 4);
+}
+// The pre-pass of a bounded accept, one wave per candidate: a goal reached in mid-chunk leaves all-zero rows behind it, so what
+// a candidate's node would cost is known only after the zero-row filter -- the commit kernel's ballot over the rows of the
+// chunks that ran.  f = cost[parent] + kept edge states + 1 + h(end xy) goes to node_id[b], where the scan reads it before it
+// writes the id.  C > 0: a forest, the candidate's tree is its parent's (parent / C), with that tree's counter row and goal.
+// A tree without an incumbent prunes nothing: its candidates skip the count.
+__global__ void __launch_bounds__(64)
+accept_cost_kernel(ditree_tree t, ditree_round r, const int32_t* __restrict__ counters, int C, BoundArg bd) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int par = r.parent[b];
+  const int tr = C > 0 ? par / C : 0;
+  const int U = bound_of(counters + (size_t)tr * 8, bd.cost);
+  if (U == 0x7fffffff || (r.status[b] & 0xff) == DITREE_ST_COLLIDED) {
+    if (lane == 0) r.node_id[b] = 0;
+    return;
+  }
+  const int A = t.A, S = t.state_dim;
+  const double* cs = r.states + (size_t)b * t.n_chunks * (A + 1) * S;
+  const int rows_s = r.chunks_run[b] * (A + 1);
+  int ns = 0;
+  for (int row = 0; row < rows_s; ++row) {
+    const double v = lane < S ? cs[(size_t)row * S + lane] : 0.0;
+    if (__ballot(v != 0.0) != 0ull) ++ns;
+  }
+  if (lane == 0) {
+    const double ex = r.end_state[(size_t)b * S], ey = r.end_state[(size_t)b * S + 1];
+    r.node_id[b] = bd.cost[par] + ns + 1 + bound_h(ex, ey, bd.goal_xy[2 * tr], bd.goal_xy[2 * tr + 1], bd.goal_radius, bd.reach);
+  }
+}
+// key[n] = cost[n] + h(xy[n]) for nodes [first, first + n) (ditree_bound_keys: the roots; C > 0: node n belongs to tree n / C).
+__global__ void bound_keys_kernel(const double2* __restrict__ xy, int first, int n, int C, BoundArg bd) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int k = first + i, tr = C > 0 ? k / C : 0;
+  const double2 p = xy[k];
+  bd.key[k] = bd.cost[k] + bound_h(p.x, p.y, bd.goal_xy[2 * tr], bd.goal_xy[2 * tr + 1], bd.goal_radius, bd.reach);
 }
 __global__ void __launch_bounds__(1024)
 forest_accept_best_scan_kernel(ditree_tree t, ditree_round r, const int32_t* __restrict__ off, int32_t* __restrict__ counters, int C) {
@@ -1343,10 +1499,12 @@ forest_accept_scan_kernel(ditree_tree t, ditree_round r, const int32_t* __restri
 // FOREST: the phantom candidate is the one in the counter row of the node's own tree (id / C of the forest's counters).
 // cost != NULL (ditree_accept_best): cost[id] = rows of the path to the node = cost[parent] + kept edge states + 1; the
 // parent is a node of an earlier round, so its cost is final.
-template <bool FOREST>
+// KEY (ditree_accept_bounded): key[id] = cost[id] + h(the node's xy, its tree's goal), written where cost is.  KEY = false
+// leaves the two instantiations as they were before the flag: the trailing argument is not read.
+template <bool FOREST, bool KEY = false>
 __global__ void __launch_bounds__(64)
 accept_commit_kernel(ditree_tree t, ditree_round r, const unsigned char* __restrict__ maze, int rows, int cols,
-                     AheadArg ts, const int32_t* __restrict__ forest_counters, int C, int32_t* __restrict__ cost) {
+                     AheadArg ts, const int32_t* __restrict__ forest_counters, int C, int32_t* __restrict__ cost, BoundArg bd) {
   const int b = blockIdx.x;
   const int id = r.node_id[b];
   if (id < 0) return;
@@ -1415,6 +1573,10 @@ accept_commit_kernel(ditree_tree t, ditree_round r, const unsigned char* __restr
     t.edge_nstates[id] = ns;
     t.edge_nactions[id] = na;
     if (cost != nullptr) cost[id] = cost[par] + ns + 1;
+    if constexpr (KEY) {
+      const int tr = FOREST ? id / C : 0;
+      bd.key[id] = cost[par] + ns + 1 + bound_h(ex, ey, bd.goal_xy[2 * tr], bd.goal_xy[2 * tr + 1], bd.goal_radius, bd.reach);
+    }
     if (t.edge_owner != nullptr) t.edge_owner[id] = owner;
     if (t.obstacle_ahead != nullptr)                                   // RRT.py:202-205 (run_type > 0)
       t.obstacle_ahead[id] = obstacle_ahead_dev(ex, ey, psi, maze, rows, cols, ts) ? 1 : 0;
@@ -1512,22 +1674,42 @@ void launch_round_unpack(const ditree_tree& t, const ditree_round& r, const doub
 void launch_accept(const ditree_tree& t, const ditree_round& r, int emulate_sticky, const unsigned char* maze, int rows,
                    int cols, const AheadArg& ts, hipStream_t s) {
   hipLaunchKernelGGL(accept_scan_kernel, dim3(1), dim3(1024), 0, s, t, r, emulate_sticky);
-  hipLaunchKernelGGL(accept_commit_kernel<false>, dim3(r.B), dim3(64), 0, s, t, r, maze, rows, cols, ts, nullptr, 0, nullptr);
+  hipLaunchKernelGGL(accept_commit_kernel<false>, dim3(r.B), dim3(64), 0, s, t, r, maze, rows, cols, ts, nullptr, 0, nullptr, BoundArg{});
 }
 void launch_accept_best(const ditree_tree& t, const ditree_round& r, int32_t* cost, const unsigned char* maze, int rows, int cols,
                         const AheadArg& ts, hipStream_t s) {
   hipLaunchKernelGGL(accept_best_scan_kernel, dim3(1), dim3(1024), 0, s, t, r);
-  hipLaunchKernelGGL(accept_commit_kernel<false>, dim3(r.B), dim3(64), 0, s, t, r, maze, rows, cols, ts, nullptr, 0, cost);
+  hipLaunchKernelGGL(accept_commit_kernel<false>, dim3(r.B), dim3(64), 0, s, t, r, maze, rows, cols, ts, nullptr, 0, cost, BoundArg{});
   hipLaunchKernelGGL(accept_pick_kernel, dim3(1), dim3(1024), 0, s, t, r, cost);
 }
 void launch_forest_accept(const ditree_tree& t, const ditree_round& r, const int32_t* off, int32_t* counters, int T, int C,
                           int emulate_sticky, const unsigned char* maze, int rows, int cols, const AheadArg& ts, hipStream_t s) {
   hipLaunchKernelGGL(forest_accept_scan_kernel, dim3(T), dim3(1024), 0, s, t, r, off, counters, C, emulate_sticky);
-  hipLaunchKernelGGL(accept_commit_kernel<true>, dim3(r.B), dim3(64), 0, s, t, r, maze, rows, cols, ts, counters, C, nullptr);
+  hipLaunchKernelGGL(accept_commit_kernel<true>, dim3(r.B), dim3(64), 0, s, t, r, maze, rows, cols, ts, counters, C, nullptr, BoundArg{});
 }
 void launch_forest_accept_best(const ditree_tree& t, const ditree_round& r, const int32_t* off, int32_t* counters, int T, int C,
                                int32_t* cost, const unsigned char* maze, int rows, int cols, const AheadArg& ts, hipStream_t s) {
   hipLaunchKernelGGL(forest_accept_best_scan_kernel, dim3(T), dim3(1024), 0, s, t, r, off, counters, C);
-  hipLaunchKernelGGL(accept_commit_kernel<true>, dim3(r.B), dim3(64), 0, s, t, r, maze, rows, cols, ts, counters, C, cost);
+  hipLaunchKernelGGL(accept_commit_kernel<true>, dim3(r.B), dim3(64), 0, s, t, r, maze, rows, cols, ts, counters, C, cost, BoundArg{});
   hipLaunchKernelGGL(forest_accept_pick_kernel, dim3(T), dim3(1024), 0, s, r, off, counters, cost);
+}
+// The bounded accept (include/ditree.h ditree_accept_bounded): cost pre-pass -> bounded scan -> commit with the key column ->
+// pick with the stats row.
+void launch_accept_bounded(const ditree_tree& t, const ditree_round& r, const BoundArg& bd, const unsigned char* maze, int rows,
+                           int cols, const AheadArg& ts, hipStream_t s) {
+  hipLaunchKernelGGL(accept_cost_kernel, dim3(r.B), dim3(64), 0, s, t, r, t.counters, 0, bd);
+  hipLaunchKernelGGL(accept_bounded_scan_kernel, dim3(1), dim3(1024), 0, s, t, r, bd);
+  hipLaunchKernelGGL((accept_commit_kernel<false, true>), dim3(r.B), dim3(64), 0, s, t, r, maze, rows, cols, ts, nullptr, 0, bd.cost, bd);
+  hipLaunchKernelGGL(accept_bounded_pick_kernel, dim3(1), dim3(1024), 0, s, t, r, bd);
+}
+void launch_forest_accept_bounded(const ditree_tree& t, const ditree_round& r, const int32_t* off, int32_t* counters, int T, int C,
+                                  const BoundArg& bd, const unsigned char* maze, int rows, int cols, const AheadArg& ts,
+                                  hipStream_t s) {
+  hipLaunchKernelGGL(accept_cost_kernel, dim3(r.B), dim3(64), 0, s, t, r, counters, C, bd);
+  hipLaunchKernelGGL(forest_accept_bounded_scan_kernel, dim3(T), dim3(1024), 0, s, t, r, off, counters, C, bd);
+  hipLaunchKernelGGL((accept_commit_kernel<true, true>), dim3(r.B), dim3(64), 0, s, t, r, maze, rows, cols, ts, counters, C, bd.cost, bd);
+  hipLaunchKernelGGL(forest_accept_bounded_pick_kernel, dim3(T), dim3(1024), 0, s, r, off, counters, C, bd);
+}
+void launch_bound_keys(const double* xy, int first, int n, int C, const BoundArg& bd, hipStream_t s) {
+  hipLaunchKernelGGL(bound_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, s, (const double2*)xy, first, n, C, bd);
 }

@@ -18,20 +18,27 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import Round, RoundParams, Tree, check, lib
+from ._lib import Bound, Round, RoundParams, Tree, check, lib
 from .ops import CAR_NORM, Context, _dbl, _flt, _ptr, local_axis
 
 CNT_NODES, CNT_GOAL, CNT_LATCH, CNT_ITERS, CNT_CANDS, CNT_STICKY, CNT_OVERFLOW, CNT_PHANTOM = range(8)
+# include/ditree.h ditree_bound.stats: the bound after the last accept, candidates pruned since the reset, no open node left,
+# candidates pruned by the last accept
+ST_BOUND, ST_PRUNED, ST_EXHAUSTED, ST_PRUNED_ROUND = range(4)
+NO_BOUND = 2 ** 31 - 1
+STATS_ROOT = np.array([NO_BOUND, 0, 0, 0], dtype=np.int32)
 
 
 class DeviceTree:
     """planners/base_planner.py:24-34 ``Node`` as a struct of arrays in HBM (include/ditree.h ditree_tree).  ``state_dim`` /
     ``action_dim``: 6 / 2 for the car, 29 / 8 for the ant; ``hist``: keep the last three rows of every node's edge (what the
     first sampler call of a child sees with obs_history 3 -- the ant); ``cost``: keep every node's path cost (the rows
-    ``tree_path`` returns for it), which the ``solution`` modes other than "first" rank goal nodes by."""
+    ``tree_path`` returns for it), which the ``solution`` modes other than "first" rank goal nodes by; ``key``: keep beside it
+    every node's key = cost + the rows it still needs at best (include/ditree.h "branch and bound": "anytime_pruned"), and a
+    stats row behind the counters, in the same small buffer, so that one copy reads both."""
 
     def __init__(self, ctx: Context, capacity: int, n_chunks: int, A: int, track_obstacle_ahead: bool = False,
-                 state_dim: int = 6, action_dim: int = 2, hist: bool = False, cost: bool = False):
+                 state_dim: int = 6, action_dim: int = 2, hist: bool = False, cost: bool = False, key: bool = False):
         dev = ctx.device
         self.capacity, self.n_chunks, self.A = capacity, n_chunks, A
         self.S, self.D = S, D = int(state_dim), int(action_dim)
@@ -46,14 +53,18 @@ class DeviceTree:
         self.edge_actions = torch.zeros(capacity, n_chunks * A, D, dtype=f64, device=dev)
         self.edge_nstates = torch.zeros(capacity, dtype=i32, device=dev)
         self.edge_nactions = torch.zeros(capacity, dtype=i32, device=dev)
-        self.counters = torch.zeros(8, dtype=i32, device=dev)
+        self._cnt_buf = torch.zeros(12 if key else 8, dtype=i32, device=dev)     # counters [+ the bound's stats row]
+        self.counters = self._cnt_buf[:8]
+        self.stats = self._cnt_buf[8:] if key else None
+        self.stats_host = STATS_ROOT.copy() if key else None
         # RRT.py:202-205: per-node check_obstacle_ahead flag, kept only for run_type > 0
         self.obstacle_ahead = torch.zeros(capacity, dtype=u8, device=dev) if track_obstacle_ahead else None
         # rank holding each node's edge rows (sharded rounds keep trajectories on the producing rank); -1 = every rank
         self.edge_owner = torch.full((capacity,), -1, dtype=i32, device=dev)
         self.hist = torch.zeros(capacity, 3, S, dtype=f64, device=dev) if hist else None
         self.hist_n = torch.zeros(capacity, dtype=i32, device=dev) if hist else None
-        self.cost = torch.zeros(capacity, dtype=i32, device=dev) if cost else None      # not part of the descriptor
+        self.cost = torch.zeros(capacity, dtype=i32, device=dev) if cost or key else None   # not part of the descriptor
+        self.key = torch.zeros(capacity, dtype=i32, device=dev) if key else None             # nor this (ditree_bound)
         self.desc = Tree(capacity, n_chunks, A, S, D, *[None if t is None else t.data_ptr() for t in (
             self.state, self.xy, self.parent, self.last_action, self.has_prev, self.num_visit,
             self.edge_states, self.edge_actions, self.edge_nstates, self.edge_nactions, self.obstacle_ahead,
@@ -83,12 +94,17 @@ class DeviceTree:
         self.counters[CNT_NODES] = 1
         self.counters[CNT_GOAL] = -1
         self.counters[CNT_PHANTOM] = -1
+        if self.stats is not None:                      # the root's key is the engine's to set: it knows the goal
+            self.stats.copy_(torch.as_tensor(STATS_ROOT))
+            self.stats_host = STATS_ROOT.copy()
         self.n_nodes_host = 1
 
     def read_counters(self):
-        c = self.counters.cpu().numpy()
+        c = self._cnt_buf.cpu().numpy()                 # one small copy: the counters and, where kept, the stats row
         self.n_nodes_host = int(c[CNT_NODES])
-        return c
+        if self.stats is not None:
+            self.stats_host = c[8:]
+        return c[:8]
 
 
 class RoundBuffers:
@@ -248,12 +264,26 @@ def tree_path(tr, node, n_nodes, base=0, edge_rows=None):
     return path, actions
 
 
-SOLUTIONS = ("first", "best_of_round", "anytime")
+SOLUTIONS = ("first", "best_of_round", "anytime", "anytime_pruned")
+ANYTIME = ("anytime", "anytime_pruned")           # the modes that plan on after the first goal-reaching round
+CAR_GOAL_RADIUS = 0.5                             # car_env.py:346-351, the rollout's goal test
+CAR_REACH = 5 * 0.02                              # planners/base_planner.py:87 max_v x the car env's dt: metres per path row
+
+
+def check_reach(reach):
+    """The metres a path row is assumed to cover at most ("anytime_pruned"): a positive finite number."""
+    try:
+        r = float(reach)
+    except (TypeError, ValueError):
+        r = float("nan")
+    if not (np.isfinite(r) and r > 0.0):
+        raise ValueError(f"reach must be a positive finite number of metres per path row, got {reach!r}")
+    return r
 
 
 def check_solution(solution, emulate_sticky_done, world_size=1, run_type=0):
-    """The scope of the ``solution`` modes other than "first" (ditree_accept_best): one rank, run_type 0, no sticky-done
-    emulation (its phantom candidate belongs to the first-goal rule)."""
+    """The scope of the ``solution`` modes other than "first" (ditree_accept_best, ditree_accept_bounded): one rank, run_type 0,
+    no sticky-done emulation (its phantom candidate belongs to the first-goal rule)."""
     if solution not in SOLUTIONS:
         raise ValueError(f"solution must be one of {SOLUTIONS}, got {solution!r}")
     if solution == "first":
@@ -271,15 +301,27 @@ class ExpansionEngine:
     """Batched RRT expansion on one GPU (optionally one shard of a multi-GPU round).  ``solution``: which goal-reaching
     candidate becomes the goal node -- "first" (the reference's: the lowest index, the rest of the round dropped), or, through
     ditree_accept_best, the cheapest one ("best_of_round", "anytime": every non-collided candidate of the round is appended
-    and ``goal_node`` is the incumbent, which later rounds may replace)."""
+    and ``goal_node`` is the incumbent, which later rounds may replace).  "anytime_pruned" is "anytime" until the tree holds an
+    incumbent and branch and bound from then on (include/ditree.h "branch and bound"): with ``reach`` metres per path row
+    (an assumption about the dynamics, not a theorem -- a smaller value prunes more and may prune a branch that would have
+    won), parents are chosen among the nodes that can still lead to a shorter path, candidates that cannot beat the incumbent
+    get no node, and ``exhausted`` says that no node is open any more.  A single ``prop_duration`` entry only
+    (ditree_chunk_budget runs its own, unmasked nearest-node search)."""
     STATE_DIM, ACTION_DIM, HIST = 6, 2, False
 
     def __init__(self, ctx: Context, maze, start_state, goal_state, edge_length=64, action_horizon=8,
                  pred_horizon=64, local_map_size=20, local_map_scale=0.2, s_global=1.0, batch=1024,
                  capacity=65536, k_steps=1, emulate_sticky_done=True, norm=CAR_NORM, rank=0, world_size=1,
-                 process_group=None, early_exit=False, run_type=0, goal_scale=None, prop_duration=None, solution="first"):
+                 process_group=None, early_exit=False, run_type=0, goal_scale=None, prop_duration=None, solution="first",
+                 reach=None):
         check_solution(solution, emulate_sticky_done, world_size, run_type)
         self.solution = solution
+        self.pruned = solution == "anytime_pruned"
+        if reach is not None and not self.pruned:
+            raise ValueError(f"reach belongs to solution='anytime_pruned' (got solution={solution!r})")
+        self.reach = check_reach(CAR_REACH if reach is None else reach) if self.pruned else None
+        if self.pruned and prop_duration is not None and len(prop_duration) > 1:
+            raise NotImplementedError("solution='anytime_pruned': a single prop_duration entry (the chunk-budget search is not masked)")
         self.ctx = ctx
         self.maze = np.asarray(maze, dtype=np.float32)
         # planners/RRT.py:26,149-152: per-visit edge lengths; the tree's edge capacity is the longest entry
@@ -305,7 +347,7 @@ class ExpansionEngine:
         self.init_main_path = None          # (P, >=2) reference path of an earlier plan (run_type > 0)
         self.tree = DeviceTree(ctx, capacity, self.n_chunks, self.A, track_obstacle_ahead=self.run_type > 0,
                                state_dim=self.STATE_DIM, action_dim=self.ACTION_DIM, hist=self.HIST,
-                               cost=solution != "first")
+                               cost=solution != "first", key=self.pruned)
         # sharded rounds exchange ceil(batch / world) fixed slots per rank: size the round buffers for whole slots, so a batch
         # that does not divide by the rank count is fine (the last rank's tail slots stay unused)
         per = (batch + world_size - 1) // world_size
@@ -321,7 +363,47 @@ class ExpansionEngine:
         t0, dt = get_timesteps("exp", k_steps, 4.0)
         self.t0, self.dt = t0.numpy().copy(), dt.numpy().copy()
         ctx.upload_maze(self.maze, owner=self)
+        if self.pruned:
+            self._init_bound(1, self.tree.stats)
         self.reset(start_state, goal_state)
+
+    # ------------------------------------------------------------------ the bound of "anytime_pruned"
+    def _init_bound(self, n_trees, stats):
+        """The ditree_bound descriptor: the tree's cost and key columns, one goal row per tree and the stats rows."""
+        self._bound_goals = torch.zeros(n_trees, 2, dtype=torch.float64, device=self.ctx.device)
+        self._bound_roots = []
+        self.bound = Bound(self.tree.cost.data_ptr(), self.tree.key.data_ptr(), self._bound_goals.data_ptr(), CAR_GOAL_RADIUS,
+                           self.reach, stats.data_ptr())
+
+    def _bound_goal_rows(self):
+        return np.asarray(self.env_goal, dtype=np.float64)[None, :2]
+
+    _BOUND_TREE_CAPACITY = 0                            # ditree_bound_keys: a single tree
+
+    def _bound_sync(self):
+        """Before a launch that reads the bound: the goal rows as they are now (a facade sets ``env_goal`` after ``reset``) and
+        the key of every root reset since -- on the device, by the function that keys every other node."""
+        if not self._bound_roots:
+            return
+        self._bound_goals.copy_(torch.as_tensor(np.ascontiguousarray(self._bound_goal_rows())))
+        for r in self._bound_roots:
+            check(self.ctx._h, lib().ditree_bound_keys(self.ctx._h, C.byref(self.tree.desc), C.byref(self.bound), int(r), 1,
+                                                       self._BOUND_TREE_CAPACITY, self.ctx.stream), "bound_keys")
+        self._bound_roots = []
+
+    @property
+    def exhausted(self):
+        """"anytime_pruned": no node of the tree can be open after the last accept (key[root] >= the incumbent's cost)."""
+        return self.pruned and bool(self.tree.stats_host[ST_EXHAUSTED])
+
+    @property
+    def pruned_candidates(self):
+        return int(self.tree.stats_host[ST_PRUNED]) if self.pruned else 0
+
+    def closed_nodes(self):
+        """Nodes whose key is at or past the incumbent's cost (0 without an incumbent); one reduction and one scalar copy."""
+        u = int(self.tree.stats_host[ST_BOUND])
+        return 0 if u == NO_BOUND else int((self.tree.key[:self.tree.n_nodes_host] >= u).sum().item())
 
     # ------------------------------------------------------------------ state
     def reset(self, start_state, goal_state):
@@ -331,6 +413,8 @@ class ExpansionEngine:
             raise ValueError(f"start_state must have {self.STATE_DIM} elements")
         self._derive_env_goal()
         self.tree.reset(self.start_state)
+        if self.pruned:
+            self._bound_roots = [0]
         self.generation = getattr(self, "generation", 0) + 1      # consumers caching per-tree data (node_list) key on it
 
     def _derive_env_goal(self):
@@ -445,7 +529,12 @@ class ExpansionEngine:
         self.ensure_maze()
         rp = RoundParams()
         keep = self._round_params(rp, samples, cond_goal, noise, inject_actions, step_noise, lo, hi)
-        if n > 0:
+        if n > 0 and self.pruned:
+            self._bound_sync()
+            rd = self.rb.desc(lo, n)
+            check(self.ctx._h, lib().ditree_expand_round_bounded(self.ctx._h, C.byref(self.tree.desc), C.byref(rd), C.byref(rp),
+                                                                  C.byref(self.bound), self.ctx.stream), "expand_round_bounded")
+        elif n > 0:
             rd = self.rb.desc(lo, n)
             check(self.ctx._h, lib().ditree_expand_round(self.ctx._h, C.byref(self.tree.desc), C.byref(rd),
                                                           C.byref(rp), self.ctx.stream), "expand_round")
@@ -513,6 +602,10 @@ class ExpansionEngine:
         if self.solution == "first":
             check(self.ctx._h, lib().ditree_accept(self.ctx._h, C.byref(self.tree.desc), C.byref(rd), self.sticky,
                                                     self.ctx.stream), "accept")
+        elif self.pruned:
+            self._bound_sync()
+            check(self.ctx._h, lib().ditree_accept_bounded(self.ctx._h, C.byref(self.tree.desc), C.byref(rd),
+                                                            C.byref(self.bound), self.ctx.stream), "accept_bounded")
         else:
             check(self.ctx._h, lib().ditree_accept_best(self.ctx._h, C.byref(self.tree.desc), C.byref(rd),
                                                          self.tree.cost.data_ptr(), self.ctx.stream), "accept_best")

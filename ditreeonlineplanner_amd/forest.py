@@ -24,8 +24,8 @@ import numpy as np
 import torch
 
 from ._lib import MAX_ATLAS_CELLS, MAX_SCENES, ST_GOAL, Forest, ForestScenes, RoundParams, check, lib
-from .engine import (CNT_GOAL, CNT_NODES, CNT_PHANTOM, AntExpansionEngine, ExpansionEngine, ant_cell_centre, env_goal_of,
-                     tree_path)
+from .engine import (CNT_GOAL, CNT_NODES, CNT_PHANTOM, NO_BOUND, ST_BOUND, ST_EXHAUSTED, ST_PRUNED, STATS_ROOT,
+                     AntExpansionEngine, ExpansionEngine, ant_cell_centre, env_goal_of, tree_path)
 from .ops import CAR_NORM, Context, _dbl
 
 
@@ -48,7 +48,12 @@ class ForestTrees:
             raise ValueError(f"n_trees * tree_capacity = {T * Cap} does not fit the int32 node numbering")
         self.T, self.C = T, Cap
         dev = ctx.device
-        self.fcounters = torch.zeros(T, 8, dtype=torch.int32, device=dev)
+        # every tree's counter row and, behind them, every tree's stats row of the "anytime_pruned" bound: one small buffer, so
+        # that one copy per round reads both
+        self._fcnt_buf = torch.zeros(T * 12, dtype=torch.int32, device=dev)
+        self.fcounters = self._fcnt_buf[:T * 8].view(T, 8)
+        self.fstats = self._fcnt_buf[T * 8:].view(T, 4)
+        self.stats_host = np.tile(STATS_ROOT, (T, 1))
         self.off_host = (C.c_int32 * (T + 1))()
         self.off_dev = torch.zeros(T + 1, dtype=torch.int32, device=dev)
         self.n_nodes_host = np.ones(T, dtype=np.int64)
@@ -91,6 +96,10 @@ class ForestTrees:
             tr.hist_n[r] = 1
         if tr.cost is not None:
             tr.cost[r] = 1
+        if self.pruned:                               # the root's key follows on the device before the next launch (_bound_sync)
+            self.fstats[t] = self._stats_row
+            self.stats_host[t] = STATS_ROOT
+            self._bound_roots.append(r)
         self.fcounters[t] = self._root_row
         self.cnt_host[t] = self._ROOT
         self.n_nodes_host[t] = 1
@@ -103,6 +112,37 @@ class ForestTrees:
         if row is None:
             row = self._root_row_dev = torch.as_tensor(self._ROOT, device=self.fcounters.device)
         return row
+
+    @property
+    def _stats_row(self):
+        row = getattr(self, "_stats_row_dev", None)
+        if row is None:
+            row = self._stats_row_dev = torch.as_tensor(STATS_ROOT, device=self.fcounters.device)
+        return row
+
+    def _init_bound(self, n_trees, stats):            # one goal row and one stats row per tree
+        super()._init_bound(self.T, self.fstats)
+
+    def _bound_goal_rows(self):
+        return np.tile(np.asarray(self.env_goal, dtype=np.float64)[None, :2], (self.T, 1))
+
+    @property
+    def _BOUND_TREE_CAPACITY(self):
+        return self.C
+
+    def exhausted(self, t):
+        """"anytime_pruned": no node of tree t can be open after the last accept."""
+        return self.pruned and bool(self.stats_host[self._tree_index(t), ST_EXHAUSTED])
+
+    def pruned_candidates(self, t):
+        return int(self.stats_host[self._tree_index(t), ST_PRUNED]) if self.pruned else 0
+
+    def closed_nodes(self, t):
+        """Nodes of tree t whose key is at or past its incumbent's cost (0 without an incumbent)."""
+        t = self._tree_index(t)
+        u = int(self.stats_host[t, ST_BOUND])
+        base = t * self.C
+        return 0 if u == NO_BOUND else int((self.tree.key[base: base + int(self.n_nodes_host[t])] >= u).sum().item())
 
     def _tree_index(self, t):
         t = int(t)
@@ -150,6 +190,9 @@ class ForestTrees:
         rd = self.rb.desc(0, B)
         if self.solution == "first":
             entry, what, args = *self._ACCEPT, self._accept_args()
+        elif self.pruned:
+            self._bound_sync()
+            entry, what, args = "ditree_forest_accept_bounded", "forest_accept_bounded", (C.byref(self.bound),)
         else:                                         # car forests only (ExpansionEngine's ``solution``)
             entry, what, args = "ditree_forest_accept_best", "forest_accept_best", (self.tree.cost.data_ptr(),)
         check(self.ctx._h, getattr(lib(), entry)(self.ctx._h, C.byref(self.tree.desc), C.byref(self.fdesc), C.byref(rd),
@@ -159,7 +202,9 @@ class ForestTrees:
         return cnt
 
     def read_counters(self):
-        self.cnt_host = self.fcounters.cpu().numpy()
+        buf = self._fcnt_buf.cpu().numpy()            # one small copy: the counter rows and the stats rows
+        self.cnt_host = buf[:self.T * 8].reshape(self.T, 8)
+        self.stats_host = buf[self.T * 8:].reshape(self.T, 4)
         self.n_nodes_host = self.cnt_host[:, CNT_NODES].astype(np.int64)
         return self.cnt_host
 
@@ -227,13 +272,14 @@ class ForestEngine(ForestTrees, ExpansionEngine):
 
     def __init__(self, ctx: Context, maze, start_state, goal_state, n_trees, tree_capacity, edge_length=64, action_horizon=8,
                  pred_horizon=64, local_map_size=20, local_map_scale=0.2, s_global=1.0, batch=1024, k_steps=1,
-                 emulate_sticky_done=True, norm=CAR_NORM, early_exit=False, goal_scale=None, prop_duration=None, solution="first"):
+                 emulate_sticky_done=True, norm=CAR_NORM, early_exit=False, goal_scale=None, prop_duration=None, solution="first",
+                 reach=None):
         capacity = self._init_forest(ctx, n_trees, tree_capacity)
         super().__init__(ctx, maze, start_state, goal_state, edge_length=edge_length, action_horizon=action_horizon,
                          pred_horizon=pred_horizon, local_map_size=local_map_size, local_map_scale=local_map_scale,
                          s_global=s_global, batch=batch, capacity=capacity, k_steps=k_steps,
                          emulate_sticky_done=emulate_sticky_done, norm=norm, early_exit=early_exit, run_type=0,
-                         goal_scale=goal_scale, prop_duration=prop_duration, solution=solution)
+                         goal_scale=goal_scale, prop_duration=prop_duration, solution=solution, reach=reach)
 
     def expand_round(self, samples, cond_goal, noise=None, inject_actions=None, counts_per_tree=None, step_noise=None,
                      accept=True):
@@ -257,8 +303,17 @@ class ForestEngine(ForestTrees, ExpansionEngine):
                                                   self._sched_chunks, len(self.schedule), self._budget_parent.data_ptr(),
                                                   self._budget.data_ptr(), self.ctx.stream), "forest_chunk_budget")
 
+    _SCENES = None                                    # a scene forest: its ditree_forest_scenes descriptor
+
     def _launch_round(self, rd, rp):
         h = self.ctx._h
+        if self.pruned:
+            self._bound_sync()
+            sd = None if self._SCENES is None else C.byref(self._SCENES)
+            check(h, lib().ditree_forest_expand_round_bounded(h, C.byref(self.tree.desc), C.byref(self.fdesc), sd, C.byref(rd),
+                                                              C.byref(rp), C.byref(self.bound), self.ctx.stream),
+                  "forest_expand_round_bounded")
+            return
         check(h, lib().ditree_forest_expand_round(h, C.byref(self.tree.desc), C.byref(self.fdesc), C.byref(rd), C.byref(rp),
                                                   self.ctx.stream), "forest_expand_round")
 
@@ -428,7 +483,16 @@ class SceneForestEngine(SceneTrees, ForestEngine):
         self._init_scenes(ctx, scenes, n_trees)
         super().__init__(ctx, self.scene_mazes[0], self.scene_starts[0], self.scene_goals[0], n_trees, tree_capacity, **kw)
 
+    @property
+    def _SCENES(self):
+        return self.sdesc
+
+    def _bound_goal_rows(self):                       # each tree's own scene's goal
+        return np.stack([self.scene_env_goals[self.tree_scene(t)] for t in range(self.T)])
+
     def _launch_round(self, rd, rp):
+        if self.pruned:
+            return ForestEngine._launch_round(self, rd, rp)
         h = self.ctx._h
         check(h, lib().ditree_forest_expand_round_scenes(h, C.byref(self.tree.desc), C.byref(self.fdesc), C.byref(self.sdesc),
                                                          C.byref(rd), C.byref(rp), self.ctx.stream), "forest_expand_round_scenes")

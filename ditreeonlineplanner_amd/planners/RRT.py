@@ -23,6 +23,16 @@ Constructor kwargs, ``plan() -> (path f32 (P,6)|None, actions f32 (A,2)|None)``,
                        ``emulate_sticky_done=False`` (its default then) and cover the car, one rank, run_type 0.
                        ``results`` gains ``solutions`` (goal nodes appended) and ``first_solution_candidates`` (candidates
                        processed up to and including the first goal-reaching round, or None).
+                       "anytime_pruned": "anytime" until a plan holds an incumbent, branch and bound from then on -- a parent
+                       is chosen only among the nodes whose key (path rows so far + rows still needed at best) is below the
+                       incumbent's rows, a candidate that cannot beat the incumbent gets no node, and the plan ends as soon
+                       as no node is open, before the budgets do.  ``bound_speed`` (this mode only; default ``max_v`` = 5, the
+                       reference's velocity range) sets the metres a path row is assumed to cover at most, ``bound_speed *
+                       env_dt`` (0.1 m for the car).  The dynamics have no hard speed limit, so this bound is a setting and
+                       not a theorem: a smaller ``bound_speed`` prunes more and may prune a branch that would have won.
+                       Same scope as "anytime", and a single ``prop_duration`` entry.  ``results`` gains
+                       ``pruned_candidates``, ``closed_nodes`` (nodes whose key is at or past the final incumbent's rows,
+                       counted once at the end) and ``bound_exhausted``.
 All of the reference's ``run_type`` values: 0 "Original"; 1 "Original+Ref" (obstacle-ahead flags per node, sampling
 biased to the part of ``init_main_path`` behind the obstacle, furthest-along-path fallback); 2 "OM+Ref" (sample
 positions drawn from the EDT prior); 3 "OM+LB+Ref" (prior log-blended with the start -> goal Gaussian, refreshed at
@@ -36,7 +46,7 @@ import time
 import numpy as np
 import torch
 
-from ..engine import CNT_GOAL, CNT_ITERS, AntExpansionEngine, ExpansionEngine, default_shard
+from ..engine import ANYTIME, CNT_GOAL, CNT_ITERS, AntExpansionEngine, ExpansionEngine, default_shard
 from .base_planner import BasePlanner, Node
 
 
@@ -88,7 +98,8 @@ class RRT_Planner(BasePlanner):
             norm=getattr(sampler, "norm", None) if getattr(sampler, "norm", None) is not None else None,
             emulate_sticky_done=sticky, early_exit=kwargs.get("early_exit", True),
             run_type=self.run_type, goal_scale=getattr(sampler, "local_map_size", None),
-            rank=self.rank, world_size=self.world_size, process_group=self.process_group, solution=self.solution)
+            rank=self.rank, world_size=self.world_size, process_group=self.process_group, solution=self.solution,
+            reach=self.bound_reach)
         self._engine.env_goal = np.asarray(self.env.goal, dtype=np.float64)
         self._engine.ddpm = self._ddpm
         from concurrent.futures import ThreadPoolExecutor
@@ -100,6 +111,9 @@ class RRT_Planner(BasePlanner):
         sol = self.solution
         if sol not in SOLUTIONS:
             raise ValueError(f"solution must be one of {SOLUTIONS}, got {sol!r}")
+        self.bound_speed = self.bound_reach = None
+        if "bound_speed" in kwargs and sol != "anytime_pruned":
+            raise ValueError(f"bound_speed belongs to solution='anytime_pruned' (got solution={sol!r})")
         if sol == "first":
             return
         if kwargs.get("emulate_sticky_done", False):
@@ -112,6 +126,16 @@ class RRT_Planner(BasePlanner):
             raise NotImplementedError(f"solution={sol!r}: one rank (world_size {world}; a sharded round keeps solution='first')")
         if self.run_type != 0:
             raise NotImplementedError(f"solution={sol!r}: run_type 0 only (run_type {self.run_type} keeps solution='first')")
+        if sol != "anytime_pruned":
+            return
+        if len(self.prop_duration_schedule) > 1:
+            raise NotImplementedError(f"solution={sol!r}: a single prop_duration entry (the chunk-budget search of a schedule is "
+                                      "not masked by the bound)")
+        v = kwargs.get("bound_speed", self.max_v)
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or v <= 0:
+            raise ValueError(f"bound_speed must be a positive finite number, got {v!r}")
+        self.bound_speed = float(v)
+        self.bound_reach = self.bound_speed * float(self.env_dt)      # metres a path row is assumed to cover at most
 
     # ------------------------------------------------------------------ ant (BASELINE config 3)
     def _init_ant_engine(self, sampler, kwargs):
@@ -183,6 +207,8 @@ class RRT_Planner(BasePlanner):
         self.failed_node_list = []
         self.results = {"iterations": 0, "time": 0, "path": None, "actions": None, "number_of_nodes": 0, "solutions": 0,
                         "first_solution_candidates": None}
+        if self.solution == "anytime_pruned":
+            self.results.update(pruned_candidates=0, closed_nodes=0, bound_exhausted=False)
         out = self.env.reset(options=self.options)
         if self.is_ant:
             if isinstance(out, tuple) and isinstance(out[0], dict) and "desired_goal" in out[0]:
@@ -388,7 +414,9 @@ class RRT_Planner(BasePlanner):
             if goal is not None:
                 if first_at is None:
                     first_at = drawn
-                if self.solution != "anytime":
+                if self.solution not in ANYTIME:
+                    break
+                if eng.exhausted:                # "anytime_pruned": no node is open any more, the plan ends before its budgets
                     break
         if pending is not None:
             pending.result()                     # never leave the helper running on the global RNGs
@@ -402,6 +430,9 @@ class RRT_Planner(BasePlanner):
             self.env.prob_map = orig_prob_map
         self.results["solutions"] = (0 if goal is None else 1) if first else int(solutions_dev.item())
         self.results["first_solution_candidates"] = first_at
+        if self.solution == "anytime_pruned":
+            self.results.update(pruned_candidates=eng.pruned_candidates, closed_nodes=eng.closed_nodes(),
+                                bound_exhausted=bool(eng.exhausted))
         if goal is not None:
             if not self.is_ant:
                 self.env.done = True
@@ -433,7 +464,7 @@ class RRT_Planner(BasePlanner):
                                  pred_horizon=e.P, local_map_size=e.lm_n, local_map_scale=e.lm_scale, s_global=e.s_global,
                                  batch=batch, k_steps=e.k_steps, emulate_sticky_done=bool(e.sticky), norm=e.norm,
                                  early_exit=bool(e.early_exit), goal_scale=e.goal_scale, prop_duration=e.schedule,
-                                 solution=self.solution)
+                                 solution=self.solution, reach=e.reach)
             self._forest, self._forest_key = f, key
         f.ddpm = e.ddpm
         f.update_maze(self.maze)
@@ -490,7 +521,8 @@ def _scene_settings(pl):
     return [("ctx", pl.ctx), ("sampler", pl.sampler), ("action_horizon", e.A), ("pred_horizon", e.P), ("local map size", e.lm_n),
             ("local map scale", float(e.lm_scale)), ("s_global", float(e.s_global)), ("k_steps", e.k_steps),
             ("norm", e.norm.tobytes()), ("emulate_sticky_done", e.sticky), ("early_exit", e.early_exit),
-            ("prop_duration", tuple(e.schedule)), ("batch", pl.batch), ("solution", getattr(pl, "solution", "first"))]
+            ("prop_duration", tuple(e.schedule)), ("batch", pl.batch), ("solution", getattr(pl, "solution", "first")),
+            ("bound_speed", getattr(pl, "bound_speed", None))]
 
 
 def _check_scene_planners(planners):
@@ -555,7 +587,7 @@ def plan_scenario_runs(planners, seeds, concurrent=None, tree_capacity=None):
     eng = SceneForestEngine(ctx, scenes, T, int(tree_capacity), action_horizon=e.A, pred_horizon=e.P, local_map_size=e.lm_n,
                             local_map_scale=e.lm_scale, s_global=e.s_global, batch=T * batch, k_steps=e.k_steps,
                             emulate_sticky_done=bool(e.sticky), norm=e.norm, early_exit=bool(e.early_exit),
-                            goal_scale=e.goal_scale, prop_duration=e.schedule, solution=p0.solution)
+                            goal_scale=e.goal_scale, prop_duration=e.schedule, solution=p0.solution, reach=e.reach)
     eng.ddpm = e.ddpm
     if network:
         sampler.ensure_bound(T * batch)

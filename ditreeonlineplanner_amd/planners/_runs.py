@@ -95,10 +95,12 @@ def run_jobs(eng, jobs, batch, device):
     ``planner.solution`` (one value for all jobs): with "first" and "best_of_round" a run finishes with its first goal-reaching
     round, with "anytime" on its own budgets only; a finished run's node is its tree's goal node -- for the two new modes the
     incumbent -- else the fallback.  Every dict carries ``solutions`` (goal nodes appended) and ``first_solution_candidates``
-    (the run's candidates up to and including its first goal-reaching round, or None)."""
+    (the run's candidates up to and including its first goal-reaching round, or None).  "anytime_pruned" is "anytime" with one
+    more ending: a run whose tree has no open node left after a round (``eng.exhausted(t)``) finishes there with its incumbent,
+    and its tree takes the next job; its dict carries ``pruned_candidates``, ``closed_nodes`` and ``bound_exhausted`` too."""
     import torch
     from ..common import map_utils
-    from ..engine import CNT_GOAL, CNT_ITERS
+    from ..engine import ANYTIME, CNT_GOAL, CNT_ITERS
     if not jobs:
         return []
     T = eng.T
@@ -108,6 +110,8 @@ def run_jobs(eng, jobs, batch, device):
     K = len(eng.ddpm[0]) if (network and eng.ddpm is not None) else 0
     solution = getattr(jobs[0].planner, "solution", "first")
     first = solution == "first"
+    anytime = solution in ANYTIME
+    pruned = solution == "anytime_pruned"
     results = [None] * len(jobs)
     queue = list(range(len(jobs)))[::-1]
     slots = [None] * T                    # per tree: [job index, RunStreams, drawn, start time, first_solution_candidates]
@@ -143,6 +147,9 @@ def run_jobs(eng, jobs, batch, device):
             "path_time": None if path is None else len(path) * job.planner.env_dt, "cc_calls": cc,
             "solutions": (0 if goal is None else 1) if first else int(solutions_dev[t].item()),
             "first_solution_candidates": first_at}
+        if pruned:
+            results[i].update(pruned_candidates=eng.pruned_candidates(t), closed_nodes=eng.closed_nodes(t),
+                              bound_exhausted=bool(eng.exhausted(t)))
         start(t)
 
     with caller_states_kept():
@@ -196,7 +203,7 @@ def run_jobs(eng, jobs, batch, device):
                 if int(cnt[t, CNT_GOAL]) >= 0:
                     if slots[t][4] is None:
                         slots[t][4] = slots[t][2]
-                    if solution != "anytime":
+                    if not anytime or (pruned and eng.exhausted(t)):
                         finish(t, eng.goal_node(t))
     if not ant:
         map_utils.add_cc_calls(total_cc)        # the counter the drivers read (run_scenarios.py:338,343), once

@@ -691,6 +691,72 @@ int32_t ditree_forest_expand_round_scenes(ditree_ctx* ctx, const ditree_tree* tr
 int32_t ditree_forest_fallback_goals(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const double* goal_xy,
                                      int32_t* out_node, void* stream);
 
+/* ------------------------------------------------------------------ branch and bound: the planner's "anytime_pruned" mode
+ * Extends ditree_accept_best (the cost column and the incumbent in counters[1]) by a bound: once a tree holds an incumbent,
+ * only nodes that can still lead to a shorter path are selected as parents, and only candidates that can still beat it get a
+ * node.  All quantities are int32 path rows, like cost.
+ *   h(x, y) = 0 unless q = (sqrt(fma(dy, dy, dx*dx)) - goal_radius) / reach > 0 (a NaN distance gives 0), else
+ *             min(ceil(q), 2^30); (dx, dy) = (x, y) - the tree's goal.  reach = the metres one path row is ASSUMED to cover at
+ *             most: the dynamics have no hard speed limit, so the bound is a setting, not a theorem.
+ *   key[n]  = cost[n] + h(xy[n]); a node is open while key[n] < U, else closed.  Closed nodes stay in the tree.
+ *   U       = cost[counters[1]], or INT32_MAX while counters[1] < 0 -- read on the device; counters[1] is written by the accept's
+ *             pick alone, so the nearest-node search and the accept of one round use the incumbent the round before left.
+ * Single tree: goal_xy (1, 2), stats (4,), and the tree's own counters.  Forest: goal_xy (T, 2) -- each tree's own goal, which
+ * covers scene forests --, stats (T, 4), key / cost indexed by the global slot, the forest's counter block. */
+typedef struct {
+  int32_t* cost;                 /* [dev] (capacity,) as ditree_accept_best's; the caller sets cost[root] = 1 at reset */
+  int32_t* key;                  /* [dev] (capacity,) written by the accept for every node it appends; roots: ditree_bound_keys */
+  const double* goal_xy;         /* [dev] (T, 2) the goal the rollout tests against (the car: env.goal) */
+  double goal_radius;            /* the goal test's radius (the car: 0.5) */
+  double reach;                  /* > 0 */
+  int32_t* stats;                /* [dev] (T, 4): [0] U after the last accept, [1] candidates pruned since the reset, [2] 1 when
+                                    key[root] >= U -- no node of the tree can be open: the plan is exhausted --, [3] candidates
+                                    pruned by the last accept.  The caller sets (INT32_MAX, 0, 0, 0) at reset. */
+} ditree_bound;
+/* Every call of this section refuses by name (DITREE_E_ARG) before anything is launched: "bound: descriptor missing",
+ * "bound: cost array missing", "bound: key column missing", "bound: goal_xy missing", "bound: stats rows missing",
+ * "bound: reach must be > 0", "bound: goal_radius must be >= 0 and finite", and -- the calls that take a round --
+ * "bound: one rank (round->shard must be 0)". */
+
+/* key[n] = cost[n] + h(xy[n]) for nodes [first, first + n) -- the roots after a reset, or any range (tests).  tree_capacity:
+ * 0 for a single tree, else the forest's C (node n belongs to tree n / C and uses goal_xy row n / C). */
+int32_t ditree_bound_keys(ditree_ctx* ctx, const ditree_tree* tree, const ditree_bound* bound, int32_t first, int32_t n,
+                          int32_t tree_capacity, void* stream);
+/* ditree_nn_argmin among the open nodes of tree->xy[0 .. n_nodes): squared distance, ties to the lowest open index, the scan
+ * order and reduction of ditree_nn_argmin -- with U = INT32_MAX its result bit for bit.  No open node: what an all-NaN scan
+ * returns (node 0); a planner never launches such a round (stats[2]).  out_state / out_prev_action / out_has_prev [dev]
+ * (B, S) / (B, D) / (B,): the gathered node rows, or all three NULL.  bound->goal_xy, reach and stats are not read. */
+int32_t ditree_nn_argmin_bounded(ditree_ctx* ctx, const ditree_tree* tree, const ditree_bound* bound, const double* queries,
+                                 int32_t q_stride, int32_t B, int32_t n_nodes, int32_t* out_idx, double* out_state,
+                                 double* out_prev_action, uint8_t* out_has_prev, void* stream);
+/* ditree_forest_nn_argmin among each tree's open nodes, under that tree's own U (no open node: the tree's root). */
+int32_t ditree_forest_nn_argmin_bounded(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
+                                        const ditree_bound* bound, const double* queries, int32_t q_stride, int32_t B,
+                                        int32_t* out_idx, double* out_state, double* out_prev_action, uint8_t* out_has_prev,
+                                        void* stream);
+/* ditree_expand_round with the masked nearest-node search; every other step is ditree_expand_round's.  Also refused:
+ * "expand_round_bounded: chunk budgets are not built (p->chunk_budget must be NULL)" -- ditree_chunk_budget runs its own
+ * unmasked search. */
+int32_t ditree_expand_round_bounded(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round,
+                                    const ditree_round_params* p, const ditree_bound* bound, void* stream);
+/* ditree_forest_expand_round (scenes == NULL) or ditree_forest_expand_round_scenes with the masked search per tree. */
+int32_t ditree_forest_expand_round_bounded(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
+                                           const ditree_forest_scenes* scenes, const ditree_round* round,
+                                           const ditree_round_params* p, const ditree_bound* bound, void* stream);
+/* ditree_accept_best under the bound.  In candidate order every candidate counts (counters[4]), adds its chunks (counters[3])
+ * and visits its parent; a collided candidate gets no node; a candidate that did not collide has c = cost[parent] + kept edge
+ * states + 1 (kept: after the zero-row filter, so a pre-pass counts the rows before ids are assigned) and f = c + h(end xy),
+ * and gets a node slot only if f < U -- else it is pruned: node id -1, stats[1] and [3].  A goal candidate has h = 0: it gets a
+ * node only when strictly cheaper than the incumbent.  counters[6] is raised only by a candidate that was neither collided nor
+ * pruned.  Commit: ditree_accept_best's, with key[id] beside cost[id].  Pick: ditree_accept_best's, then stats[0] and [2].
+ * While counters[1] < 0 nothing is pruned and every array equals ditree_accept_best's.  round->node_id is scratch during the
+ * call (it carries f between the pre-pass and the scan). */
+int32_t ditree_accept_bounded(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round, const ditree_bound* bound,
+                              void* stream);
+/* ditree_forest_accept_best under each tree's own bound; an empty range leaves the tree and its stats row untouched. */
+int32_t ditree_forest_accept_bounded(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
+                                     const ditree_round* round, const ditree_bound* bound, void* stream);
+
 /* One expansion round of the ANT (BASELINE config 3; cfgs/antmaze.yaml + run_scenarios.py:123-132: action_horizon 2, edge
  * length 48 = 24 chunks, pred_horizon 16, obs_history 3, local map 16 x 16 @ 0.8, s_global 4) against a tree with state_dim
  * 29, action_dim 8 and `hist`: planners/RRT.py:131-194 batched --
