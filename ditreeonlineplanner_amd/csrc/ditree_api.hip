@@ -426,6 +426,19 @@ static int check_round(ditree_ctx* ctx, const ditree_round* r) {
   return DITREE_OK;
 }
 
+// The tail of every accept entry point, after its own checks: the accept of one tree, or (f != NULL, validated by the caller)
+// of a forest.  cost: the cost column of the best and the bounded mode (bounded: bound->cost), NULL in the first mode.
+static int accept_impl(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* f, const ditree_round* round, AcceptMode mode,
+                       int emulate_sticky, int32_t* cost, const ditree_bound* bound, void* stream) {
+  if (round->B == 0) return DITREE_OK;
+  const TreeSet ts = f ? TreeSet{f->off, f->counters, f->n_trees, f->tree_capacity}
+                       : TreeSet{nullptr, tree->counters, 1, tree->capacity};
+  launch_accept(*tree, *round, ts, mode, emulate_sticky, cost, bound, ctx->maze, ctx->rows, ctx->cols, ahead_samples(),
+                (hipStream_t)stream);
+  HIP_TRY(ctx, hipGetLastError());
+  return DITREE_OK;
+}
+
 int32_t ditree_accept(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round, int32_t emulate_sticky,
                       void* stream) {
   if (!ctx) return DITREE_E_ARG;
@@ -439,10 +452,7 @@ int32_t ditree_accept(ditree_ctx* ctx, const ditree_tree* tree, const ditree_rou
     return set_err(ctx, DITREE_E_ARG, "accept: a sharded round on a tree with `hist` needs the round's hist / hist_n arrays");
   if (emulate_sticky && (tree->state_dim != 6 || tree->action_dim != 2))
     return set_err(ctx, DITREE_E_ARG, "accept: the sticky-done emulation is the car env's (car_env.py:254,266)");
-  const AheadArg ts = ahead_samples();
-  launch_accept(*tree, *round, emulate_sticky, ctx->maze, ctx->rows, ctx->cols, ts, (hipStream_t)stream);
-  HIP_TRY(ctx, hipGetLastError());
-  return DITREE_OK;
+  return accept_impl(ctx, tree, nullptr, round, AcceptMode::first, emulate_sticky, nullptr, nullptr, stream);
 }
 
 // What ditree_accept_best and ditree_forest_accept_best refuse by name before anything is launched.
@@ -462,10 +472,7 @@ int32_t ditree_accept_best(ditree_ctx* ctx, const ditree_tree* tree, const ditre
   if (rc) return rc;
   if (round->B == 0) return DITREE_OK;
   if (tree->obstacle_ahead && !ctx->maze) return set_err(ctx, DITREE_E_STATE, "accept_best: obstacle-ahead flags need the maze");
-  const AheadArg ts = ahead_samples();
-  launch_accept_best(*tree, *round, cost, ctx->maze, ctx->rows, ctx->cols, ts, (hipStream_t)stream);
-  HIP_TRY(ctx, hipGetLastError());
-  return DITREE_OK;
+  return accept_impl(ctx, tree, nullptr, round, AcceptMode::best, 0, cost, nullptr, stream);
 }
 
 int32_t ditree_round_pack(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round, double* records_out,
@@ -1010,19 +1017,14 @@ static int expand_round_impl(ditree_ctx* ctx, const ditree_tree* tree, const dit
   }
   const double gx = tree_scene ? 0.0 : p->goal_xy[0], gy = tree_scene ? 0.0 : p->goal_xy[1];   // scenes: each row's own goal
   launch_round_begin(round->status, round->chunks_run, round->chunk_steps, B, nC, s);
-  if (f && bd)
-    launch_nn_forest_bounded(p->samples, 6, B, tree->xy, f->off, f->n_trees, f->counters, f->tree_capacity, round->parent,
-                             tree->state, tree->last_action, tree->has_prev, ctx->cur_state, ctx->prev_action, ctx->has_prev,
-                             bd->key, bd->cost, s);
-  else if (bd)
-    launch_nn_argmin_bounded(p->samples, 6, B, tree->xy, p->n_nodes, round->parent, tree->state, tree->last_action,
-                             tree->has_prev, ctx->cur_state, ctx->prev_action, ctx->has_prev, bd->key, bd->cost, tree->counters, s);
-  else if (f)
+  const int32_t* key = bd ? bd->key : nullptr;
+  const int32_t* cost = bd ? bd->cost : nullptr;
+  if (f)
     launch_nn_forest(p->samples, 6, B, tree->xy, f->off, f->n_trees, f->counters, f->tree_capacity, 0, round->parent, tree->state,
-                     tree->last_action, tree->has_prev, ctx->cur_state, ctx->prev_action, ctx->has_prev, s);
+                     tree->last_action, tree->has_prev, ctx->cur_state, ctx->prev_action, ctx->has_prev, s, 6, 2, key, cost);
   else
     launch_nn_argmin(p->samples, 6, B, tree->xy, p->n_nodes, round->parent, tree->state, tree->last_action,
-                     tree->has_prev, ctx->cur_state, ctx->prev_action, ctx->has_prev, s);
+                     tree->has_prev, ctx->cur_state, ctx->prev_action, ctx->has_prev, s, 6, 2, key, cost, tree->counters);
   const int64_t st_stride = (int64_t)nC * (A + 1) * 6, ac_stride = (int64_t)nC * A * 2;
   // One call of the round's chunk body on n rows: local map -> conditioning -> sampler (or the action tape) -> rollout.  Plain
   // chunk loop: every row at chunk j (idx = nrow = NULL, n = B).  Pool: the rows idx[0..n) with noise rows nrow, each at the chunk
@@ -1138,12 +1140,7 @@ int32_t ditree_forest_accept(ditree_ctx* ctx, const ditree_tree* tree, const dit
   if (rc) return rc;
   if (round->shard > 0 || tree->obstacle_ahead || tree->hist)
     return set_err(ctx, DITREE_E_ARG, "forest_accept: a forest is one rank's run_type-0 car tree (no shards, obstacle flags or hist)");
-  if (round->B == 0) return DITREE_OK;
-  const AheadArg ts = ahead_samples();
-  launch_forest_accept(*tree, *round, forest->off, forest->counters, forest->n_trees, forest->tree_capacity, emulate_sticky,
-                       ctx->maze, ctx->rows, ctx->cols, ts, (hipStream_t)stream);
-  HIP_TRY(ctx, hipGetLastError());
-  return DITREE_OK;
+  return accept_impl(ctx, tree, forest, round, AcceptMode::first, emulate_sticky, nullptr, nullptr, stream);
 }
 
 int32_t ditree_forest_accept_best(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const ditree_round* round,
@@ -1157,12 +1154,7 @@ int32_t ditree_forest_accept_best(ditree_ctx* ctx, const ditree_tree* tree, cons
   if (rc) return rc;
   if (tree->obstacle_ahead || tree->hist)
     return set_err(ctx, DITREE_E_ARG, "forest_accept_best: a forest is one rank's run_type-0 car tree (no obstacle flags or hist)");
-  if (round->B == 0) return DITREE_OK;
-  const AheadArg ts = ahead_samples();
-  launch_forest_accept_best(*tree, *round, forest->off, forest->counters, forest->n_trees, forest->tree_capacity, cost, ctx->maze,
-                            ctx->rows, ctx->cols, ts, (hipStream_t)stream);
-  HIP_TRY(ctx, hipGetLastError());
-  return DITREE_OK;
+  return accept_impl(ctx, tree, forest, round, AcceptMode::best, 0, cost, nullptr, stream);
 }
 
 int32_t ditree_forest_chunk_budget(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const double* samples,
@@ -1330,7 +1322,8 @@ int32_t ditree_bound_keys(ditree_ctx* ctx, const ditree_tree* tree, const ditree
   if (first < 0 || n < 0 || tree_capacity < 0 || (int64_t)first + n > tree->capacity)
     return set_err(ctx, DITREE_E_ARG, "bound_keys: nodes [first, first + n) must lie in the tree; tree_capacity >= 0");
   if (n == 0) return DITREE_OK;
-  launch_bound_keys(tree->xy, first, n, tree_capacity, *bound, (hipStream_t)stream);
+  // a single tree (tree_capacity 0) is the forest of one tree: every node of it lies in tree 0
+  launch_bound_keys(tree->xy, first, n, tree_capacity > 0 ? tree_capacity : tree->capacity, *bound, (hipStream_t)stream);
   HIP_TRY(ctx, hipGetLastError());
   return DITREE_OK;
 }
@@ -1348,9 +1341,9 @@ int32_t ditree_nn_argmin_bounded(ditree_ctx* ctx, const ditree_tree* tree, const
   if (!queries || !out_idx || B < 0 || q_stride < 2 || n_nodes <= 0 || n_nodes > tree->capacity ||
       (gather && (!out_state || !out_prev_action || !out_has_prev)))
     return set_err(ctx, DITREE_E_ARG, "nn_argmin_bounded: bad argument (the three gather outputs come together)");
-  launch_nn_argmin_bounded(queries, q_stride, B, tree->xy, n_nodes, out_idx, gather ? tree->state : nullptr, tree->last_action,
-                           tree->has_prev, out_state, out_prev_action, out_has_prev, bound->key, bound->cost, tree->counters,
-                           (hipStream_t)stream, tree->state_dim, tree->action_dim);
+  launch_nn_argmin(queries, q_stride, B, tree->xy, n_nodes, out_idx, gather ? tree->state : nullptr, tree->last_action,
+                   tree->has_prev, out_state, out_prev_action, out_has_prev, (hipStream_t)stream, tree->state_dim, tree->action_dim,
+                   bound->key, bound->cost, tree->counters);
   HIP_TRY(ctx, hipGetLastError());
   return DITREE_OK;
 }
@@ -1368,9 +1361,9 @@ int32_t ditree_forest_nn_argmin_bounded(ditree_ctx* ctx, const ditree_tree* tree
   const bool gather = out_state || out_prev_action || out_has_prev;
   if (!queries || !out_idx || q_stride < 2 || (gather && (!out_state || !out_prev_action || !out_has_prev)))
     return set_err(ctx, DITREE_E_ARG, "forest_nn_argmin_bounded: bad argument (the three gather outputs come together)");
-  launch_nn_forest_bounded(queries, q_stride, B, tree->xy, forest->off, forest->n_trees, forest->counters, forest->tree_capacity,
-                           out_idx, gather ? tree->state : nullptr, tree->last_action, tree->has_prev, out_state, out_prev_action,
-                           out_has_prev, bound->key, bound->cost, (hipStream_t)stream, tree->state_dim, tree->action_dim);
+  launch_nn_forest(queries, q_stride, B, tree->xy, forest->off, forest->n_trees, forest->counters, forest->tree_capacity, 0,
+                   out_idx, gather ? tree->state : nullptr, tree->last_action, tree->has_prev, out_state, out_prev_action,
+                   out_has_prev, (hipStream_t)stream, tree->state_dim, tree->action_dim, bound->key, bound->cost);
   HIP_TRY(ctx, hipGetLastError());
   return DITREE_OK;
 }
@@ -1417,11 +1410,7 @@ int32_t ditree_accept_bounded(ditree_ctx* ctx, const ditree_tree* tree, const di
   if (rc) return rc;
   if (tree->obstacle_ahead || tree->hist)
     return set_err(ctx, DITREE_E_ARG, "accept_bounded: a run_type-0 car tree (no obstacle flags or hist)");
-  if (round->B == 0) return DITREE_OK;
-  const AheadArg ts = ahead_samples();
-  launch_accept_bounded(*tree, *round, *bound, ctx->maze, ctx->rows, ctx->cols, ts, (hipStream_t)stream);
-  HIP_TRY(ctx, hipGetLastError());
-  return DITREE_OK;
+  return accept_impl(ctx, tree, nullptr, round, AcceptMode::bounded, 0, bound->cost, bound, stream);
 }
 
 int32_t ditree_forest_accept_bounded(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
@@ -1435,12 +1424,7 @@ int32_t ditree_forest_accept_bounded(ditree_ctx* ctx, const ditree_tree* tree, c
   if (rc) return rc;
   if (tree->obstacle_ahead || tree->hist)
     return set_err(ctx, DITREE_E_ARG, "forest_accept_bounded: a forest is one rank's run_type-0 car tree (no obstacle flags or hist)");
-  if (round->B == 0) return DITREE_OK;
-  const AheadArg ts = ahead_samples();
-  launch_forest_accept_bounded(*tree, *round, forest->off, forest->counters, forest->n_trees, forest->tree_capacity, *bound,
-                               ctx->maze, ctx->rows, ctx->cols, ts, (hipStream_t)stream);
-  HIP_TRY(ctx, hipGetLastError());
-  return DITREE_OK;
+  return accept_impl(ctx, tree, forest, round, AcceptMode::bounded, 0, bound->cost, bound, stream);
 }
 
 int32_t ditree_forest_fallback_goals(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const double* goal_xy,
@@ -1482,12 +1466,7 @@ int32_t ditree_forest_accept_ant(ditree_ctx* ctx, const ditree_tree* tree, const
   if (!ctx) return DITREE_E_ARG;
   const int rc = check_ant_forest(ctx, tree, forest, round, "forest_accept_ant");
   if (rc) return rc;
-  if (round->B == 0) return DITREE_OK;
-  const AheadArg ts = ahead_samples();               // not read: the tree has no obstacle flags
-  launch_forest_accept(*tree, *round, forest->off, forest->counters, forest->n_trees, forest->tree_capacity, 0, ctx->maze, ctx->rows,
-                       ctx->cols, ts, (hipStream_t)stream);
-  HIP_TRY(ctx, hipGetLastError());
-  return DITREE_OK;
+  return accept_impl(ctx, tree, forest, round, AcceptMode::first, 0, nullptr, nullptr, stream);
 }
 
 // planners/RRT.py:227-254 (run_type 0) for every tree of an ant forest

@@ -111,27 +111,22 @@ int set_err(ditree_ctx* ctx, int code, const std::string& msg);
 
 // geom_kernels.hip launchers (all asynchronous on `s`)
 void launch_maze_convert(const float* src, unsigned char* dst, int n, hipStream_t s);
+// key != NULL: the masked search of the "anytime_pruned" mode (only nodes with key[n] < cost[incumbent] take part); a single
+// tree's incumbent is read from `counters`, a forest's from each tree's row of its own counters
 void launch_nn_argmin(const double* queries, int q_stride, int B, const double* node_xy, int N,
                       int32_t* out_idx, const double* node_state, const double* node_last_action,
                       const uint8_t* node_has_prev, double* out_state, double* out_prev_action,
-                      uint8_t* out_has_prev, hipStream_t s, int S = 6, int D = 2);
+                      uint8_t* out_has_prev, hipStream_t s, int S = 6, int D = 2, const int32_t* key = nullptr,
+                      const int32_t* cost = nullptr, const int32_t* counters = nullptr);
 void launch_nn_forest(const double* queries, int q_stride, int B, const double* node_xy, const int32_t* off, int T,
                       const int32_t* counters, int C, int skip, int32_t* out_idx, const double* node_state,
                       const double* node_last_action, const uint8_t* node_has_prev, double* out_state, double* out_prev_action,
-                      uint8_t* out_has_prev, hipStream_t s, int S = 6, int D = 2);
+                      uint8_t* out_has_prev, hipStream_t s, int S = 6, int D = 2, const int32_t* key = nullptr,
+                      const int32_t* cost = nullptr);
 void launch_forest_fallback(const double* goals, int T, const double* node_xy, const int32_t* counters, int C, int32_t* out_idx,
                             hipStream_t s);
 // the bound of the "anytime_pruned" rounds travels to the kernels as the public descriptor (include/ditree.h ditree_bound)
 using BoundArg = ditree_bound;
-void launch_nn_argmin_bounded(const double* queries, int q_stride, int B, const double* node_xy, int N, int32_t* out_idx,
-                              const double* node_state, const double* node_last_action, const uint8_t* node_has_prev,
-                              double* out_state, double* out_prev_action, uint8_t* out_has_prev, const int32_t* key,
-                              const int32_t* cost, const int32_t* counters, hipStream_t s, int S = 6, int D = 2);
-void launch_nn_forest_bounded(const double* queries, int q_stride, int B, const double* node_xy, const int32_t* off, int T,
-                              const int32_t* counters, int C, int32_t* out_idx, const double* node_state,
-                              const double* node_last_action, const uint8_t* node_has_prev, double* out_state,
-                              double* out_prev_action, uint8_t* out_has_prev, const int32_t* key, const int32_t* cost,
-                              hipStream_t s, int S = 6, int D = 2);
 void launch_bound_keys(const double* xy, int first, int n, int C, const BoundArg& bd, hipStream_t s);
 void launch_local_map_scenes(const SceneArg& sc, const double* state, const int32_t* active, const int32_t* idx, int B, int n,
                              const AxisArg& axis, double s_global, float* out, hipStream_t s, int state_stride);
@@ -194,19 +189,18 @@ void launch_policy_begin(const SceneArg& sc, const ditree_policy_batch& b, hipSt
 void launch_policy_episode(const SceneArg& sc, const ditree_policy_batch& b, int n_run, const double* actions, int64_t act_stride,
                            int act_dense, int step_limit, int32_t* count, hipStream_t s);
 struct AheadArg { double t[30]; };
-void launch_accept(const ditree_tree& t, const ditree_round& r, int emulate_sticky, const unsigned char* maze, int rows,
-                   int cols, const AheadArg& ts, hipStream_t s);
-void launch_forest_accept(const ditree_tree& t, const ditree_round& r, const int32_t* off, int32_t* counters, int T, int C,
-                          int emulate_sticky, const unsigned char* maze, int rows, int cols, const AheadArg& ts, hipStream_t s);
-void launch_accept_best(const ditree_tree& t, const ditree_round& r, int32_t* cost, const unsigned char* maze, int rows, int cols,
-                        const AheadArg& ts, hipStream_t s);
-void launch_forest_accept_best(const ditree_tree& t, const ditree_round& r, const int32_t* off, int32_t* counters, int T, int C,
-                               int32_t* cost, const unsigned char* maze, int rows, int cols, const AheadArg& ts, hipStream_t s);
-void launch_accept_bounded(const ditree_tree& t, const ditree_round& r, const BoundArg& bd, const unsigned char* maze, int rows,
-                           int cols, const AheadArg& ts, hipStream_t s);
-void launch_forest_accept_bounded(const ditree_tree& t, const ditree_round& r, const int32_t* off, int32_t* counters, int T, int C,
-                                  const BoundArg& bd, const unsigned char* maze, int rows, int cols, const AheadArg& ts,
-                                  hipStream_t s);
+// Which trees an accept works on: a forest is {forest->off, forest->counters, n_trees, tree_capacity}, a single tree the forest
+// of one tree {NULL, tree->counters, 1, tree->capacity}.  off == NULL: the one tree takes the whole round.  Tree k owns counter
+// row k and node slots [k * C, (k + 1) * C).
+struct TreeSet {
+  const int32_t* off;
+  int32_t* counters;
+  int T, C;
+};
+enum class AcceptMode { first, best, bounded };   // ditree_accept, ditree_accept_best, ditree_accept_bounded
+void launch_accept(const ditree_tree& t, const ditree_round& r, const TreeSet& ts, AcceptMode mode, int emulate_sticky,
+                   int32_t* cost, const BoundArg* bd, const unsigned char* maze, int rows, int cols, const AheadArg& ahead,
+                   hipStream_t s);
 void launch_obstacle_ahead(const unsigned char* maze, int rows, int cols, const double* state, int stride, int B,
                            const AheadArg& ts, uint8_t* out, hipStream_t s);
 void launch_fallback_select(const ditree_tree& t, int n_nodes, double gx, double gy, const double* path_dev, int P,

@@ -141,20 +141,11 @@ nn_argmin_kernel(const double* __restrict__ queries, int q_stride, int B, const 
 }
 void launch_nn_argmin(const double* queries, int q_stride, int B, const double* node_xy, int N, int32_t* out_idx,
                       const double* node_state, const double* node_last_action, const uint8_t* node_has_prev,
-                      double* out_state, double* out_prev_action, uint8_t* out_has_prev, hipStream_t s, int S, int D) {
+                      double* out_state, double* out_prev_action, uint8_t* out_has_prev, hipStream_t s, int S, int D,
+                      const int32_t* key, const int32_t* cost, const int32_t* counters) {
   int waves = (B + NN_QPW - 1) / NN_QPW;
   int blocks = (waves + 3) / 4;
-  hipLaunchKernelGGL(nn_argmin_kernel<false>, dim3(blocks), dim3(256), 0, s, queries, q_stride, B,
-                     (const double2*)node_xy, N, out_idx, node_state, node_last_action, node_has_prev, out_state,
-                     out_prev_action, out_has_prev, S, D, nullptr, nullptr, nullptr);
-}
-void launch_nn_argmin_bounded(const double* queries, int q_stride, int B, const double* node_xy, int N, int32_t* out_idx,
-                              const double* node_state, const double* node_last_action, const uint8_t* node_has_prev,
-                              double* out_state, double* out_prev_action, uint8_t* out_has_prev, const int32_t* key,
-                              const int32_t* cost, const int32_t* counters, hipStream_t s, int S, int D) {
-  int waves = (B + NN_QPW - 1) / NN_QPW;
-  int blocks = (waves + 3) / 4;
-  hipLaunchKernelGGL(nn_argmin_kernel<true>, dim3(blocks), dim3(256), 0, s, queries, q_stride, B,
+  hipLaunchKernelGGL(key ? nn_argmin_kernel<true> : nn_argmin_kernel<false>, dim3(blocks), dim3(256), 0, s, queries, q_stride, B,
                      (const double2*)node_xy, N, out_idx, node_state, node_last_action, node_has_prev, out_state,
                      out_prev_action, out_has_prev, S, D, key, cost, counters);
 }
@@ -246,19 +237,10 @@ nn_forest_kernel(const double* __restrict__ queries, int q_stride, int B, const 
 void launch_nn_forest(const double* queries, int q_stride, int B, const double* node_xy, const int32_t* off, int T,
                       const int32_t* counters, int C, int skip, int32_t* out_idx, const double* node_state,
                       const double* node_last_action, const uint8_t* node_has_prev, double* out_state, double* out_prev_action,
-                      uint8_t* out_has_prev, hipStream_t s, int S, int D) {
-  hipLaunchKernelGGL(nn_forest_kernel<false>, dim3((B + 3) / 4), dim3(256), 0, s, queries, q_stride, B, (const double2*)node_xy,
-                     off, T, counters, C, skip, out_idx, node_state, node_last_action, node_has_prev, out_state, out_prev_action,
-                     out_has_prev, S, D, nullptr, nullptr);
-}
-void launch_nn_forest_bounded(const double* queries, int q_stride, int B, const double* node_xy, const int32_t* off, int T,
-                              const int32_t* counters, int C, int32_t* out_idx, const double* node_state,
-                              const double* node_last_action, const uint8_t* node_has_prev, double* out_state,
-                              double* out_prev_action, uint8_t* out_has_prev, const int32_t* key, const int32_t* cost,
-                              hipStream_t s, int S, int D) {
-  hipLaunchKernelGGL((nn_forest_kernel<false, true>), dim3((B + 3) / 4), dim3(256), 0, s, queries, q_stride, B,
-                     (const double2*)node_xy, off, T, counters, C, 0, out_idx, node_state, node_last_action, node_has_prev,
-                     out_state, out_prev_action, out_has_prev, S, D, key, cost);
+                      uint8_t* out_has_prev, hipStream_t s, int S, int D, const int32_t* key, const int32_t* cost) {
+  hipLaunchKernelGGL((key ? nn_forest_kernel<false, true> : nn_forest_kernel<false>), dim3((B + 3) / 4), dim3(256), 0, s, queries,
+                     q_stride, B, (const double2*)node_xy, off, T, counters, C, skip, out_idx, node_state, node_last_action,
+                     node_has_prev, out_state, out_prev_action, out_has_prev, S, D, key, cost);
 }
 // The fallback choice of every tree (planners/RRT.py:233-237): query t is tree t's goal, the scan covers its nodes 1.. with the
 // norm as the key.
@@ -1195,50 +1177,97 @@ void launch_fallback_select(const ditree_tree& t, int n_nodes, double gx, double
 }
 
 // ------------------------------------------------------------------------- accept + commit
-// Phase 1 (one workgroup): the reference's sequential accept order (RRT.py:179-217) as a
-// scan.  counters: [0] n_nodes [1] goal node [2] env.done latched [3] chunk iterations
-// [4] candidates [5] sticky triggered [6] capacity overflow [7] phantom candidate (scratch).
-// The scan of one tree over its B candidates (status / chunks_run / parent / node_id already offset to the tree's first
-// candidate): counters is the tree's row, its nodes are slots [node_base, node_base + cap); node ids, the goal node and the
-// phantom are written in the global numbering (node_base + local slot, cand_base + local candidate).
-__device__ __forceinline__ void accept_scan_tree(int32_t* __restrict__ counters, int32_t* __restrict__ num_visit,
-                                                 const int32_t* __restrict__ status, const int32_t* __restrict__ chunks_run,
-                                                 const int32_t* __restrict__ parent, int32_t* __restrict__ node_id, int B,
-                                                 int node_base, int cap, int cand_base, int emulate_sticky) {
-  __shared__ int s_first_goal, s_first_gac, s_total, s_iters;
+// Which trees an accept works on (ditree_internal.h TreeSet): a forest, or a single tree as the forest of one tree.  A tree's
+// counter row: [0] n_nodes [1] goal node [2] env.done latched [3] chunk iterations [4] candidates [5] sticky triggered
+// [6] capacity overflow [7] phantom candidate (scratch).
+__device__ __forceinline__ int32_t* tree_counters(const TreeSet& ts, int tr) { return ts.counters + (size_t)tr * 8; }
+// The slice of the work-group's tree, blockIdx.x: its counter row, its candidates [lo, lo + n) of the round, its node slots
+// [node_base, node_base + C), and its stats row -- formed in the BOUND instantiations alone, NULL in the others.
+struct TreeSlice {
+  int32_t* counters;
+  int32_t* stats;
+  int lo, n, node_base;
+};
+// false: the tree has no candidate in this round -- the work-group returns before any barrier and leaves the tree and its
+// stats row untouched (as an empty round does).
+template <bool BOUND>
+__device__ __forceinline__ bool tree_slice(const TreeSet& ts, const ditree_round& r, int32_t* __restrict__ stats_rows,
+                                           TreeSlice& sl) {
+  const int tr = blockIdx.x;
+  sl.lo = ts.off ? ts.off[tr] : 0;
+  sl.n = ts.off ? ts.off[tr + 1] - sl.lo : r.B;
+  if (sl.n <= 0) return false;
+  sl.counters = tree_counters(ts, tr);
+  sl.node_base = tr * ts.C;
+  sl.stats = nullptr;
+  if constexpr (BOUND) sl.stats = stats_rows + (size_t)tr * 4;
+  return true;
+}
+
+// Phase 1 (one work-group per tree; trees run in parallel): the reference's sequential accept order (RRT.py:179-217) as a
+// scan over the tree's candidates.  Node ids, the goal node and the phantom are written in the global numbering (node_base +
+// local slot, lo + local candidate).  Every scanned candidate counts, adds its chunks and visits its parent.
+//   first    (ditree_accept): the scan ends at the round's first goal row, or at the phantom row of the sticky-done emulation;
+//            the rows behind it get no node.
+//   best     (ditree_accept_best): every candidate in index order, nothing cut at a goal and no phantom.  The goal node is
+//            chosen after the commit (accept_pick_kernel), so counters[1], [2] and [5] are not touched here.
+//   bounded  (ditree_accept_bounded): as best, and on entry node_id[b] holds f = cost + h of candidate b (accept_cost_kernel); a
+//            candidate that did not collide gets a slot only if f < U, U the tree's bound as of the round's start, else it is
+//            pruned: node id -1, counted in stats[1] (since the tree's reset) and stats[3] (this round).  The overflow flag is
+//            raised by unpruned rows alone, because only they are ranked.
+template <AcceptMode MODE>
+__device__ __forceinline__ void accept_scan_tree(const TreeSlice& sl, int cap, int32_t* __restrict__ num_visit,
+                                                 const ditree_round& r, int emulate_sticky, const int32_t* __restrict__ cost) {
+  __shared__ int s_first_goal, s_first_gac, s_iters, s_pruned;
   __shared__ int s_wave_sum[16];
-  const int tid = threadIdx.x;
-  if (tid == 0) { s_first_goal = 0x7fffffff; s_first_gac = 0x7fffffff; s_total = 0; s_iters = 0; }
-  __syncthreads();
-  for (int b = tid; b < B; b += blockDim.x) {
-    int st = status[b];
-    if ((st & 0xff) == DITREE_ST_GOAL) atomicMin(&s_first_goal, b);
-    if (emulate_sticky && (st & 0xff) == DITREE_ST_COLLIDED && (st & DITREE_ST_FLAG_GOAL_AT_COLLISION))
-      atomicMin(&s_first_gac, b);
+  int32_t* __restrict__ counters = sl.counters;
+  const int32_t* __restrict__ status = r.status + sl.lo;
+  const int32_t* __restrict__ chunks_run = r.chunks_run + sl.lo;
+  const int32_t* __restrict__ parent = r.parent + sl.lo;
+  int32_t* __restrict__ node_id = r.node_id + sl.lo;
+  const int B = sl.n, tid = threadIdx.x;
+  if (tid == 0) {
+    s_iters = 0;
+    if constexpr (MODE == AcceptMode::first) { s_first_goal = 0x7fffffff; s_first_gac = 0x7fffffff; }
+    if constexpr (MODE == AcceptMode::bounded) s_pruned = 0;
   }
   __syncthreads();
-  const int g = s_first_goal, c = s_first_gac;
-  const bool latched_in = emulate_sticky && counters[2] != 0;
-  int last = B - 1, phantom = -1, goal_cand = -1;
-  bool latch_out = latched_in;
-  if (latched_in) {
-    phantom = 0; last = 0; goal_cand = 0;
-  } else if (c != 0x7fffffff && (g == 0x7fffffff || g > c)) {
-    if (c + 1 < B) { phantom = c + 1; last = c + 1; goal_cand = c + 1; latch_out = true; }
-    else { latch_out = true; }
-  } else if (g != 0x7fffffff) {
-    last = g; goal_cand = g;
+  int last = B - 1, phantom = -1, goal_cand = -1, U = 0x7fffffff;
+  bool latch_out = false;
+  if constexpr (MODE == AcceptMode::first) {
+    for (int b = tid; b < B; b += blockDim.x) {
+      int st = status[b];
+      if ((st & 0xff) == DITREE_ST_GOAL) atomicMin(&s_first_goal, b);
+      if (emulate_sticky && (st & 0xff) == DITREE_ST_COLLIDED && (st & DITREE_ST_FLAG_GOAL_AT_COLLISION))
+        atomicMin(&s_first_gac, b);
+    }
+    __syncthreads();
+    const int g = s_first_goal, c = s_first_gac;
+    const bool latched_in = emulate_sticky && counters[2] != 0;
+    latch_out = latched_in;
+    if (latched_in) {
+      phantom = 0; last = 0; goal_cand = 0;
+    } else if (c != 0x7fffffff && (g == 0x7fffffff || g > c)) {
+      if (c + 1 < B) { phantom = c + 1; last = c + 1; goal_cand = c + 1; latch_out = true; }
+      else { latch_out = true; }
+    } else if (g != 0x7fffffff) {
+      last = g; goal_cand = g;
+    }
   }
+  if constexpr (MODE == AcceptMode::bounded) U = bound_of(counters, cost);
   const int n0 = counters[0];
   // ordered prefix sum of accepted flags over candidates 0..last, 1024 at a time
   int base = 0;
   for (int start = 0; start <= last; start += blockDim.x) {
-    int b = start + tid;
+    const int b = start + tid;
     int acc = 0, it = 0;
     if (b <= last) {
-      int st = status[b] & 0xff;
-      acc = (b == phantom) ? 1 : (st != DITREE_ST_COLLIDED);
-      it = (b == phantom) ? 1 : chunks_run[b];
+      const bool ph = MODE == AcceptMode::first && b == phantom;
+      acc = ph ? 1 : ((status[b] & 0xff) != DITREE_ST_COLLIDED);
+      if constexpr (MODE == AcceptMode::bounded) {
+        if (acc && !(node_id[b] < U)) { acc = 0; atomicAdd(&s_pruned, 1); }
+      }
+      it = ph ? 1 : chunks_run[b];
       atomicAdd(&num_visit[parent[b]], 1);
     }
     // wave inclusive scan
@@ -1259,186 +1288,86 @@ __device__ __forceinline__ void accept_scan_tree(int32_t* __restrict__ counters,
     int chunk_total = 0;
     for (int w = 0; w < (int)(blockDim.x >> 6); ++w) chunk_total += s_wave_sum[w];
     if (b <= last) {
-      int rank = base + woff + v - acc;                 // exclusive rank
-      int id = acc ? (n0 + rank) : -1;
-      if (id >= cap) id = -1;
-      node_id[b] = id < 0 ? -1 : node_base + id;
-    }
-    base += chunk_total;
-    __syncthreads();
-  }
-  for (int b = last + 1 + tid; b < B; b += blockDim.x) node_id[b] = -1;
-  __syncthreads();
-  if (tid == 0) {
-    int total = base;
-    int n1 = n0 + total;
-    if (n1 > cap) { n1 = cap; counters[6] = 1; }
-    counters[0] = n1;
-    if (goal_cand >= 0) {
-      int gid = node_id[goal_cand];
-      counters[1] = gid;
-    }
-    counters[2] = (emulate_sticky && latch_out && phantom < 0) ? 1 : ((phantom >= 0) ? 1 : counters[2]);
-    counters[3] += s_iters;
-    counters[4] += last + 1;
-    if (phantom >= 0) counters[5] = 1;
-    counters[7] = phantom < 0 ? -1 : cand_base + phantom;
-  }
-}
-// The scan of ditree_accept_best: every candidate of the round in index order, nothing cut at a goal and no sticky-done
-// phantom.  A candidate gets a node slot iff it did not collide; the goal node is chosen after the commit (accept_pick_tree),
-// so counters[1], [2] and [5] are not touched here.  Arguments as accept_scan_tree's.
-// BOUND (ditree_accept_bounded): on entry node_id[b] holds f = cost + h of candidate b (accept_cost_kernel); a candidate that
-// did not collide gets a slot only if f < U, U the tree's bound as of the round's start, else it is pruned: node id -1, counted
-// in stats[1] (since the tree's reset) and stats[3] (this round).  The overflow flag is raised by unpruned rows alone, because
-// only they are ranked.  Every candidate still counts, adds its chunks and visits its parent.
-template <bool BOUND = false>
-__device__ __forceinline__ void accept_best_scan_tree(int32_t* __restrict__ counters, int32_t* __restrict__ num_visit,
-                                                      const int32_t* __restrict__ status, const int32_t* __restrict__ chunks_run,
-                                                      const int32_t* __restrict__ parent, int32_t* __restrict__ node_id, int B,
-                                                      int node_base, int cap, const int32_t* __restrict__ cost = nullptr,
-                                                      int32_t* __restrict__ stats = nullptr) {
-  __shared__ int s_iters;
-  __shared__ int s_pruned;
-  __shared__ int s_wave_sum[16];
-  const int tid = threadIdx.x;
-  if (tid == 0) s_iters = 0;
-  if constexpr (BOUND) {
-    if (tid == 0) s_pruned = 0;
-  }
-  __syncthreads();
-  const int n0 = counters[0];
-  int U = 0x7fffffff;
-  if constexpr (BOUND) U = bound_of(counters, cost);
-  // ordered prefix sum of accepted flags over all B candidates, 1024 at a time
-  int base = 0;
-  for (int start = 0; start < B; start += blockDim.x) {
-    const int b = start + tid;
-    int acc = 0, it = 0;
-    if (b < B) {
-      acc = (status[b] & 0xff) != DITREE_ST_COLLIDED;
-      if constexpr (BOUND) {
-        if (acc && !(node_id[b] < U)) { acc = 0; atomicAdd(&s_pruned, 1); }
-      }
-      it = chunks_run[b];
-      atomicAdd(&num_visit[parent[b]], 1);
-    }
-    int v = acc;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      int o = __shfl_up(v, d);
-      if ((tid & 63) >= d) v += o;
-    }
-    int itw = it;
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) itw += __shfl_xor(itw, m);
-    if ((tid & 63) == 63) s_wave_sum[tid >> 6] = v;
-    if ((tid & 63) == 0) atomicAdd(&s_iters, itw);
-    __syncthreads();
-    int woff = 0;
-    for (int w = 0; w < (tid >> 6); ++w) woff += s_wave_sum[w];
-    int chunk_total = 0;
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) chunk_total += s_wave_sum[w];
-    if (b < B) {
       int id = acc ? (n0 + base + woff + v - acc) : -1;   // n0 + exclusive rank
       if (id >= cap) id = -1;
-      node_id[b] = id < 0 ? -1 : node_base + id;
+      node_id[b] = id < 0 ? -1 : sl.node_base + id;
     }
     base += chunk_total;
+    __syncthreads();
+  }
+  if constexpr (MODE == AcceptMode::first) {
+    for (int b = last + 1 + tid; b < B; b += blockDim.x) node_id[b] = -1;
     __syncthreads();
   }
   if (tid == 0) {
     int n1 = n0 + base;
     if (n1 > cap) { n1 = cap; counters[6] = 1; }
     counters[0] = n1;
+    if constexpr (MODE == AcceptMode::first) {
+      if (goal_cand >= 0) counters[1] = node_id[goal_cand];
+      counters[2] = (emulate_sticky && latch_out && phantom < 0) ? 1 : ((phantom >= 0) ? 1 : counters[2]);
+      if (phantom >= 0) counters[5] = 1;
+    }
     counters[3] += s_iters;
-    counters[4] += B;
-    counters[7] = -1;
-    if constexpr (BOUND) { stats[1] += s_pruned; stats[3] = s_pruned; }
+    counters[4] += last + 1;
+    counters[7] = phantom < 0 ? -1 : sl.lo + phantom;
+    if constexpr (MODE == AcceptMode::bounded) { sl.stats[1] += s_pruned; sl.stats[3] = s_pruned; }
   }
 }
-// The pick of ditree_accept_best, after the commit: among the round's goal candidates that got a node slot, the smallest
+template <AcceptMode MODE>
+__global__ void __launch_bounds__(1024)
+accept_scan_kernel(ditree_tree t, ditree_round r, TreeSet ts, int emulate_sticky, BoundArg bd) {
+  TreeSlice sl;
+  if (!tree_slice<MODE == AcceptMode::bounded>(ts, r, bd.stats, sl)) return;
+  accept_scan_tree<MODE>(sl, ts.C, t.num_visit, r, emulate_sticky, bd.cost);
+}
+// The pick of ditree_accept_best, after the commit: among the tree's goal candidates that got a node slot, the smallest
 // (cost[node], candidate index); it replaces the incumbent counters[1] only when there is none or its cost is strictly smaller.
-__device__ __forceinline__ void accept_pick_tree(int32_t* __restrict__ counters, const int32_t* __restrict__ status,
-                                                 const int32_t* __restrict__ node_id, const int32_t* __restrict__ cost, int B) {
+// Candidate indices are compared within the tree: the offset lo is common to all of them.
+// BOUND (ditree_accept_bounded): thread 0, which wrote the incumbent, also writes the bound the next round will use and whether
+// any node can still be open -- key[root] is the smallest key a tree can hold below its root, so key[root] >= U closes the
+// whole tree.  stats: [0] U, [1] candidates pruned since the reset, [2] exhausted, [3] candidates pruned this round.
+template <bool BOUND>
+__global__ void __launch_bounds__(1024)
+accept_pick_kernel(ditree_round r, TreeSet ts, const int32_t* __restrict__ cost, BoundArg bd) {
+  TreeSlice sl;
+  if (!tree_slice<BOUND>(ts, r, bd.stats, sl)) return;
   __shared__ unsigned long long s_best;
+  const int32_t* __restrict__ status = r.status + sl.lo;
+  const int32_t* __restrict__ node_id = r.node_id + sl.lo;
   const int tid = threadIdx.x;
   if (tid == 0) s_best = ~0ull;
   __syncthreads();
-  for (int b = tid; b < B; b += blockDim.x) {
+  for (int b = tid; b < sl.n; b += blockDim.x) {
     const int id = node_id[b];
     if ((status[b] & 0xff) == DITREE_ST_GOAL && id >= 0)  // a collided candidate's goal-at-collision flag is not a goal
       atomicMin(&s_best, ((unsigned long long)(unsigned)cost[id] << 32) | (unsigned)b);
   }
   __syncthreads();
-  if (tid == 0 && s_best != ~0ull) {
-    const int c = (int)(s_best >> 32), b = (int)(s_best & 0xffffffffull);
-    const int inc = counters[1];
-    if (inc < 0 || c < cost[inc]) counters[1] = node_id[b];
+  if (tid == 0) {
+    if (s_best != ~0ull) {
+      const int c = (int)(s_best >> 32), b = (int)(s_best & 0xffffffffull);
+      const int inc = sl.counters[1];
+      if (inc < 0 || c < cost[inc]) sl.counters[1] = node_id[b];
+    }
+    if constexpr (BOUND) {
+      const int U = bound_of(sl.counters, cost);
+      sl.stats[0] = U;
+      sl.stats[2] = bd.key[sl.node_base] >= U ? 1 : 0;
+    }
   }
-}
-// The tail of a bounded pick (thread 0, which also wrote the incumbent just above): the bound the next round will use and
-// whether any node can still be open -- key[root] is the smallest key a tree can hold below its root, so key[root] >= U closes
-// the whole tree.  stats: [0] U, [1] candidates pruned since the reset, [2] exhausted, [3] candidates pruned this round.
-__device__ __forceinline__ void bound_stats_tree(const int32_t* __restrict__ counters, const int32_t* __restrict__ cost,
-                                                 const int32_t* __restrict__ key, int root, int32_t* __restrict__ stats) {
-  if (threadIdx.x == 0) {
-    const int U = bound_of(counters, cost);
-    stats[0] = U;
-    stats[2] = key[root] >= U ? 1 : 0;
-  }
-}
-__global__ void __launch_bounds__(1024)
-accept_scan_kernel(ditree_tree t, ditree_round r, int emulate_sticky) {
-  accept_scan_tree(t.counters, t.num_visit, r.status, r.chunks_run, r.parent, r.node_id, r.B, 0, t.capacity, 0, emulate_sticky);
-}
-__global__ void __launch_bounds__(1024)
-accept_best_scan_kernel(ditree_tree t, ditree_round r) {
-  accept_best_scan_tree(t.counters, t.num_visit, r.status, r.chunks_run, r.parent, r.node_id, r.B, 0, t.capacity);
-}
-__global__ void __launch_bounds__(1024)
-accept_pick_kernel(ditree_tree t, ditree_round r, const int32_t* __restrict__ cost) {
-  accept_pick_tree(t.counters, r.status, r.node_id, cost, r.B);
-}
-__global__ void __launch_bounds__(1024)
-accept_bounded_scan_kernel(ditree_tree t, ditree_round r, BoundArg bd) {
-  accept_best_scan_tree<true>(t.counters, t.num_visit, r.status, r.chunks_run, r.parent, r.node_id, r.B, 0, t.capacity, bd.cost,
-                              bd.stats);
-}
-__global__ void __launch_bounds__(1024)
-accept_bounded_pick_kernel(ditree_tree t, ditree_round r, BoundArg bd) {
-  accept_pick_tree(t.counters, r.status, r.node_id, bd.cost, r.B);
-  bound_stats_tree(t.counters, bd.cost, bd.key, 0, bd.stats);
-}
-__global__ void __launch_bounds__(1024)
-forest_accept_bounded_scan_kernel(ditree_tree t, ditree_round r, const int32_t* __restrict__ off, int32_t* __restrict__ counters,
-                                  int C, BoundArg bd) {
-  const int tr = blockIdx.x;
-  const int lo = off[tr], n = off[tr + 1] - lo;
-  if (n <= 0) return;
-  accept_best_scan_tree<true>(counters + (size_t)tr * 8, t.num_visit, r.status + lo, r.chunks_run + lo, r.parent + lo,
-                              r.node_id + lo, n, tr * C, C, bd.cost, bd.stats + (size_t)tr * 4);
-}
-__global__ void __launch_bounds__(1024)
-forest_accept_bounded_pick_kernel(ditree_round r, const int32_t* __restrict__ off, int32_t* __restrict__ counters, int C,
-                                  BoundArg bd) {
-  const int tr = blockIdx.x;
-  const int lo = off[tr], n = off[tr + 1] - lo;
-  if (n <= 0) return;
-  accept_pick_tree(counters + (size_t)tr * 8, r.status + lo, r.node_id + lo, bd.cost, n);
-  bound_stats_tree(counters + (size_t)tr * 8, bd.cost, bd.key, tr * C, bd.stats + (size_t)tr * 4);
 }
 // The pre-pass of a bounded accept, one wave per candidate: a goal reached in mid-chunk leaves all-zero rows behind it, so what
 // a candidate's node would cost is known only after the zero-row filter -- the commit kernel's ballot over the rows of the
 // chunks that ran.  f = cost[parent] + kept edge states + 1 + h(end xy) goes to node_id[b], where the scan reads it before it
-// writes the id.  C > 0: a forest, the candidate's tree is its parent's (parent / C), with that tree's counter row and goal.
+// writes the id.  The candidate's tree is its parent's (parent / C), with that tree's counter row and goal.
 // A tree without an incumbent prunes nothing: its candidates skip the count.
 __global__ void __launch_bounds__(64)
-accept_cost_kernel(ditree_tree t, ditree_round r, const int32_t* __restrict__ counters, int C, BoundArg bd) {
+accept_cost_kernel(ditree_tree t, ditree_round r, TreeSet ts, BoundArg bd) {
   const int b = blockIdx.x, lane = threadIdx.x;
   const int par = r.parent[b];
-  const int tr = C > 0 ? par / C : 0;
-  const int U = bound_of(counters + (size_t)tr * 8, bd.cost);
+  const int tr = par / ts.C;
+  const int U = bound_of(tree_counters(ts, tr), bd.cost);
   if (U == 0x7fffffff || (r.status[b] & 0xff) == DITREE_ST_COLLIDED) {
     if (lane == 0) r.node_id[b] = 0;
     return;
@@ -1456,61 +1385,36 @@ accept_cost_kernel(ditree_tree t, ditree_round r, const int32_t* __restrict__ co
     r.node_id[b] = bd.cost[par] + ns + 1 + bound_h(ex, ey, bd.goal_xy[2 * tr], bd.goal_xy[2 * tr + 1], bd.goal_radius, bd.reach);
   }
 }
-// key[n] = cost[n] + h(xy[n]) for nodes [first, first + n) (ditree_bound_keys: the roots; C > 0: node n belongs to tree n / C).
+// key[n] = cost[n] + h(xy[n]) for nodes [first, first + n) (ditree_bound_keys: the roots); node n belongs to tree n / C, C as
+// in a TreeSet.
 __global__ void bound_keys_kernel(const double2* __restrict__ xy, int first, int n, int C, BoundArg bd) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const int k = first + i, tr = C > 0 ? k / C : 0;
+  const int k = first + i, tr = k / C;
   const double2 p = xy[k];
   bd.key[k] = bd.cost[k] + bound_h(p.x, p.y, bd.goal_xy[2 * tr], bd.goal_xy[2 * tr + 1], bd.goal_radius, bd.reach);
-}
-__global__ void __launch_bounds__(1024)
-forest_accept_best_scan_kernel(ditree_tree t, ditree_round r, const int32_t* __restrict__ off, int32_t* __restrict__ counters, int C) {
-  const int tr = blockIdx.x;
-  const int lo = off[tr], n = off[tr + 1] - lo;
-  if (n <= 0) return;
-  accept_best_scan_tree(counters + (size_t)tr * 8, t.num_visit, r.status + lo, r.chunks_run + lo, r.parent + lo, r.node_id + lo, n,
-                        tr * C, C);
-}
-__global__ void __launch_bounds__(1024)
-forest_accept_pick_kernel(ditree_round r, const int32_t* __restrict__ off, int32_t* __restrict__ counters,
-                          const int32_t* __restrict__ cost) {
-  const int tr = blockIdx.x;
-  const int lo = off[tr], n = off[tr + 1] - lo;
-  if (n <= 0) return;
-  // candidate indices are compared within the tree: the offset lo is common to all of them
-  accept_pick_tree(counters + (size_t)tr * 8, r.status + lo, r.node_id + lo, cost, n);
-}
-// A forest: one work-group per tree over its candidate range [off[t], off[t+1]); trees run in parallel.  An empty range leaves
-// the tree untouched (as ditree_accept does for an empty round).
-__global__ void __launch_bounds__(1024)
-forest_accept_scan_kernel(ditree_tree t, ditree_round r, const int32_t* __restrict__ off, int32_t* __restrict__ counters, int C,
-                          int emulate_sticky) {
-  const int tr = blockIdx.x;
-  const int lo = off[tr], n = off[tr + 1] - lo;
-  if (n <= 0) return;
-  accept_scan_tree(counters + (size_t)tr * 8, t.num_visit, r.status + lo, r.chunks_run + lo, r.parent + lo, r.node_id + lo, n,
-                   tr * C, C, lo, emulate_sticky);
 }
 
 // Phase 2: one wave per candidate copies the accepted edge into its node slot, dropping
 // all-zero rows (RRT.py:196-199).  State / action width S / D at run time (car 6 / 2, ant 29 / 8; S, D <= 64: a lane per
 // component, the zero-row test is one ballot).
-// FOREST: the phantom candidate is the one in the counter row of the node's own tree (id / C of the forest's counters).
+// The node's tree is id / C (0 for a single tree, whose ids stay below its capacity): the phantom candidate is the one in that
+// tree's counter row.
 // cost != NULL (ditree_accept_best): cost[id] = rows of the path to the node = cost[parent] + kept edge states + 1; the
 // parent is a node of an earlier round, so its cost is final.
 // KEY (ditree_accept_bounded): key[id] = cost[id] + h(the node's xy, its tree's goal), written where cost is.  KEY = false
-// leaves the two instantiations as they were before the flag: the trailing argument is not read.
-template <bool FOREST, bool KEY = false>
+// does not read the trailing argument.
+template <bool KEY>
 __global__ void __launch_bounds__(64)
 accept_commit_kernel(ditree_tree t, ditree_round r, const unsigned char* __restrict__ maze, int rows, int cols,
-                     AheadArg ts, const int32_t* __restrict__ forest_counters, int C, int32_t* __restrict__ cost, BoundArg bd) {
+                     AheadArg ahead, TreeSet ts, int32_t* __restrict__ cost, BoundArg bd) {
   const int b = blockIdx.x;
   const int id = r.node_id[b];
   if (id < 0) return;
   const int lane = threadIdx.x;
   const int A = t.A, nC = t.n_chunks, S = t.state_dim, D = t.action_dim;
-  const int phantom = FOREST ? forest_counters[(size_t)(id / C) * 8 + 7] : t.counters[7];
+  const int tr = id / ts.C;
+  const int phantom = tree_counters(ts, tr)[7];
   const int par = r.parent[b];
   const size_t es_cap = (size_t)nC * (A + 1), ea_cap = (size_t)nC * A;
   double* es = t.edge_states + (size_t)id * es_cap * S;
@@ -1573,13 +1477,11 @@ accept_commit_kernel(ditree_tree t, ditree_round r, const unsigned char* __restr
     t.edge_nstates[id] = ns;
     t.edge_nactions[id] = na;
     if (cost != nullptr) cost[id] = cost[par] + ns + 1;
-    if constexpr (KEY) {
-      const int tr = FOREST ? id / C : 0;
+    if constexpr (KEY)
       bd.key[id] = cost[par] + ns + 1 + bound_h(ex, ey, bd.goal_xy[2 * tr], bd.goal_xy[2 * tr + 1], bd.goal_radius, bd.reach);
-    }
     if (t.edge_owner != nullptr) t.edge_owner[id] = owner;
     if (t.obstacle_ahead != nullptr)                                   // RRT.py:202-205 (run_type > 0)
-      t.obstacle_ahead[id] = obstacle_ahead_dev(ex, ey, psi, maze, rows, cols, ts) ? 1 : 0;
+      t.obstacle_ahead[id] = obstacle_ahead_dev(ex, ey, psi, maze, rows, cols, ahead) ? 1 : 0;
   }
   if (lane < D) {
     double la;
@@ -1671,45 +1573,25 @@ void launch_round_unpack(const ditree_tree& t, const ditree_round& r, const doub
   hipLaunchKernelGGL(round_unpack_kernel, dim3((r.B + 127) / 128), dim3(128), 0, s, t, r, rec, record_doubles(t));
 }
 
-void launch_accept(const ditree_tree& t, const ditree_round& r, int emulate_sticky, const unsigned char* maze, int rows,
-                   int cols, const AheadArg& ts, hipStream_t s) {
-  hipLaunchKernelGGL(accept_scan_kernel, dim3(1), dim3(1024), 0, s, t, r, emulate_sticky);
-  hipLaunchKernelGGL(accept_commit_kernel<false>, dim3(r.B), dim3(64), 0, s, t, r, maze, rows, cols, ts, nullptr, 0, nullptr, BoundArg{});
-}
-void launch_accept_best(const ditree_tree& t, const ditree_round& r, int32_t* cost, const unsigned char* maze, int rows, int cols,
-                        const AheadArg& ts, hipStream_t s) {
-  hipLaunchKernelGGL(accept_best_scan_kernel, dim3(1), dim3(1024), 0, s, t, r);
-  hipLaunchKernelGGL(accept_commit_kernel<false>, dim3(r.B), dim3(64), 0, s, t, r, maze, rows, cols, ts, nullptr, 0, cost, BoundArg{});
-  hipLaunchKernelGGL(accept_pick_kernel, dim3(1), dim3(1024), 0, s, t, r, cost);
-}
-void launch_forest_accept(const ditree_tree& t, const ditree_round& r, const int32_t* off, int32_t* counters, int T, int C,
-                          int emulate_sticky, const unsigned char* maze, int rows, int cols, const AheadArg& ts, hipStream_t s) {
-  hipLaunchKernelGGL(forest_accept_scan_kernel, dim3(T), dim3(1024), 0, s, t, r, off, counters, C, emulate_sticky);
-  hipLaunchKernelGGL(accept_commit_kernel<true>, dim3(r.B), dim3(64), 0, s, t, r, maze, rows, cols, ts, counters, C, nullptr, BoundArg{});
-}
-void launch_forest_accept_best(const ditree_tree& t, const ditree_round& r, const int32_t* off, int32_t* counters, int T, int C,
-                               int32_t* cost, const unsigned char* maze, int rows, int cols, const AheadArg& ts, hipStream_t s) {
-  hipLaunchKernelGGL(forest_accept_best_scan_kernel, dim3(T), dim3(1024), 0, s, t, r, off, counters, C);
-  hipLaunchKernelGGL(accept_commit_kernel<true>, dim3(r.B), dim3(64), 0, s, t, r, maze, rows, cols, ts, counters, C, cost, BoundArg{});
-  hipLaunchKernelGGL(forest_accept_pick_kernel, dim3(T), dim3(1024), 0, s, r, off, counters, cost);
-}
-// The bounded accept (include/ditree.h ditree_accept_bounded): cost pre-pass -> bounded scan -> commit with the key column ->
-// pick with the stats row.
-void launch_accept_bounded(const ditree_tree& t, const ditree_round& r, const BoundArg& bd, const unsigned char* maze, int rows,
-                           int cols, const AheadArg& ts, hipStream_t s) {
-  hipLaunchKernelGGL(accept_cost_kernel, dim3(r.B), dim3(64), 0, s, t, r, t.counters, 0, bd);
-  hipLaunchKernelGGL(accept_bounded_scan_kernel, dim3(1), dim3(1024), 0, s, t, r, bd);
-  hipLaunchKernelGGL((accept_commit_kernel<false, true>), dim3(r.B), dim3(64), 0, s, t, r, maze, rows, cols, ts, nullptr, 0, bd.cost, bd);
-  hipLaunchKernelGGL(accept_bounded_pick_kernel, dim3(1), dim3(1024), 0, s, t, r, bd);
-}
-void launch_forest_accept_bounded(const ditree_tree& t, const ditree_round& r, const int32_t* off, int32_t* counters, int T, int C,
-                                  const BoundArg& bd, const unsigned char* maze, int rows, int cols, const AheadArg& ts,
-                                  hipStream_t s) {
-  hipLaunchKernelGGL(accept_cost_kernel, dim3(r.B), dim3(64), 0, s, t, r, counters, C, bd);
-  hipLaunchKernelGGL(forest_accept_bounded_scan_kernel, dim3(T), dim3(1024), 0, s, t, r, off, counters, C, bd);
-  hipLaunchKernelGGL((accept_commit_kernel<true, true>), dim3(r.B), dim3(64), 0, s, t, r, maze, rows, cols, ts, counters, C, bd.cost, bd);
-  hipLaunchKernelGGL(forest_accept_bounded_pick_kernel, dim3(T), dim3(1024), 0, s, r, off, counters, C, bd);
+// The accept of a round on the trees `ts`: scan -> commit; best: with the cost column, then the pick; bounded (bd != NULL,
+// cost = bd->cost): the cost pre-pass first, the commit writes the key column too, the pick the stats rows.
+void launch_accept(const ditree_tree& t, const ditree_round& r, const TreeSet& ts, AcceptMode mode, int emulate_sticky,
+                   int32_t* cost, const BoundArg* bd, const unsigned char* maze, int rows, int cols, const AheadArg& ahead,
+                   hipStream_t s) {
+  const BoundArg b = bd ? *bd : BoundArg{};
+  const dim3 trees(ts.T), cands(r.B);
+  const bool bounded = mode == AcceptMode::bounded;
+  const auto scan = mode == AcceptMode::first  ? accept_scan_kernel<AcceptMode::first>
+                    : mode == AcceptMode::best ? accept_scan_kernel<AcceptMode::best>
+                                               : accept_scan_kernel<AcceptMode::bounded>;
+  if (bounded) hipLaunchKernelGGL(accept_cost_kernel, cands, dim3(64), 0, s, t, r, ts, b);
+  hipLaunchKernelGGL(scan, trees, dim3(1024), 0, s, t, r, ts, emulate_sticky, b);
+  hipLaunchKernelGGL(bounded ? accept_commit_kernel<true> : accept_commit_kernel<false>, cands, dim3(64), 0, s, t, r, maze, rows,
+                     cols, ahead, ts, cost, b);
+  if (mode != AcceptMode::first)
+    hipLaunchKernelGGL(bounded ? accept_pick_kernel<true> : accept_pick_kernel<false>, trees, dim3(1024), 0, s, r, ts, cost, b);
 }
 void launch_bound_keys(const double* xy, int first, int n, int C, const BoundArg& bd, hipStream_t s) {
   hipLaunchKernelGGL(bound_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, s, (const double2*)xy, first, n, C, bd);
 }
+

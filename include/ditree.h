@@ -641,7 +641,9 @@ typedef struct {
 int32_t ditree_forest_expand_round(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
                                    const ditree_round* round, const ditree_round_params* p, void* stream);
 /* ditree_accept per tree: one work-group per tree applies the single-tree rules (first goal, sticky-done phantom, accepted prefix,
- * iteration / candidate counts, overflow at the tree's own C) to its counter row and writes global node ids from t * C + n_t. */
+ * iteration / candidate counts, overflow at the tree's own C) to its counter row and writes global node ids from t * C + n_t.
+ * The accept calls of a single tree and of a forest (this one, _accept_best, _accept_bounded, _accept_ant) run the same kernels:
+ * a single tree is accepted as the forest of one tree {its own counters, C = tree->capacity} whose range is the whole round. */
 int32_t ditree_forest_accept(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const ditree_round* round,
                              int32_t emulate_sticky, void* stream);
 /* ditree_accept_best per tree: one work-group per tree scans its candidate range (ids from t * C + n_t, overflow at the tree's

@@ -1,5 +1,5 @@
-"""GPU: ditree_accept_best / ditree_forest_accept_best (accept_best_scan_tree, accept_commit_kernel's cost column and
-accept_pick_tree) against the sequential restatement of tests/accept_best_ref.py, on rounds written straight into the device
+"""GPU: ditree_accept_best / ditree_forest_accept_best (accept_scan_kernel<best>, accept_commit_kernel's cost column and
+accept_pick_kernel) against the sequential restatement of tests/accept_best_ref.py, on rounds written straight into the device
 arrays: round sizes around the wave (63 / 64 / 65), around the scan's 1024-wide pass (1024 / 1025) and past two passes
 (2500); forests of 1, 3 and 64 trees with empty candidate ranges.  Every comparison is exact: node ids, whole counter rows,
 the cost column, num_visit and every tree array.  Then the invariant the planner relies on -- a node's cost is the number of

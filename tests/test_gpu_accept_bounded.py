@@ -1,4 +1,4 @@
-"""GPU: ditree_accept_bounded / ditree_forest_accept_bounded (accept_cost_kernel, accept_best_scan_tree<true>, the commit
+"""GPU: ditree_accept_bounded / ditree_forest_accept_bounded (accept_cost_kernel, accept_scan_kernel<bounded>, the commit
 kernel's key column, the pick's stats row) against the sequential restatement of tests/anytime_pruned_ref.py, on rounds written
 straight into the device arrays in the manner of tests/test_gpu_accept_best.py and at its sizes.  Every comparison is exact:
 node ids, whole counter and stats rows, the cost and key columns, num_visit and every tree array."""

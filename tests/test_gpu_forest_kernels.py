@@ -1,5 +1,5 @@
-"""GPU: the forest kernels (nn_forest_kernel, forest_accept_scan_kernel / accept_commit_kernel<true>, row_scene_kernel and the
-SCENES rollout) against plain numpy / Python written here and the oracle's own functions, at the tree sizes real runs reach:
+"""GPU: the forest kernels (nn_forest_kernel, accept_scan_kernel<first> / accept_commit_kernel on a forest's trees,
+row_scene_kernel and the SCENES rollout) against plain numpy / Python written here and the oracle's own functions, at the tree sizes real runs reach:
 trees past the 512-node trip of the search, 256 trees of one candidate, 2 500 candidates of one tree, a full scene table.
 The entry points are called directly on tree contents and rounds written straight into the device arrays.  Every comparison is
 exact (indices, flags, counters, copied doubles) except the scene rollout's states (1e-9, test_rollout_chunk_vs_oracle's bound).
