@@ -67,6 +67,101 @@ static int run_ready_pool(ditree_ctx* ctx, const char* who, const ditree_round* 
   return DITREE_OK;
 }
 
+// The rows one launch of a chunk half works on: candidates idx[0..n) (NULL: 0..n) whose noise rows are nrow[0..n) (NULL: the
+// dense row number), all at chunk j -- or, j < 0 (the pool), each at the chunk its chunks_run counter names.
+struct RowSet {
+  const int32_t* idx;
+  const int32_t* nrow;
+  int n, j;
+  size_t jo() const { return j < 0 ? 0 : (size_t)j; }     // the chunk offset the host adds to the round's arrays
+  // noise rows per step of nrow: the pool's lists index the (B * n_chunks, ...) row view, a chunk loop's the candidates
+  int64_t noise_rows(int n_chunks) const { return j < 0 ? 1 : n_chunks; }
+};
+
+// ---- round scratch (ditree_internal.h RoundScratch)
+static hipError_t free_round_scratch(RoundScratch* rs) {
+  void** ptrs[] = {(void**)&rs->state, (void**)&rs->hist, (void**)&rs->hist_n, (void**)&rs->prev_action, (void**)&rs->has_prev,
+                   (void**)&rs->lmap,  (void**)&rs->cond, (void**)&rs->act,    (void**)&rs->idx,         (void**)&rs->nrow};
+  hipError_t first = hipSuccess;
+  for (void** p : ptrs) {
+    const hipError_t e = *p ? hipFree(*p) : hipSuccess;
+    if (first == hipSuccess) first = e;
+    *p = nullptr;
+  }
+  rs->B = rs->lm = rs->P = 0;
+  return first;
+}
+
+// Reserve `rs` for B candidates, an lm x lm local map and P predicted actions of a robot with S-wide states, D-wide actions and a
+// C-wide conditioning vector; hist_rows > 0: that many history rows per candidate instead of the live state.  Sizes only grow, and
+// growing waits for the device first: launches in flight may still read the old buffers.
+static int ensure_round_scratch(ditree_ctx* ctx, RoundScratch* rs, int B, int lm, int P, int S, int D, int C, int hist_rows) {
+  if (!ctx->alive_cnt) HIP_TRY(ctx, hipMalloc((void**)&ctx->alive_cnt, 16));
+  if (!ctx->alive_cnt_host) HIP_TRY(ctx, hipHostMalloc((void**)&ctx->alive_cnt_host, 16, hipHostMallocDefault));
+  if (B <= rs->B && lm <= rs->lm && P <= rs->P) return DITREE_OK;
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  const size_t nb = (size_t)std::max(B, rs->B), nl = (size_t)std::max(lm, rs->lm), np = (size_t)std::max(P, rs->P);
+  HIP_TRY(ctx, free_round_scratch(rs));                   // B = lm = P = 0: a failed allocation below leaves "nothing reserved"
+  const struct { void** p; size_t bytes; } bufs[] = {
+      {(void**)&rs->state, hist_rows ? 0 : nb * S * sizeof(double)},
+      {(void**)&rs->hist, nb * hist_rows * S * sizeof(double)},
+      {(void**)&rs->hist_n, hist_rows ? nb * sizeof(int32_t) : 0},
+      {(void**)&rs->prev_action, nb * D * sizeof(double)},
+      {(void**)&rs->has_prev, nb},
+      {(void**)&rs->lmap, nb * nl * nl * sizeof(float)},
+      {(void**)&rs->cond, nb * C * sizeof(float)},
+      {(void**)&rs->act, nb * np * D * sizeof(double)},
+      {(void**)&rs->idx, nb * sizeof(int32_t)},
+      {(void**)&rs->nrow, nb * sizeof(int32_t)}};
+  for (const auto& b : bufs)
+    if (b.bytes) HIP_TRY(ctx, hipMalloc(b.p, b.bytes));
+  rs->B = (int)nb;
+  rs->lm = (int)nl;
+  rs->P = (int)np;
+  return DITREE_OK;
+}
+static int ensure_car_scratch(ditree_ctx* ctx, int B, int lm, int P) { return ensure_round_scratch(ctx, &ctx->car, B, lm, P, 6, 2, 7, 0); }
+
+// The nearest-node search among the first n_nodes nodes of one tree, or (f != NULL) for every query in its own tree of a forest,
+// each up to its counter row's node count.  bd != NULL: the masked search of the "anytime_pruned" mode.  out_state != NULL: the
+// chosen node's state, last action and flag are gathered into the three outputs.
+static void launch_nn(const ditree_tree* tree, const ditree_forest* f, int n_nodes, const ditree_bound* bd, const double* queries,
+                      int q_stride, int B, int32_t* out_idx, double* out_state, double* out_prev_action, uint8_t* out_has_prev,
+                      hipStream_t s) {
+  const double* node_state = out_state ? tree->state : nullptr;
+  const int32_t* key = bd ? bd->key : nullptr;
+  const int32_t* cost = bd ? bd->cost : nullptr;
+  if (f)
+    launch_nn_forest(queries, q_stride, B, tree->xy, f->off, f->n_trees, f->counters, f->tree_capacity, 0, out_idx, node_state,
+                     tree->last_action, tree->has_prev, out_state, out_prev_action, out_has_prev, s, tree->state_dim,
+                     tree->action_dim, key, cost);
+  else
+    launch_nn_argmin(queries, q_stride, B, tree->xy, n_nodes, out_idx, node_state, tree->last_action, tree->has_prev, out_state,
+                     out_prev_action, out_has_prev, s, tree->state_dim, tree->action_dim, key, cost, tree->counters);
+}
+
+// What a call that runs the sampler refuses before anything is launched: an incomplete schedule (t0 with dt, or with ddpm_coef
+// for the DDPM branch, whose K > 1 steps need step noise) and a loaded denoiser other than the one the caller's buffers are sized
+// for (P, lm_n, D-wide actions, C-wide conditioning).  who: the entry point's name in the messages; noise_shape: the tail of the
+// step-noise message; car_needs: the tail of the car's mismatch message (NULL: the ant's own text).
+static int check_sampler(ditree_ctx* ctx, const char* who, const float* t0, const float* dt, const float* ddpm_coef,
+                         const float* step_noise, int K, int P, int lm_n, int D, int C, const char* noise_shape,
+                         const char* car_needs) {
+  const std::string w(who);
+  if (!t0 || (!dt && !ddpm_coef) || K < 1) return set_err(ctx, DITREE_E_ARG, w + ": flow schedule missing");
+  if (ddpm_coef && !step_noise && K > 1) return set_err(ctx, DITREE_E_ARG, w + ": the DDPM branch needs step_noise" + noise_shape);
+  // the scratch buffers are sized from the caller's P / lm_n; the denoiser strides them by ITS dimensions
+  int32_t d5[5];
+  if (ditree_denoise_dims(ctx, d5) != DITREE_OK) return DITREE_E_STATE;
+  if (P == d5[0] && lm_n == d5[2] && d5[1] == D && d5[3] == C) return DITREE_OK;
+  const std::string p0 = std::to_string(d5[0]), ad = std::to_string(d5[1]), map = std::to_string(d5[2]), cond = std::to_string(d5[3]);
+  if (!car_needs)
+    return set_err(ctx, DITREE_E_ARG, w + ": the loaded denoiser is not the ant network (P " + p0 + ", action_dim " + ad + ", cond " +
+                   cond + ", map " + map + "; need P = params.P, 8, 97, map = params.lm_n)");
+  return set_err(ctx, DITREE_E_ARG, w + ": pred_horizon " + std::to_string(P) + " / local map " + std::to_string(lm_n) +
+                 " do not match the loaded denoiser (P " + p0 + ", action_dim " + ad + ", map " + map + ", cond " + cond + car_needs);
+}
+
 // checked copy of the caller's ant model into the kernels' argument block (also mppi_kernels.hip)
 int fill_ant_model(ditree_ctx* ctx, const ditree_ant_model* m, AntModelArg* a) {
   if (!(m->h > 0.0) || !(m->frame_skip >= 1.0) || m->frame_skip > 64.0 || m->frame_skip != (double)(int)m->frame_skip)
@@ -110,14 +205,8 @@ void ditree_ctx_destroy(ditree_ctx* ctx) {
   ditree_comm_destroy(ctx);
   denoise_destroy(ctx);
   if (ctx->maze) hipFree(ctx->maze);
-  if (ctx->cur_state) hipFree(ctx->cur_state);
-  if (ctx->prev_action) hipFree(ctx->prev_action);
-  if (ctx->has_prev) hipFree(ctx->has_prev);
-  if (ctx->lmap) hipFree(ctx->lmap);
-  if (ctx->cond) hipFree(ctx->cond);
-  if (ctx->act64) hipFree(ctx->act64);
-  if (ctx->alive_idx) hipFree(ctx->alive_idx);
-  if (ctx->alive_nrow) hipFree(ctx->alive_nrow);
+  free_round_scratch(&ctx->car);
+  free_round_scratch(&ctx->ant);
   if (ctx->alive_cnt) hipFree(ctx->alive_cnt);
   if (ctx->alive_cnt_host) hipHostFree(ctx->alive_cnt_host);
   if (ctx->path_dev) hipFree(ctx->path_dev);
@@ -125,8 +214,6 @@ void ditree_ctx_destroy(ditree_ctx* ctx) {
   if (ctx->mppi_minkey) hipFree(ctx->mppi_minkey);
   if (ctx->scene_tab) hipFree(ctx->scene_tab);
   if (ctx->row_scene) hipFree(ctx->row_scene);
-  void* ant[] = {ctx->ant_hist, ctx->ant_hist_n, ctx->ant_idx, ctx->ant_nrow, ctx->ant_prev, ctx->ant_hasprev, ctx->ant_cond, ctx->ant_lmap, ctx->ant_act};
-  for (void* q : ant) if (q) hipFree(q);
   delete ctx;
 }
 
@@ -587,32 +674,30 @@ int32_t ditree_comm_destroy(ditree_ctx* ctx) {
   return DITREE_OK;
 }
 
-static int ensure_scratch(ditree_ctx* ctx, int B, int lm_n, int P) {
-  if (B <= ctx->scratch_B && lm_n <= ctx->scratch_lm && P <= ctx->scratch_P) return DITREE_OK;
-  HIP_TRY(ctx, hipDeviceSynchronize());
-  void** ptrs[] = {(void**)&ctx->cur_state, (void**)&ctx->prev_action, (void**)&ctx->has_prev, (void**)&ctx->lmap,
-                   (void**)&ctx->cond, (void**)&ctx->act64, (void**)&ctx->alive_idx, (void**)&ctx->alive_nrow, (void**)&ctx->alive_cnt};
-  int nb = B > ctx->scratch_B ? B : ctx->scratch_B;
-  int nl = lm_n > ctx->scratch_lm ? lm_n : ctx->scratch_lm;
-  int np = P > ctx->scratch_P ? P : ctx->scratch_P;
-  ctx->scratch_B = ctx->scratch_lm = ctx->scratch_P = 0;      // a failed allocation below leaves "nothing reserved"
-  for (auto p : ptrs) {
-    if (*p) HIP_TRY(ctx, hipFree(*p));
-    *p = nullptr;
-  }
-  HIP_TRY(ctx, hipMalloc((void**)&ctx->cur_state, (size_t)nb * 6 * sizeof(double)));
-  HIP_TRY(ctx, hipMalloc((void**)&ctx->prev_action, (size_t)nb * 2 * sizeof(double)));
-  HIP_TRY(ctx, hipMalloc((void**)&ctx->has_prev, (size_t)nb));
-  HIP_TRY(ctx, hipMalloc((void**)&ctx->lmap, (size_t)nb * nl * nl * sizeof(float)));
-  HIP_TRY(ctx, hipMalloc((void**)&ctx->cond, (size_t)nb * 7 * sizeof(float)));
-  HIP_TRY(ctx, hipMalloc((void**)&ctx->act64, (size_t)nb * np * 2 * sizeof(double)));
-  HIP_TRY(ctx, hipMalloc((void**)&ctx->alive_idx, (size_t)nb * sizeof(int32_t)));
-  HIP_TRY(ctx, hipMalloc((void**)&ctx->alive_nrow, (size_t)nb * sizeof(int32_t)));
-  HIP_TRY(ctx, hipMalloc((void**)&ctx->alive_cnt, 16));
-  if (!ctx->alive_cnt_host) HIP_TRY(ctx, hipHostMalloc((void**)&ctx->alive_cnt_host, 16, hipHostMallocDefault));
-  ctx->scratch_B = nb;
-  ctx->scratch_lm = nl;
-  ctx->scratch_P = np;
+static SceneArg scene_arg(const ditree_ctx* ctx) { return SceneArg{ctx->scene_tab, ctx->atlas_cells, ctx->max_scene_cells}; }
+
+// The (B,) row -> scene scratch of scene-forest rounds; its address lives in the device scene table's header.
+static int ensure_row_scene(ditree_ctx* ctx, int B, hipStream_t s) {
+  if (B <= ctx->row_scene_cap) return DITREE_OK;
+  HIP_TRY(ctx, hipStreamSynchronize(s));                // the previous scratch may still be read
+  if (ctx->row_scene) HIP_TRY(ctx, hipFree(ctx->row_scene));
+  ctx->row_scene = nullptr;
+  ctx->row_scene_cap = 0;
+  HIP_TRY(ctx, hipMalloc((void**)&ctx->row_scene, (size_t)B * sizeof(int32_t)));
+  ctx->row_scene_cap = B;
+  HIP_TRY(ctx, hipMemcpyAsync(&ctx->scene_tab->row_scene, &ctx->row_scene, sizeof(ctx->row_scene), hipMemcpyHostToDevice, s));
+  HIP_TRY(ctx, hipStreamSynchronize(s));                // the source is a ctx field that the next growth overwrites
+  return DITREE_OK;
+}
+
+// The scene argument of a scene forest's round (forest and tree_scene validated by the caller): the table, and every row's scene
+// id written into the row -> scene scratch.
+static int round_scenes(ditree_ctx* ctx, const ditree_forest* f, const int32_t* tree_scene, int B, hipStream_t s, SceneArg* sc) {
+  *sc = scene_arg(ctx);
+  if (B == 0) return DITREE_OK;
+  const int rc = ensure_row_scene(ctx, B, s);
+  if (rc) return rc;
+  launch_row_scene(f->off, f->n_trees, tree_scene, B, ctx->row_scene, s);
   return DITREE_OK;
 }
 
@@ -620,7 +705,7 @@ static int ensure_scratch(ditree_ctx* ctx, int B, int lm_n, int P) {
 // scenes (an ant scene forest, validated by the caller): each row's maze and desired goal come from the scene table, so neither
 // an uploaded single maze nor p->desired_goal is required.
 static int check_ant_round(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round, const ditree_ant_round_params* p,
-                           int need_sampler, int* P_out, bool scenes = false) {
+                           int need_sampler, bool scenes = false) {
   int rc = check_tree(ctx, tree);
   if (rc) return rc;
   rc = check_round(ctx, round);
@@ -630,44 +715,10 @@ static int check_ant_round(ditree_ctx* ctx, const ditree_tree* tree, const ditre
     return set_err(ctx, DITREE_E_ARG, "expand_round_ant: the tree must have state_dim 29, action_dim 8 and hist / hist_n");
   if (!p || !p->cond_goal || !p->norm || (!scenes && !p->desired_goal) || !p->axis || !(p->s_global > 0.0) || p->P < tree->A)
     return set_err(ctx, DITREE_E_ARG, "expand_round_ant: bad parameters");
-  if (need_sampler) {
-    if (!p->noise && !p->inject_actions) return set_err(ctx, DITREE_E_ARG, "expand_round_ant: neither noise nor inject_actions");
-    if (!p->inject_actions) {
-      if (!p->t0 || (!p->dt && !p->ddpm_coef) || p->K < 1) return set_err(ctx, DITREE_E_ARG, "expand_round_ant: flow schedule missing");
-      if (p->ddpm_coef && !p->step_noise && p->K > 1) return set_err(ctx, DITREE_E_ARG, "expand_round_ant: the DDPM branch needs step_noise");
-      int32_t d5[5];
-      if (ditree_denoise_dims(ctx, d5) != DITREE_OK) return DITREE_E_STATE;
-      if (d5[1] != ANT_D || d5[3] != 97 || p->lm_n != d5[2] || p->P != d5[0])
-        return set_err(ctx, DITREE_E_ARG, "expand_round_ant: the loaded denoiser is not the ant network (P " + std::to_string(d5[0]) +
-                       ", action_dim " + std::to_string(d5[1]) + ", cond " + std::to_string(d5[3]) + ", map " + std::to_string(d5[2]) +
-                       "; need P = params.P, 8, 97, map = params.lm_n)");
-    }
-  }
-  *P_out = p->P;
-  return DITREE_OK;
-}
-
-static int ensure_ant_scratch(ditree_ctx* ctx, int B, int P, int lm) {
-  if (B <= ctx->ant_B && P <= ctx->ant_P && lm <= ctx->ant_lm) return DITREE_OK;
-  HIP_TRY(ctx, hipDeviceSynchronize());
-  void** ptrs[] = {(void**)&ctx->ant_hist, (void**)&ctx->ant_hist_n, (void**)&ctx->ant_idx, (void**)&ctx->ant_nrow, (void**)&ctx->ant_prev,
-                   (void**)&ctx->ant_hasprev, (void**)&ctx->ant_cond, (void**)&ctx->ant_lmap, (void**)&ctx->ant_act};
-  const size_t nb = (size_t)std::max(B, ctx->ant_B), np = (size_t)std::max(P, ctx->ant_P), nl = (size_t)std::max(lm, ctx->ant_lm);
-  ctx->ant_B = ctx->ant_P = ctx->ant_lm = 0;            // a failed allocation below leaves "nothing reserved", not stale sizes
-  for (auto q : ptrs) { if (*q) HIP_TRY(ctx, hipFree(*q)); *q = nullptr; }
-  HIP_TRY(ctx, hipMalloc((void**)&ctx->ant_hist, nb * 3 * ANT_S * sizeof(double)));
-  HIP_TRY(ctx, hipMalloc((void**)&ctx->ant_hist_n, nb * sizeof(int32_t)));
-  HIP_TRY(ctx, hipMalloc((void**)&ctx->ant_idx, nb * sizeof(int32_t)));
-  HIP_TRY(ctx, hipMalloc((void**)&ctx->ant_nrow, nb * sizeof(int32_t)));
-  HIP_TRY(ctx, hipMalloc((void**)&ctx->ant_prev, nb * ANT_D * sizeof(double)));
-  HIP_TRY(ctx, hipMalloc((void**)&ctx->ant_hasprev, nb));
-  HIP_TRY(ctx, hipMalloc((void**)&ctx->ant_cond, nb * 97 * sizeof(float)));
-  HIP_TRY(ctx, hipMalloc((void**)&ctx->ant_lmap, nb * nl * nl * sizeof(float)));
-  HIP_TRY(ctx, hipMalloc((void**)&ctx->ant_act, nb * np * ANT_D * sizeof(double)));
-  if (!ctx->alive_cnt) HIP_TRY(ctx, hipMalloc((void**)&ctx->alive_cnt, 16));
-  if (!ctx->alive_cnt_host) HIP_TRY(ctx, hipHostMalloc((void**)&ctx->alive_cnt_host, 16, hipHostMallocDefault));
-  ctx->ant_B = (int)nb; ctx->ant_P = (int)np; ctx->ant_lm = (int)nl;
-  return DITREE_OK;
+  if (!need_sampler) return DITREE_OK;
+  if (!p->noise && !p->inject_actions) return set_err(ctx, DITREE_E_ARG, "expand_round_ant: neither noise nor inject_actions");
+  if (p->inject_actions) return DITREE_OK;
+  return check_sampler(ctx, "expand_round_ant", p->t0, p->dt, p->ddpm_coef, p->step_noise, p->K, p->P, p->lm_n, ANT_D, 97, "", nullptr);
 }
 
 // The begin step of an ant round on one tree, or (f != NULL, validated by the caller) on a forest: only the nearest-node search
@@ -675,8 +726,7 @@ static int ensure_ant_scratch(ditree_ctx* ctx, int B, int P, int lm) {
 static int ant_round_begin_impl(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* f, const ditree_round* round,
                                 const ditree_ant_round_params* p, void* stream, bool scenes = false) {
   if (!ctx) return DITREE_E_ARG;
-  int P = 0;
-  int rc = check_ant_round(ctx, tree, round, p, 0, &P, scenes);
+  int rc = check_ant_round(ctx, tree, round, p, 0, scenes);
   if (rc) return rc;
   if (!p->samples || (!f && (p->n_nodes <= 0 || p->n_nodes > tree->capacity)))
     return set_err(ctx, DITREE_E_ARG, "ant_round_begin: samples / n_nodes");
@@ -684,17 +734,13 @@ static int ant_round_begin_impl(ditree_ctx* ctx, const ditree_tree* tree, const 
   if (B == 0) return DITREE_OK;
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  rc = ensure_ant_scratch(ctx, B, P, p->lm_n);
+  RoundScratch& a = ctx->ant;
+  rc = ensure_round_scratch(ctx, &a, B, p->lm_n, p->P, ANT_S, ANT_D, 97, 3);
   if (rc) return rc;
   launch_round_begin(round->status, round->chunks_run, round->chunk_steps, B, tree->n_chunks, s);
   // RRT.py:141-147: nearest node -> curr_state (the live state of the round: round->end_state), prev_actions, prev_states
-  if (f)
-    launch_nn_forest(p->samples, ANT_S, B, tree->xy, f->off, f->n_trees, f->counters, f->tree_capacity, 0, round->parent, tree->state,
-                     tree->last_action, tree->has_prev, round->end_state, ctx->ant_prev, ctx->ant_hasprev, s, ANT_S, ANT_D);
-  else
-    launch_nn_argmin(p->samples, ANT_S, B, tree->xy, p->n_nodes, round->parent, tree->state, tree->last_action, tree->has_prev,
-                     round->end_state, ctx->ant_prev, ctx->ant_hasprev, s, ANT_S, ANT_D);
-  launch_ant_gather_hist(round->parent, tree->hist, tree->hist_n, B, ctx->ant_hist, ctx->ant_hist_n, s);   // parents are global ids
+  launch_nn(tree, f, p->n_nodes, nullptr, p->samples, ANT_S, B, round->parent, round->end_state, a.prev_action, a.has_prev, s);
+  launch_ant_gather_hist(round->parent, tree->hist, tree->hist_n, B, a.hist, a.hist_n, s);   // parents are global ids
   ctx->ant_n_run = B;
   ctx->ant_run_idx = nullptr;
   HIP_TRY(ctx, hipGetLastError());
@@ -706,130 +752,134 @@ int32_t ditree_ant_round_begin(ditree_ctx* ctx, const ditree_tree* tree, const d
   return ant_round_begin_impl(ctx, tree, nullptr, round, p, stream);
 }
 
-// The sample half of chunk j; scp != NULL (an ant scene forest): the local map is cut from each row's own scene.
-static int ant_chunk_sample_impl(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round,
-                                 const ditree_ant_round_params* p, int32_t j, void* stream, const SceneArg* scp) {
-  if (!ctx) return DITREE_E_ARG;
-  int P = 0;
-  int rc = check_ant_round(ctx, tree, round, p, 1, &P, scp != nullptr);
-  if (rc) return rc;
-  const int B = round->B, nC = tree->n_chunks, A = tree->A;
-  if (j < 0 || j >= nC) return set_err(ctx, DITREE_E_ARG, "ant_chunk_sample: chunk index out of range");
-  if (B == 0) return DITREE_OK;
-  if (B > ctx->ant_B) return set_err(ctx, DITREE_E_STATE, "ant_chunk_sample: call ditree_ant_round_begin first");
-  hipStream_t s = (hipStream_t)stream;
-  if (p->early_exit && j > 0) {
-    // RRT.py:179-184: a collided edge is abandoned -- the chunk runs on the candidates that are still alive
-    launch_compact_alive(round->status, B, ctx->ant_idx, ctx->alive_cnt, s);
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->alive_cnt_host, ctx->alive_cnt, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(ctx, hipStreamSynchronize(s));
-    ctx->ant_n_run = *ctx->alive_cnt_host;
-    ctx->ant_run_idx = ctx->ant_idx;
-  } else if (j == 0) {
-    ctx->ant_n_run = B;
-    ctx->ant_run_idx = nullptr;
-  }
-  const int n_run = ctx->ant_n_run;
-  const int32_t* idx = ctx->ant_run_idx;
-  if (n_run == 0) return DITREE_OK;
+// A chunk of the ant round is a sample half and a step half, each on a row set (RowSet).  The plain round runs them for
+// j = 0..n_chunks-1 on every row, the pool at j = -1 on the ready list, and the stepped API hands the caller's simulator the
+// actions in between.
+// The sample half: local map -> conditioning -> sampler, or the action tape.  scp != NULL (an ant scene forest): the local map is
+// cut from each row's own scene.
+static int ant_sample_half(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round, const ditree_ant_round_params* p,
+                           const SceneArg* scp, const RowSet& rows, hipStream_t s) {
+  if (rows.n == 0) return DITREE_OK;
+  RoundScratch& a = ctx->ant;
+  const int nC = tree->n_chunks, A = tree->A, P = p->P;
+  const size_t jo = rows.jo();
+  // A chunk loop leaves the chunk's actions in round->actions, where the caller of the stepped API reads them between the halves;
+  // the pool's rollout takes them from where they are.
+  double* chunk_actions = rows.j < 0 ? nullptr : round->actions + jo * A * ANT_D;
   const int64_t ac_stride = (int64_t)nC * A * ANT_D;
-  if (p->inject_actions)
-    launch_ant_copy_actions(p->inject_actions + (size_t)j * P * ANT_D, (int64_t)nC * P * ANT_D, 0, idx, round->status, n_run, A,
-                            round->actions + (size_t)j * A * ANT_D, ac_stride, s);
+  if (p->inject_actions && chunk_actions)
+    launch_ant_copy_actions(p->inject_actions + jo * P * ANT_D, (int64_t)nC * P * ANT_D, 0, rows.idx, round->status, rows.n, A,
+                            chunk_actions, ac_stride, s);
   if (p->inject_actions && !p->cond_out) {               // action tapes need neither the map nor the conditioning
     HIP_TRY(ctx, hipGetLastError());
     return DITREE_OK;
   }
   AxisArg ax;
-  rc = fill_axis(ctx, p->axis, p->lm_n, &ax);
+  int rc = fill_axis(ctx, p->axis, p->lm_n, &ax);
   if (rc) return rc;
   AntNormArg nm;
   fill_ant_norm(p->norm, &nm);
   // RRT.py:158-166: the local map is cut at the chunk's start state (x, y, element 2)
   if (scp)
-    launch_local_map_scenes(*scp, round->end_state, round->status, idx, n_run, p->lm_n, ax, p->s_global, ctx->ant_lmap, s, ANT_S);
+    launch_local_map_scenes(*scp, round->end_state, round->status, rows.idx, rows.n, p->lm_n, ax, p->s_global, a.lmap, s, ANT_S);
   else
-    launch_local_map(ctx->maze, ctx->rows, ctx->cols, round->end_state, round->status, idx, n_run, p->lm_n, ax, p->s_global, 1,
-                     ctx->ant_lmap, s, ANT_S);
-  launch_cond_vector_ant(ctx->ant_hist, 3, ctx->ant_hist_n, ctx->ant_prev, ctx->ant_hasprev, p->cond_goal, idx, n_run, nm,
-                         p->lm_size, ctx->ant_cond, s);
+    launch_local_map(ctx->maze, ctx->rows, ctx->cols, round->end_state, round->status, rows.idx, rows.n, p->lm_n, ax, p->s_global, 1,
+                     a.lmap, s, ANT_S);
+  launch_cond_vector_ant(a.hist, 3, a.hist_n, a.prev_action, a.has_prev, p->cond_goal, rows.idx, rows.n, nm, p->lm_size, a.cond, s);
   if (p->cond_out) {
-    if (idx) return set_err(ctx, DITREE_E_ARG, "expand_round_ant: cond_out is a test output of rounds without early_exit");
-    HIP_TRY(ctx, hipMemcpy2DAsync(p->cond_out + (size_t)j * 97, (size_t)nC * 97 * sizeof(float), ctx->ant_cond, 97 * sizeof(float),
-                                  97 * sizeof(float), (size_t)B, hipMemcpyDeviceToDevice, s));
+    if (rows.idx) return set_err(ctx, DITREE_E_ARG, "expand_round_ant: cond_out is a test output of rounds without early_exit");
+    HIP_TRY(ctx, hipMemcpy2DAsync(p->cond_out + jo * 97, (size_t)nC * 97 * sizeof(float), a.cond, 97 * sizeof(float),
+                                  97 * sizeof(float), (size_t)rows.n, hipMemcpyDeviceToDevice, s));
   }
   if (p->inject_actions) {
     HIP_TRY(ctx, hipGetLastError());
     return DITREE_OK;
   }
-  rc = round_sampler(ctx, p->noise + (size_t)j * P * ANT_D, (int64_t)nC * P * ANT_D, idx, ctx->ant_lmap, ctx->ant_cond, n_run, p->K, p->t0,
-                     p->dt, p->ddpm_coef, p->step_noise ? p->step_noise + (size_t)j * p->K * P * ANT_D : nullptr,
-                     (int64_t)nC * p->K * P * ANT_D, (int64_t)P * ANT_D, p->norm + 54, ctx->ant_act, s);
+  // start noise rows of (P, 8) and, for the DDPM branch, step noise rows of (K, P, 8)
+  const int64_t nrows = rows.noise_rows(nC);
+  rc = round_sampler(ctx, p->noise + jo * P * ANT_D, nrows * P * ANT_D, rows.nrow, a.lmap, a.cond, rows.n, p->K, p->t0, p->dt,
+                     p->ddpm_coef, p->step_noise ? p->step_noise + jo * p->K * P * ANT_D : nullptr, nrows * p->K * P * ANT_D,
+                     (int64_t)P * ANT_D, p->norm + 54, a.act, s);
   if (rc) return rc;
-  launch_ant_copy_actions(ctx->ant_act, (int64_t)P * ANT_D, 1, idx, round->status, n_run, A, round->actions + (size_t)j * A * ANT_D,
-                          ac_stride, s);
+  if (chunk_actions)
+    launch_ant_copy_actions(a.act, (int64_t)P * ANT_D, 1, rows.idx, round->status, rows.n, A, chunk_actions, ac_stride, s);
   HIP_TRY(ctx, hipGetLastError());
+  return DITREE_OK;
+}
+
+// The step half: the rollout of the chunk's A actions.  model != NULL: the stand-in dynamics; else `tape` holds the observations,
+// (A, 29) rows tape_stride doubles apart per candidate, already offset to chunk j by the caller (the pool: the round's whole tape).
+static int ant_step_half(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round, const ditree_ant_round_params* p,
+                         const SceneArg* scp, const AntModelArg* model, const double* tape, int64_t tape_stride, const RowSet& rows,
+                         hipStream_t s) {
+  if (rows.n == 0) return DITREE_OK;
+  RoundScratch& a = ctx->ant;
+  const int nC = tree->n_chunks, A = tree->A, P = p->P;
+  const size_t jo = rows.jo();
+  const double* acts = p->inject_actions ? p->inject_actions + jo * P * ANT_D : a.act;    // (B, n_chunks, P, 8) by candidate, or dense
+  const int64_t act_stride = p->inject_actions ? (int64_t)nC * P * ANT_D : (int64_t)P * ANT_D;
+  const int64_t st_stride = (int64_t)nC * (A + 1) * ANT_S, ac_stride = (int64_t)nC * A * ANT_D;
+  const double gx = scp ? 0.0 : p->desired_goal[0], gy = scp ? 0.0 : p->desired_goal[1];   // scenes: each row's own goal
+  // rows at different chunks: the per-chunk strides the kernel then adds itself
+  const AntChunkStrides cs = rows.j < 0 ? AntChunkStrides{(int64_t)(A + 1) * ANT_S, (int64_t)A * ANT_D, (int64_t)P * ANT_D, (int64_t)A * ANT_S}
+                                        : AntChunkStrides{0, 0, 0, 0};
+  launch_ant_rollout(ctx->maze, ctx->rows, ctx->cols, model, round->end_state, acts, act_stride, tape, tape_stride, round->status,
+                     rows.n, A, gx, gy, p->goal_radius, p->ball_radius, p->s_global, round->states + jo * (A + 1) * ANT_S,
+                     ditree_strides{st_stride, ANT_S, 1}, round->actions + jo * A * ANT_D, ditree_strides{ac_stride, ANT_D, 1},
+                     round->chunk_steps + jo, nC, round->chunks_run, a.prev_action, a.has_prev, a.hist, a.hist_n, rows.idx,
+                     p->inject_actions ? 0 : 1, s, rows.j < 0, cs, scp);
+  HIP_TRY(ctx, hipGetLastError());
+  return DITREE_OK;
+}
+
+// What both stepped chunk calls check first; `who` names the entry point in its own messages.
+static int check_ant_chunk_call(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round, const ditree_ant_round_params* p,
+                                int j, const char* who) {
+  if (!ctx) return DITREE_E_ARG;
+  const int rc = check_ant_round(ctx, tree, round, p, 1);
+  if (rc) return rc;
+  if (j < 0 || j >= tree->n_chunks) return set_err(ctx, DITREE_E_ARG, std::string(who) + ": chunk index out of range");
+  if (round->B > ctx->ant.B) return set_err(ctx, DITREE_E_STATE, std::string(who) + ": call ditree_ant_round_begin first");
   return DITREE_OK;
 }
 
 int32_t ditree_ant_chunk_sample(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round,
                                 const ditree_ant_round_params* p, int32_t j, void* stream) {
-  return ant_chunk_sample_impl(ctx, tree, round, p, j, stream, nullptr);
-}
-
-static int ant_chunk_step_impl(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round, const ditree_ant_round_params* p,
-                               int j, const double* obs, int64_t obs_stride, const AntModelArg* model, hipStream_t s,
-                               const SceneArg* scp = nullptr) {
-  const int B = round->B, nC = tree->n_chunks, A = tree->A, P = p->P;
-  const int n_run = ctx->ant_n_run;
-  if (n_run == 0) return DITREE_OK;
-  const double* acts;
-  int64_t act_stride;
-  int act_dense;
-  if (p->inject_actions) {
-    acts = p->inject_actions + (size_t)j * P * ANT_D;
-    act_stride = (int64_t)nC * P * ANT_D;
-    act_dense = 0;
-  } else {
-    acts = ctx->ant_act;
-    act_stride = (int64_t)P * ANT_D;
-    act_dense = 1;
+  const int rc = check_ant_chunk_call(ctx, tree, round, p, j, "ant_chunk_sample");
+  if (rc) return rc;
+  const int B = round->B;
+  if (B == 0) return DITREE_OK;
+  hipStream_t s = (hipStream_t)stream;
+  if (p->early_exit && j > 0) {
+    // RRT.py:179-184: a collided edge is abandoned -- the chunk runs on the candidates that are still alive
+    launch_compact_alive(round->status, B, ctx->ant.idx, ctx->alive_cnt, s);
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->alive_cnt_host, ctx->alive_cnt, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    ctx->ant_n_run = *ctx->alive_cnt_host;
+    ctx->ant_run_idx = ctx->ant.idx;
+  } else if (j == 0) {
+    ctx->ant_n_run = B;
+    ctx->ant_run_idx = nullptr;
   }
-  const int64_t st_stride = (int64_t)nC * (A + 1) * ANT_S, ac_stride = (int64_t)nC * A * ANT_D;
-  const double gx = scp ? 0.0 : p->desired_goal[0], gy = scp ? 0.0 : p->desired_goal[1];   // scenes: each row's own goal
-  launch_ant_rollout(ctx->maze, ctx->rows, ctx->cols, model, round->end_state, acts, act_stride, obs, obs_stride, round->status,
-                     n_run, A, gx, gy, p->goal_radius, p->ball_radius, p->s_global,
-                     round->states + (size_t)j * (A + 1) * ANT_S, ditree_strides{st_stride, ANT_S, 1},
-                     round->actions + (size_t)j * A * ANT_D, ditree_strides{ac_stride, ANT_D, 1}, round->chunk_steps + j, nC,
-                     round->chunks_run, ctx->ant_prev, ctx->ant_hasprev, ctx->ant_hist, ctx->ant_hist_n, ctx->ant_run_idx, act_dense,
-                     s, 0, AntChunkStrides{0, 0, 0, 0}, scp);
-  (void)B;
-  HIP_TRY(ctx, hipGetLastError());
-  return DITREE_OK;
+  return ant_sample_half(ctx, tree, round, p, nullptr, RowSet{ctx->ant_run_idx, ctx->ant_run_idx, ctx->ant_n_run, j}, s);
 }
 
 int32_t ditree_ant_chunk_step(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round,
                               const ditree_ant_round_params* p, int32_t j, const double* next_obs, void* stream) {
-  if (!ctx) return DITREE_E_ARG;
-  int P = 0;
-  int rc = check_ant_round(ctx, tree, round, p, 1, &P);
+  const int rc = check_ant_chunk_call(ctx, tree, round, p, j, "ant_chunk_step");
   if (rc) return rc;
-  if (j < 0 || j >= tree->n_chunks) return set_err(ctx, DITREE_E_ARG, "ant_chunk_step: chunk index out of range");
   if (round->B == 0) return DITREE_OK;
-  if (round->B > ctx->ant_B) return set_err(ctx, DITREE_E_STATE, "ant_chunk_step: call ditree_ant_round_begin first");
   if (!next_obs) return set_err(ctx, DITREE_E_ARG, "ant_chunk_step: next_obs (B, A, 29) is required");
-  return ant_chunk_step_impl(ctx, tree, round, p, j, next_obs, (int64_t)tree->A * ANT_S, nullptr, (hipStream_t)stream);
+  return ant_step_half(ctx, tree, round, p, nullptr, nullptr, next_obs, (int64_t)tree->A * ANT_S,
+                       RowSet{ctx->ant_run_idx, ctx->ant_run_idx, ctx->ant_n_run, j}, (hipStream_t)stream);
 }
-
-static int ensure_row_scene(ditree_ctx* ctx, int B, hipStream_t s);
 
 // The ant round of one tree, or (f != NULL, validated by the caller) of a forest: only the begin step differs.  An ant scene
 // forest (tree_scene != NULL, validated by the caller) reads each row's maze and desired goal from the scene table instead.
 static int expand_round_ant_impl(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* f, const ditree_round* round,
                                  const ditree_ant_round_params* p, void* stream, const int32_t* tree_scene = nullptr) {
   if (!ctx) return DITREE_E_ARG;
-  int P = 0;
-  int rc = check_ant_round(ctx, tree, round, p, 1, &P, tree_scene != nullptr);
+  int rc = check_ant_round(ctx, tree, round, p, 1, tree_scene != nullptr);
   if (rc) return rc;
   AntModelArg ma;
   const AntModelArg* model = nullptr;
@@ -843,76 +893,36 @@ static int expand_round_ant_impl(ditree_ctx* ctx, const ditree_tree* tree, const
   } else {
     return set_err(ctx, DITREE_E_ARG, "expand_round_ant: dynamics must be DITREE_ANT_DYN_TAPE or DITREE_ANT_DYN_MODEL");
   }
+  const int B = round->B, nC = tree->n_chunks, A = tree->A;
+  hipStream_t s = (hipStream_t)stream;
+  if (p->early_exit && B > 0 && p->cond_out)
+    return set_err(ctx, DITREE_E_ARG, "expand_round_ant: cond_out is a test output of rounds without early_exit");
   SceneArg sc{};
   const SceneArg* scp = nullptr;
-  if (p->early_exit && round->B > 0 && p->cond_out)
-    return set_err(ctx, DITREE_E_ARG, "expand_round_ant: cond_out is a test output of rounds without early_exit");
   if (tree_scene) {
-    sc = SceneArg{ctx->scene_tab, ctx->atlas_cells, ctx->max_scene_cells};
+    rc = round_scenes(ctx, f, tree_scene, B, s, &sc);
+    if (rc) return rc;
     scp = &sc;
-    if (round->B > 0) {
-      rc = ensure_row_scene(ctx, round->B, (hipStream_t)stream);
-      if (rc) return rc;
-      launch_row_scene(f->off, f->n_trees, tree_scene, round->B, ctx->row_scene, (hipStream_t)stream);
-    }
   }
-  const double gx = scp ? 0.0 : p->desired_goal[0], gy = scp ? 0.0 : p->desired_goal[1];   // scenes: each row's own goal
   rc = ant_round_begin_impl(ctx, tree, f, round, p, stream, scp != nullptr);
-  if (rc) return rc;
-  const int nC = tree->n_chunks, A = tree->A;
-  if (p->early_exit && round->B > 0) {
+  if (rc || B == 0) return rc;
+  const int64_t tape_stride = (int64_t)nC * A * ANT_S;
+  if (p->early_exit) {
     // the pool-scheduled form of the car round's early exit (ditree_expand_round): calls packed to whole tile-waves (2048
     // candidates for the ant network) from the ready list, rows of one launch at different chunks of their edges
-    hipStream_t s = (hipStream_t)stream;
     const int quantum = p->inject_actions ? 64 : denoise_wave_quantum(ctx);
-    AxisArg ax;
-    rc = fill_axis(ctx, p->axis, p->lm_n, &ax);
-    if (rc) return rc;
-    AntNormArg nm;
-    fill_ant_norm(p->norm, &nm);
-    const int64_t st_stride = (int64_t)nC * (A + 1) * ANT_S, ac_stride = (int64_t)nC * A * ANT_D;
-    const AntChunkStrides cs{(int64_t)(A + 1) * ANT_S, (int64_t)A * ANT_D, (int64_t)P * ANT_D, (int64_t)A * ANT_S};
-    rc = run_ready_pool(ctx, "expand_round_ant", round, nullptr, nC, quantum, ctx->ant_idx, ctx->ant_nrow, s, [&](int take) -> int {
-      const double* acts;
-      int64_t act_stride;
-      int act_dense = 1;
-      if (p->inject_actions) {
-        acts = p->inject_actions;
-        act_stride = (int64_t)nC * P * ANT_D;
-        act_dense = 0;
-      } else {
-        if (scp)
-          launch_local_map_scenes(sc, round->end_state, round->status, ctx->ant_idx, take, p->lm_n, ax, p->s_global, ctx->ant_lmap, s,
-                                  ANT_S);
-        else
-          launch_local_map(ctx->maze, ctx->rows, ctx->cols, round->end_state, round->status, ctx->ant_idx, take, p->lm_n, ax,
-                           p->s_global, 1, ctx->ant_lmap, s, ANT_S);
-        launch_cond_vector_ant(ctx->ant_hist, 3, ctx->ant_hist_n, ctx->ant_prev, ctx->ant_hasprev, p->cond_goal, ctx->ant_idx, take, nm,
-                               p->lm_size, ctx->ant_cond, s);
-        const int src = round_sampler(ctx, p->noise, (int64_t)P * ANT_D, ctx->ant_nrow, ctx->ant_lmap, ctx->ant_cond, take, p->K, p->t0,
-                                      p->dt, p->ddpm_coef, p->step_noise, (int64_t)p->K * P * ANT_D, (int64_t)P * ANT_D, p->norm + 54,
-                                      ctx->ant_act, s);
-        if (src) return src;
-        acts = ctx->ant_act;
-        act_stride = (int64_t)P * ANT_D;
-      }
-      launch_ant_rollout(ctx->maze, ctx->rows, ctx->cols, model, round->end_state, acts, act_stride, p->next_obs_tape,
-                         (int64_t)nC * A * ANT_S, round->status, take, A, gx, gy, p->goal_radius,
-                         p->ball_radius, p->s_global, round->states, ditree_strides{st_stride, ANT_S, 1}, round->actions,
-                         ditree_strides{ac_stride, ANT_D, 1}, round->chunk_steps, nC, round->chunks_run, ctx->ant_prev, ctx->ant_hasprev,
-                         ctx->ant_hist, ctx->ant_hist_n, ctx->ant_idx, act_dense, s, 1, cs, scp);
-      return DITREE_OK;
+    rc = run_ready_pool(ctx, "expand_round_ant", round, nullptr, nC, quantum, ctx->ant.idx, ctx->ant.nrow, s, [&](int take) -> int {
+      const RowSet rows{ctx->ant.idx, ctx->ant.nrow, take, -1};
+      const int src = ant_sample_half(ctx, tree, round, p, scp, rows, s);
+      return src ? src : ant_step_half(ctx, tree, round, p, scp, model, p->next_obs_tape, tape_stride, rows, s);
     });
-    if (rc) return rc;
-    HIP_TRY(ctx, hipGetLastError());
-    return DITREE_OK;
+    return rc;
   }
   for (int j = 0; j < nC; ++j) {
-    rc = ant_chunk_sample_impl(ctx, tree, round, p, j, stream, scp);
+    const RowSet rows{nullptr, nullptr, B, j};
+    rc = ant_sample_half(ctx, tree, round, p, scp, rows, s);
     if (rc) return rc;
-    if (ctx->ant_n_run == 0) break;
-    const double* obs = model ? nullptr : p->next_obs_tape + (size_t)j * A * ANT_S;
-    rc = ant_chunk_step_impl(ctx, tree, round, p, j, obs, (int64_t)nC * A * ANT_S, model, (hipStream_t)stream, scp);
+    rc = ant_step_half(ctx, tree, round, p, scp, model, model ? nullptr : p->next_obs_tape + (size_t)j * A * ANT_S, tape_stride, rows, s);
     if (rc) return rc;
   }
   return DITREE_OK;
@@ -923,24 +933,34 @@ int32_t ditree_expand_round_ant(ditree_ctx* ctx, const ditree_tree* tree, const 
   return expand_round_ant_impl(ctx, tree, nullptr, round, p, stream);
 }
 
+// planners/RRT.py:149-152 for the B candidates of a round, behind both chunk-budget entry points (`who` in the messages) after
+// their tree / forest check.  f != NULL: parents are global node ids, so "earlier candidates with the same parent" never crosses trees.
+static int chunk_budget_impl(ditree_ctx* ctx, const char* who, const ditree_tree* tree, const ditree_forest* f, int n_nodes,
+                             const double* samples, int B, const int32_t* schedule_chunks, int n_schedule, int32_t* parent_scratch,
+                             int32_t* budget_out, void* stream) {
+  const std::string w(who);
+  if (B == 0) return DITREE_OK;
+  if (!samples || !schedule_chunks || !parent_scratch || !budget_out || B < 0 || n_schedule < 1 || n_schedule > 16 ||
+      (!f && (n_nodes <= 0 || n_nodes > tree->capacity)))
+    return set_err(ctx, DITREE_E_ARG, w + ": bad argument (1..16 schedule entries)");
+  for (int i = 0; i < n_schedule; ++i)
+    if (schedule_chunks[i] < 1 || schedule_chunks[i] > tree->n_chunks)
+      return set_err(ctx, DITREE_E_ARG, w + ": a schedule entry exceeds the tree's edge capacity (n_chunks)");
+  hipStream_t s = (hipStream_t)stream;
+  launch_nn(tree, f, n_nodes, nullptr, samples, tree->state_dim, B, parent_scratch, nullptr, nullptr, nullptr, s);
+  launch_chunk_budget(parent_scratch, B, tree->num_visit, schedule_chunks, n_schedule, budget_out, s);
+  HIP_TRY(ctx, hipGetLastError());
+  return DITREE_OK;
+}
+
 int32_t ditree_chunk_budget(ditree_ctx* ctx, const ditree_tree* tree, const double* samples, int32_t B, int32_t n_nodes,
                             const int32_t* schedule_chunks, int32_t n_schedule, int32_t* parent_scratch, int32_t* budget_out,
                             void* stream) {
   if (!ctx) return DITREE_E_ARG;
-  int rc = check_tree(ctx, tree);
+  const int rc = check_tree(ctx, tree);
   if (rc) return rc;
-  if (B == 0) return DITREE_OK;
-  if (!samples || !schedule_chunks || !parent_scratch || !budget_out || B < 0 || n_schedule < 1 || n_schedule > 16 ||
-      n_nodes <= 0 || n_nodes > tree->capacity)
-    return set_err(ctx, DITREE_E_ARG, "chunk_budget: bad argument (1..16 schedule entries)");
-  for (int i = 0; i < n_schedule; ++i)
-    if (schedule_chunks[i] < 1 || schedule_chunks[i] > tree->n_chunks)
-      return set_err(ctx, DITREE_E_ARG, "chunk_budget: a schedule entry exceeds the tree's edge capacity (n_chunks)");
-  hipStream_t s = (hipStream_t)stream;
-  launch_nn_argmin(samples, tree->state_dim, B, tree->xy, n_nodes, parent_scratch, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, s);
-  launch_chunk_budget(parent_scratch, B, tree->num_visit, schedule_chunks, n_schedule, budget_out, s);
-  HIP_TRY(ctx, hipGetLastError());
-  return DITREE_OK;
+  return chunk_budget_impl(ctx, "chunk_budget", tree, nullptr, n_nodes, samples, B, schedule_chunks, n_schedule, parent_scratch,
+                           budget_out, stream);
 }
 
 int32_t ditree_round_stats(ditree_ctx* ctx, int32_t* stats4) {
@@ -949,20 +969,6 @@ int32_t ditree_round_stats(ditree_ctx* ctx, int32_t* stats4) {
   stats4[1] = ctx->ee_waves;
   stats4[2] = denoise_wave_quantum(ctx);
   stats4[3] = 0;
-  return DITREE_OK;
-}
-
-// The (B,) row -> scene scratch of scene-forest rounds; its address lives in the device scene table's header.
-static int ensure_row_scene(ditree_ctx* ctx, int B, hipStream_t s) {
-  if (B <= ctx->row_scene_cap) return DITREE_OK;
-  HIP_TRY(ctx, hipStreamSynchronize(s));                // the previous scratch may still be read
-  if (ctx->row_scene) HIP_TRY(ctx, hipFree(ctx->row_scene));
-  ctx->row_scene = nullptr;
-  ctx->row_scene_cap = 0;
-  HIP_TRY(ctx, hipMalloc((void**)&ctx->row_scene, (size_t)B * sizeof(int32_t)));
-  ctx->row_scene_cap = B;
-  HIP_TRY(ctx, hipMemcpyAsync(&ctx->scene_tab->row_scene, &ctx->row_scene, sizeof(ctx->row_scene), hipMemcpyHostToDevice, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));                // the source is a ctx field that the next growth overwrites
   return DITREE_OK;
 }
 
@@ -981,26 +987,19 @@ static int expand_round_impl(ditree_ctx* ctx, const ditree_tree* tree, const dit
   if (!p || !p->samples || !p->cond_goal || !p->norm || (!tree_scene && !p->goal_xy) || !p->axis ||
       (!f && (p->n_nodes <= 0 || p->n_nodes > tree->capacity)) || p->P < tree->A || (!p->noise && !p->inject_actions))
     return set_err(ctx, DITREE_E_ARG, "expand_round: bad parameters");
-  if (!p->inject_actions && (!p->t0 || (!p->dt && !p->ddpm_coef) || p->K <= 0))
-    return set_err(ctx, DITREE_E_ARG, "expand_round: flow schedule missing");
-  if (!p->inject_actions && p->ddpm_coef && !p->step_noise && p->K > 1)
-    return set_err(ctx, DITREE_E_ARG, "expand_round: the DDPM branch needs step_noise (B, n_chunks, K, P, 2)");
   if (tree->state_dim != 6 || tree->action_dim != 2)
     return set_err(ctx, DITREE_E_ARG, "expand_round: the car round needs a tree with state_dim 6 / action_dim 2 (ant: ditree_expand_round_ant)");
   const int B = round->B, A = tree->A, nC = tree->n_chunks, P = p->P;
   if (!p->inject_actions) {
-    // the scratch buffers below are sized from the caller's P / lm_n; the denoiser strides them by ITS dimensions
-    int32_t d5[5];
-    if (ditree_denoise_dims(ctx, d5) != DITREE_OK) return DITREE_E_STATE;
-    if (P != d5[0] || p->lm_n != d5[2] || d5[1] != 2 || d5[3] != 7)
-      return set_err(ctx, DITREE_E_ARG, "expand_round: pred_horizon " + std::to_string(P) + " / local map " + std::to_string(p->lm_n) +
-                     " do not match the loaded denoiser (P " + std::to_string(d5[0]) + ", action_dim " + std::to_string(d5[1]) +
-                     ", map " + std::to_string(d5[2]) + ", cond " + std::to_string(d5[3]) + "; the car engine needs action_dim 2, cond 7)");
+    rc = check_sampler(ctx, "expand_round", p->t0, p->dt, p->ddpm_coef, p->step_noise, p->K, P, p->lm_n, 2, 7,
+                       " (B, n_chunks, K, P, 2)", "; the car engine needs action_dim 2, cond 7)");
+    if (rc) return rc;
   }
   if (B == 0) return DITREE_OK;
   hipStream_t s = (hipStream_t)stream;
-  rc = ensure_scratch(ctx, B, p->lm_n, P);
+  rc = ensure_car_scratch(ctx, B, p->lm_n, P);
   if (rc) return rc;
+  RoundScratch& c = ctx->car;
   AxisArg ax;
   rc = fill_axis(ctx, p->axis, p->lm_n, &ax);
   if (rc) return rc;
@@ -1009,29 +1008,20 @@ static int expand_round_impl(ditree_ctx* ctx, const ditree_tree* tree, const dit
   SceneArg sc{};
   const SceneArg* scp = nullptr;
   if (tree_scene) {
-    rc = ensure_row_scene(ctx, B, s);
+    rc = round_scenes(ctx, f, tree_scene, B, s, &sc);
     if (rc) return rc;
-    sc = SceneArg{ctx->scene_tab, ctx->atlas_cells, ctx->max_scene_cells};
     scp = &sc;
-    launch_row_scene(f->off, f->n_trees, tree_scene, B, ctx->row_scene, s);
   }
   const double gx = tree_scene ? 0.0 : p->goal_xy[0], gy = tree_scene ? 0.0 : p->goal_xy[1];   // scenes: each row's own goal
   launch_round_begin(round->status, round->chunks_run, round->chunk_steps, B, nC, s);
-  const int32_t* key = bd ? bd->key : nullptr;
-  const int32_t* cost = bd ? bd->cost : nullptr;
-  if (f)
-    launch_nn_forest(p->samples, 6, B, tree->xy, f->off, f->n_trees, f->counters, f->tree_capacity, 0, round->parent, tree->state,
-                     tree->last_action, tree->has_prev, ctx->cur_state, ctx->prev_action, ctx->has_prev, s, 6, 2, key, cost);
-  else
-    launch_nn_argmin(p->samples, 6, B, tree->xy, p->n_nodes, round->parent, tree->state, tree->last_action,
-                     tree->has_prev, ctx->cur_state, ctx->prev_action, ctx->has_prev, s, 6, 2, key, cost, tree->counters);
+  launch_nn(tree, f, p->n_nodes, bd, p->samples, 6, B, round->parent, c.state, c.prev_action, c.has_prev, s);
   const int64_t st_stride = (int64_t)nC * (A + 1) * 6, ac_stride = (int64_t)nC * A * 2;
-  // One call of the round's chunk body on n rows: local map -> conditioning -> sampler (or the action tape) -> rollout.  Plain
-  // chunk loop: every row at chunk j (idx = nrow = NULL, n = B).  Pool: the rows idx[0..n) with noise rows nrow, each at the chunk
-  // its chunks_run counter names (j = -1, cs = the per-chunk strides the kernel then adds itself).
-  auto chunk_body = [&](const int32_t* idx, const int32_t* nrow, int n, int j, ChunkStrides cs) -> int {
-    const size_t jo = j < 0 ? 0 : (size_t)j;              // the chunk offset the host adds
-    const int64_t nrows = j < 0 ? 1 : nC;                 // noise rows per index step: the (B * n_chunks, ...) view, or candidates
+  // One call of the round's chunk body on a row set: local map -> conditioning -> sampler (or the action tape) -> rollout.  Plain
+  // chunk loop: every row at chunk j.  Pool: the ready list, each row at the chunk its chunks_run counter names (j = -1; the
+  // kernel then adds the per-chunk strides itself).
+  auto chunk_body = [&](const RowSet& rows) -> int {
+    const size_t jo = rows.jo();
+    const int64_t nrows = rows.noise_rows(nC);
     const double* acts;
     int64_t act_stride;
     int act_dense = 1;
@@ -1041,24 +1031,25 @@ static int expand_round_impl(ditree_ctx* ctx, const ditree_tree* tree, const dit
       act_dense = 0;
     } else {
       if (scp)
-        launch_local_map_scenes(sc, ctx->cur_state, round->status, idx, n, p->lm_n, ax, p->s_global, ctx->lmap, s, 6);
+        launch_local_map_scenes(sc, c.state, round->status, rows.idx, rows.n, p->lm_n, ax, p->s_global, c.lmap, s, 6);
       else
-        launch_local_map(ctx->maze, ctx->rows, ctx->cols, ctx->cur_state, round->status, idx, n, p->lm_n, ax, p->s_global, 1,
-                         ctx->lmap, s);
-      launch_cond_vector(ctx->cur_state, ctx->prev_action, ctx->has_prev, p->cond_goal, idx, n, nm, p->lm_size, ctx->cond, s);
+        launch_local_map(ctx->maze, ctx->rows, ctx->cols, c.state, round->status, rows.idx, rows.n, p->lm_n, ax, p->s_global, 1,
+                         c.lmap, s);
+      launch_cond_vector(c.state, c.prev_action, c.has_prev, p->cond_goal, rows.idx, rows.n, nm, p->lm_size, c.cond, s);
       double an[4] = {p->norm[12], p->norm[13], p->norm[14], p->norm[15]};
       // start noise rows of (P, 2) and, for the DDPM branch, step noise rows of (K, P, 2)
-      const int src = round_sampler(ctx, p->noise + jo * P * 2, nrows * P * 2, nrow, ctx->lmap, ctx->cond, n, p->K, p->t0, p->dt,
+      const int src = round_sampler(ctx, p->noise + jo * P * 2, nrows * P * 2, rows.nrow, c.lmap, c.cond, rows.n, p->K, p->t0, p->dt,
                                     p->ddpm_coef, p->step_noise ? p->step_noise + jo * p->K * P * 2 : nullptr,
-                                    nrows * p->K * P * 2, (int64_t)P * 2, an, ctx->act64, s);
+                                    nrows * p->K * P * 2, (int64_t)P * 2, an, c.act, s);
       if (src) return src;
-      acts = ctx->act64;
+      acts = c.act;
       act_stride = (int64_t)P * 2;
     }
-    launch_car_rollout_ex(ctx->maze, ctx->rows, ctx->cols, ctx->cur_state, acts, act_stride, round->status, n, A, gx, gy,
+    const ChunkStrides cs = rows.j < 0 ? ChunkStrides{(int64_t)(A + 1) * 6, (int64_t)A * 2, (int64_t)P * 2} : ChunkStrides{0, 0, 0};
+    launch_car_rollout_ex(ctx->maze, ctx->rows, ctx->cols, c.state, acts, act_stride, round->status, rows.n, A, gx, gy,
                           round->states + jo * (A + 1) * 6, ditree_strides{st_stride, 6, 1}, round->actions + jo * A * 2,
-                          ditree_strides{ac_stride, 2, 1}, round->chunk_steps + jo, nC, round->chunks_run, ctx->prev_action,
-                          ctx->has_prev, idx, act_dense, s, p->chunk_budget, j, cs, scp);
+                          ditree_strides{ac_stride, 2, 1}, round->chunk_steps + jo, nC, round->chunks_run, c.prev_action,
+                          c.has_prev, rows.idx, act_dense, s, p->chunk_budget, rows.j, cs, scp);
     return DITREE_OK;
   };
   // Early exit (p->early_exit): what the reference does by abandoning a collided edge (planners/RRT.py:179-184) -- a chunk runs
@@ -1072,14 +1063,13 @@ static int expand_round_impl(ditree_ctx* ctx, const ditree_tree* tree, const dit
   // loop (tests: traces, rounds, full-size rounds).  Costs one 4-byte D2H per call.
   if (p->early_exit) {
     const int quantum = p->inject_actions ? 64 : denoise_wave_quantum(ctx);
-    const ChunkStrides cs{(int64_t)(A + 1) * 6, (int64_t)A * 2, (int64_t)P * 2};
-    rc = run_ready_pool(ctx, "expand_round", round, p->chunk_budget, nC, quantum, ctx->alive_idx, ctx->alive_nrow, s,
-                        [&](int take) { return chunk_body(ctx->alive_idx, ctx->alive_nrow, take, -1, cs); });
+    rc = run_ready_pool(ctx, "expand_round", round, p->chunk_budget, nC, quantum, c.idx, c.nrow, s,
+                        [&](int take) { return chunk_body(RowSet{c.idx, c.nrow, take, -1}); });
   } else {
-    for (int j = 0; j < nC && !rc; ++j) rc = chunk_body(nullptr, nullptr, B, j, ChunkStrides{0, 0, 0});
+    for (int j = 0; j < nC && !rc; ++j) rc = chunk_body(RowSet{nullptr, nullptr, B, j});
   }
   if (rc) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(round->end_state, ctx->cur_state, (size_t)B * 6 * sizeof(double), hipMemcpyDeviceToDevice, s));
+  HIP_TRY(ctx, hipMemcpyAsync(round->end_state, c.state, (size_t)B * 6 * sizeof(double), hipMemcpyDeviceToDevice, s));
   HIP_TRY(ctx, hipGetLastError());
   return DITREE_OK;
 }
@@ -1161,21 +1151,10 @@ int32_t ditree_forest_chunk_budget(ditree_ctx* ctx, const ditree_tree* tree, con
                                    int32_t B, const int32_t* schedule_chunks, int32_t n_schedule, int32_t* parent_scratch,
                                    int32_t* budget_out, void* stream) {
   if (!ctx) return DITREE_E_ARG;
-  int rc = check_forest(ctx, tree, forest, B, "forest_chunk_budget");
+  const int rc = check_forest(ctx, tree, forest, B, "forest_chunk_budget");
   if (rc) return rc;
-  if (B == 0) return DITREE_OK;
-  if (!samples || !schedule_chunks || !parent_scratch || !budget_out || n_schedule < 1 || n_schedule > 16)
-    return set_err(ctx, DITREE_E_ARG, "forest_chunk_budget: bad argument (1..16 schedule entries)");
-  for (int i = 0; i < n_schedule; ++i)
-    if (schedule_chunks[i] < 1 || schedule_chunks[i] > tree->n_chunks)
-      return set_err(ctx, DITREE_E_ARG, "forest_chunk_budget: a schedule entry exceeds the tree's edge capacity (n_chunks)");
-  hipStream_t s = (hipStream_t)stream;
-  // parents are global node ids: "earlier candidates with the same parent" never crosses trees
-  launch_nn_forest(samples, 6, B, tree->xy, forest->off, forest->n_trees, forest->counters, forest->tree_capacity, 0, parent_scratch,
-                   nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, s);
-  launch_chunk_budget(parent_scratch, B, tree->num_visit, schedule_chunks, n_schedule, budget_out, s);
-  HIP_TRY(ctx, hipGetLastError());
-  return DITREE_OK;
+  return chunk_budget_impl(ctx, "forest_chunk_budget", tree, forest, 0, samples, B, schedule_chunks, n_schedule, parent_scratch,
+                           budget_out, stream);
 }
 
 int32_t ditree_forest_nn_argmin(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const double* queries,
@@ -1185,21 +1164,38 @@ int32_t ditree_forest_nn_argmin(ditree_ctx* ctx, const ditree_tree* tree, const 
   if (rc) return rc;
   if (B == 0) return DITREE_OK;
   if (!queries || !out_idx || q_stride < 2) return set_err(ctx, DITREE_E_ARG, "forest_nn_argmin: bad argument");
-  launch_nn_forest(queries, q_stride, B, tree->xy, forest->off, forest->n_trees, forest->counters, forest->tree_capacity, 0, out_idx,
-                   nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream);
+  launch_nn(tree, forest, 0, nullptr, queries, q_stride, B, out_idx, nullptr, nullptr, nullptr, (hipStream_t)stream);
   HIP_TRY(ctx, hipGetLastError());
   return DITREE_OK;
 }
 
-// planners/RRT.py:227-254 for every tree of a checked forest: the T query rows `goals` (T, 2) on the host (a temporary or the
-// caller's memory, hence the sync) -> ctx->cur_state (T, 6) -> one launch.
-static int forest_fallback_impl(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const double* goals,
-                                int32_t* out_node, hipStream_t s) {
-  const int T = forest->n_trees;
-  const int rc = ensure_scratch(ctx, T, 1, 1);
+// planners/RRT.py:227-254 for every tree of a forest, behind the four fallback entry points (`who` in the messages).  ant: an ant
+// forest's check instead of a car forest's.  per_tree: goal_xy is (T, 2), one goal per tree; else one goal, copied T times.  The T
+// query rows travel from the host (a temporary or the caller's memory, hence the sync) to the car scratch's state rows -> one launch.
+static int forest_fallback_impl(ditree_ctx* ctx, const char* who, const ditree_tree* tree, const ditree_forest* forest, bool ant,
+                                bool per_tree, const double* goal_xy, int32_t* out_node, void* stream) {
+  if (!ctx) return DITREE_E_ARG;
+  int rc = check_forest(ctx, tree, forest, -1, who, ant);
   if (rc) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->cur_state, goals, (size_t)T * 2 * sizeof(double), hipMemcpyHostToDevice, s));
-  launch_forest_fallback(ctx->cur_state, T, tree->xy, forest->counters, forest->tree_capacity, out_node, s);
+  const std::string w(who);
+  if (per_tree) {
+    if (!goal_xy) return set_err(ctx, DITREE_E_ARG, w + ": goals array (T, 2) missing");
+    if (!out_node) return set_err(ctx, DITREE_E_ARG, w + ": out_node missing");
+  } else if (!goal_xy || !out_node) {
+    return set_err(ctx, DITREE_E_ARG, w + ": bad argument");
+  }
+  const int T = forest->n_trees;
+  std::vector<double> copies;
+  if (!per_tree) {
+    copies.resize((size_t)T * 2);
+    for (int t = 0; t < T; ++t) { copies[(size_t)t * 2] = goal_xy[0]; copies[(size_t)t * 2 + 1] = goal_xy[1]; }
+    goal_xy = copies.data();
+  }
+  hipStream_t s = (hipStream_t)stream;
+  rc = ensure_car_scratch(ctx, T, 1, 1);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->car.state, goal_xy, (size_t)T * 2 * sizeof(double), hipMemcpyHostToDevice, s));
+  launch_forest_fallback(ctx->car.state, T, tree->xy, forest->counters, forest->tree_capacity, out_node, s);
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipStreamSynchronize(s));
   return DITREE_OK;
@@ -1207,13 +1203,7 @@ static int forest_fallback_impl(ditree_ctx* ctx, const ditree_tree* tree, const 
 
 int32_t ditree_forest_fallback(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const double* goal_xy,
                                int32_t* out_node, void* stream) {
-  if (!ctx) return DITREE_E_ARG;
-  int rc = check_forest(ctx, tree, forest, -1, "forest_fallback");
-  if (rc) return rc;
-  if (!goal_xy || !out_node) return set_err(ctx, DITREE_E_ARG, "forest_fallback: bad argument");
-  std::vector<double> q((size_t)forest->n_trees * 2);   // T copies of the goal as the queries
-  for (int t = 0; t < forest->n_trees; ++t) { q[(size_t)t * 2] = goal_xy[0]; q[(size_t)t * 2 + 1] = goal_xy[1]; }
-  return forest_fallback_impl(ctx, tree, forest, q.data(), out_node, (hipStream_t)stream);
+  return forest_fallback_impl(ctx, "forest_fallback", tree, forest, false, false, goal_xy, out_node, stream);
 }
 
 // ---- scene forests (include/ditree.h "scene forests")
@@ -1328,24 +1318,30 @@ int32_t ditree_bound_keys(ditree_ctx* ctx, const ditree_tree* tree, const ditree
   return DITREE_OK;
 }
 
+// The masked nearest-node search behind both bounded entry points (`who` in the messages) after their tree / forest check.
+static int nn_argmin_bounded_impl(ditree_ctx* ctx, const char* who, const ditree_tree* tree, const ditree_forest* f, int n_nodes,
+                                  const ditree_bound* bound, const double* queries, int q_stride, int B, int32_t* out_idx,
+                                  double* out_state, double* out_prev_action, uint8_t* out_has_prev, void* stream) {
+  const int rc = check_bound(ctx, bound, nullptr, true);
+  if (rc) return rc;
+  if (B == 0) return DITREE_OK;
+  const bool gather = out_state || out_prev_action || out_has_prev;
+  if (!queries || !out_idx || B < 0 || q_stride < 2 || (!f && (n_nodes <= 0 || n_nodes > tree->capacity)) ||
+      (gather && (!out_state || !out_prev_action || !out_has_prev)))
+    return set_err(ctx, DITREE_E_ARG, std::string(who) + ": bad argument (the three gather outputs come together)");
+  launch_nn(tree, f, n_nodes, bound, queries, q_stride, B, out_idx, out_state, out_prev_action, out_has_prev, (hipStream_t)stream);
+  HIP_TRY(ctx, hipGetLastError());
+  return DITREE_OK;
+}
+
 int32_t ditree_nn_argmin_bounded(ditree_ctx* ctx, const ditree_tree* tree, const ditree_bound* bound, const double* queries,
                                  int32_t q_stride, int32_t B, int32_t n_nodes, int32_t* out_idx, double* out_state,
                                  double* out_prev_action, uint8_t* out_has_prev, void* stream) {
   if (!ctx) return DITREE_E_ARG;
-  int rc = check_tree(ctx, tree);
+  const int rc = check_tree(ctx, tree);
   if (rc) return rc;
-  rc = check_bound(ctx, bound, nullptr, true);
-  if (rc) return rc;
-  if (B == 0) return DITREE_OK;
-  const bool gather = out_state || out_prev_action || out_has_prev;
-  if (!queries || !out_idx || B < 0 || q_stride < 2 || n_nodes <= 0 || n_nodes > tree->capacity ||
-      (gather && (!out_state || !out_prev_action || !out_has_prev)))
-    return set_err(ctx, DITREE_E_ARG, "nn_argmin_bounded: bad argument (the three gather outputs come together)");
-  launch_nn_argmin(queries, q_stride, B, tree->xy, n_nodes, out_idx, gather ? tree->state : nullptr, tree->last_action,
-                   tree->has_prev, out_state, out_prev_action, out_has_prev, (hipStream_t)stream, tree->state_dim, tree->action_dim,
-                   bound->key, bound->cost, tree->counters);
-  HIP_TRY(ctx, hipGetLastError());
-  return DITREE_OK;
+  return nn_argmin_bounded_impl(ctx, "nn_argmin_bounded", tree, nullptr, n_nodes, bound, queries, q_stride, B, out_idx, out_state,
+                                out_prev_action, out_has_prev, stream);
 }
 
 int32_t ditree_forest_nn_argmin_bounded(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
@@ -1353,19 +1349,10 @@ int32_t ditree_forest_nn_argmin_bounded(ditree_ctx* ctx, const ditree_tree* tree
                                         int32_t* out_idx, double* out_state, double* out_prev_action, uint8_t* out_has_prev,
                                         void* stream) {
   if (!ctx) return DITREE_E_ARG;
-  int rc = check_forest(ctx, tree, forest, B, "forest_nn_argmin_bounded");
+  const int rc = check_forest(ctx, tree, forest, B, "forest_nn_argmin_bounded");
   if (rc) return rc;
-  rc = check_bound(ctx, bound, nullptr, true);
-  if (rc) return rc;
-  if (B == 0) return DITREE_OK;
-  const bool gather = out_state || out_prev_action || out_has_prev;
-  if (!queries || !out_idx || q_stride < 2 || (gather && (!out_state || !out_prev_action || !out_has_prev)))
-    return set_err(ctx, DITREE_E_ARG, "forest_nn_argmin_bounded: bad argument (the three gather outputs come together)");
-  launch_nn_forest(queries, q_stride, B, tree->xy, forest->off, forest->n_trees, forest->counters, forest->tree_capacity, 0,
-                   out_idx, gather ? tree->state : nullptr, tree->last_action, tree->has_prev, out_state, out_prev_action,
-                   out_has_prev, (hipStream_t)stream, tree->state_dim, tree->action_dim, bound->key, bound->cost);
-  HIP_TRY(ctx, hipGetLastError());
-  return DITREE_OK;
+  return nn_argmin_bounded_impl(ctx, "forest_nn_argmin_bounded", tree, forest, 0, bound, queries, q_stride, B, out_idx, out_state,
+                                out_prev_action, out_has_prev, stream);
 }
 
 int32_t ditree_expand_round_bounded(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round,
@@ -1429,12 +1416,7 @@ int32_t ditree_forest_accept_bounded(ditree_ctx* ctx, const ditree_tree* tree, c
 
 int32_t ditree_forest_fallback_goals(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const double* goal_xy,
                                      int32_t* out_node, void* stream) {
-  if (!ctx) return DITREE_E_ARG;
-  int rc = check_forest(ctx, tree, forest, -1, "forest_fallback_goals");
-  if (rc) return rc;
-  if (!goal_xy) return set_err(ctx, DITREE_E_ARG, "forest_fallback_goals: goals array (T, 2) missing");
-  if (!out_node) return set_err(ctx, DITREE_E_ARG, "forest_fallback_goals: out_node missing");
-  return forest_fallback_impl(ctx, tree, forest, goal_xy, out_node, (hipStream_t)stream);
+  return forest_fallback_impl(ctx, "forest_fallback_goals", tree, forest, false, true, goal_xy, out_node, stream);
 }
 
 // ---- ant forests (include/ditree.h "ant forests")
@@ -1472,13 +1454,7 @@ int32_t ditree_forest_accept_ant(ditree_ctx* ctx, const ditree_tree* tree, const
 // planners/RRT.py:227-254 (run_type 0) for every tree of an ant forest
 int32_t ditree_forest_fallback_ant(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const double* goal_xy,
                                    int32_t* out_node, void* stream) {
-  if (!ctx) return DITREE_E_ARG;
-  const int rc = check_ant_forest(ctx, tree, forest, nullptr, "forest_fallback_ant");
-  if (rc) return rc;
-  if (!goal_xy || !out_node) return set_err(ctx, DITREE_E_ARG, "forest_fallback_ant: bad argument");
-  std::vector<double> q((size_t)forest->n_trees * 2);   // T copies of the goal as the queries
-  for (int t = 0; t < forest->n_trees; ++t) { q[(size_t)t * 2] = goal_xy[0]; q[(size_t)t * 2 + 1] = goal_xy[1]; }
-  return forest_fallback_impl(ctx, tree, forest, q.data(), out_node, (hipStream_t)stream);
+  return forest_fallback_impl(ctx, "forest_fallback_ant", tree, forest, true, false, goal_xy, out_node, stream);
 }
 
 // ---- ant scene forests (include/ditree.h "ant scene forests")
@@ -1495,12 +1471,7 @@ int32_t ditree_forest_expand_round_ant_scenes(ditree_ctx* ctx, const ditree_tree
 
 int32_t ditree_forest_fallback_goals_ant(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const double* goal_xy,
                                          int32_t* out_node, void* stream) {
-  if (!ctx) return DITREE_E_ARG;
-  const int rc = check_ant_forest(ctx, tree, forest, nullptr, "forest_fallback_goals_ant");
-  if (rc) return rc;
-  if (!goal_xy) return set_err(ctx, DITREE_E_ARG, "forest_fallback_goals_ant: goals array (T, 2) missing");
-  if (!out_node) return set_err(ctx, DITREE_E_ARG, "forest_fallback_goals_ant: out_node missing");
-  return forest_fallback_impl(ctx, tree, forest, goal_xy, out_node, (hipStream_t)stream);
+  return forest_fallback_impl(ctx, "forest_fallback_goals_ant", tree, forest, true, true, goal_xy, out_node, stream);
 }
 
 // ---- policy roll-outs (include/ditree.h "policy roll-outs"): every check runs on the host before anything is launched
@@ -1526,7 +1497,7 @@ int32_t ditree_policy_begin(ditree_ctx* ctx, const ditree_policy_batch* batch, v
   if (rc) return rc;
   ctx->policy_key = nullptr;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  launch_policy_begin(SceneArg{ctx->scene_tab, ctx->atlas_cells, ctx->max_scene_cells}, *batch, (hipStream_t)stream);
+  launch_policy_begin(scene_arg(ctx), *batch, (hipStream_t)stream);
   HIP_TRY(ctx, hipGetLastError());
   ctx->policy_key = batch->idx;
   ctx->policy_n = batch->N;
@@ -1548,15 +1519,9 @@ int32_t ditree_policy_chunk(ditree_ctx* ctx, const ditree_policy_batch* batch, c
   if (!p->tape) {
     if (!p->norm || !p->axis || !(p->s_global > 0.0))
       return set_err(ctx, DITREE_E_ARG, "policy_chunk: norm, axis and s_global > 0 are required with the network");
-    if (!p->t0 || (!p->dt && !p->ddpm_coef) || p->K < 1) return set_err(ctx, DITREE_E_ARG, "policy_chunk: flow schedule missing");
-    if (p->ddpm_coef && !p->step_noise && p->K > 1)
-      return set_err(ctx, DITREE_E_ARG, "policy_chunk: the DDPM branch needs step_noise (N, K, P, 2)");
-    int32_t d5[5];
-    if (ditree_denoise_dims(ctx, d5) != DITREE_OK) return DITREE_E_STATE;
-    if (P != d5[0] || p->lm_n != d5[2] || d5[1] != 2 || d5[3] != 7)
-      return set_err(ctx, DITREE_E_ARG, "policy_chunk: pred_horizon " + std::to_string(P) + " / local map " + std::to_string(p->lm_n) +
-                     " do not match the loaded denoiser (P " + std::to_string(d5[0]) + ", action_dim " + std::to_string(d5[1]) +
-                     ", map " + std::to_string(d5[2]) + ", cond " + std::to_string(d5[3]) + "; the car's is action_dim 2, cond 7)");
+    rc = check_sampler(ctx, "policy_chunk", p->t0, p->dt, p->ddpm_coef, p->step_noise, p->K, P, p->lm_n, 2, 7, " (N, K, P, 2)",
+                       "; the car's is action_dim 2, cond 7)");
+    if (rc) return rc;
   }
   if (ctx->policy_key != batch->idx || ctx->policy_n < 0 || ctx->policy_n > N)
     return set_err(ctx, DITREE_E_STATE, "policy_chunk: call ditree_policy_begin on this batch first");
@@ -1565,9 +1530,9 @@ int32_t ditree_policy_chunk(ditree_ctx* ctx, const ditree_policy_batch* batch, c
   if (n == 0) return DITREE_OK;
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  rc = ensure_scratch(ctx, N, p->tape ? 1 : p->lm_n, p->tape ? 1 : P);
+  rc = ensure_car_scratch(ctx, N, p->tape ? 1 : p->lm_n, p->tape ? 1 : P);
   if (rc) return rc;
-  const SceneArg sc{ctx->scene_tab, ctx->atlas_cells, ctx->max_scene_cells};
+  const SceneArg sc = scene_arg(ctx);
   const double* acts = p->tape;
   int64_t act_stride = (int64_t)P * 2;
   int act_dense = 0;
@@ -1581,13 +1546,13 @@ int32_t ditree_policy_chunk(ditree_ctx* ctx, const ditree_policy_batch* batch, c
     rc = ensure_row_scene(ctx, N, s);
     if (rc) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(ctx->row_scene, batch->scene, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-    launch_local_map_scenes(sc, batch->state, batch->status, batch->idx, n, p->lm_n, ax, p->s_global, ctx->lmap, s, 6);
-    launch_cond_vector(batch->state, batch->last_action, batch->has_prev, batch->goal_xy, batch->idx, n, nm, p->lm_size, ctx->cond, s);
+    launch_local_map_scenes(sc, batch->state, batch->status, batch->idx, n, p->lm_n, ax, p->s_global, ctx->car.lmap, s, 6);
+    launch_cond_vector(batch->state, batch->last_action, batch->has_prev, batch->goal_xy, batch->idx, n, nm, p->lm_size, ctx->car.cond, s);
     double an[4] = {p->norm[12], p->norm[13], p->norm[14], p->norm[15]};
-    rc = round_sampler(ctx, p->noise, (int64_t)P * 2, batch->idx, ctx->lmap, ctx->cond, n, p->K, p->t0, p->dt, p->ddpm_coef,
-                       p->step_noise, (int64_t)p->K * P * 2, (int64_t)P * 2, an, ctx->act64, s);
+    rc = round_sampler(ctx, p->noise, (int64_t)P * 2, batch->idx, ctx->car.lmap, ctx->car.cond, n, p->K, p->t0, p->dt, p->ddpm_coef,
+                       p->step_noise, (int64_t)p->K * P * 2, (int64_t)P * 2, an, ctx->car.act, s);
     if (rc) { ctx->policy_key = nullptr; return rc; }
-    acts = ctx->act64;
+    acts = ctx->car.act;
     act_dense = 1;
   }
   ctx->policy_key = nullptr;                         // until the new list and its length are known

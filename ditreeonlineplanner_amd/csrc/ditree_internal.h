@@ -47,6 +47,22 @@ struct SceneArg {
   int atlas_cells, max_cells;
 };
 
+// The scratch of one robot's rounds (ensure_round_scratch in ditree_api.hip): reserved for B candidates, a local map of lm x lm
+// and P predicted actions; S / D / C below are the robot's state, action and conditioning widths.
+struct RoundScratch {
+  int B = 0, lm = 0, P = 0;
+  double* state = nullptr;          // (B, S) live state of a round without history rows (the car; the ant's is round->end_state)
+  double* hist = nullptr;           // (B, rows, S) history rows of the live state and (B,) how many are valid (the ant)
+  int32_t* hist_n = nullptr;
+  double* prev_action = nullptr;    // (B, D)
+  uint8_t* has_prev = nullptr;      // (B,)
+  float* lmap = nullptr;            // (B, lm, lm)
+  float* cond = nullptr;            // (B, C)
+  double* act = nullptr;            // (B, P, D) the sampler's actions
+  int32_t* idx = nullptr;           // (B,) compacted candidate indices (early-exit rounds)
+  int32_t* nrow = nullptr;          // (B,) their rows of the (B * n_chunks, P, D) noise view
+};
+
 struct ditree_ctx {
   int device = 0;
   std::string err;
@@ -54,36 +70,17 @@ struct ditree_ctx {
   unsigned char* maze = nullptr;
   int rows = 0, cols = 0;
   size_t maze_cap = 0;
-  // expand-round scratch (sized for scratch_B candidates)
-  int scratch_B = 0;
-  double* cur_state = nullptr;      // (B,6)
-  double* prev_action = nullptr;    // (B,2)
-  uint8_t* has_prev = nullptr;      // (B,)
-  float* lmap = nullptr;            // (B,n,n)
-  float* cond = nullptr;            // (B,7)
-  double* act64 = nullptr;          // (B,P,2)
-  int scratch_lm = 0, scratch_P = 0;
-  int32_t* alive_idx = nullptr;     // (B,) compacted candidate indices (early-exit rounds)
-  int32_t* alive_nrow = nullptr;    // (B,) their rows of the (B * n_chunks, P, D) noise view
-  int32_t* alive_cnt = nullptr;     // device scalar
-  int ee_calls = 0, ee_waves = 0;   // denoiser calls / tile-waves of the last early-exit round (ditree_round_stats)
+  // round scratch, one per robot so that alternating engines on one context never reallocate: the car's (S 6, D 2, cond 7; also
+  // the query rows of the forest fallback and the sampler buffers of the policy roll-outs) and the ant's (29, 8, 97, 3 history rows)
+  RoundScratch car, ant;
+  int32_t* alive_cnt = nullptr;       // 16-byte device scalar block: list lengths of the early-exit rounds and the policy roll-outs
   int32_t* alive_cnt_host = nullptr;  // pinned host copy
-  double* path_dev = nullptr;       // reference path xy for the fallback selection
+  int ee_calls = 0, ee_waves = 0;     // denoiser calls / tile-waves of the last early-exit round (ditree_round_stats)
+  double* path_dev = nullptr;         // reference path xy for the fallback selection
   int path_cap = 0;
-  // ant round scratch (ditree_expand_round_ant): (B, 3, 29) history + valid rows, (B, 8) previous action, flags, (B, 97) cond
-  int ant_B = 0;
-  double* ant_hist = nullptr;
-  int32_t* ant_hist_n = nullptr;
-  int32_t* ant_idx = nullptr;       // alive candidates of an early-exit round
-  int32_t* ant_nrow = nullptr;      // their rows of the (B * n_chunks, P, 8) noise view
-  int ant_n_run = 0;                // rows the current chunk runs on (ditree_ant_chunk_sample -> _step)
+  // the stepped ant round (ditree_ant_chunk_sample -> _step): the rows the current chunk runs on and their list (NULL: all)
+  int ant_n_run = 0;
   const int32_t* ant_run_idx = nullptr;
-  double* ant_prev = nullptr;
-  uint8_t* ant_hasprev = nullptr;
-  float* ant_cond = nullptr;
-  float* ant_lmap = nullptr;
-  double* ant_act = nullptr;
-  int ant_P = 0, ant_lm = 0;
   double* mppi_partial = nullptr;   // partial sums of the MPPI update, sized for the ant (256 slices of 3 + 8 * 64 doubles)
   unsigned long long* mppi_minkey = nullptr;   // running minimum of the rollout costs (order-preserving integer image)
   DenoiserState* dn = nullptr;
