@@ -885,6 +885,33 @@ __device__ __forceinline__ void mm16_snake(f32x4_t (&acc)[4][8], const short8_t 
     }
 }
 
+// Activation fragment addresses as loop invariants (LM = 16, 32, 64; LM = 0: L at run time, none).
+// Fragment (mb, tap t) of a lane reads row lrow0 + d, d = halo_frag_step(mb) + t: 16 rows per mb plus the two halo rows of
+// every sample boundary crossed, which for 16 | L does not depend on the wave.  Its byte address in the A block is
+//     (lrow0 + d) * 128 + (((plane * 4 + h4) ^ ((lrow0 + d) & 7)) << 4)
+//   = [lrow0 * 128 + ((h4 ^ ((lrow0 + (d & 7)) & 7)) << 4)]  ^  plane * 64   +  d * 128
+// a per-lane base that only depends on d & 7 (3 / 5 / 8 distinct values at L >= 64 / 32 / 16), one XOR for the lo plane, and
+// a constant that goes into the immediate offset of ds_read_b128 together with the buffer offset (< 64 KB).  The bases hold
+// the LDS address of the block itself (lds0), so that no add is left in front of a read: the XOR then needs the block on a
+// 128-byte boundary, which the halo kernels declare.
+template <int LM>
+__device__ __forceinline__ constexpr int halo_frag_step(int mb) {
+  return LM == 16 ? 18 * mb : LM == 32 ? 16 * mb + 2 * (mb >> 1) : 16 * mb;
+}
+template <int LM>
+__device__ __forceinline__ constexpr unsigned halo_frag_keys() {      // bit k: some fragment has d & 7 = k
+  unsigned m = 0;
+  for (int mb = 0; mb < 4; ++mb)
+    for (int t = 0; t < 3; ++t) m |= 1u << ((halo_frag_step<LM>(mb) + t) & 7);
+  return m;
+}
+template <int LM>
+__device__ __forceinline__ void halo_frag_bases(unsigned (&abase)[8], unsigned lds0, int lrow0, int h4) {
+#pragma unroll
+  for (int k = 0; k < 8; ++k) abase[k] = LM != 0 ? lds0 + (unsigned)(lrow0 * 128 + ((h4 ^ ((lrow0 + k) & 7)) << 4)) : 0u;
+}
+__device__ __forceinline__ short8_t halo_frag_read(unsigned addr) { return *(const LDS_AS short8_t*)(size_t)addr; }
+
 #ifdef HALO16_STAMP   // diagnostic build only: in-kernel clock of the K loop (MI355X_MICROARCH.md, DVFS give-back (6))
 __device__ unsigned long long g_halo_stamp[8];
 extern "C" int ditree_debug_halo_stamp(unsigned long long* out) {
@@ -906,9 +933,10 @@ extern "C" int ditree_debug_x3_stamp(unsigned long long* out, unsigned int* coun
   return rc;
 }
 #endif
-template <int ET>
-__global__ void __launch_bounds__(512, 2) conv3_halo16_kernel(ConvGemmParams p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
+template <int ET, int LM>
+__device__ __forceinline__ void conv3_halo16_body(const ConvGemmParams& p) {
+  extern __shared__ __attribute__((aligned(128))) char smem_halo[];   // 128: halo_frag_bases
+  static_assert(LM == 0 || LM == 16 || LM == 32 || LM == 64, "L at run time, or L = 16, 32, 64 (halo_frag_step)");
   constexpr int A_BUF = 40960, W_BUF = 32768, W_BASE = 2 * A_BUF;
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);          // wave index: uniform, keeps every wave-level offset in SGPRs
@@ -956,18 +984,21 @@ __global__ void __launch_bounds__(512, 2) conv3_halo16_kernel(ConvGemmParams p) 
     }
   }
   const int w_tap = p.Cin * 2;
-  auto issue_a = [&](int c, int i) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rsrc, (LDS_AS void*)(smem + (c & 1) * A_BUF + (w + 8 * i) * 1024), 16,
+  // par = parity of the LDS buffer the request / the read goes to ((c & 1) activations, ((c + t) & 1) weights): a constant in
+  // the two-chunk loop body
+  auto issue_a = [&](int par, int c, int i) {
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rsrc, (LDS_AS void*)(smem_halo + par * A_BUF + (w + 8 * i) * 1024), 16,
                                              i < 4 ? pa0 : pa4, c * 128 + (i < 4 ? i * a_piece : 0), 0, 0);
   };
-  auto issue_w = [&](int c, int t, int q) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, (LDS_AS void*)(smem + W_BASE + ((c + t) & 1) * W_BUF + (w * 4 + q) * 1024),
+  auto issue_w = [&](int par, int c, int t, int q) {
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, (LDS_AS void*)(smem_halo + W_BASE + par * W_BUF + (w * 4 + q) * 1024),
                                              16, pb, (int)wq[q] + c * 128 + t * w_tap, 0, 0);
   };
 
   // ---- fragment addressing ---------------------------------------------------------------------
   // row of the A block of fragment row (wm*64 + mb*16 + r4): lrow0 + a wave-uniform step (16 rows per mb plus the
-  // two halo rows of every sample boundary crossed; 16 | L)
+  // two halo rows of every sample boundary crossed; 16 | L) + tap.  LM != 0: every address is one of the per-lane bases
+  // + an immediate (halo_frag_bases)
   int lrow0;
   {
     const int ml = wm * 64 + r4;
@@ -977,8 +1008,13 @@ __global__ void __launch_bounds__(512, 2) conv3_halo16_kernel(ConvGemmParams p) 
   int lstep[4];
 #pragma unroll
   for (int mb = 0; mb < 4; ++mb) lstep[mb] = 16 * mb + 2 * (((wm * 64 + 16 * mb) / L) - ((wm * 64) / L));
-  const int swl = r4 & 7;
-  const int b_row_off = (wn * 128 + r4) * 128;
+  unsigned abase[8];
+  halo_frag_bases<LM>(abase, (unsigned)(size_t)(LDS_AS char*)smem_halo, lrow0, h4);
+  // weight fragments of the fixed forms: one base per ks; buffer, half and jj are immediates (< 48 KB above W_BASE)
+  unsigned bbase[2];
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks)
+    bbase[ks] = (unsigned)(size_t)(LDS_AS char*)smem_halo + (unsigned)(W_BASE + (wn * 128 + r4) * 128 + ((((ks << 2) | h4) ^ (r4 & 7)) << 4));
 
   f32x4_t acc[4][8];
 #pragma unroll
@@ -987,20 +1023,29 @@ __global__ void __launch_bounds__(512, 2) conv3_halo16_kernel(ConvGemmParams p) 
     for (int j = 0; j < 8; ++j) acc[mb][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
   short8_t af[2][4], bq[2][4];
-  auto rdA = [&](int set, int c, int t, int ks) {
-    const char* ab = smem + (c & 1) * A_BUF;
+  auto rdA = [&](int set, int par, int t, int ks) {
 #pragma unroll
     for (int mb = 0; mb < 4; ++mb) {
-      const int row = lrow0 + lstep[mb] + t;
-      const int ps = (((ks << 2) | h4) ^ (row & 7)) << 4;
-      af[set][mb] = *(const short8_t*)(ab + row * 128 + ps);
+      if constexpr (LM != 0) {          // one base register (ks = 1: one XOR) + an immediate
+        const int d = halo_frag_step<LM>(mb) + t;
+        af[set][mb] = halo_frag_read((abase[d & 7] ^ (unsigned)(ks << 6)) + (unsigned)(par * A_BUF + d * 128));
+      } else {
+        const int row = lrow0 + lstep[mb] + t;
+        const int ps = (((ks << 2) | h4) ^ (row & 7)) << 4;
+        af[set][mb] = *(const short8_t*)(smem_halo + par * A_BUF + row * 128 + ps);
+      }
     }
   };
-  auto rdB = [&](int set, int c, int t, int ks, int half) {
-    const char* wb = smem + W_BASE + ((c + t) & 1) * W_BUF + b_row_off + half * 8192;
-    const int psb = (((ks << 2) | h4) ^ swl) << 4;
+  auto rdB = [&](int set, int par, int ks, int half) {
+    if constexpr (LM != 0) {
 #pragma unroll
-    for (int jj = 0; jj < 4; ++jj) bq[set][jj] = *(const short8_t*)(wb + jj * 2048 + psb);
+      for (int jj = 0; jj < 4; ++jj) bq[set][jj] = halo_frag_read(bbase[ks] + (unsigned)(par * W_BUF + half * 8192 + jj * 2048));
+    } else {
+      const char* wb = smem_halo + W_BASE + par * W_BUF + (wn * 128 + r4) * 128 + half * 8192;
+      const int psb = (((ks << 2) | h4) ^ (r4 & 7)) << 4;
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) bq[set][jj] = *(const short8_t*)(wb + jj * 2048 + psb);
+    }
   };
   auto mm = [&](int aset, int bset, int half, int mb, int jj) {
     acc[mb][half * 4 + jj] = mfma16<ET>(af[aset][mb], bq[bset][jj], acc[mb][half * 4 + jj]);
@@ -1009,34 +1054,48 @@ __global__ void __launch_bounds__(512, 2) conv3_halo16_kernel(ConvGemmParams p) 
 
   // One K-step (chunk c, tap T); flags as in conv3_halo_kernel.  On entry af[0] = A(ks 0), bq[0] = B(ks 0, half 0).
   // Wave priorities and the placement of the LDS-DMA requests: see conv3_halo16x3_kernel (same scheme, four phases).
-  auto step = [&](auto tT, auto tNext, auto tIW, auto tIA, auto tVM, int c) {
+  auto step = [&](auto tT, auto tNext, auto tIW, auto tIA, auto tVM, auto tPar, int c) {
     constexpr int T = decltype(tT)::value;
     constexpr bool HAS_NEXT = decltype(tNext)::value, ISSUE_W = decltype(tIW)::value, ISSUE_A = decltype(tIA)::value;
     constexpr int VM = decltype(tVM)::value;
     constexpr int NV = ISSUE_W ? 4 : 0;
-    asm volatile("" : "+v"(lrow0));    // keep the fragment-address arithmetic inside the step (hoisted it spills)
+    constexpr int PAR = decltype(tPar)::value;      // c & 1 where the caller knows it, -1 where not
+    auto par = [&](int known, int x) { return PAR >= 0 ? known : (x & 1); };
+    const int pa = par(PAR, c);                     // activation buffer of chunk c
+    const int pw = par((PAR + T) & 1, c + T);       // weight buffer of step (c, T)
+    // keep the fragment addresses what they are inside a step: the fixed forms one base register + an immediate (with the
+    // XORed ks = 1 bases hoisted out of the loop they spill), the run-time form its arithmetic (hoisted it spills)
+    if constexpr (LM != 0) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+        if ((halo_frag_keys<LM>() >> i) & 1) asm volatile("" : "+v"(abase[i]));
+    } else {
+      asm volatile("" : "+v"(lrow0));
+    }
+    if constexpr (LM != 0) asm volatile("" : "+v"(bbase[0]), "+v"(bbase[1]));
     // Each phase is its own scheduling region (sched_barrier), inside it the fragment reads for the NEXT phase
     // are issued first, then the 16 MFMAs: hipcc otherwise sinks the reads to the end of the phase and the next
     // phase waits for LDS in front of every MFMA.
     __builtin_amdgcn_s_setprio(2);
-    rdB(1, c, T, 0, 1);                 // phase (0,0)
+    rdB(1, pw, 0, 1);                   // phase (0,0)
     mm16(0, 0, 0);
     __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
     __builtin_amdgcn_sched_group_barrier(0x008, 16, 0);
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_setprio(1);
-    rdA(1, c, T, 1);                    // phase (0,1)
-    rdB(0, c, T, 1, 0);
+    rdA(1, pa, T, 1);                   // phase (0,1)
+    rdB(0, pw, 1, 0);
     mm16(0, 1, 1);
     __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
     __builtin_amdgcn_sched_group_barrier(0x008, 16, 0);
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_setprio(0);
-    rdB(1, c, T, 1, 1);                 // phase (1,0) + the activation pieces of chunk c+1 (T = 0: 0..2, T = 1: 3, 4)
+    rdB(1, pw, 1, 1);                   // phase (1,0) + the activation pieces of chunk c+1 (T = 0: 0..2, T = 1: 3, 4)
     mm16(1, 0, 0);
     if constexpr (ISSUE_A && T != 2) {
-      if constexpr (T == 0) { issue_a(c + 1, 0); issue_a(c + 1, 1); issue_a(c + 1, 2); }
-      else { issue_a(c + 1, 3); issue_a(c + 1, 4); }
+      const int pa1 = par(PAR ^ 1, c + 1);
+      if constexpr (T == 0) { issue_a(pa1, c + 1, 0); issue_a(pa1, c + 1, 1); issue_a(pa1, c + 1, 2); }
+      else { issue_a(pa1, c + 1, 3); issue_a(pa1, c + 1, 4); }
       __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
       __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
       __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
@@ -1057,8 +1116,9 @@ __global__ void __launch_bounds__(512, 2) conv3_halo16_kernel(ConvGemmParams p) 
       __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_s_setprio(3);
       constexpr int T1 = (T + 1) % 3;
-      rdA(0, c + (T + 1) / 3, T1, 0);
-      rdB(0, c + (T + 1) / 3, T1, 0, 0);
+      const int cn = c + (T + 1) / 3;
+      rdA(0, par(PAR ^ ((T + 1) / 3), cn), T1, 0);
+      rdB(0, par((PAR + T + 1) & 1, cn + T1), 0, 0);
     }
     constexpr int T2 = (T + 2) % 3;
     const int c2 = c + (T + 2) / 3;
@@ -1072,7 +1132,7 @@ __global__ void __launch_bounds__(512, 2) conv3_halo16_kernel(ConvGemmParams p) 
         // phase together: one issue behind every second MFMA instead of all in a row leaves the partner wave MFMAs to
         // issue in between (-1.7 % kernel time).
         const int d = (i & 1) ? -1 : (i >> 1);
-        if constexpr (ISSUE_W) { if (d >= 0 && d < 4) issue_w(c2, T2, d); }
+        if constexpr (ISSUE_W) { if (d >= 0 && d < 4) issue_w(par((PAR + T) & 1, c2 + T2), c2, T2, d); }      // c2 + T2 = c + T + 2 - 2 [T > 0]
       }
     if constexpr (HAS_NEXT) __builtin_amdgcn_sched_group_barrier(0x100, 8, 1);
 #pragma unroll
@@ -1091,25 +1151,46 @@ __global__ void __launch_bounds__(512, 2) conv3_halo16_kernel(ConvGemmParams p) 
 
   // ---- prologue: A(0), W(0,0) -> visible; then W(0,1) in flight ----------------------------------------
 #pragma unroll
-  for (int i = 0; i < 5; ++i) issue_a(0, i);
+  for (int i = 0; i < 5; ++i) issue_a(0, 0, i);
 #pragma unroll
-  for (int q = 0; q < 4; ++q) issue_w(0, 0, q);
+  for (int q = 0; q < 4; ++q) issue_w(0, 0, 0, q);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
 #pragma unroll
-  for (int q = 0; q < 4; ++q) issue_w(0, 1, q);
+  for (int q = 0; q < 4; ++q) issue_w(1, 0, 1, q);
   rdA(0, 0, 0, 0);
-  rdB(0, 0, 0, 0, 0);
+  rdB(0, 0, 0, 0);
 
 #ifdef HALO16_STAMP
   const unsigned long long st0 = __builtin_amdgcn_s_memtime(), rt0 = __builtin_amdgcn_s_memrealtime();
 #endif
   // Issue order and counted waits as in conv3_halo16x3_kernel: vmcnt(3) at the barrier of T = 0 (the three activation
   // pieces requested in this step may stay in flight), vmcnt(2) at T = 1, vmcnt(0) at T = 2 (whole next activation stage).
-  for (int c = 0; c < nc - 2; ++c) {
-    step(I0{}, Tt{}, Tt{}, Tt{}, I3{}, c);
-    step(I1{}, Tt{}, Tt{}, Tt{}, I2{}, c);
-    step(I2{}, Tt{}, Tt{}, Tt{}, I0{}, c);
+  // Two chunks per trip: the buffer parities are constants and go into the immediates of the fragment reads and of the
+  // LDS-DMA destinations; an odd chunk left over and the tails take the parity from c (constant parities there cost
+  // registers: the compiler spills).
+  using PR = std::integral_constant<int, -1>;
+  int c = 0;
+  if constexpr (LM != 0) {
+    for (; c + 1 < nc - 2; c += 2) {
+      step(I0{}, Tt{}, Tt{}, Tt{}, I3{}, I0{}, c);
+      step(I1{}, Tt{}, Tt{}, Tt{}, I2{}, I0{}, c);
+      step(I2{}, Tt{}, Tt{}, Tt{}, I0{}, I0{}, c);
+      step(I0{}, Tt{}, Tt{}, Tt{}, I3{}, I1{}, c + 1);
+      step(I1{}, Tt{}, Tt{}, Tt{}, I2{}, I1{}, c + 1);
+      step(I2{}, Tt{}, Tt{}, Tt{}, I0{}, I1{}, c + 1);
+    }
+    for (; c < nc - 2; ++c) {                         // full waits: spills may sit here, as in the tails
+      step(I0{}, Tt{}, Tt{}, Tt{}, I0{}, PR{}, c);
+      step(I1{}, Tt{}, Tt{}, Tt{}, I0{}, PR{}, c);
+      step(I2{}, Tt{}, Tt{}, Tt{}, I0{}, PR{}, c);
+    }
+  } else {
+    for (; c < nc - 2; ++c) {
+      step(I0{}, Tt{}, Tt{}, Tt{}, I3{}, PR{}, c);
+      step(I1{}, Tt{}, Tt{}, Tt{}, I2{}, PR{}, c);
+      step(I2{}, Tt{}, Tt{}, Tt{}, I0{}, PR{}, c);
+    }
   }
 #ifdef HALO16_STAMP
   if (blockIdx.x == 100 && tid == 0 && nc >= 32) {
@@ -1118,25 +1199,33 @@ __global__ void __launch_bounds__(512, 2) conv3_halo16_kernel(ConvGemmParams p) 
     g_halo_stamp[2] = (unsigned long long)(nc - 2) * 3;
   }
 #endif
-  // The counted waits are only used inside the loop above, whose body holds no other vector-memory operation.  The two
-  // tail chunks wait for everything: register spills the compiler may place here (scratch accesses count in vmcnt) must
-  // not take part in a counted wait.
+  // The counted waits are only used inside the loop above, whose body holds no other vector-memory operation.  The
+  // chunks behind it wait for everything: register spills the compiler may place here (scratch accesses count in vmcnt)
+  // must not take part in a counted wait.
   {
     const int c = nc - 2;
-    step(I0{}, Tt{}, Tt{}, Tt{}, I0{}, c);          // the activation stage of the last chunk
-    step(I1{}, Tt{}, Tt{}, Tt{}, I0{}, c);
-    step(I2{}, Tt{}, Tt{}, Ff{}, I0{}, c);
+    step(I0{}, Tt{}, Tt{}, Tt{}, I0{}, PR{}, c);    // the activation stage of the last chunk
+    step(I1{}, Tt{}, Tt{}, Tt{}, I0{}, PR{}, c);
+    step(I2{}, Tt{}, Tt{}, Ff{}, I0{}, PR{}, c);
   }
   {
     const int c = nc - 1;
-    step(I0{}, Tt{}, Tt{}, Ff{}, I0{}, c);
-    step(I1{}, Tt{}, Ff{}, Ff{}, I0{}, c);
-    step(I2{}, Ff{}, Ff{}, Ff{}, I0{}, c);
+    step(I0{}, Tt{}, Tt{}, Ff{}, I0{}, PR{}, c);
+    step(I1{}, Tt{}, Ff{}, Ff{}, I0{}, PR{}, c);
+    step(I2{}, Ff{}, Ff{}, Ff{}, I0{}, PR{}, c);
   }
   __builtin_amdgcn_s_setprio(0);
   __syncthreads();
-  gemm_epilogue16<ET, false>(p, acc, smem, tm, tn, tid, lane, r4, h4, wm, wn);
+  // the epilogue derives its lane indices anew: only tid stays live across the K loop
+  int te = tid;
+  asm volatile("" : "+v"(te));
+  gemm_epilogue16<ET, false>(p, acc, smem_halo, tm, tn, te, te & 63, te & 15, (te & 63) >> 4, wm, wn);
 }
+// L at run time (what is left: L = 128 / 256), and L = 16 / 32 / 64 with fixed fragment addresses
+template <int ET>
+__global__ void __launch_bounds__(512, 2) conv3_halo16_kernel(ConvGemmParams p) { conv3_halo16_body<ET, 0>(p); }
+template <int ET, int LM>
+__global__ void __launch_bounds__(512, 2) conv3_halo16_fixed_kernel(ConvGemmParams p) { conv3_halo16_body<ET, LM>(p); }
 
 // =================================================================================================
 // conv3_halo16x3_kernel: the halo kernel for the split (hi + lo) formats.
@@ -1156,12 +1245,13 @@ __global__ void __launch_bounds__(512, 2) conv3_halo16_kernel(ConvGemmParams p) 
 //     -- wait, barrier, read-ahead of the next step's A_hi / W_lo(0) --   P6 A_lo x W_hi(1) + the LDS-DMA issue.
 //   The small cross terms are accumulated first.
 // =================================================================================================
-template <int ET, bool SHORT = false, bool SPLITK = false, int NP = 5>
-__global__ void __launch_bounds__(512, 2) conv3_halo16x3_kernel(ConvGemmParams p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
+template <int ET, bool SHORT, bool SPLITK, int NP, int LM>
+__device__ __forceinline__ void conv3_halo16x3_body(const ConvGemmParams& p) {
+  extern __shared__ __attribute__((aligned(128))) char smem_halo[];   // 128: halo_frag_bases
   // NP staging pieces of 64 rows: 5 hold the 256 + 2 S <= 320 padded rows of a tile at L >= 8; L = 4 (64 samples x 6 padded rows =
   // 384) takes a sixth -- 2 x 48 KB of activations + 2 x 32 KB of weights = all 160 KB of LDS
   static_assert(NP == 5 || NP == 6, "five or six activation pieces");
+  static_assert(LM == 0 || (!SHORT && !SPLITK && NP == 5), "fixed fragment addresses: whole-tile, five-piece form, L >= 16");
   constexpr int A_BUF = NP * 8192, W_BUF = 32768, W_BASE = 2 * A_BUF;
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1215,12 +1305,14 @@ __global__ void __launch_bounds__(512, 2) conv3_halo16x3_kernel(ConvGemmParams p
     }
   }
   const int w_tap = (p.Cin >> 5) * w_step;                            // one tap = Cin / 32 chunks further
-  auto issue_a = [&](int v, int i) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rsrc, (LDS_AS void*)(smem + (v & 1) * A_BUF + (w + 8 * i) * 1024), 16,
+  // par = parity of the LDS buffer the request / the read goes to ((v & 1) activations, ((v + t) & 1) weights): a constant in
+  // the two-chunk loop body of the LM forms
+  auto issue_a = [&](int par, int v, int i) {
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rsrc, (LDS_AS void*)(smem_halo + par * A_BUF + (w + 8 * i) * 1024), 16,
                                              i < 4 ? pa0 : (i == 4 ? pa4 : pa5), v * 64 + (i < 4 ? i * a_piece : 0), 0, 0);
   };
-  auto issue_w = [&](int v, int t, int q) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, (LDS_AS void*)(smem + W_BASE + ((v + t) & 1) * W_BUF + (w * 4 + q) * 1024),
+  auto issue_w = [&](int par, int v, int t, int q) {
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, (LDS_AS void*)(smem_halo + W_BASE + par * W_BUF + (w * 4 + q) * 1024),
                                              16, pb, (int)wq[q] + v * w_step + t * w_tap, 0, 0);
   };
 
@@ -1233,6 +1325,8 @@ __global__ void __launch_bounds__(512, 2) conv3_halo16x3_kernel(ConvGemmParams p
   int lstep[4];
 #pragma unroll
   for (int mb = 0; mb < 4; ++mb) lstep[mb] = 16 * mb + 2 * (((wm * 64 + 16 * mb) / L) - ((wm * 64) / L));
+  unsigned abase[8];
+  halo_frag_bases<LM>(abase, (unsigned)(size_t)(LDS_AS char*)smem_halo, lrow0, h4);
   const int swl = r4 & 7;
   const int b_row_off = (wn * 128 + r4) * 128;
 
@@ -1244,17 +1338,22 @@ __global__ void __launch_bounds__(512, 2) conv3_halo16x3_kernel(ConvGemmParams p
 
   short8_t af[2][4], bq[2][4];
   // pl: 0 = hi plane, 1 = lo plane (slots 0..3 / 4..7 of the row)
-  auto rdA = [&](int set, int v, int t, int pl) {
-    const char* ab = smem + (v & 1) * A_BUF;
+  auto rdA = [&](int set, int par, int t, int pl) {
+    const char* ab = smem_halo + par * A_BUF;
 #pragma unroll
     for (int mb = 0; mb < 4; ++mb) {
-      const int row = lrow0 + lstep[mb] + t;
-      const int ps = (((pl << 2) | h4) ^ (row & 7)) << 4;
-      af[set][mb] = *(const short8_t*)(ab + row * 128 + ps);
+      if constexpr (LM != 0) {          // one base register (the lo plane: one XOR) + an immediate
+        const int d = halo_frag_step<LM>(mb) + t;
+        af[set][mb] = halo_frag_read((abase[d & 7] ^ (unsigned)(pl << 6)) + (unsigned)(par * A_BUF + d * 128));
+      } else {
+        const int row = lrow0 + lstep[mb] + t;
+        const int ps = (((pl << 2) | h4) ^ (row & 7)) << 4;
+        af[set][mb] = *(const short8_t*)(ab + row * 128 + ps);
+      }
     }
   };
-  auto rdB = [&](int set, int v, int t, int pl, int half) {
-    const char* wb = smem + W_BASE + ((v + t) & 1) * W_BUF + b_row_off + half * 8192;
+  auto rdB = [&](int set, int par, int pl, int half) {
+    const char* wb = smem_halo + W_BASE + par * W_BUF + b_row_off + half * 8192;
     const int psb = (((pl << 2) | h4) ^ swl) << 4;
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj) bq[set][jj] = *(const short8_t*)(wb + jj * 2048 + psb);
@@ -1283,28 +1382,40 @@ __global__ void __launch_bounds__(512, 2) conv3_halo16x3_kernel(ConvGemmParams p
   // moment.  The address FIFO filled, and the younger waves sat 1 500 - 3 000 cycles in ONE buffer_load (MFMAs queued behind
   // it in program order).  The activation pieces now go out in the middle of the following steps (3 in P4 of T = 0, 2 in
   // P4 of T = 1), 16 - 24 KB per CU at a time.
-  auto step = [&](auto tT, auto tNext, auto tIW, auto tIA, auto tVM, int v) {
+  auto step = [&](auto tT, auto tNext, auto tIW, auto tIA, auto tVM, auto tPar, int v) {
     constexpr int T = decltype(tT)::value;
     constexpr bool HAS_NEXT = decltype(tNext)::value, ISSUE_W = decltype(tIW)::value, ISSUE_A = decltype(tIA)::value;
     constexpr int VM = decltype(tVM)::value;
-    asm volatile("" : "+v"(lrow0));
+    constexpr int PAR = decltype(tPar)::value;      // v & 1 where the caller knows it, -1 where not
+    auto par = [&](int known, int x) { return PAR >= 0 ? known : (x & 1); };
+    const int pa = par(PAR, v);                     // activation buffer of chunk v
+    const int pw = par((PAR + T) & 1, v + T);       // weight buffer of step (v, T)
+    // keep the fragment addresses what they are inside a step: the fixed forms one base register + an immediate (with the
+    // XORed lo-plane bases hoisted out of the loop they spill), the generic form its arithmetic (hoisted it spills)
+    if constexpr (LM != 0) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+        if ((halo_frag_keys<LM>() >> i) & 1) asm volatile("" : "+v"(abase[i]));
+    } else {
+      asm volatile("" : "+v"(lrow0));
+    }
     PSTAMP(0);
     __builtin_amdgcn_s_setprio(2);
-    rdB(1, v, T, 1, 1);                 // P1: A_hi x W_lo(0); fetch W_lo(1)
+    rdB(1, pw, 1, 1);                   // P1: A_hi x W_lo(0); fetch W_lo(1)
     mm16(0, 0, 0);
     __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
     __builtin_amdgcn_sched_group_barrier(0x008, 16, 0);
     __builtin_amdgcn_sched_barrier(0);
     PSTAMP(1);
-    rdB(0, v, T, 0, 0);                 // P2: A_hi x W_lo(1); fetch W_hi(0) and A_lo
-    rdA(1, v, T, 1);
+    rdB(0, pw, 0, 0);                   // P2: A_hi x W_lo(1); fetch W_hi(0) and A_lo
+    rdA(1, pa, T, 1);
     mm16(0, 1, 1);
     __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
     __builtin_amdgcn_sched_group_barrier(0x008, 16, 0);
     __builtin_amdgcn_sched_barrier(0);
     PSTAMP(2);
     __builtin_amdgcn_s_setprio(1);
-    rdB(1, v, T, 0, 1);                 // P3: A_hi x W_hi(0); fetch W_hi(1)
+    rdB(1, pw, 0, 1);                   // P3: A_hi x W_hi(0); fetch W_hi(1)
     mm16(0, 0, 0);
     __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
     __builtin_amdgcn_sched_group_barrier(0x008, 16, 0);
@@ -1312,8 +1423,9 @@ __global__ void __launch_bounds__(512, 2) conv3_halo16x3_kernel(ConvGemmParams p
     PSTAMP(3);
     mm16(1, 0, 0);                      // P4: A_lo x W_hi(0) + the activation pieces of chunk v+1 (T = 0: 0..2, T = 1: 3, 4)
     if constexpr (ISSUE_A && T != 2) {
-      if constexpr (T == 0) { issue_a(v + 1, 0); issue_a(v + 1, 1); issue_a(v + 1, 2); }
-      else { issue_a(v + 1, 3); issue_a(v + 1, 4); if constexpr (NP == 6) issue_a(v + 1, 5); }
+      const int pa1 = par(PAR ^ 1, v + 1);
+      if constexpr (T == 0) { issue_a(pa1, v + 1, 0); issue_a(pa1, v + 1, 1); issue_a(pa1, v + 1, 2); }
+      else { issue_a(pa1, v + 1, 3); issue_a(pa1, v + 1, 4); if constexpr (NP == 6) issue_a(pa1, v + 1, 5); }
       __builtin_amdgcn_sched_group_barrier(0x008, 4, 2);
       __builtin_amdgcn_sched_group_barrier(0x020, 1, 2);
       __builtin_amdgcn_sched_group_barrier(0x008, 4, 2);
@@ -1336,8 +1448,9 @@ __global__ void __launch_bounds__(512, 2) conv3_halo16x3_kernel(ConvGemmParams p
       __builtin_amdgcn_s_setprio(3);
       PSTAMP(6);
       constexpr int T1 = (T + 1) % 3;
-      rdA(0, v + (T + 1) / 3, T1, 0);               // next step's A_hi and W_lo(0)
-      rdB(0, v + (T + 1) / 3, T1, 1, 0);
+      const int vn = v + (T + 1) / 3;
+      rdA(0, par(PAR ^ ((T + 1) / 3), vn), T1, 0);  // next step's A_hi and W_lo(0)
+      rdB(0, par((PAR + T + 1) & 1, vn + T1), 1, 0);
     }
     constexpr int T2 = (T + 2) % 3;
     const int v2 = v + (T + 2) / 3;
@@ -1348,7 +1461,7 @@ __global__ void __launch_bounds__(512, 2) conv3_halo16x3_kernel(ConvGemmParams p
         mm(1, 1, 1, mb, (mb & 1) ? 3 - jj : jj);
         const int i = mb * 4 + jj;
         const int d = (i & 1) ? -1 : (i >> 1);
-        if constexpr (ISSUE_W) { if (d >= 0 && d < 4) issue_w(v2, T2, d); }
+        if constexpr (ISSUE_W) { if (d >= 0 && d < 4) issue_w(par((PAR + T) & 1, v2 + T2), v2, T2, d); }      // v2 + T2 = v + T + 2 - 2 [T > 0]
       }
     if constexpr (HAS_NEXT) __builtin_amdgcn_sched_group_barrier(0x100, 8, 1);
     constexpr int NV = ISSUE_W ? 4 : 0;
@@ -1372,15 +1485,15 @@ __global__ void __launch_bounds__(512, 2) conv3_halo16x3_kernel(ConvGemmParams p
   const unsigned long long xs0 = __builtin_amdgcn_s_memrealtime();
 #endif
 #pragma unroll
-  for (int i = 0; i < NP; ++i) issue_a(v_lo, i);
+  for (int i = 0; i < NP; ++i) issue_a(v_lo & 1, v_lo, i);
 #pragma unroll
-  for (int q = 0; q < 4; ++q) issue_w(v_lo, 0, q);
+  for (int q = 0; q < 4; ++q) issue_w(v_lo & 1, v_lo, 0, q);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
 #pragma unroll
-  for (int q = 0; q < 4; ++q) issue_w(v_lo, 1, q);
-  rdA(0, v_lo, 0, 0);
-  rdB(0, v_lo, 0, 1, 0);
+  for (int q = 0; q < 4; ++q) issue_w((v_lo & 1) ^ 1, v_lo, 1, q);
+  rdA(0, v_lo & 1, 0, 0);
+  rdB(0, v_lo & 1, 1, 0);
 #ifdef HALO16_STAMP
   const unsigned long long xs1 = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -1390,10 +1503,24 @@ __global__ void __launch_bounds__(512, 2) conv3_halo16x3_kernel(ConvGemmParams p
   // pieces requested behind the previous barrier -- what was requested after them may stay in flight: vmcnt(3) at T = 0,
   // vmcnt(2) at T = 1 -- and the barrier of T = 2 the whole activation stage of the next chunk: vmcnt(0).
   using IT1 = std::integral_constant<int, NP == 6 ? 3 : 2>;      // activation pieces requested in P4 of T = 1
-  for (int v = v_lo; v < nv - 2; ++v) {
-    step(I0{}, Tt{}, Tt{}, Tt{}, I3{}, v);
-    step(I1{}, Tt{}, Tt{}, Tt{}, IT1{}, v);
-    step(I2{}, Tt{}, Tt{}, Tt{}, I0{}, v);
+  using PR = std::integral_constant<int, -1>;                     // buffer parity from v
+  int v = v_lo;
+  if constexpr (LM != 0) {
+    // two chunks per trip: the buffer parities are constants and go into the immediates of the fragment reads and of the
+    // LDS-DMA destinations (v_lo = 0: no split-K form)
+    for (; v + 1 < nv - 2; v += 2) {
+      step(I0{}, Tt{}, Tt{}, Tt{}, I3{}, I0{}, v);
+      step(I1{}, Tt{}, Tt{}, Tt{}, IT1{}, I0{}, v);
+      step(I2{}, Tt{}, Tt{}, Tt{}, I0{}, I0{}, v);
+      step(I0{}, Tt{}, Tt{}, Tt{}, I3{}, I1{}, v + 1);
+      step(I1{}, Tt{}, Tt{}, Tt{}, IT1{}, I1{}, v + 1);
+      step(I2{}, Tt{}, Tt{}, Tt{}, I0{}, I1{}, v + 1);
+    }
+  }
+  for (; v < nv - 2; ++v) {             // every chunk of the generic forms; an odd chunk left over in the fixed ones
+    step(I0{}, Tt{}, Tt{}, Tt{}, I3{}, PR{}, v);
+    step(I1{}, Tt{}, Tt{}, Tt{}, IT1{}, PR{}, v);
+    step(I2{}, Tt{}, Tt{}, Tt{}, I0{}, PR{}, v);
   }
 #ifdef X3_PHASE_STAMP
   if (blockIdx.x == 100 && lane == 0 && nv == 64) {
@@ -1404,15 +1531,15 @@ __global__ void __launch_bounds__(512, 2) conv3_halo16x3_kernel(ConvGemmParams p
 #endif
   {
     const int v = nv - 2;               // tails wait for everything (no counted wait next to possible spill traffic)
-    step(I0{}, Tt{}, Tt{}, Tt{}, I0{}, v);          // the activation stage of the last chunk
-    step(I1{}, Tt{}, Tt{}, Tt{}, I0{}, v);
-    step(I2{}, Tt{}, Tt{}, Ff{}, I0{}, v);
+    step(I0{}, Tt{}, Tt{}, Tt{}, I0{}, PR{}, v);    // the activation stage of the last chunk
+    step(I1{}, Tt{}, Tt{}, Tt{}, I0{}, PR{}, v);
+    step(I2{}, Tt{}, Tt{}, Ff{}, I0{}, PR{}, v);
   }
   {
     const int v = nv - 1;
-    step(I0{}, Tt{}, Tt{}, Ff{}, I0{}, v);
-    step(I1{}, Tt{}, Ff{}, Ff{}, I0{}, v);
-    step(I2{}, Ff{}, Ff{}, Ff{}, I0{}, v);
+    step(I0{}, Tt{}, Tt{}, Ff{}, I0{}, PR{}, v);
+    step(I1{}, Tt{}, Ff{}, Ff{}, I0{}, PR{}, v);
+    step(I2{}, Ff{}, Ff{}, Ff{}, I0{}, PR{}, v);
   }
   __builtin_amdgcn_s_setprio(0);
   __syncthreads();
@@ -1428,11 +1555,11 @@ __global__ void __launch_bounds__(512, 2) conv3_halo16x3_kernel(ConvGemmParams p
       for (int j = 0; j < 8; ++j) *(f32x4_t*)(mine + ((mb * 8 + j) * 512 + tid) * 4) = acc[mb][j];
     __threadfence();                                          // the slab is visible device-wide before the arrival is counted
     __syncthreads();
-    int* s_last = (int*)smem;
+    int* s_last = (int*)smem_halo;
     if (tid == 0) *s_last = atomicAdd(p.sk_cnt + tile, 1) == p.splitk - 1;
     __syncthreads();
     const bool last = *s_last != 0;
-    __syncthreads();                                          // smem is the epilogue's from here on
+    __syncthreads();                                          // smem_halo is the epilogue's from here on
     if (!last) return;
     __threadfence();
 #pragma unroll
@@ -1448,7 +1575,7 @@ __global__ void __launch_bounds__(512, 2) conv3_halo16x3_kernel(ConvGemmParams p
     }
     if (tid == 0) p.sk_cnt[tile] = 0;                         // ready for the next launch on this stream
   }
-  gemm_epilogue16<ET, true, SHORT>(p, acc, smem, tm, tn, tid, lane, r4, h4, wm, wn);
+  gemm_epilogue16<ET, true, SHORT>(p, acc, smem_halo, tm, tn, tid, lane, r4, h4, wm, wn);
 #ifdef HALO16_STAMP
   __syncthreads();
   if (tid == 0) {
@@ -1463,6 +1590,11 @@ __global__ void __launch_bounds__(512, 2) conv3_halo16x3_kernel(ConvGemmParams p
   }
 #endif
 }
+// L at run time (the SHORT, six-piece and split-K forms, and L = 128 / 256), and L = 16 / 32 / 64 with fixed fragment addresses
+template <int ET, bool SHORT = false, bool SPLITK = false, int NP = 5>
+__global__ void __launch_bounds__(512, 2) conv3_halo16x3_kernel(ConvGemmParams p) { conv3_halo16x3_body<ET, SHORT, SPLITK, NP, 0>(p); }
+template <int ET, int LM>
+__global__ void __launch_bounds__(512, 2) conv3_halo16x3_fixed_kernel(ConvGemmParams p) { conv3_halo16x3_body<ET, false, false, 5, LM>(p); }
 
 // =================================================================================================
 // conv2d_small_kernel: implicit-GEMM Conv2d for the local-map encoder (bf16), 64 x 64 tiles.
@@ -1672,9 +1804,11 @@ __global__ void __launch_bounds__(512, 2) gemm16_kernel(ConvGemmParams p) {
   const int tap_bytes = p.lda * 2;                                   // one activation row further per tap
   // scalar source offsets of (virtual) K-step kv: activations / weights
   auto src_off = [&](int k, int& ao, int& wo) {
+    // (both are wave-uniform, but the compiler keeps the split forms' weight offset in a VGPR and then wraps every LDS-DMA
+    // request that takes it as its scalar offset in a waterfall loop: four per K-step.  readfirstlane pins them to SGPRs)
     const int t = k / nc, c = k - t * nc;
-    ao = t * tap_bytes + c * KB;
-    wo = k * w_step;
+    ao = __builtin_amdgcn_readfirstlane(t * tap_bytes + c * KB);
+    wo = __builtin_amdgcn_readfirstlane(k * w_step);
   };
   auto issue = [&](int kv) {                                         // K-step kv -> buffers kv & 1
     int ao, wo;
@@ -1865,7 +1999,8 @@ enum { TV_SPLIT = 1,     // hi + lo planes
        TV_SHORT = 2,     // L = 8 / 4: per-lane sample indices in the epilogue
        TV_SPLITK = 4,    // latency mode of the split halo kernel: gridDim.y work-groups per tile
        TV_NP6 = 8,       // L = 4 on the split halo kernel: six activation pieces, all 160 KB of LDS
-       TV_C2D = 16 };    // implicit Conv2d addressing
+       TV_C2D = 16,      // implicit Conv2d addressing
+       TV_L16 = 32, TV_L32 = 64, TV_L64 = 128 };   // whole-tile halo forms at L = 16, 32, 64: fixed fragment addresses
 struct TileVariant {
   void (*kernel)(ConvGemmParams);
   unsigned lds_bytes;    // dynamic LDS of a work-group
@@ -1879,6 +2014,18 @@ static const TileVariant k_tiles[] = {
     {conv3_halo16_kernel<1>, 147456, 512, TILE_HALO, ST_F16, 0, 0},
     {conv3_halo16x3_kernel<0>, 147456, 512, TILE_HALO, ST_BF16, TV_SPLIT, 0},
     {conv3_halo16x3_kernel<1>, 147456, 512, TILE_HALO, ST_F16, TV_SPLIT, 0},
+    {conv3_halo16_fixed_kernel<0, 16>, 147456, 512, TILE_HALO, ST_BF16, TV_L16, 0},
+    {conv3_halo16_fixed_kernel<1, 16>, 147456, 512, TILE_HALO, ST_F16, TV_L16, 0},
+    {conv3_halo16_fixed_kernel<0, 32>, 147456, 512, TILE_HALO, ST_BF16, TV_L32, 0},
+    {conv3_halo16_fixed_kernel<1, 32>, 147456, 512, TILE_HALO, ST_F16, TV_L32, 0},
+    {conv3_halo16_fixed_kernel<0, 64>, 147456, 512, TILE_HALO, ST_BF16, TV_L64, 0},
+    {conv3_halo16_fixed_kernel<1, 64>, 147456, 512, TILE_HALO, ST_F16, TV_L64, 0},
+    {conv3_halo16x3_fixed_kernel<0, 16>, 147456, 512, TILE_HALO, ST_BF16, TV_SPLIT | TV_L16, 0},
+    {conv3_halo16x3_fixed_kernel<1, 16>, 147456, 512, TILE_HALO, ST_F16, TV_SPLIT | TV_L16, 0},
+    {conv3_halo16x3_fixed_kernel<0, 32>, 147456, 512, TILE_HALO, ST_BF16, TV_SPLIT | TV_L32, 0},
+    {conv3_halo16x3_fixed_kernel<1, 32>, 147456, 512, TILE_HALO, ST_F16, TV_SPLIT | TV_L32, 0},
+    {conv3_halo16x3_fixed_kernel<0, 64>, 147456, 512, TILE_HALO, ST_BF16, TV_SPLIT | TV_L64, 0},
+    {conv3_halo16x3_fixed_kernel<1, 64>, 147456, 512, TILE_HALO, ST_F16, TV_SPLIT | TV_L64, 0},
     {conv3_halo16x3_kernel<0, true>, 147456, 512, TILE_HALO, ST_BF16, TV_SPLIT | TV_SHORT, 0},
     {conv3_halo16x3_kernel<1, true>, 147456, 512, TILE_HALO, ST_F16, TV_SPLIT | TV_SHORT, 0},
     {conv3_halo16x3_kernel<0, false, true>, 147456, 512, TILE_HALO, ST_BF16, TV_SPLIT | TV_SPLITK, 0},
@@ -1925,10 +2072,12 @@ static const TileVariant* pick_tile(const ConvGemmParams& p, int fmt) {
   // instantiation.  L = 4: 64 samples x 6 padded rows = 384 staged rows, the six-piece instantiation (no split-K form).
   const bool l_ok = p.L >= 16 || (p.L == 8 && split) || (p.L == 4 && split && p.splitk <= 1);
   if (tile16 && p.taps == 3 && p.in_stride == 1 && p.in_Lp == p.L + 2 && (256 % p.L) == 0 && l_ok && p.Cin >= 192) {
-    if (!split) return find_tile(TILE_HALO, st, 0);
+    const unsigned flen = p.L == 64 ? TV_L64 : (p.L == 32 ? TV_L32 : (p.L == 16 ? TV_L16 : 0));     // L = 128 / 256: run-time form
+    if (!split) return find_tile(TILE_HALO, st, flen);
     const unsigned fshort = p.L <= 8 ? TV_SHORT : 0;
     if (p.splitk > 1) return find_tile(TILE_HALO, st, TV_SPLIT | fshort | TV_SPLITK);   // latency mode (denoise.h)
-    return find_tile(TILE_HALO, st, TV_SPLIT | fshort | (p.L == 4 ? TV_NP6 : 0));
+    if (p.L >= 16) return find_tile(TILE_HALO, st, TV_SPLIT | flen);
+    return find_tile(TILE_HALO, st, TV_SPLIT | TV_SHORT | (p.L == 4 ? TV_NP6 : 0));
   }
   // gemm16 tile.  L = 8 and 4 (the ant config's lower levels): a 16-row block of the epilogue spans 2 or 4 samples
   const bool short_l = p.L == 8 || p.L == 4;
