@@ -173,6 +173,7 @@ SIGNATURES = {
     "ditree_follow_plan": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _pd, _f64, _f64, _vp, _vp, _vp]),
     "ditree_accept": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Round), _i32, _vp]),
     "ditree_accept_best": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Round), _vp, _vp]),
+    "ditree_tree_rebase": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Tree), _i32, _pd, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ditree_round_pack": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Round), _vp, _vp]),
     "ditree_round_unpack": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Round), _vp, _vp]),
     "ditree_record_doubles": (_i32, [C.POINTER(Tree)]),

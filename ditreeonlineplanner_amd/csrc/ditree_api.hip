@@ -562,6 +562,48 @@ int32_t ditree_accept_best(ditree_ctx* ctx, const ditree_tree* tree, const ditre
   return accept_impl(ctx, tree, nullptr, round, AcceptMode::best, 0, cost, nullptr, stream);
 }
 
+// ---- re-planning on a kept tree (include/ditree.h): every host-side check runs before anything is launched; the node count
+// and the anchor's row counts live on the device and are checked there (dst->counters[0]).
+int32_t ditree_tree_rebase(ditree_ctx* ctx, const ditree_tree* src, const ditree_tree* dst, int32_t anchor,
+                           const double* root_state, int32_t drop_states, int32_t drop_actions, const int32_t* cost_src,
+                           int32_t* cost_dst, int32_t* scratch, void* stream) {
+  if (!ctx) return DITREE_E_ARG;
+  int rc = check_tree(ctx, src);
+  if (rc) return rc;
+  rc = check_tree(ctx, dst);
+  if (rc) return rc;
+  if (src->hist || dst->hist || src->state_dim != 6 || src->action_dim != 2)
+    return set_err(ctx, DITREE_E_ARG, "tree_rebase: the car (a tree with state_dim 6, action_dim 2 and no hist)");
+  if (src->n_chunks != dst->n_chunks || src->A != dst->A || src->state_dim != dst->state_dim || src->action_dim != dst->action_dim)
+    return set_err(ctx, DITREE_E_ARG, "tree_rebase: src and dst differ in shape");
+  if (dst->capacity < src->capacity) return set_err(ctx, DITREE_E_ARG, "tree_rebase: dst->capacity below src->capacity");
+  if ((src->obstacle_ahead == nullptr) != (dst->obstacle_ahead == nullptr))
+    return set_err(ctx, DITREE_E_ARG, "tree_rebase: obstacle_ahead in one tree only");
+  const void* a[] = {src->state, src->xy, src->parent, src->last_action, src->has_prev, src->num_visit, src->edge_states,
+                     src->edge_actions, src->edge_nstates, src->edge_nactions, src->obstacle_ahead, src->edge_owner,
+                     src->counters, cost_src};
+  const void* b[] = {dst->state, dst->xy, dst->parent, dst->last_action, dst->has_prev, dst->num_visit, dst->edge_states,
+                     dst->edge_actions, dst->edge_nstates, dst->edge_nactions, dst->obstacle_ahead, dst->edge_owner,
+                     dst->counters, cost_dst};
+  for (const void* p : a)
+    for (const void* q : b)
+      if (p != nullptr && p == q) return set_err(ctx, DITREE_E_ARG, "tree_rebase: src and dst share a buffer");
+  if (anchor < 0 || anchor >= src->capacity) return set_err(ctx, DITREE_E_ARG, "tree_rebase: anchor out of range");
+  if (!root_state && (drop_states != 0 || drop_actions != 0))
+    return set_err(ctx, DITREE_E_ARG, "tree_rebase: drop counts belong to a root_state");
+  if ((cost_src == nullptr) != (cost_dst == nullptr))
+    return set_err(ctx, DITREE_E_ARG, "tree_rebase: cost_src and cost_dst come together");
+  if (!scratch) return set_err(ctx, DITREE_E_ARG, "tree_rebase: scratch missing");
+  if (!ctx->maze) return set_err(ctx, DITREE_E_STATE, "tree_rebase: no maze uploaded");
+  RebaseArg arg{anchor, root_state != nullptr, drop_states, drop_actions, {0}};
+  if (root_state)
+    for (int k = 0; k < src->state_dim; ++k) arg.root[k] = root_state[k];
+  launch_tree_rebase(*src, *dst, arg, cost_src, cost_dst, scratch, ctx->maze, ctx->rows, ctx->cols, ahead_samples(),
+                     (hipStream_t)stream);
+  HIP_TRY(ctx, hipGetLastError());
+  return DITREE_OK;
+}
+
 int32_t ditree_round_pack(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round, double* records_out,
                           void* stream) {
   if (!ctx) return DITREE_E_ARG;

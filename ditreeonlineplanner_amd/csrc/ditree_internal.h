@@ -200,6 +200,15 @@ void launch_accept(const ditree_tree& t, const ditree_round& r, const TreeSet& t
                    hipStream_t s);
 void launch_obstacle_ahead(const unsigned char* maze, int rows, int cols, const double* state, int stride, int B,
                            const AheadArg& ts, uint8_t* out, hipStream_t s);
+// ditree_tree_rebase: the anchor, whether a fresh root (its state by value: the car's 6 doubles) goes in front of it, and the
+// rows the anchor's edge loses then
+struct RebaseArg {
+  int anchor, fresh_root, drop_states, drop_actions;
+  double root[8];
+};
+void launch_tree_rebase(const ditree_tree& src, const ditree_tree& dst, const RebaseArg& a, const int32_t* cost_src,
+                        int32_t* cost_dst, int32_t* scratch, const unsigned char* maze, int rows, int cols, const AheadArg& ahead,
+                        hipStream_t s);
 void launch_fallback_select(const ditree_tree& t, int n_nodes, double gx, double gy, const double* path_dev, int P,
                             int32_t* out_node, hipStream_t s);
 void launch_follow_plan(double* state_io, const float* actions, int n_actions, int action_idx, const float* path, int P,

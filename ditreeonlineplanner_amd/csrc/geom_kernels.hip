@@ -1595,3 +1595,191 @@ void launch_bound_keys(const double* xy, int first, int n, int C, const BoundArg
   hipLaunchKernelGGL(bound_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, s, (const double2*)xy, first, n, C, bd);
 }
 
+
+// ------------------------------------------------------------------------- re-planning on a kept tree (ditree_tree_rebase)
+// include/ditree.h "re-planning on a kept tree".  src is read only; every kernel derives the node count and the device-side
+// refusal from src itself, so all of them take the same branch.  The flag words of the keep passes are (ancestor << 1) | ok,
+// ancestor -1 = the chain has reached the anchor (ok: nothing on it is blocked) or left the subtree (ok = 0).
+__device__ __forceinline__ int rebase_nodes(const ditree_tree& src) {
+  const int n = src.counters[0];
+  return n > src.capacity ? src.capacity : n;
+}
+__device__ __forceinline__ int rebase_status(const ditree_tree& src, const RebaseArg& a, int n) {
+  if (a.anchor >= n) return DITREE_REBASE_E_ANCHOR;
+  if (a.fresh_root) {
+    const int ns = src.edge_nstates[a.anchor], na = src.edge_nactions[a.anchor];
+    if (!(a.drop_states > 0 && a.drop_states < ns && a.drop_actions >= 0 && a.drop_actions < na)) return DITREE_REBASE_E_DROP;
+  }
+  return 0;
+}
+// One wave per node: is any kept row of its edge, or its state, in collision on the staged maze?  The anchor keeps the rows
+// from drop_states on (a fresh root) or none (it becomes the root).  A NaN row collides (ball_collides: out of the map).
+__global__ void __launch_bounds__(256)
+rebase_valid_kernel(ditree_tree src, RebaseArg a, const unsigned char* __restrict__ maze, int rows, int cols,
+                    int32_t* __restrict__ flag) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+  stage_maze(lds, maze, rows * cols);
+  const int n = rebase_nodes(src);
+  if (rebase_status(src, a, n) != 0) return;
+  const int m = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (m >= n) return;
+  const int par = m == a.anchor ? -1 : src.parent[m];
+  if (m < a.anchor || (m != a.anchor && (par < a.anchor || par >= m))) {       // (accept appends in order: parent < child)
+    if (lane == 0) flag[m] = -2;
+    return;
+  }
+  const int S = src.state_dim, cap = src.n_chunks * (src.A + 1);
+  int ns = src.edge_nstates[m];
+  ns = ns < 0 ? 0 : (ns > cap ? cap : ns);
+  const int first = m == a.anchor ? (a.fresh_root ? a.drop_states : ns) : 0;
+  const double* es = src.edge_states + (size_t)m * cap * S;
+  const double* st = src.state + (size_t)m * S;
+  bool bad = false;
+  for (int r = first + lane; r <= ns; r += 64) {               // row ns: the node's own state
+    const double* p = r < ns ? es + (size_t)r * S : st;
+    bad |= car_collides(p[0], p[1], p[2], lds, rows, cols);
+  }
+  const bool blocked = __ballot(bad) != 0ull;
+  if (lane == 0) flag[m] = par * 2 + (blocked ? 0 : 1);
+}
+// One pointer-doubling pass: a chain of 2^k hops is covered after k passes.
+__global__ void __launch_bounds__(256)
+rebase_keep_pass_kernel(ditree_tree src, const int32_t* __restrict__ in, int32_t* __restrict__ out) {
+  const int m = blockIdx.x * blockDim.x + threadIdx.x;
+  if (m >= rebase_nodes(src)) return;
+  int v = in[m];
+  const int anc = v >> 1;
+  if (anc >= 0) {
+    const int w = in[anc];
+    v = (w >> 1) * 2 + (v & w & 1);
+  }
+  out[m] = v;
+}
+// New ids = exclusive scan of the keep flags (+ 1 behind a fresh root), 1024 nodes at a time, and dst's counter row.  An
+// anchor that becomes the root is kept even when the car's own pose collides: its flag then only cuts off what hangs below.
+// A refused call writes its status to dst->counters[0] and nothing else.
+__global__ void __launch_bounds__(1024)
+rebase_scan_kernel(ditree_tree src, ditree_tree dst, RebaseArg a, const int32_t* __restrict__ flag, int32_t* __restrict__ new_id) {
+  __shared__ int s_wave_sum[16];
+  __shared__ int s_goal;
+  const int tid = threadIdx.x;
+  const int n = rebase_nodes(src);
+  const int status = rebase_status(src, a, n);
+  if (status != 0) {
+    if (tid == 0) dst.counters[0] = status;
+    return;
+  }
+  const int goal = src.counters[1];
+  if (tid == 0) s_goal = -1;
+  __syncthreads();
+  int base = a.fresh_root ? 1 : 0;
+  for (int start = 0; start < n; start += blockDim.x) {
+    const int m = start + tid;
+    const int keep = m < n ? ((flag[m] & 1) | (!a.fresh_root && m == a.anchor)) : 0;
+    int v = keep;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      int o = __shfl_up(v, d);
+      if ((tid & 63) >= d) v += o;
+    }
+    if ((tid & 63) == 63) s_wave_sum[tid >> 6] = v;
+    __syncthreads();
+    int woff = 0, total = 0;
+    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) {
+      if (w < (tid >> 6)) woff += s_wave_sum[w];
+      total += s_wave_sum[w];
+    }
+    if (m < n) {
+      const int id = keep ? base + woff + v - 1 : -1;
+      new_id[m] = id;
+      if (m == goal) s_goal = id;
+    }
+    base += total;
+    __syncthreads();
+  }
+  if (tid == 0) {
+    dst.counters[0] = base;
+    dst.counters[1] = s_goal;
+    for (int k = 2; k < 7; ++k) dst.counters[k] = 0;
+    dst.counters[7] = -1;
+  }
+}
+// One wave per kept node moves it to its new slot (accept_commit_kernel's fields).  The edge rows of the car are whole double2
+// pairs (S = 6, D = 2), so a node's edge is one flat copy; the anchor's starts behind its dropped rows.  The obstacle-ahead
+// flag is evaluated on the current maze, as the commit does for a new node; the root's is 0, as DeviceTree.reset leaves it.
+__global__ void __launch_bounds__(256)
+rebase_move_kernel(ditree_tree src, ditree_tree dst, RebaseArg a, const int32_t* __restrict__ new_id,
+                   const int32_t* __restrict__ cost_src, int32_t* __restrict__ cost_dst, const unsigned char* __restrict__ maze,
+                   int rows, int cols, AheadArg ahead) {
+  const int n = rebase_nodes(src);
+  if (rebase_status(src, a, n) != 0) return;
+  const int m = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (m >= n) return;
+  const int S = src.state_dim, D = src.action_dim;
+  const bool anchor = m == a.anchor, root = anchor && !a.fresh_root;
+  if (anchor && a.fresh_root) {                        // node 0, whether or not the anchor survives behind it
+    if (lane < S) dst.state[lane] = a.root[lane];
+    if (lane < 2) dst.xy[lane] = a.root[lane];
+    if (lane < D) dst.last_action[lane] = 0.0;
+    if (lane == 0) {
+      dst.parent[0] = -1;
+      dst.has_prev[0] = 0;
+      dst.num_visit[0] = 0;
+      dst.edge_nstates[0] = 0;
+      dst.edge_nactions[0] = 0;
+      if (cost_dst != nullptr) cost_dst[0] = 1;
+      if (dst.edge_owner != nullptr) dst.edge_owner[0] = -1;
+      if (dst.obstacle_ahead != nullptr) dst.obstacle_ahead[0] = 0;
+    }
+  }
+  const int id = new_id[m];
+  if (id < 0) return;
+  const int es_cap = src.n_chunks * (src.A + 1), ea_cap = src.n_chunks * src.A;
+  int ns = min(max(src.edge_nstates[m], 0), es_cap), na = min(max(src.edge_nactions[m], 0), ea_cap);
+  int s0 = 0, a0 = 0;
+  if (root) { ns = 0; na = 0; }
+  else if (anchor) { s0 = a.drop_states; a0 = a.drop_actions; ns = max(ns - s0, 0); na = max(na - a0, 0); }
+  const double2* es = (const double2*)(src.edge_states + ((size_t)m * es_cap + s0) * S);
+  const double2* ea = (const double2*)(src.edge_actions + ((size_t)m * ea_cap + a0) * D);
+  double2* ds = (double2*)(dst.edge_states + (size_t)id * es_cap * S);
+  double2* da = (double2*)(dst.edge_actions + (size_t)id * ea_cap * D);
+  for (int k = lane; k < ns * S / 2; k += 64) ds[k] = es[k];
+  for (int k = lane; k < na * D / 2; k += 64) da[k] = ea[k];
+  double sv = 0.0;
+  if (lane < S) {
+    sv = src.state[(size_t)m * S + lane];
+    dst.state[(size_t)id * S + lane] = sv;
+  }
+  if (lane < 2) dst.xy[(size_t)id * 2 + lane] = sv;
+  if (lane < D) dst.last_action[(size_t)id * D + lane] = root ? 0.0 : src.last_action[(size_t)m * D + lane];
+  const double ex = __shfl(sv, 0), ey = __shfl(sv, 1), psi = __shfl(sv, 2);
+  if (lane == 0) {
+    // the anchor's cost: 1 as the root, else the fresh root's row + its kept edge rows + its own state
+    const int c_anchor = a.fresh_root ? 2 + src.edge_nstates[a.anchor] - a.drop_states : 1;
+    dst.parent[id] = anchor ? (a.fresh_root ? 0 : -1) : new_id[src.parent[m]];
+    dst.has_prev[id] = root ? 0 : src.has_prev[m];
+    dst.num_visit[id] = src.num_visit[m];
+    dst.edge_nstates[id] = ns;
+    dst.edge_nactions[id] = na;
+    if (cost_dst != nullptr) cost_dst[id] = anchor ? c_anchor : cost_src[m] - cost_src[a.anchor] + c_anchor;
+    if (dst.edge_owner != nullptr) dst.edge_owner[id] = src.edge_owner != nullptr ? src.edge_owner[m] : -1;
+    if (dst.obstacle_ahead != nullptr)
+      dst.obstacle_ahead[id] = (!root && obstacle_ahead_dev(ex, ey, psi, maze, rows, cols, ahead)) ? 1 : 0;
+  }
+}
+// scratch: [0, cap) and [cap, 2 cap) the two flag buffers of the keep passes, [2 cap, 3 cap) the new ids.
+void launch_tree_rebase(const ditree_tree& src, const ditree_tree& dst, const RebaseArg& a, const int32_t* cost_src,
+                        int32_t* cost_dst, int32_t* scratch, const unsigned char* maze, int rows, int cols, const AheadArg& ahead,
+                        hipStream_t s) {
+  const int cap = src.capacity;
+  int32_t* buf[2] = {scratch, scratch + cap};
+  int32_t* new_id = scratch + 2 * (size_t)cap;
+  const size_t lds = ((size_t)rows * cols + 15) & ~(size_t)15;
+  const dim3 waves((cap + 3) / 4), threads((cap + 255) / 256);
+  hipLaunchKernelGGL(rebase_valid_kernel, waves, dim3(256), lds, s, src, a, maze, rows, cols, buf[0]);
+  int cur = 0;
+  for (int64_t hops = 1; hops < cap; hops *= 2, cur ^= 1)
+    hipLaunchKernelGGL(rebase_keep_pass_kernel, threads, dim3(256), 0, s, src, buf[cur], buf[cur ^ 1]);
+  hipLaunchKernelGGL(rebase_scan_kernel, dim3(1), dim3(1024), 0, s, src, dst, a, buf[cur], new_id);
+  hipLaunchKernelGGL(rebase_move_kernel, waves, dim3(256), 0, s, src, dst, a, new_id, cost_src, cost_dst, maze, rows, cols, ahead);
+}

@@ -430,6 +430,80 @@ class ExpansionEngine:
         if self.ctx.maze_owner is not self:
             self.ctx.upload_maze(self.maze, owner=self)
 
+    # ------------------------------------------------------------------ re-planning on a kept tree
+    def rebase(self, anchor, root_state=None, drop_states=0, drop_actions=0):
+        """Re-root the tree at the car instead of wiping it (include/ditree.h "re-planning on a kept tree"): the subtree of
+        ``anchor`` that still clears this engine's maze, compacted to the front.  ``drop_states == 0``: the car stands on
+        ``anchor``, which becomes the root (``root_state``, where given, replaces its state: the car's real one).
+        ``drop_states > 0``: the car is inside ``anchor``'s edge -- ``root_state`` becomes a fresh root and ``anchor`` its only
+        child, its edge without the first ``drop_states`` state rows and ``drop_actions`` action rows.  The goal is the one the
+        tree was grown for.  Returns ``(kept, dropped)``: the nodes of the old tree that are in the new one, and the rest.
+        The second tree is allocated on the first call and the two swap roles from then on."""
+        if self.HIST:
+            raise NotImplementedError("rebase: the car (the ant's tree keeps edge histories)")
+        if type(self) is not ExpansionEngine:
+            raise NotImplementedError(f"rebase: a single tree ({type(self).__name__} is not built)")
+        if self.world > 1 or getattr(self, "_sharded", False):
+            raise NotImplementedError(f"rebase: one rank (world_size {self.world}: a sharded tree keeps edge rows on other ranks)")
+        if self.pruned:
+            raise NotImplementedError("rebase: solution='anytime_pruned' is not built (key column, stats row, closed nodes)")
+        fresh_root = int(drop_states) > 0
+        if fresh_root and root_state is None:
+            raise ValueError("rebase: drop_states > 0 needs the root_state")
+        if not fresh_root and int(drop_actions) != 0:
+            raise ValueError("rebase: drop_actions without drop_states")
+        root = None if root_state is None else np.ascontiguousarray(root_state, dtype=np.float64)
+        if root is not None and root.shape != (self.STATE_DIM,):
+            raise ValueError(f"root_state must have {self.STATE_DIM} elements")
+        self.ensure_maze()
+        old = self.tree
+        if getattr(self, "_spare_tree", None) is None:
+            self._spare_tree = DeviceTree(self.ctx, old.capacity, self.n_chunks, self.A,
+                                          track_obstacle_ahead=old.obstacle_ahead is not None, state_dim=self.STATE_DIM,
+                                          action_dim=self.ACTION_DIM, hist=self.HIST, cost=old.cost is not None)
+            self._rebase_scratch = torch.zeros(3 * old.capacity, dtype=torch.int32, device=self.ctx.device)
+        new = self._spare_tree
+        n_old = old.n_nodes_host
+        rs = root.ctypes.data_as(C.POINTER(C.c_double)) if fresh_root else None
+        cost = (None, None) if old.cost is None else (old.cost.data_ptr(), new.cost.data_ptr())
+        check(self.ctx._h, lib().ditree_tree_rebase(self.ctx._h, C.byref(old.desc), C.byref(new.desc), int(anchor), rs,
+                                                    int(drop_states), int(drop_actions), cost[0], cost[1],
+                                                    self._rebase_scratch.data_ptr(), self.ctx.stream), "tree_rebase")
+        cnt = new.read_counters()                 # the one D2H: the new size, or the device's refusal
+        if cnt[CNT_NODES] <= 0:
+            new.n_nodes_host = 0
+            raise ValueError(f"rebase: refused on the device ({'drop counts' if cnt[CNT_NODES] == -1 else 'anchor'} out of "
+                             f"range: anchor {anchor}, drop_states {drop_states}, drop_actions {drop_actions}, {n_old} nodes)")
+        self.tree, self._spare_tree = new, old    # every descriptor with tree pointers is the DeviceTree's own
+        if root is not None:
+            self.start_state = root.copy()
+            if not fresh_root:
+                s = torch.as_tensor(root, device=new.state.device)
+                new.state[0] = s
+                new.xy[0] = s[:2]
+        self.rebase_ids = self._rebase_scratch[2 * old.capacity:]      # old id -> new id (-1: dropped) until the next rebase
+        self.generation += 1
+        kept = int(cnt[CNT_NODES]) - (1 if fresh_root else 0)
+        return kept, n_old - kept
+
+    def chain_rows(self, node):
+        """The chain root .. ``node`` with what the tree holds for it in f64: ids, per-node edge row counts (states, actions)
+        and per node the rows ``tree_path`` strings together -- its edge states, then its state (the root: its state alone)."""
+        n = self.tree.n_nodes_host
+        parents = self.tree.parent[:n].cpu().numpy()
+        chain = []
+        k = int(node)
+        while k >= 0:
+            chain.append(k)
+            k = int(parents[k])
+        chain = chain[::-1]
+        idx = torch.as_tensor(chain, device=self.tree.state.device, dtype=torch.long)
+        st, es = self.tree.state[idx].cpu().numpy(), self.tree.edge_states[idx].cpu().numpy()
+        ns, na = self.tree.edge_nstates[idx].cpu().numpy(), self.tree.edge_nactions[idx].cpu().numpy()
+        ns[0] = na[0] = 0
+        rows = [np.concatenate([es[j, :ns[j]], st[j][None]]) for j in range(len(chain))]
+        return chain, ns.astype(int).tolist(), na.astype(int).tolist(), rows
+
     def shard(self, B):
         """Contiguous candidate block of this rank."""
         per = (B + self.world - 1) // self.world

@@ -33,6 +33,15 @@ Constructor kwargs, ``plan() -> (path f32 (P,6)|None, actions f32 (A,2)|None)``,
                        Same scope as "anytime", and a single ``prop_duration`` entry.  ``results`` gains
                        ``pruned_candidates``, ``closed_nodes`` (nodes whose key is at or past the final incumbent's rows,
                        counted once at the end) and ``bound_exhausted``.
+  ``reuse_tree``       (default False) ``reset(start_state=...)`` keeps the tree of the last plan where the car still stands on
+                       that plan and the goal is unchanged: it is re-rooted at the car, the branches the current maze blocks
+                       are dropped with everything behind them, and the rest is compacted on the device
+                       (``ExpansionEngine.rebase``).  ``reuse_tol`` (default 1e-3: m, m, rad, m/s; 1 % of the collision ball's
+                       0.1 m radius) is how close ``start_state`` must be to a row of the plan.  Anything else -- no plan yet,
+                       the car off its plan, another goal -- is the reset as ever.  ``plan()`` on a tree that kept its goal node
+                       returns that node's path at once ("first", "best_of_round") or plans on with it as the incumbent
+                       ("anytime").  ``results`` gains ``reused_nodes`` / ``dropped_nodes`` (0 after a fresh reset), and
+                       ``number_of_nodes`` counts the reused nodes.  The car, one rank, not "anytime_pruned".
 All of the reference's ``run_type`` values: 0 "Original"; 1 "Original+Ref" (obstacle-ahead flags per node, sampling
 biased to the part of ``init_main_path`` behind the obstacle, furthest-along-path fallback); 2 "OM+Ref" (sample
 positions drawn from the EDT prior); 3 "OM+LB+Ref" (prior log-blended with the start -> goal Gaussian, refreshed at
@@ -80,6 +89,7 @@ class RRT_Planner(BasePlanner):
         self.capacity = int(kwargs.get("capacity", 65536))
         self.solution = kwargs.get("solution", "first")
         self._check_solution(kwargs)
+        self._check_reuse(kwargs)
         sticky = kwargs.get("emulate_sticky_done", self.solution == "first")
         lm = self.local_map_size if isinstance(self.local_map_size, (int, float)) else self.local_map_size[0]
         d_rank, d_world, d_pg = default_shard()
@@ -136,6 +146,24 @@ class RRT_Planner(BasePlanner):
             raise ValueError(f"bound_speed must be a positive finite number, got {v!r}")
         self.bound_speed = float(v)
         self.bound_reach = self.bound_speed * float(self.env_dt)      # metres a path row is assumed to cover at most
+
+    def _check_reuse(self, kwargs):
+        """``reuse_tree``: refused by name where it is not built, before the device is touched."""
+        self.reuse_tree = bool(kwargs.get("reuse_tree", False))
+        self.reuse_tol = float(kwargs.get("reuse_tol", 1e-3))
+        self._remembered = None                      # _reuse.RememberedPlan of the last returned plan
+        self._edge_phase = {}                        # node id -> (state rows, action rows) re-bases took off its edge's front
+        if not self.reuse_tree:
+            return
+        if not (np.isfinite(self.reuse_tol) and self.reuse_tol >= 0):
+            raise ValueError(f"reuse_tol must be a finite number >= 0, got {kwargs.get('reuse_tol')!r}")
+        if self.is_ant:
+            raise NotImplementedError("reuse_tree=True: the car only (env_id='antmaze' resets its tree)")
+        world = int(kwargs.get("world_size", default_shard()[1]))
+        if world > 1:
+            raise NotImplementedError(f"reuse_tree=True: one rank (world_size {world}; a sharded tree keeps edge rows on other ranks)")
+        if self.solution == "anytime_pruned":
+            raise NotImplementedError("reuse_tree=True: solution='anytime_pruned' is not built (key column, stats row, closed nodes)")
 
     # ------------------------------------------------------------------ ant (BASELINE config 3)
     def _init_ant_engine(self, sampler, kwargs):
@@ -209,14 +237,65 @@ class RRT_Planner(BasePlanner):
                         "first_solution_candidates": None}
         if self.solution == "anytime_pruned":
             self.results.update(pruned_candidates=0, closed_nodes=0, bound_exhausted=False)
+        if self.reuse_tree:
+            self.results.update(reused_nodes=0, dropped_nodes=0)
         out = self.env.reset(options=self.options)
         if self.is_ant:
             if isinstance(out, tuple) and isinstance(out[0], dict) and "desired_goal" in out[0]:
                 self._engine._desired_arg = np.asarray(out[0]["desired_goal"], dtype=np.float64)[:2].copy()
             self._engine.reset(self.start_node.state, self.goal_state)
             return
-        self._engine.reset(self.start_node.state, self.goal_state)
+        if not (self.reuse_tree and start_state is not None and self._reuse_reset()):
+            self._remembered, self._edge_phase = None, {}
+            self._engine.reset(self.start_node.state, self.goal_state)
         self._engine.env_goal = np.asarray(self.env.goal, dtype=np.float64)
+
+    def _reuse_reset(self):
+        """``reset(start_state=...)`` with ``reuse_tree``: re-base the tree at the car where it stands on the remembered plan
+        (planners/_reuse.py), grown for this goal.  False: nothing to keep -- the caller resets as ever."""
+        from ._reuse import locate
+        plan, eng = self._remembered, self._engine
+        if plan is None or not np.array_equal(plan.goal_state, self.goal_state):
+            return False
+        where = locate(plan, self.start_node.state, self.reuse_tol, eng.A)
+        if where is None:
+            return False
+        anchor, drop_states, drop_actions = where
+        kept, dropped = eng.rebase(anchor, root_state=self.start_node.state, drop_states=drop_states, drop_actions=drop_actions)
+        self.results.update(reused_nodes=kept, dropped_nodes=dropped)
+        # what is left of the plan, under the new ids: the chain from the anchor to its last kept node
+        tail = plan.chain[plan.chain.index(anchor):]
+        ids = eng.rebase_ids[torch.as_tensor(tail, device=self.ctx.device, dtype=torch.long)].cpu().numpy()
+        last = 0
+        for v in ids:
+            if v < 0:
+                break
+            last = int(v)
+        # the rows that re-bases have taken off the front of an edge stay known under the node's new id: behind a fresh root it
+        # is the anchor's edge that lost rows (again); an anchor that became the root has no edge any more
+        old = self._edge_phase
+        self._edge_phase = {}
+        if old:
+            keys = list(old)
+            new = eng.rebase_ids[torch.as_tensor(keys, device=self.ctx.device, dtype=torch.long)].cpu().numpy()
+            self._edge_phase = {int(v): old[k] for k, v in zip(keys, new) if v > 0}
+        if drop_states > 0 and int(ids[0]) == 1:
+            s0, a0 = old.get(anchor, (0, 0))
+            self._edge_phase[1] = (s0 + drop_states, a0 + drop_actions)
+        self._remembered = self._remember(last)
+        return True
+
+    def _remember(self, node):
+        """The chain root .. ``node`` in the tree's f64 (``path`` is float32), for the next ``reset(start_state=...)``."""
+        from ._reuse import RememberedPlan
+        chain, ns, na, rows = self._engine.chain_rows(node)
+        return RememberedPlan(chain, ns, na, rows, self.goal_state, [self._edge_phase.get(c, (0, 0)) for c in chain])
+
+    def handle_goal_reached(self, node_index, iterations, start_time):
+        out = super().handle_goal_reached(node_index, iterations, start_time)
+        if self.reuse_tree:
+            self._remembered = self._remember(node_index)
+        return out
 
     def update_maze(self, new_maze):
         self.maze = np.float32(new_maze)
@@ -350,12 +429,19 @@ class RRT_Planner(BasePlanner):
     def plan(self):
         eng = self._engine
         dev = self.ctx.device
+        # a re-based tree (reuse_tree) may still hold its goal node: the modes that end at their first goal return its path at
+        # once -- no round, no draw from any generator --, the anytime mode plans on with it as the incumbent
+        kept_goal = eng.goal_node if self.reuse_tree and self.results.get("reused_nodes", 0) > 0 else None
+        if kept_goal is not None and self.solution not in ANYTIME:
+            self.results.update(solutions=1, first_solution_candidates=0)
+            self.env.done = True
+            return self.handle_goal_reached(kept_goal, 0, time.time())
         network = hasattr(self.sampler, "ensure_bound")
         if network:
             self.sampler.ensure_bound(eng.shard(self.batch)[2])
         start_time = time.time()
         drawn = 0
-        goal = None
+        goal = kept_goal
         has_pm = hasattr(self.env, "prob_map")               # the gym ant env has none (the reference reads it: RRT.py:122)
         orig_prob_map = self.env.prob_map.copy() if has_pm else None
         if self.run_type >= 3:
@@ -379,7 +465,7 @@ class RRT_Planner(BasePlanner):
         steps_dev = torch.zeros((), dtype=torch.int64, device=dev)     # env steps = two-ball collision tests (cc_calls)
         first = self.solution == "first"
         solutions_dev = None if first else torch.zeros((), dtype=torch.int64, device=dev)
-        first_at = None                                                # candidates drawn when the first goal node appeared
+        first_at = None if kept_goal is None else 0                    # candidates drawn when the first goal node appeared
         while eng.agree((time.time() - start_time) < self.time_budget):
             if self.max_candidates is not None and drawn >= self.max_candidates:
                 break

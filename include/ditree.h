@@ -759,6 +759,43 @@ int32_t ditree_accept_bounded(ditree_ctx* ctx, const ditree_tree* tree, const di
 int32_t ditree_forest_accept_bounded(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
                                      const ditree_round* round, const ditree_bound* bound, void* stream);
 
+/* ------------------------------------------------------------------ re-planning on a kept tree
+ * The online driver re-plans from wherever the car stands on its plan (run_scenarios_with_lidar_DiTree.py:397-516).  Instead of
+ * starting from an empty tree, ditree_tree_rebase re-roots the tree at the car, keeps the branches that grow from there and
+ * still clear the maze uploaded to the ctx, and compacts them to the front of a SECOND tree `dst` of the same shape (src is only
+ * read; src and dst share no buffer).  n = src->counters[0] is read on the device.
+ *   root_state == NULL: the car stands on node `anchor`, which becomes node 0 (drop_states = drop_actions = 0).
+ *   root_state != NULL ([host] S doubles, read during the call): the car is inside anchor's edge.  Node 0 is a fresh node with
+ *     that state; anchor becomes node 1 with parent 0 and its edge without the first drop_states state rows and the first
+ *     drop_actions action rows, 0 < drop_states < edge_nstates[anchor], 0 <= drop_actions < edge_nactions[anchor].
+ *   Node 0 is a root as after a reset: parent -1, no edge rows, has_prev 0, last_action 0, obstacle_ahead 0, cost 1; its
+ *   num_visit is anchor's when anchor became it, 0 when it is fresh.
+ * Node m is kept iff it is anchor or a descendant of it and no node on the chain anchor .. m is blocked.  A node is blocked when
+ * car_collides(x, y, psi) holds for its state or for a kept row of its edge states (a NaN row collides); of anchor's edge only
+ * the rows behind the dropped ones count, and none when it becomes the root -- that root is kept even if the car's own pose
+ * collides, its subtree then is not.  A blocked anchor leaves node 0 alone: a fresh reset.
+ * New ids: the exclusive scan of the keep flags (+ 1 behind a fresh root), so parent < child still holds; parents are remapped.
+ * Moved per kept node: state, xy, last_action, has_prev, num_visit, edge_owner, both edge arrays and row counts; obstacle_ahead
+ * (where the trees have it) is evaluated again on the current maze.  cost_src / cost_dst [dev] (capacity,) int32, both or
+ * neither: the cost column of ditree_accept_best, re-based to the rows of the new paths -- cost'[m] = cost[m] - cost[anchor] +
+ * cost'[anchor], cost'[anchor] = 1 as the root, else 1 + its kept edge rows + 1.
+ * dst->counters: [0] nodes of dst, [1] the new id of src's goal node / incumbent or -1 when it was not kept, [2..6] 0, [7] -1.
+ * scratch [dev]: 3 * src->capacity int32; when the call returns, scratch[2 * capacity + m] is the new id of node m < n, -1 for
+ * a node that was dropped.
+ * Checked on the device, because n and the row counts live there: a refused call writes DITREE_REBASE_E_DROP (drop counts out
+ * of range) or DITREE_REBASE_E_ANCHOR (anchor >= n) to dst->counters[0] -- a tree holds at least its root, so a count <= 0 is the
+ * status word -- and touches nothing else of dst.
+ * Refused before anything is launched, DITREE_E_ARG: "tree_rebase: the car (a tree with state_dim 6, action_dim 2 and no
+ * hist)", "tree_rebase: src and dst share a buffer", "tree_rebase: src and dst differ in shape", "tree_rebase: dst->capacity
+ * below src->capacity", "tree_rebase: anchor out of range", "tree_rebase: drop counts belong to a root_state", "tree_rebase:
+ * cost_src and cost_dst come together", "tree_rebase: scratch missing", "tree_rebase: obstacle_ahead in one tree only";
+ * DITREE_E_STATE: "tree_rebase: no maze uploaded". */
+#define DITREE_REBASE_E_DROP (-1)
+#define DITREE_REBASE_E_ANCHOR (-2)
+int32_t ditree_tree_rebase(ditree_ctx* ctx, const ditree_tree* src, const ditree_tree* dst, int32_t anchor,
+                           const double* root_state /*[host] S or NULL*/, int32_t drop_states, int32_t drop_actions,
+                           const int32_t* cost_src, int32_t* cost_dst, int32_t* scratch, void* stream);
+
 /* One expansion round of the ANT (BASELINE config 3; cfgs/antmaze.yaml + run_scenarios.py:123-132: action_horizon 2, edge
  * length 48 = 24 chunks, pred_horizon 16, obs_history 3, local map 16 x 16 @ 0.8, s_global 4) against a tree with state_dim
  * 29, action_dim 8 and `hist`: planners/RRT.py:131-194 batched --
