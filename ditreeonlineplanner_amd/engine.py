@@ -13,6 +13,7 @@ before the (replicated, deterministic) accept step, so every rank holds the same
 from __future__ import annotations
 
 import ctypes as C
+from typing import Callable, NamedTuple
 
 import numpy as np
 import torch
@@ -72,24 +73,30 @@ class DeviceTree:
         self.record_doubles = int(lib().ditree_record_doubles(C.byref(self.desc)))
         self.n_nodes_host = 0
 
-    def reset(self, start_state):
+    def write_root(self, slot, span, start_state):
+        """The root row of a tree that owns the ``span`` slots from ``slot`` (the whole tree, or one tree of a forest)."""
+        r = int(slot)
         s = torch.as_tensor(np.asarray(start_state, dtype=np.float64), device=self.state.device)
-        self.state[0] = s
-        self.xy[0] = s[:2]
-        self.parent[0] = -1
-        self.last_action[0] = 0
-        self.has_prev[0] = 0
-        self.num_visit.zero_()
-        self.edge_nstates[0] = 0
-        self.edge_nactions[0] = 0
+        self.state[r] = s
+        self.xy[r] = s[:2]
+        self.parent[r] = -1
+        self.last_action[r] = 0
+        self.has_prev[r] = 0
+        self.num_visit[r:r + span].zero_()
+        self.edge_nstates[r] = 0
+        self.edge_nactions[r] = 0
+        self.edge_owner[r] = -1
+        if self.hist is not None:                       # RRT.py:146: the root's child sees curr_state[None, None, :]
+            self.hist[r].zero_()
+            self.hist[r, 2] = s
+            self.hist_n[r] = 1
+        if self.cost is not None:
+            self.cost[r] = 1                            # the root's path is its own state row
+
+    def reset(self, start_state):
+        self.write_root(0, self.capacity, start_state)
         if self.obstacle_ahead is not None:
             self.obstacle_ahead.zero_()
-        if self.hist is not None:                       # RRT.py:146: the root's child sees curr_state[None, None, :]
-            self.hist[0].zero_()
-            self.hist[0, 2] = s
-            self.hist_n[0] = 1
-        if self.cost is not None:
-            self.cost[0] = 1                            # the root's path is its own state row
         self.counters.zero_()
         self.counters[CNT_NODES] = 1
         self.counters[CNT_GOAL] = -1
@@ -235,19 +242,26 @@ def ant_cell_centre(maze, goal_state, s_global):
     return np.array([(gj + 0.5) * sg - W / 2 * sg, H / 2 * sg - (gi + 0.5) * sg])
 
 
-def tree_path(tr, node, n_nodes, base=0, edge_rows=None):
-    """planners/base_planner.py:342-363 on a ``DeviceTree``: float32 path (edge states + node states) and actions from the
-    root to ``node``.  The tree is the ``n_nodes`` slots from ``base`` (a forest's tree; ``node`` is local to it, the stored
-    parents are global).  ``edge_rows(idx, es, ea, ns, na)``: what a sharded engine does to the chain's edge rows first."""
+def parent_chain(tr, node, n_nodes, base=0):
+    """The walk from ``node`` up to the root over the stored parents, root first.  The tree is the ``n_nodes`` slots from
+    ``base`` (a forest's tree; ``node`` is local to it, the stored parents are global).  -> (local ids, their slots on the
+    tree's device)."""
     parents = tr.parent[base: base + n_nodes].cpu().numpy()
     chain = []
     k = int(node)
-    while k != -1:
+    while k >= 0:
         chain.append(k)
         p = int(parents[k])
         k = -1 if p < 0 else p - base
     chain = chain[::-1]
-    idx = torch.as_tensor(chain, device=tr.state.device, dtype=torch.long) + base
+    return chain, torch.as_tensor(chain, device=tr.state.device, dtype=torch.long) + base
+
+
+def tree_path(tr, node, n_nodes, base=0, edge_rows=None):
+    """planners/base_planner.py:342-363 on a ``DeviceTree``: float32 path (edge states + node states) and actions from the
+    root to ``node`` (``parent_chain``'s arguments).  ``edge_rows(idx, es, ea, ns, na)``: what a sharded engine does to the
+    chain's edge rows first."""
+    chain, idx = parent_chain(tr, node, n_nodes, base)
     st = tr.state[idx].cpu().numpy()
     rows = (tr.edge_states[idx], tr.edge_actions[idx], tr.edge_nstates[idx], tr.edge_nactions[idx])
     if edge_rows is not None:
@@ -295,6 +309,54 @@ def check_solution(solution, emulate_sticky_done, world_size=1, run_type=0):
         raise NotImplementedError(f"solution={solution!r}: one rank (world_size {world_size})")
     if run_type != 0:
         raise NotImplementedError(f"solution={solution!r}: run_type 0 only (got {run_type})")
+
+
+def bound_stats(pruned, row, key, base, n_nodes):
+    """The "anytime_pruned" statistics of one tree, from its stats row as of the last accept and the keys of its ``n_nodes``
+    slots from ``base``: (exhausted: no node can be open any more, key[root] >= the incumbent's cost; candidates pruned since
+    the reset; closed_nodes(): the nodes whose key is at or past the incumbent's cost, 0 without an incumbent -- one
+    reduction and one scalar copy, so it is a call)."""
+    if not pruned:
+        return False, 0, lambda: 0
+    u = int(row[ST_BOUND])
+    return (bool(row[ST_EXHAUSTED]), int(row[ST_PRUNED]),
+            lambda: 0 if u == NO_BOUND else int((key[base: base + n_nodes] >= u).sum().item()))
+
+
+class Entries(NamedTuple):
+    """What an engine calls in the library, fixed at construction by three facts -- forest or single tree, scene table or
+    single maze, ant or car -- and the ``solution`` mode: the names of its entry points, ``accept_tail(engine)`` = what its
+    accept takes behind the round descriptor (the sticky-done flag, the cost column, the bound, or nothing), and the
+    descriptors its calls take behind the tree's -- ``lead`` in every call (a forest's descriptor), ``scenes`` behind those
+    in the expand call (a scene forest's descriptor; NULL for a plain forest's bounded round, whose entry point serves both
+    kinds of forest)."""
+    expand: str
+    accept: str
+    accept_tail: Callable
+    fallback: str
+    budget: str
+    lead: tuple
+    scenes: tuple
+
+    @classmethod
+    def of(cls, solution, ant, forest=None, scenes=None):
+        f, a = ("forest_" if forest is not None else ""), ("_ant" if ant else "")
+        lead = () if forest is None else (C.byref(forest),)
+        sc = () if scenes is None else (C.byref(scenes),)
+        if solution == "anytime_pruned":
+            expand, accept, tail = f"ditree_{f}expand_round_bounded", f"ditree_{f}accept_bounded", lambda e: (C.byref(e.bound),)
+            sc = sc or ((None,) if forest is not None else ())
+        else:
+            expand = f"ditree_{f}expand_round{a}" + ("_scenes" if scenes is not None else "")
+            if solution != "first":
+                accept, tail = f"ditree_{f}accept_best", lambda e: (e.tree.cost.data_ptr(),)
+            elif ant and forest is not None:             # the ant env has no sticky-done latch
+                accept, tail = "ditree_forest_accept_ant", lambda e: ()
+            else:
+                accept, tail = f"ditree_{f}accept", lambda e: (e.sticky,)
+        fallback = "ditree_fallback_select" if forest is None else \
+            "ditree_forest_fallback" + ("_goals" if scenes is not None else "") + a
+        return cls(expand, accept, tail, fallback, f"ditree_{f}chunk_budget", lead, sc)
 
 
 class ExpansionEngine:
@@ -363,22 +425,44 @@ class ExpansionEngine:
         t0, dt = get_timesteps("exp", k_steps, 4.0)
         self.t0, self.dt = t0.numpy().copy(), dt.numpy().copy()
         ctx.upload_maze(self.maze, owner=self)
+        # a forest's descriptors exist by now (ForestTrees._init_forest, SceneTrees._init_scenes run before this constructor)
+        fdesc = getattr(self, "fdesc", None)
+        self.entries = Entries.of(solution, self.HIST, fdesc, getattr(self, "sdesc", None))
         if self.pruned:
-            self._init_bound(1, self.tree.stats)
+            if fdesc is None:
+                self._init_bound(1, 0, self.tree.stats)
+            else:
+                self._init_bound(self.T, self.C, self.fstats)
         self.reset(start_state, goal_state)
 
+    def _call(self, entry, *args):
+        """One call of the library on this engine's tree: the handle, the tree's descriptor, ``args``, the stream."""
+        check(self.ctx._h, getattr(lib(), entry)(self.ctx._h, C.byref(self.tree.desc), *args, self.ctx.stream),
+              entry[len("ditree_"):])
+
+    def round_settings(self):
+        """The keyword arguments that rebuild this engine's round program in another engine of its kind (a forest)."""
+        kw = dict(action_horizon=self.A, pred_horizon=self.P, local_map_size=self.lm_n, local_map_scale=self.lm_scale,
+                  s_global=self.s_global, k_steps=self.k_steps, norm=self.norm, early_exit=bool(self.early_exit),
+                  goal_scale=self.goal_scale)
+        if self.HIST:
+            kw.update(edge_length=self.H, dynamics=self.dynamics, model=self.model, ball_radius=self.ball_radius)
+        else:
+            kw.update(emulate_sticky_done=bool(self.sticky), prop_duration=self.schedule, solution=self.solution,
+                      reach=self.reach)
+        return kw
+
     # ------------------------------------------------------------------ the bound of "anytime_pruned"
-    def _init_bound(self, n_trees, stats):
-        """The ditree_bound descriptor: the tree's cost and key columns, one goal row per tree and the stats rows."""
+    def _init_bound(self, n_trees, tree_capacity, stats):
+        """The ditree_bound descriptor: the tree's cost and key columns, one goal row per tree and the ``stats`` rows.
+        ``tree_capacity``: the slots of each tree of a forest, 0 for a single tree (ditree_bound_keys)."""
         self._bound_goals = torch.zeros(n_trees, 2, dtype=torch.float64, device=self.ctx.device)
-        self._bound_roots = []
+        self._bound_roots, self._bound_capacity = [], int(tree_capacity)
         self.bound = Bound(self.tree.cost.data_ptr(), self.tree.key.data_ptr(), self._bound_goals.data_ptr(), CAR_GOAL_RADIUS,
                            self.reach, stats.data_ptr())
 
     def _bound_goal_rows(self):
         return np.asarray(self.env_goal, dtype=np.float64)[None, :2]
-
-    _BOUND_TREE_CAPACITY = 0                            # ditree_bound_keys: a single tree
 
     def _bound_sync(self):
         """Before a launch that reads the bound: the goal rows as they are now (a facade sets ``env_goal`` after ``reset``) and
@@ -387,23 +471,25 @@ class ExpansionEngine:
             return
         self._bound_goals.copy_(torch.as_tensor(np.ascontiguousarray(self._bound_goal_rows())))
         for r in self._bound_roots:
-            check(self.ctx._h, lib().ditree_bound_keys(self.ctx._h, C.byref(self.tree.desc), C.byref(self.bound), int(r), 1,
-                                                       self._BOUND_TREE_CAPACITY, self.ctx.stream), "bound_keys")
+            self._call("ditree_bound_keys", C.byref(self.bound), int(r), 1, self._bound_capacity)
         self._bound_roots = []
+
+    def _bound_stats(self):
+        tr = self.tree
+        return bound_stats(self.pruned, tr.stats_host, tr.key, 0, tr.n_nodes_host)
 
     @property
     def exhausted(self):
         """"anytime_pruned": no node of the tree can be open after the last accept (key[root] >= the incumbent's cost)."""
-        return self.pruned and bool(self.tree.stats_host[ST_EXHAUSTED])
+        return self._bound_stats()[0]
 
     @property
     def pruned_candidates(self):
-        return int(self.tree.stats_host[ST_PRUNED]) if self.pruned else 0
+        return self._bound_stats()[1]
 
     def closed_nodes(self):
         """Nodes whose key is at or past the incumbent's cost (0 without an incumbent); one reduction and one scalar copy."""
-        u = int(self.tree.stats_host[ST_BOUND])
-        return 0 if u == NO_BOUND else int((self.tree.key[:self.tree.n_nodes_host] >= u).sum().item())
+        return self._bound_stats()[2]()
 
     # ------------------------------------------------------------------ state
     def reset(self, start_state, goal_state):
@@ -489,15 +575,7 @@ class ExpansionEngine:
     def chain_rows(self, node):
         """The chain root .. ``node`` with what the tree holds for it in f64: ids, per-node edge row counts (states, actions)
         and per node the rows ``tree_path`` strings together -- its edge states, then its state (the root: its state alone)."""
-        n = self.tree.n_nodes_host
-        parents = self.tree.parent[:n].cpu().numpy()
-        chain = []
-        k = int(node)
-        while k >= 0:
-            chain.append(k)
-            k = int(parents[k])
-        chain = chain[::-1]
-        idx = torch.as_tensor(chain, device=self.tree.state.device, dtype=torch.long)
+        chain, idx = parent_chain(self.tree, node, self.tree.n_nodes_host)
         st, es = self.tree.state[idx].cpu().numpy(), self.tree.edge_states[idx].cpu().numpy()
         ns, na = self.tree.edge_nstates[idx].cpu().numpy(), self.tree.edge_nactions[idx].cpu().numpy()
         ns[0] = na[0] = 0
@@ -579,41 +657,63 @@ class ExpansionEngine:
         rp.lm_n, rp.lm_size, rp.s_global = self.lm_n, self.goal_scale, float(self.s_global)
         rp.early_exit = self.early_exit
         if self._budget is not None:                  # else the field keeps its NULL
-            # every rank derives the budgets of the WHOLE round (a candidate's place in its parent's visit order is global)
-            self._chunk_budget(samples, samples.shape[0])
+            # planners/RRT.py:149-152 -> ``self._budget``.  Every rank derives the budgets of the WHOLE round (a candidate's
+            # place in its parent's visit order is global); a forest's trees carry their sizes in their counter rows
+            e = self.entries
+            self._call(e.budget, *e.lead, samples.data_ptr(), samples.shape[0], *(() if e.lead else (self.tree.n_nodes_host,)),
+                       self._sched_chunks, len(self.schedule), self._budget_parent.data_ptr(), self._budget.data_ptr())
             rp.chunk_budget = self._budget[lo:hi].data_ptr() if n else None
         return keep
 
-    def _chunk_budget(self, samples, B):
-        """planners/RRT.py:149-152 for the B candidates of a round -> ``self._budget`` (the single tree's entry point)."""
-        check(self.ctx._h, lib().ditree_chunk_budget(self.ctx._h, C.byref(self.tree.desc), samples.data_ptr(), B,
-                                                      self.tree.n_nodes_host, self._sched_chunks, len(self.schedule),
-                                                      self._budget_parent.data_ptr(), self._budget.data_ptr(),
-                                                      self.ctx.stream), "chunk_budget")
+    def _params(self, samples, cond_goal, noise, inject_actions, lo, hi, step_noise=None):
+        """-> (this engine's parameter block for rows [lo, hi) of the round, what it points to)."""
+        rp = RoundParams()
+        return rp, self._round_params(rp, samples, cond_goal, noise, inject_actions, step_noise, lo, hi)
+
+    def _round_head(self, samples, cond_goal, counts_per_tree):
+        """-> B, the candidates of the round (a forest: after setting the offsets of ``counts_per_tree``)."""
+        return samples.shape[0]
+
+    def _check_round_shapes(self, B, samples, cond_goal, noise, inject_actions, next_obs_tape=None, step_fn=None):
+        """The car's shapes are the library's to check."""
 
     def expand_round(self, samples, cond_goal, noise=None, inject_actions=None, accept=True, step_noise=None):
         """samples (B,6) f64, cond_goal (B,2) f64 [device tensors, all candidates of the round];
         noise (B, n_chunks, P, 2) f32 or inject_actions (B, n_chunks, P, 2) f64 for this round; step_noise
         (B, n_chunks, K, P, 2) f32 with ``self.ddpm`` set (the sampler's DDPM branch)."""
-        B = samples.shape[0]
+        return self._round(samples, cond_goal, noise, inject_actions, step_noise, accept)
+
+    def _round(self, samples, cond_goal, noise, inject_actions, step_noise, accept, counts_per_tree=None, step_fn=None,
+               **ant):
+        """One round of every engine: head (B; a forest's offsets), shape check, this engine's maze or scene table on the
+        device, the parameter block of this rank's rows, the launch, and the tail (exchange, accept).  ``ant``: the ant
+        rounds' own tensors (``next_obs_tape``, ``cond_out``); ``step_fn``: a host-stepped ant round's simulator."""
+        B = self._round_head(samples, cond_goal, counts_per_tree)
         if B > self.batch:
             raise ValueError(f"round of {B} candidates exceeds engine batch {self.batch}")
+        if B == 0 and counts_per_tree is not None:    # no tree has a candidate: nothing to expand or accept
+            return self.cnt_host.copy() if accept else None
+        self._check_round_shapes(B, samples, cond_goal, noise, inject_actions, ant.get("next_obs_tape"), step_fn)
         lo, hi, per = self.shard(B)
-        n = hi - lo
         self.ensure_maze()
-        rp = RoundParams()
-        keep = self._round_params(rp, samples, cond_goal, noise, inject_actions, step_noise, lo, hi)
-        if n > 0 and self.pruned:
-            self._bound_sync()
-            rd = self.rb.desc(lo, n)
-            check(self.ctx._h, lib().ditree_expand_round_bounded(self.ctx._h, C.byref(self.tree.desc), C.byref(rd), C.byref(rp),
-                                                                  C.byref(self.bound), self.ctx.stream), "expand_round_bounded")
-        elif n > 0:
-            rd = self.rb.desc(lo, n)
-            check(self.ctx._h, lib().ditree_expand_round(self.ctx._h, C.byref(self.tree.desc), C.byref(rd),
-                                                          C.byref(rp), self.ctx.stream), "expand_round")
-        del keep
+        rp, keep = self._params(samples, cond_goal, noise, inject_actions, lo, hi, step_noise=step_noise, **ant)
+        if hi > lo:                                   # a rank without rows still takes part in the exchange and the accept
+            rd = self.rb.desc(lo, hi - lo)
+            if step_fn is not None:
+                self._host_stepped_round(rd, rp, lo, hi - lo, step_fn)
+            else:
+                self._launch_round(rd, rp)
+        del keep                                      # alive until the launch has been issued
+        self._B = B                                   # for ``accept()`` without an argument
         return self._finish_round(B, per, noise is not None, accept)
+
+    def _launch_round(self, rd, rp):
+        e = self.entries
+        bound = ()
+        if self.pruned:
+            self._bound_sync()
+            bound = (C.byref(self.bound),)
+        self._call(e.expand, *e.lead, *e.scenes, C.byref(rd), C.byref(rp), *bound)
 
     def _flow_only(self, rp, keep):
         """An action-tape round of an engine whose sampler is the DDPM branch: no sampler call, the schedule is irrelevant."""
@@ -659,33 +759,31 @@ class ExpansionEngine:
         mine = rb.records[self.rank * per:(self.rank + 1) * per]
         if n > 0:
             rd = rb.desc(lo, n)
-            check(self.ctx._h, lib().ditree_round_pack(self.ctx._h, C.byref(self.tree.desc), C.byref(rd), mine.data_ptr(),
-                                                        self.ctx.stream), "round_pack")
+            self._call("ditree_round_pack", C.byref(rd), mine.data_ptr())
         allgather_round_fields([rb.records], per, self.rank, self.world, self.pg)
         rd = rb.desc(0, B, shard=per)
-        check(self.ctx._h, lib().ditree_round_unpack(self.ctx._h, C.byref(self.tree.desc), C.byref(rd), rb.records.data_ptr(),
-                                                      self.ctx.stream), "round_unpack")
+        self._call("ditree_round_unpack", C.byref(rd), rb.records.data_ptr())
 
-    def accept(self, B):
+    def accept(self, B=None):
+        """The replicated accept of the last round's first ``B`` candidates (default: all of them) -> the counters (a
+        forest: every tree's row)."""
+        B = self._B if B is None else int(B)
         self.ensure_maze()                        # run_type > 0: the commit kernel evaluates check_obstacle_ahead
         if getattr(self, "_sharded", False) and (self.world > 1 or self.force_allgather):
             lo, hi, per = self.shard(B)
             rd = self.rb.desc(0, B, own=(lo, hi - lo), shard=per)
         else:
             rd = self.rb.desc(0, B)
-        if self.solution == "first":
-            check(self.ctx._h, lib().ditree_accept(self.ctx._h, C.byref(self.tree.desc), C.byref(rd), self.sticky,
-                                                    self.ctx.stream), "accept")
-        elif self.pruned:
+        e = self.entries
+        if self.pruned:
             self._bound_sync()
-            check(self.ctx._h, lib().ditree_accept_bounded(self.ctx._h, C.byref(self.tree.desc), C.byref(rd),
-                                                            C.byref(self.bound), self.ctx.stream), "accept_bounded")
-        else:
-            check(self.ctx._h, lib().ditree_accept_best(self.ctx._h, C.byref(self.tree.desc), C.byref(rd),
-                                                         self.tree.cost.data_ptr(), self.ctx.stream), "accept_best")
-        cnt = self.tree.read_counters()           # one small D2H per round: n_nodes / goal
+        self._call(e.accept, *e.lead, C.byref(rd), *e.accept_tail(self))
+        cnt = self.read_counters()                # one small D2H per round: n_nodes / goal (a forest: every tree's row)
         self._range_guard()
         return cnt
+
+    def read_counters(self):
+        return self.tree.read_counters()
 
     def _range_guard(self):
         """The tail of every accept: a round that ran the denoiser raises if the f16 range guard clamped activations."""
@@ -731,8 +829,7 @@ class ExpansionEngine:
             P = pa.shape[0]
         else:
             pa, pp, P = None, None, 0
-        check(self.ctx._h, lib().ditree_fallback_select(self.ctx._h, C.byref(self.tree.desc), n, gp, pp, P,
-                                                         out.data_ptr(), self.ctx.stream), "fallback_select")
+        self._call(self.entries.fallback, n, gp, pp, P, out.data_ptr())
         node = int(out.item())
         return None if node < 0 else node
 
@@ -822,7 +919,7 @@ class AntExpansionEngine(ExpansionEngine):
         rp.cond_out = cond_out[lo:hi].data_ptr() if (cond_out is not None and n) else None
         return rp, keep
 
-    def _check_round_shapes(self, B, samples, cond_goal, noise, inject_actions, next_obs_tape):
+    def _check_round_shapes(self, B, samples, cond_goal, noise, inject_actions, next_obs_tape=None, step_fn=None):
         if tuple(samples.shape) != (B, 29) or tuple(cond_goal.shape) != (B, 2):
             raise ValueError("samples must be (B, 29), cond_goal (B, 2)")
         shape = (B, self.n_chunks, self.P, 8)
@@ -831,41 +928,25 @@ class AntExpansionEngine(ExpansionEngine):
                 raise ValueError(f"{nm} must be {shape}, got {tuple(t.shape)}")
         if self.dynamics == "tape" and (next_obs_tape is None or tuple(next_obs_tape.shape) != (B, self.n_chunks, self.A, 29)):
             raise ValueError(f"dynamics='tape': next_obs_tape must be ({B}, {self.n_chunks}, {self.A}, 29)")
+        if self.dynamics == "host" and step_fn is None:
+            raise ValueError("dynamics='host': step_fn is required")
 
     def expand_round(self, samples, cond_goal, noise=None, inject_actions=None, accept=True, next_obs_tape=None, step_fn=None,
                      cond_out=None, step_noise=None):
         """samples (B, 29) f64, cond_goal (B, 2) f64, noise (B, n_chunks, P, 8) f32 or inject_actions (B, n_chunks, P, 8) f64
         [device tensors, all candidates of the round]; next_obs_tape (B, n_chunks, A, 29) f64 for dynamics='tape'; step_fn for
         dynamics='host'; cond_out (B, n_chunks, 97) f32: receives every sampler call's conditioning vector (tests)."""
-        B = samples.shape[0]
-        if B > self.batch:
-            raise ValueError(f"round of {B} candidates exceeds engine batch {self.batch}")
-        self._check_round_shapes(B, samples, cond_goal, noise, inject_actions, next_obs_tape)
-        if self.dynamics == "host" and step_fn is None:
-            raise ValueError("dynamics='host': step_fn is required")
-        lo, hi, per = self.shard(B)
-        n = hi - lo
-        self.ensure_maze()
-        rp, keep = self._params(samples, cond_goal, noise, inject_actions, lo, hi, next_obs_tape, cond_out, step_noise)
-        if n > 0:
-            rd = self.rb.desc(lo, n)
-            h, L, t = self.ctx._h, lib(), C.byref(self.tree.desc)
-            if self.dynamics != "host":
-                check(h, L.ditree_expand_round_ant(h, t, C.byref(rd), C.byref(rp), self.ctx.stream), "expand_round_ant")
-            else:
-                self._host_stepped_round(rd, rp, lo, n, step_fn)
-        del keep
-        return self._finish_round(B, per, noise is not None, accept)
+        return self._round(samples, cond_goal, noise, inject_actions, step_noise, accept, next_obs_tape=next_obs_tape,
+                           cond_out=cond_out, step_fn=step_fn if self.dynamics == "host" else None)
 
     def _host_stepped_round(self, rd, rp, lo, n, step_fn):
         """The caller's simulator between the two halves of every chunk (include/ditree.h ditree_ant_round_begin / _chunk_sample
         / _chunk_step): per chunk one D2H of the alive candidates' start states and actions, one H2D of their observations."""
-        h, L, t, st = self.ctx._h, lib(), C.byref(self.tree.desc), self.ctx.stream
         rb = self.rb
-        check(h, L.ditree_ant_round_begin(h, t, C.byref(rd), C.byref(rp), st), "ant_round_begin")
+        self._call("ditree_ant_round_begin", C.byref(rd), C.byref(rp))
         obs = torch.zeros(n, self.A, 29, dtype=torch.float64, device=self.ctx.device)
         for j in range(self.n_chunks):
-            check(h, L.ditree_ant_chunk_sample(h, t, C.byref(rd), C.byref(rp), j, st), "ant_chunk_sample")
+            self._call("ditree_ant_chunk_sample", C.byref(rd), C.byref(rp), j)
             alive = torch.nonzero(rb.status[lo:lo + n] == _lib.ST_OK).flatten()
             if alive.numel() == 0:
                 break
@@ -876,4 +957,4 @@ class AntExpansionEngine(ExpansionEngine):
             if o.shape != (rows.size, self.A, 29):
                 raise ValueError(f"step_fn returned {o.shape}, need {(rows.size, self.A, 29)}")
             obs[alive] = torch.as_tensor(o, device=obs.device)
-            check(h, L.ditree_ant_chunk_step(h, t, C.byref(rd), C.byref(rp), j, obs.data_ptr(), st), "ant_chunk_step")
+            self._call("ditree_ant_chunk_step", C.byref(rd), C.byref(rp), j, obs.data_ptr())

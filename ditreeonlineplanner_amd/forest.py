@@ -23,9 +23,9 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import MAX_ATLAS_CELLS, MAX_SCENES, ST_GOAL, Forest, ForestScenes, RoundParams, check, lib
-from .engine import (CNT_GOAL, CNT_NODES, CNT_PHANTOM, NO_BOUND, ST_BOUND, ST_EXHAUSTED, ST_PRUNED, STATS_ROOT,
-                     AntExpansionEngine, ExpansionEngine, ant_cell_centre, env_goal_of, tree_path)
+from ._lib import MAX_ATLAS_CELLS, MAX_SCENES, ST_GOAL, Forest, ForestScenes
+from .engine import (CNT_GOAL, CNT_NODES, CNT_PHANTOM, STATS_ROOT, AntExpansionEngine, ExpansionEngine, ant_cell_centre,
+                     bound_stats, env_goal_of, tree_path)
 from .ops import CAR_NORM, Context, _dbl
 
 
@@ -34,10 +34,9 @@ class ForestTrees:
     ``AntExpansionEngine`` for the ant): the (T, 8) counter block and the candidate offsets, ``reset`` / ``reset_tree``, the
     accept and the per-tree results.  Node numbers in its results (``goal_node``, ``fallback_node``, ``path_to``,
     ``tree_snapshot``) are LOCAL to their tree (root = 0), as a single-tree engine reports them; the device arrays
-    (``tree.parent``, ``counters``' goal node, the round's ``node_id``) hold global slot numbers.  The engine class names its
-    entry points: ``_ACCEPT`` / ``_FALLBACK`` = (symbol, what) and ``_accept_args`` (what follows the round descriptor)."""
-    _ACCEPT = ("ditree_forest_accept", "forest_accept")
-    _FALLBACK = ("ditree_forest_fallback", "forest_fallback")
+    (``tree.parent``, ``counters``' goal node, the round's ``node_id``) hold global slot numbers.  The round, the accept and the
+    entry points are the single-tree engine's (``ExpansionEngine._round``, ``engine.Entries``): a forest adds the head of a
+    round -- the candidate offsets -- and is one rank."""
 
     def _init_forest(self, ctx, n_trees, tree_capacity):
         """Before the engine's own constructor (which ends in ``reset``): -> the capacity of the one device tree."""
@@ -78,24 +77,8 @@ class ForestTrees:
         """Tree t back to its root, so a finished run's slot can take the next run (DeviceTree.reset for one tree).
         ``start_state``: the root's state (default: the forest's start)."""
         t = self._tree_index(t)
-        tr, r = self.tree, t * self.C
-        s = torch.as_tensor(self.start_state if start_state is None else np.asarray(start_state, dtype=np.float64),
-                            device=tr.state.device)
-        tr.state[r] = s
-        tr.xy[r] = s[:2]
-        tr.parent[r] = -1
-        tr.last_action[r] = 0
-        tr.has_prev[r] = 0
-        tr.num_visit[r:r + self.C].zero_()
-        tr.edge_nstates[r] = 0
-        tr.edge_nactions[r] = 0
-        tr.edge_owner[r] = -1
-        if tr.hist is not None:                       # the ant: the root's history, as DeviceTree.reset leaves it
-            tr.hist[r].zero_()
-            tr.hist[r, 2] = s
-            tr.hist_n[r] = 1
-        if tr.cost is not None:
-            tr.cost[r] = 1
+        r = t * self.C
+        self.tree.write_root(r, self.C, self.start_state if start_state is None else start_state)
         if self.pruned:                               # the root's key follows on the device before the next launch (_bound_sync)
             self.fstats[t] = self._stats_row
             self.stats_host[t] = STATS_ROOT
@@ -120,29 +103,23 @@ class ForestTrees:
             row = self._stats_row_dev = torch.as_tensor(STATS_ROOT, device=self.fcounters.device)
         return row
 
-    def _init_bound(self, n_trees, stats):            # one goal row and one stats row per tree
-        super()._init_bound(self.T, self.fstats)
-
-    def _bound_goal_rows(self):
+    def _bound_goal_rows(self):                       # one goal row per tree
         return np.tile(np.asarray(self.env_goal, dtype=np.float64)[None, :2], (self.T, 1))
 
-    @property
-    def _BOUND_TREE_CAPACITY(self):
-        return self.C
+    def _bound_stats(self, t):
+        t = self._tree_index(t)
+        return bound_stats(self.pruned, self.stats_host[t], self.tree.key, t * self.C, int(self.n_nodes_host[t]))
 
     def exhausted(self, t):
         """"anytime_pruned": no node of tree t can be open after the last accept."""
-        return self.pruned and bool(self.stats_host[self._tree_index(t), ST_EXHAUSTED])
+        return self._bound_stats(t)[0]
 
     def pruned_candidates(self, t):
-        return int(self.stats_host[self._tree_index(t), ST_PRUNED]) if self.pruned else 0
+        return self._bound_stats(t)[1]
 
     def closed_nodes(self, t):
         """Nodes of tree t whose key is at or past its incumbent's cost (0 without an incumbent)."""
-        t = self._tree_index(t)
-        u = int(self.stats_host[t, ST_BOUND])
-        base = t * self.C
-        return 0 if u == NO_BOUND else int((self.tree.key[base: base + int(self.n_nodes_host[t])] >= u).sum().item())
+        return self._bound_stats(t)[2]()
 
     def _tree_index(self, t):
         t = int(t)
@@ -164,7 +141,7 @@ class ForestTrees:
         self.off_dev.copy_(torch.from_numpy(off.astype(np.int32)))
         return off
 
-    def _begin_round(self, samples, cond_goal, counts_per_tree):
+    def _round_head(self, samples, cond_goal, counts_per_tree):
         """The head of every forest round: the offsets of ``counts_per_tree`` on the host and the device -> B = their sum."""
         if counts_per_tree is None:
             raise ValueError("counts_per_tree is required (T entries, the candidates of each tree this round)")
@@ -172,41 +149,15 @@ class ForestTrees:
         B = int(off[-1])
         if samples.shape[0] != B or cond_goal.shape[0] != B:
             raise ValueError(f"samples / cond_goal must have sum(counts_per_tree) = {B} rows")
-        if B > self.batch:
-            raise ValueError(f"round of {B} candidates exceeds engine batch {self.batch}")
         return B
 
-    def _end_round(self, B, used_denoiser, accept):
-        self._used_denoiser = bool(used_denoiser)
-        self._B = B
-        return self.accept(B) if accept else None
-
-    def _accept_args(self):
-        return (self.sticky,)
-
-    def accept(self, B=None):
-        B = self._B if B is None else int(B)
-        self.ensure_maze()
-        rd = self.rb.desc(0, B)
-        if self.solution == "first":
-            entry, what, args = *self._ACCEPT, self._accept_args()
-        elif self.pruned:
-            self._bound_sync()
-            entry, what, args = "ditree_forest_accept_bounded", "forest_accept_bounded", (C.byref(self.bound),)
-        else:                                         # car forests only (ExpansionEngine's ``solution``)
-            entry, what, args = "ditree_forest_accept_best", "forest_accept_best", (self.tree.cost.data_ptr(),)
-        check(self.ctx._h, getattr(lib(), entry)(self.ctx._h, C.byref(self.tree.desc), C.byref(self.fdesc), C.byref(rd),
-                                                 *args, self.ctx.stream), what)
-        cnt = self.read_counters().copy()             # one small D2H per round: every tree's row
-        self._range_guard()
-        return cnt
-
     def read_counters(self):
+        """-> the (T, 8) counter block, the caller's own copy (``cnt_host`` follows ``reset_tree``)."""
         buf = self._fcnt_buf.cpu().numpy()            # one small copy: the counter rows and the stats rows
         self.cnt_host = buf[:self.T * 8].reshape(self.T, 8)
         self.stats_host = buf[self.T * 8:].reshape(self.T, 4)
         self.n_nodes_host = self.cnt_host[:, CNT_NODES].astype(np.int64)
-        return self.cnt_host
+        return self.cnt_host.copy()
 
     # ------------------------------------------------------------------ results (local node numbers)
     def counters(self, t):
@@ -234,15 +185,14 @@ class ForestTrees:
     def fallback_nodes(self):
         """planners/RRT.py:227-254 (run_type 0) for every tree in one launch: local node nearest to the goal among nodes 1..,
         None for a tree that holds only its root."""
-        entry, what = self._FALLBACK
-        return self._fallback_launch(getattr(lib(), entry), what, self.goal_state[:2])
+        return self._fallback_launch(self.goal_state[:2])
 
-    def _fallback_launch(self, entry, what, goals):
-        """``entry`` (one of the two forest fallback calls) on its goal array -> each tree's local node id or None."""
+    def _fallback_launch(self, goals):
+        """The engine's forest fallback call on its goal array (one goal, or one per tree) -> each tree's local node id or
+        None."""
         out = torch.empty(self.T, dtype=torch.int32, device=self.tree.xy.device)
         ga, gp = _dbl(goals)
-        check(self.ctx._h, entry(self.ctx._h, C.byref(self.tree.desc), C.byref(self.fdesc), gp, out.data_ptr(), self.ctx.stream),
-              what)
+        self._call(self.entries.fallback, *self.entries.lead, gp, out.data_ptr())
         del ga
         ids = out.cpu().numpy()
         return [None if v < 0 else int(v) - t * self.C for t, v in enumerate(ids)]
@@ -287,35 +237,7 @@ class ForestEngine(ForestTrees, ExpansionEngine):
         step_noise (B, n_chunks, K, P, 2) f32 with ``self.ddpm`` [device tensors]: the rows of tree t are
         [off[t], off[t+1]), off = the running sum of ``counts_per_tree`` (T,), each tree's rows in its run's own order.
         Returns the (T, 8) counter block after the accept."""
-        B = self._begin_round(samples, cond_goal, counts_per_tree)
-        if B == 0:                                    # no tree has a candidate: nothing to expand or accept
-            return self.cnt_host.copy() if accept else None
-        self.ensure_maze()
-        rp = RoundParams()
-        keep = self._round_params(rp, samples, cond_goal, noise, inject_actions, step_noise, 0, B)
-        self._launch_round(self.rb.desc(0, B), rp)
-        del keep
-        return self._end_round(B, noise is not None, accept)
-
-    def _chunk_budget(self, samples, B):
-        h = self.ctx._h
-        check(h, lib().ditree_forest_chunk_budget(h, C.byref(self.tree.desc), C.byref(self.fdesc), samples.data_ptr(), B,
-                                                  self._sched_chunks, len(self.schedule), self._budget_parent.data_ptr(),
-                                                  self._budget.data_ptr(), self.ctx.stream), "forest_chunk_budget")
-
-    _SCENES = None                                    # a scene forest: its ditree_forest_scenes descriptor
-
-    def _launch_round(self, rd, rp):
-        h = self.ctx._h
-        if self.pruned:
-            self._bound_sync()
-            sd = None if self._SCENES is None else C.byref(self._SCENES)
-            check(h, lib().ditree_forest_expand_round_bounded(h, C.byref(self.tree.desc), C.byref(self.fdesc), sd, C.byref(rd),
-                                                              C.byref(rp), C.byref(self.bound), self.ctx.stream),
-                  "forest_expand_round_bounded")
-            return
-        check(h, lib().ditree_forest_expand_round(h, C.byref(self.tree.desc), C.byref(self.fdesc), C.byref(rd), C.byref(rp),
-                                                  self.ctx.stream), "forest_expand_round")
+        return self._round(samples, cond_goal, noise, inject_actions, step_noise, accept, counts_per_tree)
 
 
 class AntForestEngine(ForestTrees, AntExpansionEngine):
@@ -323,8 +245,6 @@ class AntForestEngine(ForestTrees, AntExpansionEngine):
     ``tree_capacity`` node slots, expanded together: ``AntExpansionEngine``'s round settings and dynamics ("tape" | "model")
     with ``ForestTrees``' per-tree surface.  Each tree grows exactly as in its own ``AntExpansionEngine`` fed the same rows.
     The ant env has no sticky-done latch, so no tree ever has a phantom candidate."""
-    _ACCEPT = ("ditree_forest_accept_ant", "forest_accept_ant")
-    _FALLBACK = ("ditree_forest_fallback_ant", "forest_fallback_ant")
 
     def __init__(self, ctx: Context, maze, start_state, goal_state, n_trees, tree_capacity, desired_goal=None, norm=None,
                  edge_length=48, action_horizon=2, pred_horizon=16, local_map_size=16, local_map_scale=0.8, s_global=4.0,
@@ -339,9 +259,6 @@ class AntForestEngine(ForestTrees, AntExpansionEngine):
                          early_exit=early_exit, goal_scale=goal_scale, dynamics=dynamics, model=model, ball_radius=ball_radius,
                          goal_factor=goal_factor)
 
-    def _accept_args(self):
-        return ()
-
     def expand_round(self, samples, cond_goal, noise=None, inject_actions=None, counts_per_tree=None, step_noise=None,
                      accept=True, next_obs_tape=None, cond_out=None):
         """samples (B, 29) f64, cond_goal (B, 2) f64, noise (B, n_chunks, P, 8) f32 or inject_actions (B, n_chunks, P, 8) f64,
@@ -349,20 +266,8 @@ class AntForestEngine(ForestTrees, AntExpansionEngine):
         dynamics='tape', cond_out (B, n_chunks, 97) f32 (tests) [device tensors]: the rows of tree t are [off[t], off[t+1]),
         off = the running sum of ``counts_per_tree`` (T,), each tree's rows in its run's own order.  Returns the (T, 8)
         counter block after the accept."""
-        B = self._begin_round(samples, cond_goal, counts_per_tree)
-        if B == 0:
-            return self.cnt_host.copy() if accept else None
-        self._check_round_shapes(B, samples, cond_goal, noise, inject_actions, next_obs_tape)
-        self.ensure_maze()
-        rp, keep = self._params(samples, cond_goal, noise, inject_actions, 0, B, next_obs_tape, cond_out, step_noise)
-        self._launch_round(self.rb.desc(0, B), rp)
-        del keep
-        return self._end_round(B, noise is not None, accept)
-
-    def _launch_round(self, rd, rp):
-        h = self.ctx._h
-        check(h, lib().ditree_forest_expand_round_ant(h, C.byref(self.tree.desc), C.byref(self.fdesc), C.byref(rd), C.byref(rp),
-                                                      self.ctx.stream), "forest_expand_round_ant")
+        return self._round(samples, cond_goal, noise, inject_actions, step_noise, accept, counts_per_tree,
+                           next_obs_tape=next_obs_tape, cond_out=cond_out)
 
 
 # ---------------------------------------------------------------------- scene forests
@@ -395,8 +300,7 @@ class SceneTrees:
     for the ant): the scene lists, the atlas and the scene table's upload, the scene id of every tree, ``reset`` /
     ``reset_tree(t, scene)`` and the per-tree fallback goals.  ``scenes``: a list of ``(maze, start_state, goal_state, goal)``;
     ``goal`` is what the scene table's goal column holds -- what the rollout's goal test reads: the car's ``env.goal``, the
-    ant's ``desired_goal`` -- and the engine class derives it when it is None or left out (``_scene_goal``).  The engine class
-    names its fallback entry point: ``_FALLBACK_GOALS`` = (symbol, what)."""
+    ant's ``desired_goal`` -- and the engine class derives it when it is None or left out (``_scene_goal``)."""
 
     def _init_scenes(self, ctx, scenes, n_trees):
         """Before the forest's own constructor (which ends in ``reset``)."""
@@ -464,9 +368,7 @@ class SceneTrees:
 
     def fallback_nodes(self):
         """planners/RRT.py:227-254 (run_type 0) for every tree, each against its own scene's goal_state[:2]."""
-        goals = np.stack([self.scene_goals[self.tree_scene(t)][:2] for t in range(self.T)])
-        entry, what = self._FALLBACK_GOALS
-        return self._fallback_launch(getattr(lib(), entry), what, goals)
+        return self._fallback_launch(np.stack([self.scene_goals[self.tree_scene(t)][:2] for t in range(self.T)]))
 
 
 class SceneForestEngine(SceneTrees, ForestEngine):
@@ -476,26 +378,14 @@ class SceneForestEngine(SceneTrees, ForestEngine):
     and its fallback is the node nearest to that scene's goal -- exactly as its own ``ExpansionEngine`` on that scene.  All
     mazes sit in one scene table on the device (include/ditree.h "scene forests"); no single maze is read.  The scene
     bookkeeping is ``SceneTrees``'."""
-    _FALLBACK_GOALS = ("ditree_forest_fallback_goals", "forest_fallback_goals")
     _scene_goal = staticmethod(env_goal_of)
 
     def __init__(self, ctx: Context, scenes, n_trees, tree_capacity, **kw):
         self._init_scenes(ctx, scenes, n_trees)
         super().__init__(ctx, self.scene_mazes[0], self.scene_starts[0], self.scene_goals[0], n_trees, tree_capacity, **kw)
 
-    @property
-    def _SCENES(self):
-        return self.sdesc
-
     def _bound_goal_rows(self):                       # each tree's own scene's goal
         return np.stack([self.scene_env_goals[self.tree_scene(t)] for t in range(self.T)])
-
-    def _launch_round(self, rd, rp):
-        if self.pruned:
-            return ForestEngine._launch_round(self, rd, rp)
-        h = self.ctx._h
-        check(h, lib().ditree_forest_expand_round_scenes(h, C.byref(self.tree.desc), C.byref(self.fdesc), C.byref(self.sdesc),
-                                                         C.byref(rd), C.byref(rp), self.ctx.stream), "forest_expand_round_scenes")
 
 
 class AntSceneForestEngine(SceneTrees, AntForestEngine):
@@ -507,8 +397,6 @@ class AntSceneForestEngine(SceneTrees, AntForestEngine):
     ``goal_state[:2]``: exactly as its own ``AntExpansionEngine`` on that scene.  ``goal_radius``, ``ball_radius`` and
     ``s_global`` hold for all scenes.  All mazes sit in one scene table on the device (include/ditree.h "ant scene forests");
     no single maze is read."""
-    _FALLBACK_GOALS = ("ditree_forest_fallback_goals_ant", "forest_fallback_goals_ant")
-
     def __init__(self, ctx: Context, scenes, n_trees, tree_capacity, **ant_kw):
         if "desired_goal" in ant_kw:
             raise TypeError("AntSceneForestEngine: every scene carries its own desired_goal")
@@ -519,9 +407,3 @@ class AntSceneForestEngine(SceneTrees, AntForestEngine):
 
     def _scene_goal(self, maze, goal_state):
         return ant_cell_centre(maze, goal_state, self._scene_s_global)
-
-    def _launch_round(self, rd, rp):
-        h = self.ctx._h
-        check(h, lib().ditree_forest_expand_round_ant_scenes(h, C.byref(self.tree.desc), C.byref(self.fdesc), C.byref(self.sdesc),
-                                                             C.byref(rd), C.byref(rp), self.ctx.stream),
-              "forest_expand_round_ant_scenes")

@@ -96,8 +96,10 @@ class RRT_Planner(BasePlanner):
         self.world_size = int(kwargs.get("world_size", d_world))
         self.rank = int(kwargs.get("rank", d_rank if self.world_size == d_world else 0))
         self.process_group = kwargs.get("process_group", d_pg)
+        from concurrent.futures import ThreadPoolExecutor
+        self._draw_pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="ditree-draw")
         if self.is_ant:
-            self._init_ant_engine(sampler, kwargs)
+            self._init_ant_engine(sampler, kwargs, int(lm))
             return
         self._engine = ExpansionEngine(
             self.ctx, self.maze, self.start_node.state, self.goal_state, edge_length=max(self.prop_duration_schedule),
@@ -112,8 +114,6 @@ class RRT_Planner(BasePlanner):
             reach=self.bound_reach)
         self._engine.env_goal = np.asarray(self.env.goal, dtype=np.float64)
         self._engine.ddpm = self._ddpm
-        from concurrent.futures import ThreadPoolExecutor
-        self._draw_pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="ditree-draw")
 
     def _check_solution(self, kwargs):
         """The ``solution`` modes other than "first": refused by name where they are not built, before the device is touched."""
@@ -166,7 +166,7 @@ class RRT_Planner(BasePlanner):
             raise NotImplementedError("reuse_tree=True: solution='anytime_pruned' is not built (key column, stats row, closed nodes)")
 
     # ------------------------------------------------------------------ ant (BASELINE config 3)
-    def _init_ant_engine(self, sampler, kwargs):
+    def _init_ant_engine(self, sampler, kwargs, lm):
         """env_id = 'antmaze' (cfgs/antmaze.yaml, run_scenarios.py:123-132,225-233): 29-d states, 8-d actions, action_horizon 2,
         local map 16 @ 0.8, global_map_scale 4.  Everything of the expand loop runs on the device -- sampling glue, denoiser,
         the reference's collision and goal tests on every observation, accept -- EXCEPT the env step, which is MuJoCo in the
@@ -182,7 +182,6 @@ class RRT_Planner(BasePlanner):
             raise NotImplementedError("antmaze: a single prop_duration entry")
         self.ant_dynamics = kwargs.get("ant_dynamics", "host")
         self._tape_fn = kwargs.get("next_obs_tape_fn")
-        lm = self.local_map_size if isinstance(self.local_map_size, (int, float)) else self.local_map_size[0]
         norm = getattr(sampler, "norm", None)
         if norm is None:                                        # a non-network sampler: the packaged copy of metadata/antmaze.pt
             from ..policies.fm_policy import load_metadata
@@ -192,23 +191,17 @@ class RRT_Planner(BasePlanner):
         out = getattr(self, "_reset_out", None)
         if desired is None and isinstance(out, tuple) and isinstance(out[0], dict) and "desired_goal" in out[0]:
             desired = out[0]["desired_goal"]                    # the env's goal incl. its position noise (base_planner.py:296)
-        d_rank, d_world, d_pg = default_shard()
-        self.world_size = int(kwargs.get("world_size", d_world))
-        self.rank = int(kwargs.get("rank", d_rank if self.world_size == d_world else 0))
-        self.process_group = kwargs.get("process_group", d_pg)
         if self.ant_dynamics == "host" and self.world_size > 1:
             raise NotImplementedError("antmaze with a host-side simulator: one rank (the env object is not sharded)")
         self._engine = AntExpansionEngine(
             self.ctx, self.maze, self.start_node.state, self.goal_state, desired_goal=desired, norm=norm,
             edge_length=self.prop_duration_schedule[0], action_horizon=self.action_horizon,
-            pred_horizon=getattr(sampler, "pred_horizon", 16), local_map_size=int(lm), local_map_scale=self.local_map_scale,
+            pred_horizon=getattr(sampler, "pred_horizon", 16), local_map_size=lm, local_map_scale=self.local_map_scale,
             s_global=self.s_global, batch=self.batch, capacity=self.capacity, k_steps=getattr(sampler, "num_diffusion_iters", 1),
             early_exit=kwargs.get("early_exit", True), goal_scale=getattr(sampler, "local_map_size", None),
             dynamics=self.ant_dynamics, model=kwargs.get("ant_model"), rank=self.rank, world_size=self.world_size,
             process_group=self.process_group)
         self._engine.ddpm = self._ddpm
-        from concurrent.futures import ThreadPoolExecutor
-        self._draw_pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="ditree-draw")
 
     def _ant_env_step(self, chunk, start, actions, rows):
         """planners/base_planner.py:278-279,290,298 for the alive candidates of one chunk, on the caller's env."""
@@ -538,19 +531,8 @@ class RRT_Planner(BasePlanner):
         f = getattr(self, "_forest", None)
         if f is None or self._forest_key != key:
             self._forest = f = None                      # free the previous forest's slots first
-            if self.is_ant:
-                f = AntForestEngine(self.ctx, self.maze, self.start_node.state, self.goal_state, T, tree_capacity,
-                                    desired_goal=e.env_goal, norm=e.norm, edge_length=e.H, action_horizon=e.A, pred_horizon=e.P,
-                                    local_map_size=e.lm_n, local_map_scale=e.lm_scale, s_global=e.s_global, batch=batch,
-                                    k_steps=e.k_steps, early_exit=bool(e.early_exit), goal_scale=e.goal_scale,
-                                    dynamics=e.dynamics, model=e.model, ball_radius=e.ball_radius)
-                f.goal_radius = e.goal_radius
-            else:
-                f = ForestEngine(self.ctx, self.maze, self.start_node.state, self.goal_state, T, tree_capacity, action_horizon=e.A,
-                                 pred_horizon=e.P, local_map_size=e.lm_n, local_map_scale=e.lm_scale, s_global=e.s_global,
-                                 batch=batch, k_steps=e.k_steps, emulate_sticky_done=bool(e.sticky), norm=e.norm,
-                                 early_exit=bool(e.early_exit), goal_scale=e.goal_scale, prop_duration=e.schedule,
-                                 solution=self.solution, reach=e.reach)
+            cls, kw = (AntForestEngine, {"desired_goal": e.env_goal}) if self.is_ant else (ForestEngine, {})
+            f = _forest_like(cls, e, self.maze, self.start_node.state, self.goal_state, T, tree_capacity, batch=batch, **kw)
             self._forest, self._forest_key = f, key
         f.ddpm = e.ddpm
         f.update_maze(self.maze)
@@ -584,7 +566,7 @@ class RRT_Planner(BasePlanner):
             return []
         T = len(seeds) if concurrent is None else max(1, min(int(concurrent), len(seeds)))
         if tree_capacity is None:
-            tree_capacity = self.capacity if self.max_candidates is None else min(self.capacity, int(self.max_candidates) + 1)
+            tree_capacity = _default_tree_capacity([self])
         eng = self._forest_engine(T, int(tree_capacity), T * self.batch)
         self.reset()                                        # env.reset(options) as before every sequential plan()
         if self.is_ant:
@@ -600,7 +582,52 @@ class RRT_Planner(BasePlanner):
         return results
 
 
+def _forest_like(cls, e, *args, **kw):
+    """A forest engine ``cls(ctx, *args, **kw)`` that runs the round program of the single-tree engine ``e``: its own settings,
+    and -- the ant -- its ``goal_radius`` as the value it has there (not re-derived from a factor)."""
+    f = cls(e.ctx, *args, **e.round_settings(), **kw)
+    if e.HIST:
+        f.goal_radius = e.goal_radius
+    f.ddpm = e.ddpm
+    return f
+
+
+def _default_tree_capacity(planners):
+    """Node slots per run where the caller names none: the largest max_candidates + 1, at most the planners' ``capacity``."""
+    return max(pl.capacity if pl.max_candidates is None else min(pl.capacity, int(pl.max_candidates) + 1) for pl in planners)
+
+
 # ---------------------------------------------------------------------- a scenario set at once
+def _plan_scene_runs(planners, seeds, concurrent, tree_capacity, check_planners, forest_cls, scene_goal):
+    """The body of ``plan_scenario_runs`` and ``plan_ant_scenario_runs``: ``check_planners`` is the scope check with the
+    settings list, ``forest_cls`` the scene forest, ``scene_goal(planner)`` the fourth entry of a scene after the planner's
+    ``reset()``."""
+    from ._runs import Job, run_jobs
+    planners = list(planners)
+    if not planners:
+        return []
+    if len(seeds) != len(planners):
+        raise ValueError(f"seeds: one list per planner ({len(planners)}), got {len(seeds)}")
+    check_planners(planners)
+    seeds = [[int(s) for s in ss] for ss in seeds]
+    results = [[None] * len(ss) for ss in seeds]
+    jobs = [Job(planners[i], s, (results[i], k), (i,)) for i, ss in enumerate(seeds) for k, s in enumerate(ss)]
+    if not jobs:
+        return results
+    p0 = planners[0]
+    T = len(jobs) if concurrent is None else max(1, min(int(concurrent), len(jobs)))
+    if tree_capacity is None:
+        tree_capacity = _default_tree_capacity(planners)
+    for pl in planners:
+        pl.reset()                                           # env.reset(options) as before every sequential plan()
+    scenes = [(pl.maze, pl.start_node.state, pl.goal_state, scene_goal(pl)) for pl in planners]
+    eng = _forest_like(forest_cls, p0._engine, scenes, T, int(tree_capacity), batch=T * p0.batch)
+    if hasattr(p0.sampler, "ensure_bound"):
+        p0.sampler.ensure_bound(T * p0.batch)
+    run_jobs(eng, jobs, p0.batch, p0.ctx.device)
+    return results
+
+
 def _scene_settings(pl):
     """What every planner of one scene forest must share (the forest runs one round program for all its trees)."""
     e = pl._engine
@@ -647,38 +674,8 @@ def plan_scenario_runs(planners, seeds, concurrent=None, tree_capacity=None):
     summed collision-check count is added to ``common.map_utils.cc_calls`` once.  All planners must share one ctx and one
     sampler object and agree on the round settings (ValueError names the first difference); the scope is ``plan_runs``'."""
     from ..forest import SceneForestEngine
-    from ._runs import Job, run_jobs
-    planners = list(planners)
-    if not planners:
-        return []
-    if len(seeds) != len(planners):
-        raise ValueError(f"seeds: one list per planner ({len(planners)}), got {len(seeds)}")
-    _check_scene_planners(planners)
-    seeds = [[int(s) for s in ss] for ss in seeds]
-    results = [[None] * len(ss) for ss in seeds]
-    jobs = [Job(planners[i], s, (results[i], k), (i,)) for i, ss in enumerate(seeds) for k, s in enumerate(ss)]
-    if not jobs:
-        return results
-    p0 = planners[0]
-    ctx, sampler, batch = p0.ctx, p0.sampler, p0.batch
-    T = len(jobs) if concurrent is None else max(1, min(int(concurrent), len(jobs)))
-    if tree_capacity is None:
-        caps = [pl.capacity if pl.max_candidates is None else min(pl.capacity, int(pl.max_candidates) + 1) for pl in planners]
-        tree_capacity = max(caps)
-    network = hasattr(sampler, "ensure_bound")
-    for pl in planners:
-        pl.reset()                                           # env.reset(options) as before every sequential plan()
-    scenes = [(pl.maze, pl.start_node.state, pl.goal_state, np.asarray(pl.env.goal, dtype=np.float64)) for pl in planners]
-    e = p0._engine
-    eng = SceneForestEngine(ctx, scenes, T, int(tree_capacity), action_horizon=e.A, pred_horizon=e.P, local_map_size=e.lm_n,
-                            local_map_scale=e.lm_scale, s_global=e.s_global, batch=T * batch, k_steps=e.k_steps,
-                            emulate_sticky_done=bool(e.sticky), norm=e.norm, early_exit=bool(e.early_exit),
-                            goal_scale=e.goal_scale, prop_duration=e.schedule, solution=p0.solution, reach=e.reach)
-    eng.ddpm = e.ddpm
-    if network:
-        sampler.ensure_bound(T * batch)
-    run_jobs(eng, jobs, batch, ctx.device)
-    return results
+    return _plan_scene_runs(planners, seeds, concurrent, tree_capacity, _check_scene_planners, SceneForestEngine,
+                            lambda pl: np.asarray(pl.env.goal, dtype=np.float64))
 
 
 # ---------------------------------------------------------------------- an antmaze scenario set at once
@@ -718,35 +715,5 @@ def plan_ant_scenario_runs(planners, seeds, concurrent=None, tree_capacity=None)
     ctx and one sampler object and agree on the round settings, the dynamics and its model, ``ball_radius`` and
     ``goal_radius`` (ValueError names the first difference)."""
     from ..forest import AntSceneForestEngine
-    from ._runs import Job, run_jobs
-    planners = list(planners)
-    if not planners:
-        return []
-    if len(seeds) != len(planners):
-        raise ValueError(f"seeds: one list per planner ({len(planners)}), got {len(seeds)}")
-    _check_ant_scene_planners(planners)
-    seeds = [[int(s) for s in ss] for ss in seeds]
-    results = [[None] * len(ss) for ss in seeds]
-    jobs = [Job(planners[i], s, (results[i], k), (i,)) for i, ss in enumerate(seeds) for k, s in enumerate(ss)]
-    if not jobs:
-        return results
-    p0 = planners[0]
-    ctx, sampler, batch = p0.ctx, p0.sampler, p0.batch
-    T = len(jobs) if concurrent is None else max(1, min(int(concurrent), len(jobs)))
-    if tree_capacity is None:
-        caps = [pl.capacity if pl.max_candidates is None else min(pl.capacity, int(pl.max_candidates) + 1) for pl in planners]
-        tree_capacity = max(caps)
-    for pl in planners:
-        pl.reset()                                           # env.reset(options) as before every sequential plan()
-    scenes = [(pl.maze, pl.start_node.state, pl.goal_state, pl._engine.env_goal.copy()) for pl in planners]
-    e = p0._engine
-    eng = AntSceneForestEngine(ctx, scenes, T, int(tree_capacity), norm=e.norm, edge_length=e.H, action_horizon=e.A,
-                               pred_horizon=e.P, local_map_size=e.lm_n, local_map_scale=e.lm_scale, s_global=e.s_global,
-                               batch=T * batch, k_steps=e.k_steps, early_exit=bool(e.early_exit), goal_scale=e.goal_scale,
-                               dynamics=e.dynamics, model=e.model, ball_radius=e.ball_radius)
-    eng.goal_radius = e.goal_radius
-    eng.ddpm = e.ddpm
-    if hasattr(sampler, "ensure_bound"):
-        sampler.ensure_bound(T * batch)
-    run_jobs(eng, jobs, batch, ctx.device)
-    return results
+    return _plan_scene_runs(planners, seeds, concurrent, tree_capacity, _check_ant_scene_planners, AntSceneForestEngine,
+                            lambda pl: pl._engine.env_goal.copy())
