@@ -24,33 +24,40 @@ ARRAYS = ("state", "xy", "parent", "last_action", "has_prev", "num_visit", "edge
 SENTINEL = 77
 
 
-def make_tree(parents, seed=0, short=()):
+def free_cells(maze):
+    """The free cells off the map's border, in row-major order."""
+    return [(r, c) for r in range(1, maze.shape[0] - 1) for c in range(1, maze.shape[1] - 1) if maze[r, c] == 0]
+
+
+def make_tree(parents, seed=0, short=(), cap=CAP, nch=NCH, a=A, maze=MAZE, free_list=FREE, chunks=None):
     """Host arrays of a tree with the given parents (parent < child): every state and edge row in a free cell, whole edges of
-    2 chunks (``short``: nodes with one chunk), random actions, visits and a cost column that counts path rows."""
+    ``nch`` chunks (``short``: nodes with one chunk; ``chunks``: node -> its number of chunks), random actions, visits and a
+    cost column that counts path rows.  The defaults are the module's shape: capacity 64, 2 chunks at A = 2, the 8 x 8 maze."""
     rng = np.random.default_rng(seed)
     n = len(parents)
+    es, ea = nch * (a + 1), nch * a
 
     def free():
-        r, c = FREE[rng.integers(len(FREE))]
-        return R.cell_state(MAZE, r, c, rng.uniform(-np.pi, np.pi), *rng.uniform(-0.2, 0.2, 2))
+        r, c = free_list[rng.integers(len(free_list))]
+        return R.cell_state(maze, r, c, rng.uniform(-np.pi, np.pi), *rng.uniform(-0.2, 0.2, 2))
 
-    t = dict(state=np.zeros((CAP, S)), parent=np.full(CAP, -1, dtype=np.int32), last_action=np.zeros((CAP, D)),
-             has_prev=np.zeros(CAP, dtype=np.uint8), num_visit=np.zeros(CAP, dtype=np.int32), edge_states=np.zeros((CAP, ES, S)),
-             edge_actions=np.zeros((CAP, EA, D)), edge_nstates=np.zeros(CAP, dtype=np.int32),
-             edge_nactions=np.zeros(CAP, dtype=np.int32), cost=np.zeros(CAP, dtype=np.int32),
-             edge_owner=np.full(CAP, -1, dtype=np.int32))
+    t = dict(state=np.zeros((cap, S)), parent=np.full(cap, -1, dtype=np.int32), last_action=np.zeros((cap, D)),
+             has_prev=np.zeros(cap, dtype=np.uint8), num_visit=np.zeros(cap, dtype=np.int32), edge_states=np.zeros((cap, es, S)),
+             edge_actions=np.zeros((cap, ea, D)), edge_nstates=np.zeros(cap, dtype=np.int32),
+             edge_nactions=np.zeros(cap, dtype=np.int32), cost=np.zeros(cap, dtype=np.int32),
+             edge_owner=np.full(cap, -1, dtype=np.int32))
     for m in range(n):
         t["parent"][m] = parents[m]
         t["state"][m] = free()
         t["num_visit"][m] = rng.integers(0, 5)
         t["cost"][m] = 1
         if m:
-            c = 1 if m in short else NCH
-            t["edge_nstates"][m], t["edge_nactions"][m] = c * (A + 1), c * A
-            t["edge_states"][m, :c * (A + 1)] = [free() for _ in range(c * (A + 1))]
-            t["edge_actions"][m, :c * A] = rng.uniform(-1, 1, (c * A, D))
-            t["last_action"][m], t["has_prev"][m] = t["edge_actions"][m, c * A - 1], 1
-            t["cost"][m] = t["cost"][parents[m]] + c * (A + 1) + 1
+            c = chunks[m] if chunks is not None and m in chunks else 1 if m in short else nch
+            t["edge_nstates"][m], t["edge_nactions"][m] = c * (a + 1), c * a
+            t["edge_states"][m, :c * (a + 1)] = [free() for _ in range(c * (a + 1))]
+            t["edge_actions"][m, :c * a] = rng.uniform(-1, 1, (c * a, D))
+            t["last_action"][m], t["has_prev"][m] = t["edge_actions"][m, c * a - 1], 1
+            t["cost"][m] = t["cost"][parents[m]] + c * (a + 1) + 1
     t["xy"] = t["state"][:, :2].copy()
     return t, np.array([n, -1, 1, 40, 50, 1, 1, 3], dtype=np.int32)
 
@@ -58,18 +65,18 @@ def make_tree(parents, seed=0, short=()):
 class Pair:
     """Two device trees of the shape under test and the call's scratch."""
 
-    def __init__(self, ctx, cost=True, flags=False, cap_dst=CAP):
+    def __init__(self, ctx, cost=True, flags=False, cap_dst=None, cap=CAP, nch=NCH, a=A):
         from ditreeonlineplanner_amd.engine import DeviceTree
-        self.ctx = ctx
-        self.src = DeviceTree(ctx, CAP, NCH, A, track_obstacle_ahead=flags, cost=cost)
-        self.dst = DeviceTree(ctx, cap_dst, NCH, A, track_obstacle_ahead=flags, cost=cost)
-        self.scratch = torch.zeros(3 * CAP, dtype=torch.int32, device=ctx.device)
+        self.ctx, self.cap = ctx, cap
+        self.src = DeviceTree(ctx, cap, nch, a, track_obstacle_ahead=flags, cost=cost)
+        self.dst = DeviceTree(ctx, cap if cap_dst is None else cap_dst, nch, a, track_obstacle_ahead=flags, cost=cost)
+        self.scratch = torch.zeros(3 * cap, dtype=torch.int32, device=ctx.device)
 
     def upload(self, t, counters):
         for name in ARRAYS:
             a, b = getattr(self.src, name, None), getattr(self.dst, name, None)
             if a is not None:
-                a.copy_(dev(t[name] if name in t else np.zeros(CAP)).to(a.dtype).reshape(a.shape))
+                a.copy_(dev(t[name] if name in t else np.zeros(self.cap)).to(a.dtype).reshape(a.shape))
                 b.fill_(SENTINEL)
         self.src._cnt_buf[:8].copy_(dev(counters))
         self.dst._cnt_buf[:8].fill_(SENTINEL)
@@ -91,16 +98,17 @@ class Pair:
         return {name: getattr(tree, name).cpu().numpy() for name in ARRAYS if getattr(tree, name, None) is not None}
 
 
-def run(pair, t, counters, anchor, root=None, ds=0, da=0, maze=MAZE):
-    """Upload, call, and compare dst with the restatement over its n slots; src must come back as it went in."""
+def run(pair, t, counters, anchor, root=None, ds=0, da=0, maze=MAZE, collides=None):
+    """Upload, call, and compare dst with the restatement over its n slots; src must come back as it went in.  ``collides``:
+    the restatement's collision table (tests.tree_rebase_ref.collision_table) in place of its row loop."""
     pair.ctx.upload_maze(maze)
     pair.upload(t, counters)
     tt = dict(t)
     if pair.src.cost is None:
         tt.pop("cost")
     if pair.src.obstacle_ahead is not None:
-        tt["obstacle_ahead"] = np.zeros(CAP)
-    want = R.rebase_ref(tt, counters, maze, anchor, root, ds, da)
+        tt["obstacle_ahead"] = np.zeros(pair.cap)
+    want = R.rebase_ref(tt, counters, maze, anchor, root, ds, da, collides)
     before = pair.read(pair.src)
     pair.call(anchor, root, ds, da)
     got, cnt = pair.read(pair.dst), pair.dst._cnt_buf[:8].cpu().numpy()
@@ -125,7 +133,7 @@ def run(pair, t, counters, anchor, root=None, ds=0, da=0, maze=MAZE):
     assert (got["edge_owner"][:n] == -1).all()
     for name in got:                                     # nothing is written behind the kept slots
         assert (got[name][n:] == SENTINEL).all(), name
-    ids = pair.scratch[2 * CAP: 2 * CAP + counters[0]].cpu().numpy()
+    ids = pair.scratch[2 * pair.cap: 2 * pair.cap + counters[0]].cpu().numpy()
     assert np.array_equal(ids, want["new_id"])
     return want, got
 

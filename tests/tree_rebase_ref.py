@@ -40,7 +40,19 @@ def row_collides(row, maze):
         return bool(G.is_colliding_car(np.asarray(row, dtype=np.float64), maze))
 
 
-def node_blocked(tree, m, maze, first_row):
+def collision_table(tree, n, maze):
+    """Per-row collision answers for ``rebase_ref(..., collides=)``: ``edge_states`` (n, rows) and ``state`` (n,) booleans from
+    one vectorised oracle call over all rows of the first n nodes (rows past a node's edge_nstates are answered too and never
+    looked at).  The caller checks it against ``row_collides``."""
+    def ask(rows):
+        with np.errstate(invalid="ignore"):
+            return np.asarray(G.is_colliding_car(np.asarray(rows, dtype=np.float64), maze), dtype=bool)
+    return dict(edge_states=ask(tree["edge_states"][:n]), state=ask(tree["state"][:n]))
+
+
+def node_blocked(tree, m, maze, first_row, collides=None):
+    if collides is not None:
+        return bool(collides["edge_states"][m, first_row:int(tree["edge_nstates"][m])].any() or collides["state"][m])
     rows = [tree["edge_states"][m, r] for r in range(first_row, int(tree["edge_nstates"][m]))] + [tree["state"][m]]
     for row in rows:
         if row_collides(row, maze):
@@ -48,8 +60,9 @@ def node_blocked(tree, m, maze, first_row):
     return False
 
 
-def rebase_ref(tree, counters, maze, anchor, root_state=None, drop_states=0, drop_actions=0):
-    """-> dict: ``status`` (0, or the word a refused call leaves in dst's counters[0]); and for status 0 ``n`` nodes, the node
+def rebase_ref(tree, counters, maze, anchor, root_state=None, drop_states=0, drop_actions=0, collides=None):
+    """``collides``: the rows' collision answers looked up in a ``collision_table`` instead of asked row by row (the default).
+    -> dict: ``status`` (0, or the word a refused call leaves in dst's counters[0]); and for status 0 ``n`` nodes, the node
     fields over [0, n), ``edge_states`` / ``edge_actions`` as lists of the kept rows per node, ``cost`` (where ``tree`` has
     one), ``obstacle_ahead`` (where it has one), the 8 ``counters`` and ``new_id`` of every old node (-1: dropped)."""
     n = int(counters[0])
@@ -64,7 +77,7 @@ def rebase_ref(tree, counters, maze, anchor, root_state=None, drop_states=0, dro
         first = 0
         if m == anchor:
             first = drop_states if fresh else ns_a       # as the root it keeps no edge row
-        blocked[m] = node_blocked(tree, m, maze, first)
+        blocked[m] = node_blocked(tree, m, maze, first, collides)
     kept = []
     for m in sorted(blocked):
         k, clear = m, True
