@@ -58,6 +58,11 @@ class Bound(C.Structure):
                 ("reach", C.c_double), ("stats", C.c_void_p)]
 
 
+class Near(C.Structure):
+    """include/ditree.h ditree_near: the cost column, the radius [m] and the reach [m per path row] of the near-parent search."""
+    _fields_ = [("cost", C.c_void_p), ("radius", C.c_double), ("reach", C.c_double)]
+
+
 class ForestScenes(C.Structure):
     """include/ditree.h ditree_forest_scenes: the scene id of every tree of a scene forest."""
     _fields_ = [("tree_scene", C.c_void_p), ("tree_scene_host", C.POINTER(C.c_int32))]
@@ -220,6 +225,14 @@ SIGNATURES = {
                                                   C.POINTER(RoundParams), C.POINTER(Bound), _vp]),
     "ditree_accept_bounded": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Round), C.POINTER(Bound), _vp]),
     "ditree_forest_accept_bounded": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), C.POINTER(Round), C.POINTER(Bound), _vp]),
+    "ditree_nn_argmin_near": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Near), C.POINTER(Bound), _vp, _i32, _i32, _i32, _vp, _vp, _vp,
+                                     _vp, _vp]),
+    "ditree_forest_nn_argmin_near": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), C.POINTER(Near), C.POINTER(Bound), _vp, _i32,
+                                            _i32, _vp, _vp, _vp, _vp, _vp]),
+    "ditree_expand_round_near": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Round), C.POINTER(RoundParams), C.POINTER(Bound),
+                                        C.POINTER(Near), _vp]),
+    "ditree_forest_expand_round_near": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), C.POINTER(ForestScenes), C.POINTER(Round),
+                                               C.POINTER(RoundParams), C.POINTER(Bound), C.POINTER(Near), _vp]),
     "ditree_forest_fallback_goals": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), _pd, _vp, _vp]),
     "ditree_forest_expand_round_ant": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), C.POINTER(Round), C.POINTER(AntRoundParams),
                                               _vp]),

@@ -124,14 +124,23 @@ static int ensure_car_scratch(ditree_ctx* ctx, int B, int lm, int P) { return en
 
 // The nearest-node search among the first n_nodes nodes of one tree, or (f != NULL) for every query in its own tree of a forest,
 // each up to its counter row's node count.  bd != NULL: the masked search of the "anytime_pruned" mode.  out_state != NULL: the
-// chosen node's state, last action and flag are gathered into the three outputs.
+// chosen node's state, last action and flag are gathered into the three outputs.  nr != NULL: the near-parent rule
+// (include/ditree.h "near parent") over the same candidates instead of the nearest node.
 static void launch_nn(const ditree_tree* tree, const ditree_forest* f, int n_nodes, const ditree_bound* bd, const double* queries,
                       int q_stride, int B, int32_t* out_idx, double* out_state, double* out_prev_action, uint8_t* out_has_prev,
-                      hipStream_t s) {
+                      hipStream_t s, const ditree_near* nr = nullptr) {
   const double* node_state = out_state ? tree->state : nullptr;
   const int32_t* key = bd ? bd->key : nullptr;
   const int32_t* cost = bd ? bd->cost : nullptr;
-  if (f)
+  if (nr && f)
+    launch_nn_forest_near(queries, q_stride, B, tree->xy, f->off, f->n_trees, f->counters, f->tree_capacity, out_idx, node_state,
+                          tree->last_action, tree->has_prev, out_state, out_prev_action, out_has_prev, s, tree->state_dim,
+                          tree->action_dim, key, cost, nr->cost, nr->radius, nr->reach);
+  else if (nr)
+    launch_nn_near(queries, q_stride, B, tree->xy, n_nodes, out_idx, node_state, tree->last_action, tree->has_prev, out_state,
+                   out_prev_action, out_has_prev, s, tree->state_dim, tree->action_dim, key, cost, tree->counters, nr->cost,
+                   nr->radius, nr->reach);
+  else if (f)
     launch_nn_forest(queries, q_stride, B, tree->xy, f->off, f->n_trees, f->counters, f->tree_capacity, 0, out_idx, node_state,
                      tree->last_action, tree->has_prev, out_state, out_prev_action, out_has_prev, s, tree->state_dim,
                      tree->action_dim, key, cost);
@@ -1016,10 +1025,11 @@ int32_t ditree_round_stats(ditree_ctx* ctx, int32_t* stats4) {
 
 // The car round of one tree, or (f != NULL, validated by the caller) of a forest: only the nearest-node step differs.  A scene
 // forest (tree_scene != NULL, validated by the caller) reads each row's maze and goal from the scene table instead.
-// bd != NULL (validated by the caller): the masked nearest-node search of the "anytime_pruned" mode.
+// bd != NULL (validated by the caller): the masked nearest-node search of the "anytime_pruned" mode.  nr != NULL (validated by
+// the caller): the near-parent rule in that search.
 static int expand_round_impl(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* f, const ditree_round* round,
                              const ditree_round_params* p, void* stream, const int32_t* tree_scene = nullptr,
-                             const ditree_bound* bd = nullptr) {
+                             const ditree_bound* bd = nullptr, const ditree_near* nr = nullptr) {
   if (!ctx) return DITREE_E_ARG;
   int rc = check_tree(ctx, tree);
   if (rc) return rc;
@@ -1056,7 +1066,7 @@ static int expand_round_impl(ditree_ctx* ctx, const ditree_tree* tree, const dit
   }
   const double gx = tree_scene ? 0.0 : p->goal_xy[0], gy = tree_scene ? 0.0 : p->goal_xy[1];   // scenes: each row's own goal
   launch_round_begin(round->status, round->chunks_run, round->chunk_steps, B, nC, s);
-  launch_nn(tree, f, p->n_nodes, bd, p->samples, 6, B, round->parent, c.state, c.prev_action, c.has_prev, s);
+  launch_nn(tree, f, p->n_nodes, bd, p->samples, 6, B, round->parent, c.state, c.prev_action, c.has_prev, s, nr);
   const int64_t st_stride = (int64_t)nC * (A + 1) * 6, ac_stride = (int64_t)nC * A * 2;
   // One call of the round's chunk body on a row set: local map -> conditioning -> sampler (or the action tape) -> rollout.  Plain
   // chunk loop: every row at chunk j.  Pool: the ready list, each row at the chunk its chunks_run counter names (j = -1; the
@@ -1454,6 +1464,100 @@ int32_t ditree_forest_accept_bounded(ditree_ctx* ctx, const ditree_tree* tree, c
   if (tree->obstacle_ahead || tree->hist)
     return set_err(ctx, DITREE_E_ARG, "forest_accept_bounded: a forest is one rank's run_type-0 car tree (no obstacle flags or hist)");
   return accept_impl(ctx, tree, forest, round, AcceptMode::bounded, 0, bound->cost, bound, stream);
+}
+
+// ---- near parent (include/ditree.h "near parent"): what every call of the section refuses by name before anything is launched.
+// round: the calls that take one (NULL otherwise).
+static int check_near(ditree_ctx* ctx, const ditree_near* nr, const ditree_round* round) {
+  if (!nr) return set_err(ctx, DITREE_E_ARG, "near: descriptor missing");
+  if (!nr->cost) return set_err(ctx, DITREE_E_ARG, "near: cost array missing");
+  if (!(nr->radius > 0.0) || !std::isfinite(nr->radius)) return set_err(ctx, DITREE_E_ARG, "near: radius must be > 0 and finite");
+  if (!(nr->reach > 0.0) || !std::isfinite(nr->reach)) return set_err(ctx, DITREE_E_ARG, "near: reach must be > 0 and finite");
+  if (round && round->shard != 0) return set_err(ctx, DITREE_E_ARG, "near: one rank (round->shard must be 0)");
+  return DITREE_OK;
+}
+
+// The near-parent search behind both entry points (`who` in the messages) after their tree / forest check.  bound: NULL, or the
+// mask of the "anytime_pruned" mode.
+static int nn_argmin_near_impl(ditree_ctx* ctx, const char* who, const ditree_tree* tree, const ditree_forest* f, int n_nodes,
+                               const ditree_near* near, const ditree_bound* bound, const double* queries, int q_stride, int B,
+                               int32_t* out_idx, double* out_state, double* out_prev_action, uint8_t* out_has_prev, void* stream) {
+  int rc = check_near(ctx, near, nullptr);
+  if (rc) return rc;
+  if (bound) {
+    rc = check_bound(ctx, bound, nullptr, true);
+    if (rc) return rc;
+  }
+  if (B == 0) return DITREE_OK;
+  const bool gather = out_state || out_prev_action || out_has_prev;
+  if (!queries || !out_idx || B < 0 || q_stride < 2 || (!f && (n_nodes <= 0 || n_nodes > tree->capacity)) ||
+      (gather && (!out_state || !out_prev_action || !out_has_prev)))
+    return set_err(ctx, DITREE_E_ARG, std::string(who) + ": bad argument (the three gather outputs come together)");
+  launch_nn(tree, f, n_nodes, bound, queries, q_stride, B, out_idx, out_state, out_prev_action, out_has_prev, (hipStream_t)stream,
+            near);
+  HIP_TRY(ctx, hipGetLastError());
+  return DITREE_OK;
+}
+
+int32_t ditree_nn_argmin_near(ditree_ctx* ctx, const ditree_tree* tree, const ditree_near* near, const ditree_bound* bound,
+                              const double* queries, int32_t q_stride, int32_t B, int32_t n_nodes, int32_t* out_idx,
+                              double* out_state, double* out_prev_action, uint8_t* out_has_prev, void* stream) {
+  if (!ctx) return DITREE_E_ARG;
+  const int rc = check_tree(ctx, tree);
+  if (rc) return rc;
+  return nn_argmin_near_impl(ctx, "nn_argmin_near", tree, nullptr, n_nodes, near, bound, queries, q_stride, B, out_idx, out_state,
+                             out_prev_action, out_has_prev, stream);
+}
+
+int32_t ditree_forest_nn_argmin_near(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const ditree_near* near,
+                                     const ditree_bound* bound, const double* queries, int32_t q_stride, int32_t B,
+                                     int32_t* out_idx, double* out_state, double* out_prev_action, uint8_t* out_has_prev,
+                                     void* stream) {
+  if (!ctx) return DITREE_E_ARG;
+  const int rc = check_forest(ctx, tree, forest, B, "forest_nn_argmin_near");
+  if (rc) return rc;
+  return nn_argmin_near_impl(ctx, "forest_nn_argmin_near", tree, forest, 0, near, bound, queries, q_stride, B, out_idx, out_state,
+                             out_prev_action, out_has_prev, stream);
+}
+
+int32_t ditree_expand_round_near(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round, const ditree_round_params* p,
+                                 const ditree_bound* bound, const ditree_near* near, void* stream) {
+  if (!ctx) return DITREE_E_ARG;
+  int rc = check_round(ctx, round);
+  if (rc) return rc;
+  rc = check_near(ctx, near, round);
+  if (rc) return rc;
+  if (bound) {
+    rc = check_bound(ctx, bound, round);
+    if (rc) return rc;
+  }
+  if (p && p->chunk_budget)
+    return set_err(ctx, DITREE_E_ARG, "expand_round_near: chunk budgets are not built (p->chunk_budget must be NULL)");
+  return expand_round_impl(ctx, tree, nullptr, round, p, stream, nullptr, bound, near);
+}
+
+int32_t ditree_forest_expand_round_near(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
+                                        const ditree_forest_scenes* scenes, const ditree_round* round,
+                                        const ditree_round_params* p, const ditree_bound* bound, const ditree_near* near,
+                                        void* stream) {
+  if (!ctx) return DITREE_E_ARG;
+  int rc = check_round(ctx, round);
+  if (rc) return rc;
+  rc = check_forest(ctx, tree, forest, round->B, "forest_expand_round_near");
+  if (rc) return rc;
+  if (scenes) {
+    rc = check_scenes(ctx, forest, scenes, "forest_expand_round_near");
+    if (rc) return rc;
+  }
+  rc = check_near(ctx, near, round);
+  if (rc) return rc;
+  if (bound) {
+    rc = check_bound(ctx, bound, round);
+    if (rc) return rc;
+  }
+  if (p && p->chunk_budget)
+    return set_err(ctx, DITREE_E_ARG, "expand_round_near: chunk budgets are not built (p->chunk_budget must be NULL)");
+  return expand_round_impl(ctx, tree, forest, round, p, stream, scenes ? scenes->tree_scene : nullptr, bound, near);
 }
 
 int32_t ditree_forest_fallback_goals(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const double* goal_xy,

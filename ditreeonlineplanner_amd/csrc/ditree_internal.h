@@ -122,6 +122,17 @@ void launch_nn_forest(const double* queries, int q_stride, int B, const double* 
                       const int32_t* cost = nullptr);
 void launch_forest_fallback(const double* goals, int T, const double* node_xy, const int32_t* counters, int C, int32_t* out_idx,
                             hipStream_t s);
+// the near-parent forms of the two searches (include/ditree.h ditree_near): key / bcost as launch_nn_argmin's key / cost (NULL:
+// unmasked), cost / radius / reach the near descriptor's
+void launch_nn_near(const double* queries, int q_stride, int B, const double* node_xy, int N, int32_t* out_idx,
+                    const double* node_state, const double* node_last_action, const uint8_t* node_has_prev, double* out_state,
+                    double* out_prev_action, uint8_t* out_has_prev, hipStream_t s, int S, int D, const int32_t* key,
+                    const int32_t* bcost, const int32_t* counters, const int32_t* cost, double radius, double reach);
+void launch_nn_forest_near(const double* queries, int q_stride, int B, const double* node_xy, const int32_t* off, int T,
+                           const int32_t* counters, int C, int32_t* out_idx, const double* node_state,
+                           const double* node_last_action, const uint8_t* node_has_prev, double* out_state, double* out_prev_action,
+                           uint8_t* out_has_prev, hipStream_t s, int S, int D, const int32_t* key, const int32_t* bcost,
+                           const int32_t* cost, double radius, double reach);
 // the bound of the "anytime_pruned" rounds travels to the kernels as the public descriptor (include/ditree.h ditree_bound)
 using BoundArg = ditree_bound;
 void launch_bound_keys(const double* xy, int first, int n, int C, const BoundArg& bd, hipStream_t s);

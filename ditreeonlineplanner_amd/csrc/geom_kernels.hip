@@ -250,6 +250,233 @@ void launch_forest_fallback(const double* goals, int T, const double* node_xy, c
                      counters, C, 1, out_idx, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 6, 2, nullptr, nullptr);
 }
 
+// ------------------------------------------------------------------------- near parent
+// The "choose parent" search (include/ditree.h "near parent"): among the nodes NEAR the query, the one through which the query
+// is reached in the fewest path rows.  One scan body for both kernels below: a wave serves Q queries over the n nodes behind
+// xy / key / cost (already offset to the segment), in two passes of nn_argmin_kernel's shape -- eight independent double2 loads
+// per trip, eight key loads under the mask, indices past n clamped for the load and masked for the compare.
+//   pass 1: nn_argmin_kernel's scan and its 64-lane (d2, index) reduction -> n*, the nearest node, in every lane; then
+//           tau2 = (sqrt(d2(n*)) + radius)^2, once per query.
+//   pass 2: the same nodes again, with eight cost loads.  A node takes part when d2 <= tau2, or when it is n* itself (by index:
+//           a rounding of t * t below d2(n*) cannot drop it).  Of these only a node that can still win pays the FP64 sqrt and
+//           the divide of g = cost + sqrt(d2) / reach: every candidate has d2 >= d2(n*), and sqrt, / and + round monotonically,
+//           so g >= cost + sqrt(d2(n*)) / reach, one add per node; above the lane's running minimum the node is out (equal: it
+//           may still tie, and is evaluated).  Near nodes are scattered over the lanes, so without this bound the branch is
+//           taken by a third of the wave-steps at a radius of one cell (one near lane is enough); with it, by the few nodes
+//           whose cost is within radius / reach rows of the lane's best.  The running minimum is (g, d2) with strict '<', so a
+//           lane keeps its lowest index; the reduction carries (g, d2, index): ties in g go to the smaller d2, then to the lower
+//           index.
+// res[k]: the parent's index in the segment, 0x7fffffff when no node had a distance that wins a '<' (all NaN, all closed, n = 0),
+// which the callers clamp as the existing scans do.  With equal costs g is monotone in d2 and the result is n*.
+template <bool MASK, int Q>
+__device__ __forceinline__ void near_scan(const double2* __restrict__ xy, const int32_t* __restrict__ key,
+                                          const int32_t* __restrict__ cost, int n, int U, const double (&qx)[Q],
+                                          const double (&qy)[Q], double radius, double reach, int lane, int (&res)[Q]) {
+  double best[Q];
+  int bidx[Q];
+#pragma unroll
+  for (int k = 0; k < Q; ++k) {
+    best[k] = __builtin_huge_val();
+    bidx[k] = 0x7fffffff;
+  }
+  for (int i = lane; i < n; i += 8 * WAVE) {
+    double2 p[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) p[u] = xy[min(i + u * WAVE, n - 1)];
+    int kk[8];
+    if constexpr (MASK) {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) kk[u] = key[min(i + u * WAVE, n - 1)];
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int iu = i + u * WAVE;
+      bool in = iu < n;
+      if constexpr (MASK) in = in && kk[u] < U;
+      if (in) {
+#pragma unroll
+        for (int k = 0; k < Q; ++k) {
+          double dx = qx[k] - p[u].x, dy = qy[k] - p[u].y;
+          double d = dx * dx + dy * dy;
+          if (d < best[k]) { best[k] = d; bidx[k] = iu; }
+        }
+      }
+    }
+  }
+  double tau2[Q], gfloor[Q];
+  bool any = false;
+#pragma unroll
+  for (int k = 0; k < Q; ++k) {
+    double d = best[k];
+    int ix = bidx[k];
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+      double od = __shfl_xor(d, m);
+      int oi = __shfl_xor(ix, m);
+      if (od < d || (od == d && oi < ix)) { d = od; ix = oi; }
+    }
+    bidx[k] = ix;                                       // n* in every lane
+    const double sd = sqrt(d);
+    const double t = sd + radius;
+    tau2[k] = t * t;
+    gfloor[k] = sd / reach;                             // g(n) >= cost[n] + gfloor for every candidate n
+    any = any || ix != 0x7fffffff;
+    res[k] = 0x7fffffff;
+  }
+  if (!any) return;                                     // wave-uniform: no query of the wave has a nearest node
+  double bg[Q], bd[Q];
+#pragma unroll
+  for (int k = 0; k < Q; ++k) {
+    bg[k] = __builtin_huge_val();
+    bd[k] = __builtin_huge_val();
+  }
+  for (int i = lane; i < n; i += 8 * WAVE) {
+    double2 p[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) p[u] = xy[min(i + u * WAVE, n - 1)];
+    int cc[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) cc[u] = cost[min(i + u * WAVE, n - 1)];
+    int kk[8];
+    if constexpr (MASK) {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) kk[u] = key[min(i + u * WAVE, n - 1)];
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int iu = i + u * WAVE;
+      bool in = iu < n;
+      if constexpr (MASK) in = in && kk[u] < U;
+      if (in) {
+        const double c = (double)cc[u];
+#pragma unroll
+        for (int k = 0; k < Q; ++k) {
+          double dx = qx[k] - p[u].x, dy = qy[k] - p[u].y;
+          double d = dx * dx + dy * dy;
+          if ((d <= tau2[k] || iu == bidx[k]) && !(c + gfloor[k] > bg[k])) {      // near, and not yet out by the bound on g
+            const double g = c + sqrt(d) / reach;
+            if (g < bg[k] || (g == bg[k] && d < bd[k])) { bg[k] = g; bd[k] = d; res[k] = iu; }
+          }
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < Q; ++k) {
+    double g = bg[k], d = bd[k];
+    int ix = res[k];
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+      double og = __shfl_xor(g, m), od = __shfl_xor(d, m);
+      int oi = __shfl_xor(ix, m);
+      if (og < g || (og == g && (od < d || (od == d && oi < ix)))) { g = og; d = od; ix = oi; }
+    }
+    res[k] = ix;
+  }
+}
+// nn_argmin_kernel with the near-parent rule: one wave per NN_QPW queries over nodes 0 .. N-1; MASK: only open nodes
+// (key[n] < U, U = bound_of(counters, bcost)) are candidates.  cost: the near descriptor's column.  No candidate -> node 0.
+template <bool MASK>
+__global__ void __launch_bounds__(256)
+nn_near_kernel(const double* __restrict__ queries, int q_stride, int B, const double2* __restrict__ node_xy, int N,
+               int32_t* __restrict__ out_idx, const double* __restrict__ node_state,
+               const double* __restrict__ node_last_action, const uint8_t* __restrict__ node_has_prev,
+               double* __restrict__ out_state, double* __restrict__ out_prev_action, uint8_t* __restrict__ out_has_prev, int S,
+               int D, const int32_t* __restrict__ key, const int32_t* __restrict__ bcost, const int32_t* __restrict__ counters,
+               const int32_t* __restrict__ cost, double radius, double reach) {
+  const int lane = threadIdx.x & 63;
+  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int q0 = wave * NN_QPW;
+  if (q0 >= B) return;
+  int U = 0x7fffffff;
+  if constexpr (MASK) U = bound_of(counters, bcost);
+  double qx[NN_QPW], qy[NN_QPW];
+  int res[NN_QPW];
+#pragma unroll
+  for (int k = 0; k < NN_QPW; ++k) {
+    int q = min(q0 + k, B - 1);
+    qx[k] = queries[(size_t)q * q_stride + 0];
+    qy[k] = queries[(size_t)q * q_stride + 1];
+  }
+  near_scan<MASK, NN_QPW>(node_xy, key, cost, N, U, qx, qy, radius, reach, lane, res);
+#pragma unroll
+  for (int k = 0; k < NN_QPW; ++k) {
+    int ix = res[k];
+    if (ix == 0x7fffffff) ix = 0;
+    int q = q0 + k;
+    if (q < B) {
+      if (lane == 0) out_idx[q] = ix;
+      if (node_state != nullptr) {
+        if (lane < S) out_state[(size_t)q * S + lane] = node_state[(size_t)ix * S + lane];               // S <= 64
+        if (lane >= 32 && lane < 32 + D) out_prev_action[(size_t)q * D + (lane - 32)] = node_last_action[(size_t)ix * D + (lane - 32)];
+        if (lane == 63) out_has_prev[q] = node_has_prev[ix];
+      }
+    }
+  }
+}
+void launch_nn_near(const double* queries, int q_stride, int B, const double* node_xy, int N, int32_t* out_idx,
+                    const double* node_state, const double* node_last_action, const uint8_t* node_has_prev, double* out_state,
+                    double* out_prev_action, uint8_t* out_has_prev, hipStream_t s, int S, int D, const int32_t* key,
+                    const int32_t* bcost, const int32_t* counters, const int32_t* cost, double radius, double reach) {
+  int waves = (B + NN_QPW - 1) / NN_QPW;
+  int blocks = (waves + 3) / 4;
+  hipLaunchKernelGGL(key ? nn_near_kernel<true> : nn_near_kernel<false>, dim3(blocks), dim3(256), 0, s, queries, q_stride, B,
+                     (const double2*)node_xy, N, out_idx, node_state, node_last_action, node_has_prev, out_state, out_prev_action,
+                     out_has_prev, S, D, key, bcost, counters, cost, radius, reach);
+}
+// nn_forest_kernel (NORM = false, skip = 0) with the near-parent rule: one wave per query over its tree's slots; MASK: under the
+// tree's own U.  No candidate -> the tree's root; a tree without a node -> -1, nothing gathered.
+template <bool MASK>
+__global__ void __launch_bounds__(256)
+nn_forest_near_kernel(const double* __restrict__ queries, int q_stride, int B, const double2* __restrict__ node_xy,
+                      const int32_t* __restrict__ off, int T, const int32_t* __restrict__ counters, int C,
+                      int32_t* __restrict__ out_idx, const double* __restrict__ node_state,
+                      const double* __restrict__ node_last_action, const uint8_t* __restrict__ node_has_prev,
+                      double* __restrict__ out_state, double* __restrict__ out_prev_action, uint8_t* __restrict__ out_has_prev,
+                      int S, int D, const int32_t* __restrict__ key, const int32_t* __restrict__ bcost,
+                      const int32_t* __restrict__ cost, double radius, double reach) {
+  const int lane = threadIdx.x & 63;
+  const int q = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  if (q >= B) return;
+  int t = q;
+  if (off != nullptr) {                                // the last tree whose range starts at or before q (skips empty ranges)
+    int lo = 0, hi = T - 1;
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (off[mid] <= q) lo = mid; else hi = mid - 1;
+    }
+    t = lo;
+  }
+  const int base = t * C;
+  int n = counters[t * 8];
+  n = n > C ? C : n;                                   // never past the tree's own slots
+  if (n <= 0) {
+    if (lane == 0) out_idx[q] = -1;
+    return;
+  }
+  int U = 0x7fffffff;
+  if constexpr (MASK) U = bound_of(counters + (size_t)t * 8, bcost);
+  const double qx[1] = {queries[(size_t)q * q_stride + 0]}, qy[1] = {queries[(size_t)q * q_stride + 1]};
+  int res[1];
+  near_scan<MASK, 1>(node_xy + base, MASK ? key + base : nullptr, cost + base, n, U, qx, qy, radius, reach, lane, res);
+  const int ix = base + (res[0] == 0x7fffffff ? 0 : res[0]);
+  if (lane == 0) out_idx[q] = ix;
+  if (node_state != nullptr) {
+    if (lane < S) out_state[(size_t)q * S + lane] = node_state[(size_t)ix * S + lane];
+    if (lane >= 32 && lane < 32 + D) out_prev_action[(size_t)q * D + (lane - 32)] = node_last_action[(size_t)ix * D + (lane - 32)];
+    if (lane == 63) out_has_prev[q] = node_has_prev[ix];
+  }
+}
+void launch_nn_forest_near(const double* queries, int q_stride, int B, const double* node_xy, const int32_t* off, int T,
+                           const int32_t* counters, int C, int32_t* out_idx, const double* node_state,
+                           const double* node_last_action, const uint8_t* node_has_prev, double* out_state, double* out_prev_action,
+                           uint8_t* out_has_prev, hipStream_t s, int S, int D, const int32_t* key, const int32_t* bcost,
+                           const int32_t* cost, double radius, double reach) {
+  hipLaunchKernelGGL((key ? nn_forest_near_kernel<true> : nn_forest_near_kernel<false>), dim3((B + 3) / 4), dim3(256), 0, s, queries,
+                     q_stride, B, (const double2*)node_xy, off, T, counters, C, out_idx, node_state, node_last_action,
+                     node_has_prev, out_state, out_prev_action, out_has_prev, S, D, key, bcost, cost, radius, reach);
+}
+
 // ------------------------------------------------------------------------- local map
 // One workgroup per candidate; maze staged in LDS; one thread per output cell.
 // SCENES (a scene forest, include/ditree.h "scene forests"): `maze` is the scene table (SceneTable); the work-group stages only

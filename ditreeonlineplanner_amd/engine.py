@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import Bound, Round, RoundParams, Tree, check, lib
+from ._lib import Bound, Near, Round, RoundParams, Tree, check, lib
 from .ops import CAR_NORM, Context, _dbl, _flt, _ptr, local_axis
 
 CNT_NODES, CNT_GOAL, CNT_LATCH, CNT_ITERS, CNT_CANDS, CNT_STICKY, CNT_OVERFLOW, CNT_PHANTOM = range(8)
@@ -295,6 +295,31 @@ def check_reach(reach):
     return r
 
 
+def check_near(near_radius, near_reach, solution, ant=False, prop_duration=None):
+    """The near-parent search (include/ditree.h "near parent") -> (radius [m], reach [m per path row]), or None when it is off.
+    Its scope is the cost column's -- a ``solution`` other than "first", whose own scope ``check_solution`` holds: the car, one
+    rank, run_type 0 -- and a single ``prop_duration`` entry (the chunk-budget search is the plain nearest node)."""
+    if near_radius is None:
+        if near_reach is not None:
+            raise ValueError("near_reach belongs to near_radius (near_radius is None)")
+        return None
+
+    def positive(name, v, unit):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or v <= 0:
+            raise ValueError(f"{name} must be a positive finite number of {unit}, got {v!r}")
+        return float(v)
+    radius = positive("near_radius", near_radius, "metres")
+    reach = positive("near_reach", CAR_REACH if near_reach is None else near_reach, "metres per path row")
+    if solution == "first":
+        raise ValueError("near_radius needs a solution other than 'first' (the cost column belongs to 'best_of_round', 'anytime' "
+                         "and 'anytime_pruned')")
+    if ant:
+        raise NotImplementedError("near_radius: the car only (the ant's tree has no cost column)")
+    if prop_duration is not None and len(prop_duration) > 1:
+        raise NotImplementedError("near_radius: a single prop_duration entry (the chunk-budget search is the plain nearest node)")
+    return radius, reach
+
+
 def check_solution(solution, emulate_sticky_done, world_size=1, run_type=0):
     """The scope of the ``solution`` modes other than "first" (ditree_accept_best, ditree_accept_bounded): one rank, run_type 0,
     no sticky-done emulation (its phantom candidate belongs to the first-goal rule)."""
@@ -329,7 +354,8 @@ class Entries(NamedTuple):
     accept takes behind the round descriptor (the sticky-done flag, the cost column, the bound, or nothing), and the
     descriptors its calls take behind the tree's -- ``lead`` in every call (a forest's descriptor), ``scenes`` behind those
     in the expand call (a scene forest's descriptor; NULL for a plain forest's bounded round, whose entry point serves both
-    kinds of forest)."""
+    kinds of forest).  ``near``: the rounds of an engine with ``near_radius`` go through ditree_[forest_]expand_round_near, which
+    serves every mode (the bound or NULL) and both kinds of forest; the accept and the fallback stay the mode's own."""
     expand: str
     accept: str
     accept_tail: Callable
@@ -339,7 +365,7 @@ class Entries(NamedTuple):
     scenes: tuple
 
     @classmethod
-    def of(cls, solution, ant, forest=None, scenes=None):
+    def of(cls, solution, ant, forest=None, scenes=None, near=False):
         f, a = ("forest_" if forest is not None else ""), ("_ant" if ant else "")
         lead = () if forest is None else (C.byref(forest),)
         sc = () if scenes is None else (C.byref(scenes),)
@@ -354,6 +380,9 @@ class Entries(NamedTuple):
                 accept, tail = "ditree_forest_accept_ant", lambda e: ()
             else:
                 accept, tail = f"ditree_{f}accept", lambda e: (e.sticky,)
+        if near:             # one expand entry for every mode and kind of forest: [scenes or NULL], ..., the bound or NULL, near
+            expand = f"ditree_{f}expand_round_near"
+            sc = sc or ((None,) if forest is not None else ())
         fallback = "ditree_fallback_select" if forest is None else \
             "ditree_forest_fallback" + ("_goals" if scenes is not None else "") + a
         return cls(expand, accept, tail, fallback, f"ditree_{f}chunk_budget", lead, sc)
@@ -375,7 +404,7 @@ class ExpansionEngine:
                  pred_horizon=64, local_map_size=20, local_map_scale=0.2, s_global=1.0, batch=1024,
                  capacity=65536, k_steps=1, emulate_sticky_done=True, norm=CAR_NORM, rank=0, world_size=1,
                  process_group=None, early_exit=False, run_type=0, goal_scale=None, prop_duration=None, solution="first",
-                 reach=None):
+                 reach=None, near_radius=None, near_reach=None):
         check_solution(solution, emulate_sticky_done, world_size, run_type)
         self.solution = solution
         self.pruned = solution == "anytime_pruned"
@@ -384,6 +413,7 @@ class ExpansionEngine:
         self.reach = check_reach(CAR_REACH if reach is None else reach) if self.pruned else None
         if self.pruned and prop_duration is not None and len(prop_duration) > 1:
             raise NotImplementedError("solution='anytime_pruned': a single prop_duration entry (the chunk-budget search is not masked)")
+        self.near = check_near(near_radius, near_reach, solution, self.HIST, prop_duration)
         self.ctx = ctx
         self.maze = np.asarray(maze, dtype=np.float32)
         # planners/RRT.py:26,149-152: per-visit edge lengths; the tree's edge capacity is the longest entry
@@ -427,7 +457,7 @@ class ExpansionEngine:
         ctx.upload_maze(self.maze, owner=self)
         # a forest's descriptors exist by now (ForestTrees._init_forest, SceneTrees._init_scenes run before this constructor)
         fdesc = getattr(self, "fdesc", None)
-        self.entries = Entries.of(solution, self.HIST, fdesc, getattr(self, "sdesc", None))
+        self.entries = Entries.of(solution, self.HIST, fdesc, getattr(self, "sdesc", None), near=self.near is not None)
         if self.pruned:
             if fdesc is None:
                 self._init_bound(1, 0, self.tree.stats)
@@ -449,7 +479,7 @@ class ExpansionEngine:
             kw.update(edge_length=self.H, dynamics=self.dynamics, model=self.model, ball_radius=self.ball_radius)
         else:
             kw.update(emulate_sticky_done=bool(self.sticky), prop_duration=self.schedule, solution=self.solution,
-                      reach=self.reach)
+                      reach=self.reach, near_radius=self.near and self.near[0], near_reach=self.near and self.near[1])
         return kw
 
     # ------------------------------------------------------------------ the bound of "anytime_pruned"
@@ -709,11 +739,14 @@ class ExpansionEngine:
 
     def _launch_round(self, rd, rp):
         e = self.entries
-        bound = ()
+        tail = ()
         if self.pruned:
             self._bound_sync()
-            bound = (C.byref(self.bound),)
-        self._call(e.expand, *e.lead, *e.scenes, C.byref(rd), C.byref(rp), *bound)
+            tail = (C.byref(self.bound),)
+        if self.near is not None:                     # the bound or NULL, then the near descriptor on the cost column of the
+            near = Near(self.tree.cost.data_ptr(), *self.near)      # tree as it is now (a re-base swaps the two trees)
+            tail = (*(tail or (None,)), C.byref(near))
+        self._call(e.expand, *e.lead, *e.scenes, C.byref(rd), C.byref(rp), *tail)
 
     def _flow_only(self, rp, keep):
         """An action-tape round of an engine whose sampler is the DDPM branch: no sampler call, the schedule is irrelevant."""

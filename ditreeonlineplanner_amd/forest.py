@@ -223,13 +223,14 @@ class ForestEngine(ForestTrees, ExpansionEngine):
     def __init__(self, ctx: Context, maze, start_state, goal_state, n_trees, tree_capacity, edge_length=64, action_horizon=8,
                  pred_horizon=64, local_map_size=20, local_map_scale=0.2, s_global=1.0, batch=1024, k_steps=1,
                  emulate_sticky_done=True, norm=CAR_NORM, early_exit=False, goal_scale=None, prop_duration=None, solution="first",
-                 reach=None):
+                 reach=None, near_radius=None, near_reach=None):
         capacity = self._init_forest(ctx, n_trees, tree_capacity)
         super().__init__(ctx, maze, start_state, goal_state, edge_length=edge_length, action_horizon=action_horizon,
                          pred_horizon=pred_horizon, local_map_size=local_map_size, local_map_scale=local_map_scale,
                          s_global=s_global, batch=batch, capacity=capacity, k_steps=k_steps,
                          emulate_sticky_done=emulate_sticky_done, norm=norm, early_exit=early_exit, run_type=0,
-                         goal_scale=goal_scale, prop_duration=prop_duration, solution=solution, reach=reach)
+                         goal_scale=goal_scale, prop_duration=prop_duration, solution=solution, reach=reach,
+                         near_radius=near_radius, near_reach=near_reach)
 
     def expand_round(self, samples, cond_goal, noise=None, inject_actions=None, counts_per_tree=None, step_noise=None,
                      accept=True):

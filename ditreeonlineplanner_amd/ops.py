@@ -136,6 +136,32 @@ class Context:
                                                _ptr(idx), *args, self.stream), "nn_argmin")
         return idx if outs is None else (idx, *outs)
 
+    def nn_argmin_near(self, queries, tree, cost, radius, reach, n_nodes=None, bound=None, forest=None, gather=False):
+        """The near-parent search (include/ditree.h "near parent") on a device tree (``engine.DeviceTree``): queries (B, >= 2)
+        f64, ``cost`` (capacity,) i32 -> idx (B,) i32.  ``bound`` (a ``_lib.Bound``): among the open nodes only; ``forest`` (a
+        ``_lib.Forest`` with its offsets set): every query in its own tree, ``n_nodes`` then is not read; ``gather``: also the
+        chosen nodes' state, last action and has_prev rows."""
+        dev = self.device
+        _chk(queries, torch.float64, "queries", dev)
+        _chk(cost, torch.int32, "cost", dev)
+        B = queries.shape[0]
+        idx = torch.empty(B, dtype=torch.int32, device=dev)
+        outs = None
+        if gather:
+            outs = (torch.empty(B, tree.S, dtype=torch.float64, device=dev), torch.empty(B, tree.D, dtype=torch.float64, device=dev),
+                    torch.empty(B, dtype=torch.uint8, device=dev))
+        near = _lib.Near(_ptr(cost), float(radius), float(reach))
+        bd = None if bound is None else C.byref(bound)
+        tail = (_ptr(idx), *([None] * 3 if outs is None else [_ptr(o) for o in outs]), self.stream)
+        if forest is None:
+            N = tree.n_nodes_host if n_nodes is None else int(n_nodes)
+            check(self._h, lib().ditree_nn_argmin_near(self._h, C.byref(tree.desc), C.byref(near), bd, _ptr(queries),
+                                                        queries.shape[1], B, N, *tail), "nn_argmin_near")
+        else:
+            check(self._h, lib().ditree_forest_nn_argmin_near(self._h, C.byref(tree.desc), C.byref(forest), C.byref(near), bd,
+                                                               _ptr(queries), queries.shape[1], B, *tail), "forest_nn_argmin_near")
+        return idx if outs is None else (idx, *outs)
+
     # ------------------------------------------------------------------ local map
     def local_map(self, state, n=20, scale=0.2, s_global=1.0, scaled=False, active=None, out=None):
         """state (B, >= 3) f64: columns 0, 1, 2 are x, y and the rotation the reference passes (RRT.py:158-166)."""

@@ -42,6 +42,15 @@ Constructor kwargs, ``plan() -> (path f32 (P,6)|None, actions f32 (A,2)|None)``,
                        returns that node's path at once ("first", "best_of_round") or plans on with it as the incumbent
                        ("anytime").  ``results`` gains ``reused_nodes`` / ``dropped_nodes`` (0 after a fresh reset), and
                        ``number_of_nodes`` counts the reused nodes.  The car, one rank, not "anytime_pruned".
+  ``near_radius``      (default None: off, the planner as it is without the kwarg) metres.  A sample's parent is not its nearest
+                       node but, among the nodes within ``near_radius`` of that nearest distance, the one through which the
+                       sample is reached in the fewest path rows: cost[n] + distance(n, sample) / (``near_speed * env_dt``)
+                       (include/ditree.h "near parent" -- the choose-parent step of RRT*, no rewiring).  ``near_speed``
+                       (default ``max_v``, as ``bound_speed``) is the speed a path row is assumed to cover; a setting, not a
+                       theorem.  No random stream moves: the samples are those of the same run without the kwarg.  Scope: that
+                       of the cost column -- ``solution`` "best_of_round", "anytime" or "anytime_pruned" (then among the open
+                       nodes), the car, one rank, run_type 0, a single ``prop_duration`` entry; ``plan_runs``,
+                       ``plan_scenario_runs`` and ``reuse_tree`` included.
 All of the reference's ``run_type`` values: 0 "Original"; 1 "Original+Ref" (obstacle-ahead flags per node, sampling
 biased to the part of ``init_main_path`` behind the obstacle, furthest-along-path fallback); 2 "OM+Ref" (sample
 positions drawn from the EDT prior); 3 "OM+LB+Ref" (prior log-blended with the start -> goal Gaussian, refreshed at
@@ -88,6 +97,7 @@ class RRT_Planner(BasePlanner):
         self.max_candidates = kwargs.get("max_candidates", None)
         self.capacity = int(kwargs.get("capacity", 65536))
         self.solution = kwargs.get("solution", "first")
+        self._check_near(kwargs)
         self._check_solution(kwargs)
         self._check_reuse(kwargs)
         sticky = kwargs.get("emulate_sticky_done", self.solution == "first")
@@ -111,7 +121,7 @@ class RRT_Planner(BasePlanner):
             emulate_sticky_done=sticky, early_exit=kwargs.get("early_exit", True),
             run_type=self.run_type, goal_scale=getattr(sampler, "local_map_size", None),
             rank=self.rank, world_size=self.world_size, process_group=self.process_group, solution=self.solution,
-            reach=self.bound_reach)
+            reach=self.bound_reach, near_radius=self.near_radius, near_reach=self.near_reach)
         self._engine.env_goal = np.asarray(self.env.goal, dtype=np.float64)
         self._engine.ddpm = self._ddpm
 
@@ -146,6 +156,35 @@ class RRT_Planner(BasePlanner):
             raise ValueError(f"bound_speed must be a positive finite number, got {v!r}")
         self.bound_speed = float(v)
         self.bound_reach = self.bound_speed * float(self.env_dt)      # metres a path row is assumed to cover at most
+
+    def _check_near(self, kwargs):
+        """``near_radius`` / ``near_speed``: refused by name where they are not built, before the device is touched."""
+        r = kwargs.get("near_radius")
+        self.near_radius = self.near_speed = self.near_reach = None
+        if r is None:
+            if kwargs.get("near_speed") is not None:
+                raise ValueError("near_speed belongs to near_radius (near_radius is None)")
+            return
+        v = kwargs.get("near_speed")
+        v = self.max_v if v is None else v
+        for name, x in (("near_radius", r), ("near_speed", v)):
+            if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or not np.isfinite(x) or x <= 0:
+                raise ValueError(f"{name} must be a positive finite number, got {x!r}")
+        if self.solution == "first":
+            raise ValueError("near_radius needs solution='best_of_round', 'anytime' or 'anytime_pruned' (solution='first' keeps no "
+                             "cost column)")
+        if self.is_ant:
+            raise NotImplementedError("near_radius: the car only (env_id='antmaze' keeps no cost column)")
+        world = int(kwargs.get("world_size", default_shard()[1]))
+        if world > 1:
+            raise NotImplementedError(f"near_radius: one rank (world_size {world})")
+        if self.run_type != 0:
+            raise NotImplementedError(f"near_radius: run_type 0 only (got run_type {self.run_type})")
+        if len(self.prop_duration_schedule) > 1:
+            raise NotImplementedError("near_radius: a single prop_duration entry (the chunk-budget search of a schedule is the plain "
+                                      "nearest node)")
+        self.near_radius, self.near_speed = float(r), float(v)
+        self.near_reach = self.near_speed * float(self.env_dt)        # metres a path row is assumed to cover
 
     def _check_reuse(self, kwargs):
         """``reuse_tree``: refused by name where it is not built, before the device is touched."""
@@ -635,7 +674,8 @@ def _scene_settings(pl):
             ("local map scale", float(e.lm_scale)), ("s_global", float(e.s_global)), ("k_steps", e.k_steps),
             ("norm", e.norm.tobytes()), ("emulate_sticky_done", e.sticky), ("early_exit", e.early_exit),
             ("prop_duration", tuple(e.schedule)), ("batch", pl.batch), ("solution", getattr(pl, "solution", "first")),
-            ("bound_speed", getattr(pl, "bound_speed", None))]
+            ("bound_speed", getattr(pl, "bound_speed", None)), ("near_radius", getattr(pl, "near_radius", None)),
+            ("near_speed", getattr(pl, "near_speed", None))]
 
 
 def _check_scene_planners(planners):

@@ -759,6 +759,52 @@ int32_t ditree_accept_bounded(ditree_ctx* ctx, const ditree_tree* tree, const di
 int32_t ditree_forest_accept_bounded(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
                                      const ditree_round* round, const ditree_bound* bound, void* stream);
 
+/* ------------------------------------------------------------------ near parent: the planner's `near_radius`
+ * The "choose parent" step of RRT*, without steering or rewiring: a sample's parent is not its nearest node but, among the nodes
+ * NEAR the sample, the one through which the sample is reached in the fewest path rows.  It needs the cost column of
+ * ditree_accept_best and two settings: `radius` in metres, and `reach`, the metres one path row is ASSUMED to cover (a setting,
+ * not a theorem, like ditree_bound's).
+ * For a query q the candidates C are the nodes the plain search looks at -- nodes 0 .. n_nodes-1, a forest: the query's tree's
+ * slots; with a bound only the open ones, key[n] < U, U read on the device as in the section above.
+ *   1. d2(n) = dx*dx + dy*dy, and n* = the nearest node of C as ditree_nn_argmin[_bounded] / ditree_forest_nn_argmin[_bounded]
+ *      return it: strict '<', lowest index on a tie, a NaN distance never wins.
+ *   2. t = sqrt(d2(n*)) + radius, tau2 = t * t, once per query in f64.  Near set N = {n*} + {n in C : d2(n) <= tau2}; n* is a
+ *      member by index, so a rounding of t * t below d2(n*) cannot drop it.
+ *   3. g(n) = (double)cost[n] + sqrt(d2(n)) / reach.  The parent is the member of N with the smallest g; ties go to the smaller
+ *      d2, then to the lower index.  Without the distance term an ancestor inside the radius would always beat its descendant.
+ *   4. No node of C with a distance that can win a '<': what the plain scans give -- node 0, a forest: the tree's root.
+ * If all of C has equal cost the parent is n*, bit for bit (sqrt, / and + are monotone; ties go to the smaller d2).  Nothing is
+ * read that the plain rounds do not have, and no random stream moves. */
+typedef struct {
+  const int32_t* cost;           /* [dev] (capacity,) as ditree_accept_best's (a forest: indexed by the global slot) */
+  double radius;                 /* > 0, metres */
+  double reach;                  /* > 0, metres per path row */
+} ditree_near;
+/* Every call of this section refuses by name (DITREE_E_ARG) before anything is launched: "near: descriptor missing",
+ * "near: cost array missing", "near: radius must be > 0 and finite", "near: reach must be > 0 and finite", and -- the calls that
+ * take a round -- "near: one rank (round->shard must be 0)"; with a bound, the bound's own refusals too. */
+
+/* ditree_nn_argmin_bounded's arguments and outputs with the rule above; bound == NULL: every node 0 .. n_nodes-1 is a candidate. */
+int32_t ditree_nn_argmin_near(ditree_ctx* ctx, const ditree_tree* tree, const ditree_near* near, const ditree_bound* bound,
+                              const double* queries, int32_t q_stride, int32_t B, int32_t n_nodes, int32_t* out_idx,
+                              double* out_state, double* out_prev_action, uint8_t* out_has_prev, void* stream);
+/* ditree_forest_nn_argmin_bounded's with the rule above per tree; a tree without a node gives -1 and gathers nothing. */
+int32_t ditree_forest_nn_argmin_near(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const ditree_near* near,
+                                     const ditree_bound* bound, const double* queries, int32_t q_stride, int32_t B,
+                                     int32_t* out_idx, double* out_state, double* out_prev_action, uint8_t* out_has_prev,
+                                     void* stream);
+/* ditree_expand_round (bound == NULL) or ditree_expand_round_bounded with this search; every other step is unchanged.  Also
+ * refused: "expand_round_near: chunk budgets are not built (p->chunk_budget must be NULL)" -- ditree_chunk_budget runs its own
+ * nearest-node search. */
+int32_t ditree_expand_round_near(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round, const ditree_round_params* p,
+                                 const ditree_bound* bound, const ditree_near* near, void* stream);
+/* ditree_forest_expand_round[_scenes] (bound == NULL) or ditree_forest_expand_round_bounded with this search per tree;
+ * scenes == NULL: a plain forest. */
+int32_t ditree_forest_expand_round_near(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
+                                        const ditree_forest_scenes* scenes, const ditree_round* round,
+                                        const ditree_round_params* p, const ditree_bound* bound, const ditree_near* near,
+                                        void* stream);
+
 /* ------------------------------------------------------------------ re-planning on a kept tree
  * The online driver re-plans from wherever the car stands on its plan (run_scenarios_with_lidar_DiTree.py:397-516).  Instead of
  * starting from an empty tree, ditree_tree_rebase re-roots the tree at the car, keeps the branches that grow from there and
