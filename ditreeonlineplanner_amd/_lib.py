@@ -63,6 +63,14 @@ class Near(C.Structure):
     _fields_ = [("cost", C.c_void_p), ("radius", C.c_double), ("reach", C.c_double)]
 
 
+class Sparse(C.Structure):
+    """include/ditree.h ditree_sparse: the cell size, the heading bin width and count, the table stride, each tree's map extents
+    and grid dims, the table and contender words, the active column, the (T, 4) stats rows and the accept's candidate scratch."""
+    _fields_ = [("cell", C.c_double), ("w", C.c_double), ("nh", C.c_int32), ("stride", C.c_int32), ("extent", C.c_void_p),
+                ("dims", C.c_void_p), ("dims_host", C.POINTER(C.c_int32)), ("table", C.c_void_p), ("scratch", C.c_void_p),
+                ("active", C.c_void_p), ("stats", C.c_void_p), ("cand", C.c_void_p)]
+
+
 class ForestScenes(C.Structure):
     """include/ditree.h ditree_forest_scenes: the scene id of every tree of a scene forest."""
     _fields_ = [("tree_scene", C.c_void_p), ("tree_scene_host", C.POINTER(C.c_int32))]
@@ -233,6 +241,21 @@ SIGNATURES = {
                                         C.POINTER(Near), _vp]),
     "ditree_forest_expand_round_near": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), C.POINTER(ForestScenes), C.POINTER(Round),
                                                C.POINTER(RoundParams), C.POINTER(Bound), C.POINTER(Near), _vp]),
+    "ditree_sparse_rebuild": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), C.POINTER(Sparse), _vp, _i32, _i32, _vp]),
+    "ditree_accept_sparse": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Round), _vp, C.POINTER(Bound), C.POINTER(Sparse), _vp]),
+    "ditree_forest_accept_sparse": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), C.POINTER(Round), _vp, C.POINTER(Bound),
+                                           C.POINTER(Sparse), _vp]),
+    "ditree_nn_argmin_sparse": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Sparse), C.POINTER(Near), C.POINTER(Bound), _vp, _i32, _i32,
+                                       _i32, _vp, _vp, _vp, _vp, _vp]),
+    "ditree_forest_nn_argmin_sparse": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), C.POINTER(Sparse), C.POINTER(Near),
+                                              C.POINTER(Bound), _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "ditree_chunk_budget_sparse": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), C.POINTER(Sparse), C.POINTER(Bound), _vp, _i32,
+                                          _i32, C.POINTER(_i32), _i32, _vp, _vp, _vp]),
+    "ditree_expand_round_sparse": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Round), C.POINTER(RoundParams), C.POINTER(Bound),
+                                          C.POINTER(Near), C.POINTER(Sparse), _vp]),
+    "ditree_forest_expand_round_sparse": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), C.POINTER(ForestScenes), C.POINTER(Round),
+                                                 C.POINTER(RoundParams), C.POINTER(Bound), C.POINTER(Near), C.POINTER(Sparse),
+                                                 _vp]),
     "ditree_forest_fallback_goals": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), _pd, _vp, _vp]),
     "ditree_forest_expand_round_ant": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), C.POINTER(Round), C.POINTER(AntRoundParams),
                                               _vp]),

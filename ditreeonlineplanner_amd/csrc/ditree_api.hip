@@ -125,28 +125,30 @@ static int ensure_car_scratch(ditree_ctx* ctx, int B, int lm, int P) { return en
 // The nearest-node search among the first n_nodes nodes of one tree, or (f != NULL) for every query in its own tree of a forest,
 // each up to its counter row's node count.  bd != NULL: the masked search of the "anytime_pruned" mode.  out_state != NULL: the
 // chosen node's state, last action and flag are gathered into the three outputs.  nr != NULL: the near-parent rule
-// (include/ditree.h "near parent") over the same candidates instead of the nearest node.
+// (include/ditree.h "near parent") over the same candidates instead of the nearest node.  sp != NULL: only the active nodes of the
+// sparse tree (include/ditree.h "sparse tree") are candidates.
 static void launch_nn(const ditree_tree* tree, const ditree_forest* f, int n_nodes, const ditree_bound* bd, const double* queries,
                       int q_stride, int B, int32_t* out_idx, double* out_state, double* out_prev_action, uint8_t* out_has_prev,
-                      hipStream_t s, const ditree_near* nr = nullptr) {
+                      hipStream_t s, const ditree_near* nr = nullptr, const ditree_sparse* sp = nullptr) {
   const double* node_state = out_state ? tree->state : nullptr;
   const int32_t* key = bd ? bd->key : nullptr;
   const int32_t* cost = bd ? bd->cost : nullptr;
+  const uint8_t* active = sp ? sp->active : nullptr;
   if (nr && f)
     launch_nn_forest_near(queries, q_stride, B, tree->xy, f->off, f->n_trees, f->counters, f->tree_capacity, out_idx, node_state,
                           tree->last_action, tree->has_prev, out_state, out_prev_action, out_has_prev, s, tree->state_dim,
-                          tree->action_dim, key, cost, nr->cost, nr->radius, nr->reach);
+                          tree->action_dim, key, cost, nr->cost, nr->radius, nr->reach, active);
   else if (nr)
     launch_nn_near(queries, q_stride, B, tree->xy, n_nodes, out_idx, node_state, tree->last_action, tree->has_prev, out_state,
                    out_prev_action, out_has_prev, s, tree->state_dim, tree->action_dim, key, cost, tree->counters, nr->cost,
-                   nr->radius, nr->reach);
+                   nr->radius, nr->reach, active);
   else if (f)
     launch_nn_forest(queries, q_stride, B, tree->xy, f->off, f->n_trees, f->counters, f->tree_capacity, 0, out_idx, node_state,
                      tree->last_action, tree->has_prev, out_state, out_prev_action, out_has_prev, s, tree->state_dim,
-                     tree->action_dim, key, cost);
+                     tree->action_dim, key, cost, active);
   else
     launch_nn_argmin(queries, q_stride, B, tree->xy, n_nodes, out_idx, node_state, tree->last_action, tree->has_prev, out_state,
-                     out_prev_action, out_has_prev, s, tree->state_dim, tree->action_dim, key, cost, tree->counters);
+                     out_prev_action, out_has_prev, s, tree->state_dim, tree->action_dim, key, cost, tree->counters, active);
 }
 
 // What a call that runs the sampler refuses before anything is launched: an incomplete schedule (t0 with dt, or with ddpm_coef
@@ -525,12 +527,13 @@ static int check_round(ditree_ctx* ctx, const ditree_round* r) {
 // The tail of every accept entry point, after its own checks: the accept of one tree, or (f != NULL, validated by the caller)
 // of a forest.  cost: the cost column of the best and the bounded mode (bounded: bound->cost), NULL in the first mode.
 static int accept_impl(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* f, const ditree_round* round, AcceptMode mode,
-                       int emulate_sticky, int32_t* cost, const ditree_bound* bound, void* stream) {
+                       int emulate_sticky, int32_t* cost, const ditree_bound* bound, void* stream,
+                       const ditree_sparse* sparse = nullptr) {
   if (round->B == 0) return DITREE_OK;
   const TreeSet ts = f ? TreeSet{f->off, f->counters, f->n_trees, f->tree_capacity}
                        : TreeSet{nullptr, tree->counters, 1, tree->capacity};
   launch_accept(*tree, *round, ts, mode, emulate_sticky, cost, bound, ctx->maze, ctx->rows, ctx->cols, ahead_samples(),
-                (hipStream_t)stream);
+                (hipStream_t)stream, sparse);
   HIP_TRY(ctx, hipGetLastError());
   return DITREE_OK;
 }
@@ -988,7 +991,8 @@ int32_t ditree_expand_round_ant(ditree_ctx* ctx, const ditree_tree* tree, const 
 // their tree / forest check.  f != NULL: parents are global node ids, so "earlier candidates with the same parent" never crosses trees.
 static int chunk_budget_impl(ditree_ctx* ctx, const char* who, const ditree_tree* tree, const ditree_forest* f, int n_nodes,
                              const double* samples, int B, const int32_t* schedule_chunks, int n_schedule, int32_t* parent_scratch,
-                             int32_t* budget_out, void* stream) {
+                             int32_t* budget_out, void* stream, const ditree_bound* bd = nullptr,
+                             const ditree_sparse* sp = nullptr) {
   const std::string w(who);
   if (B == 0) return DITREE_OK;
   if (!samples || !schedule_chunks || !parent_scratch || !budget_out || B < 0 || n_schedule < 1 || n_schedule > 16 ||
@@ -998,7 +1002,7 @@ static int chunk_budget_impl(ditree_ctx* ctx, const char* who, const ditree_tree
     if (schedule_chunks[i] < 1 || schedule_chunks[i] > tree->n_chunks)
       return set_err(ctx, DITREE_E_ARG, w + ": a schedule entry exceeds the tree's edge capacity (n_chunks)");
   hipStream_t s = (hipStream_t)stream;
-  launch_nn(tree, f, n_nodes, nullptr, samples, tree->state_dim, B, parent_scratch, nullptr, nullptr, nullptr, s);
+  launch_nn(tree, f, n_nodes, bd, samples, tree->state_dim, B, parent_scratch, nullptr, nullptr, nullptr, s, nullptr, sp);
   launch_chunk_budget(parent_scratch, B, tree->num_visit, schedule_chunks, n_schedule, budget_out, s);
   HIP_TRY(ctx, hipGetLastError());
   return DITREE_OK;
@@ -1026,10 +1030,11 @@ int32_t ditree_round_stats(ditree_ctx* ctx, int32_t* stats4) {
 // The car round of one tree, or (f != NULL, validated by the caller) of a forest: only the nearest-node step differs.  A scene
 // forest (tree_scene != NULL, validated by the caller) reads each row's maze and goal from the scene table instead.
 // bd != NULL (validated by the caller): the masked nearest-node search of the "anytime_pruned" mode.  nr != NULL (validated by
-// the caller): the near-parent rule in that search.
+// the caller): the near-parent rule in that search.  sp != NULL (validated by the caller): that search over the active nodes of
+// the sparse tree.
 static int expand_round_impl(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* f, const ditree_round* round,
                              const ditree_round_params* p, void* stream, const int32_t* tree_scene = nullptr,
-                             const ditree_bound* bd = nullptr, const ditree_near* nr = nullptr) {
+                             const ditree_bound* bd = nullptr, const ditree_near* nr = nullptr, const ditree_sparse* sp = nullptr) {
   if (!ctx) return DITREE_E_ARG;
   int rc = check_tree(ctx, tree);
   if (rc) return rc;
@@ -1066,7 +1071,7 @@ static int expand_round_impl(ditree_ctx* ctx, const ditree_tree* tree, const dit
   }
   const double gx = tree_scene ? 0.0 : p->goal_xy[0], gy = tree_scene ? 0.0 : p->goal_xy[1];   // scenes: each row's own goal
   launch_round_begin(round->status, round->chunks_run, round->chunk_steps, B, nC, s);
-  launch_nn(tree, f, p->n_nodes, bd, p->samples, 6, B, round->parent, c.state, c.prev_action, c.has_prev, s, nr);
+  launch_nn(tree, f, p->n_nodes, bd, p->samples, 6, B, round->parent, c.state, c.prev_action, c.has_prev, s, nr, sp);
   const int64_t st_stride = (int64_t)nC * (A + 1) * 6, ac_stride = (int64_t)nC * A * 2;
   // One call of the round's chunk body on a row set: local map -> conditioning -> sampler (or the action tape) -> rollout.  Plain
   // chunk loop: every row at chunk j.  Pool: the ready list, each row at the chunk its chunks_run counter names (j = -1; the
@@ -1558,6 +1563,201 @@ int32_t ditree_forest_expand_round_near(ditree_ctx* ctx, const ditree_tree* tree
   if (p && p->chunk_budget)
     return set_err(ctx, DITREE_E_ARG, "expand_round_near: chunk budgets are not built (p->chunk_budget must be NULL)");
   return expand_round_impl(ctx, tree, forest, round, p, stream, scenes ? scenes->tree_scene : nullptr, bound, near);
+}
+
+// ---- sparse tree (include/ditree.h "sparse tree"): what every call of the section refuses by name before anything is
+// launched.  T: the trees the descriptor's per-tree rows must cover; cost: the cost column of the calls that read one (the
+// rebuild and the accepts; `needs_cost`); accept: the accepts need the candidate scratch too.
+static int check_sparse(ditree_ctx* ctx, const ditree_sparse* sp, int T, const ditree_round* round = nullptr,
+                        bool needs_cost = false, const int32_t* cost = nullptr, bool accept = false) {
+  if (!sp) return set_err(ctx, DITREE_E_ARG, "sparse: descriptor missing");
+  if (!(sp->cell > 0.0) || !std::isfinite(sp->cell)) return set_err(ctx, DITREE_E_ARG, "sparse: cell must be > 0 and finite");
+  if (sp->nh < 1 || sp->nh > 64 || !(sp->w > 0.0) || !std::isfinite(sp->w))
+    return set_err(ctx, DITREE_E_ARG, "sparse: nh must be 1..64 and w > 0");
+  if (!sp->extent || !sp->dims || !sp->dims_host) return set_err(ctx, DITREE_E_ARG, "sparse: extent / dims missing");
+  if (!sp->table || !sp->scratch || !sp->active || !sp->stats)
+    return set_err(ctx, DITREE_E_ARG, "sparse: table, scratch, active or stats missing");
+  if (sp->stride < 1 || sp->stride > (1 << 22)) return set_err(ctx, DITREE_E_ARG, "sparse: stride must be 1..2^22");
+  for (int t = 0; t < T; ++t) {
+    const int64_t nx = sp->dims_host[2 * t], ny = sp->dims_host[2 * t + 1];
+    if (nx < 1 || ny < 1 || nx > sp->stride || ny > sp->stride || nx * ny * sp->nh > sp->stride)
+      return set_err(ctx, DITREE_E_ARG, "sparse: nx * ny * nh of tree " + std::to_string(t) + " exceeds the stride");
+  }
+  if (needs_cost && !cost) return set_err(ctx, DITREE_E_ARG, "sparse: cost array missing");
+  if (accept && !sp->cand) return set_err(ctx, DITREE_E_ARG, "sparse: cand scratch missing");
+  if (round && round->shard != 0) return set_err(ctx, DITREE_E_ARG, "sparse: one rank (round->shard must be 0)");
+  return DITREE_OK;
+}
+
+int32_t ditree_sparse_rebuild(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const ditree_sparse* sparse,
+                              const int32_t* cost, int32_t first, int32_t n, void* stream) {
+  if (!ctx) return DITREE_E_ARG;
+  int rc = forest ? check_forest(ctx, tree, forest, -1, "sparse_rebuild") : check_tree(ctx, tree);
+  if (rc) return rc;
+  const int T = forest ? forest->n_trees : 1;
+  rc = check_sparse(ctx, sparse, T, nullptr, true, cost);
+  if (rc) return rc;
+  if (tree->state_dim != 6 || tree->action_dim != 2 || tree->hist)
+    return set_err(ctx, DITREE_E_ARG, "sparse: a run_type-0 car tree (no obstacle flags or hist)");
+  if (first < 0 || n < 0 || (int64_t)first + n > T)
+    return set_err(ctx, DITREE_E_ARG, "sparse_rebuild: trees [first, first + n) must lie in the forest");
+  if (n == 0) return DITREE_OK;
+  const TreeSet ts = forest ? TreeSet{nullptr, forest->counters, T, forest->tree_capacity}
+                            : TreeSet{nullptr, tree->counters, 1, tree->capacity};
+  launch_sparse_rebuild(*tree, ts, cost, *sparse, first, n, (hipStream_t)stream);
+  HIP_TRY(ctx, hipGetLastError());
+  return DITREE_OK;
+}
+
+// The tail of both sparse accepts after their tree / forest and round check.
+static int accept_sparse_impl(ditree_ctx* ctx, const char* who, const ditree_tree* tree, const ditree_forest* f,
+                              const ditree_round* round, int32_t* cost, const ditree_bound* bound, const ditree_sparse* sparse,
+                              void* stream) {
+  int rc = check_sparse(ctx, sparse, f ? f->n_trees : 1, round, true, cost, true);
+  if (rc) return rc;
+  if (bound) {
+    rc = check_bound(ctx, bound, round);
+    if (rc) return rc;
+    if (bound->cost != cost) return set_err(ctx, DITREE_E_ARG, std::string(who) + ": cost must be bound->cost");
+  }
+  if (tree->state_dim != 6 || tree->action_dim != 2 || tree->obstacle_ahead || tree->hist)
+    return set_err(ctx, DITREE_E_ARG, "sparse: a run_type-0 car tree (no obstacle flags or hist)");
+  return accept_impl(ctx, tree, f, round, bound ? AcceptMode::bounded : AcceptMode::best, 0, cost, bound, stream, sparse);
+}
+
+int32_t ditree_accept_sparse(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round, int32_t* cost,
+                             const ditree_bound* bound, const ditree_sparse* sparse, void* stream) {
+  if (!ctx) return DITREE_E_ARG;
+  int rc = check_tree(ctx, tree);
+  if (rc) return rc;
+  rc = check_round(ctx, round);
+  if (rc) return rc;
+  return accept_sparse_impl(ctx, "accept_sparse", tree, nullptr, round, cost, bound, sparse, stream);
+}
+
+int32_t ditree_forest_accept_sparse(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
+                                    const ditree_round* round, int32_t* cost, const ditree_bound* bound,
+                                    const ditree_sparse* sparse, void* stream) {
+  if (!ctx) return DITREE_E_ARG;
+  int rc = check_round(ctx, round);
+  if (rc) return rc;
+  rc = check_forest(ctx, tree, forest, round->B, "forest_accept_sparse");
+  if (rc) return rc;
+  return accept_sparse_impl(ctx, "forest_accept_sparse", tree, forest, round, cost, bound, sparse, stream);
+}
+
+// The searches over the active nodes behind both entry points (`who` in the messages) after their tree / forest check.
+static int nn_argmin_sparse_impl(ditree_ctx* ctx, const char* who, const ditree_tree* tree, const ditree_forest* f, int n_nodes,
+                                 const ditree_sparse* sparse, const ditree_near* near, const ditree_bound* bound,
+                                 const double* queries, int q_stride, int B, int32_t* out_idx, double* out_state,
+                                 double* out_prev_action, uint8_t* out_has_prev, void* stream) {
+  int rc = check_sparse(ctx, sparse, f ? f->n_trees : 1);
+  if (rc) return rc;
+  if (near) {
+    rc = check_near(ctx, near, nullptr);
+    if (rc) return rc;
+  }
+  if (bound) {
+    rc = check_bound(ctx, bound, nullptr, true);
+    if (rc) return rc;
+  }
+  if (B == 0) return DITREE_OK;
+  const bool gather = out_state || out_prev_action || out_has_prev;
+  if (!queries || !out_idx || B < 0 || q_stride < 2 || (!f && (n_nodes <= 0 || n_nodes > tree->capacity)) ||
+      (gather && (!out_state || !out_prev_action || !out_has_prev)))
+    return set_err(ctx, DITREE_E_ARG, std::string(who) + ": bad argument (the three gather outputs come together)");
+  launch_nn(tree, f, n_nodes, bound, queries, q_stride, B, out_idx, out_state, out_prev_action, out_has_prev, (hipStream_t)stream,
+            near, sparse);
+  HIP_TRY(ctx, hipGetLastError());
+  return DITREE_OK;
+}
+
+int32_t ditree_nn_argmin_sparse(ditree_ctx* ctx, const ditree_tree* tree, const ditree_sparse* sparse, const ditree_near* near,
+                                const ditree_bound* bound, const double* queries, int32_t q_stride, int32_t B, int32_t n_nodes,
+                                int32_t* out_idx, double* out_state, double* out_prev_action, uint8_t* out_has_prev, void* stream) {
+  if (!ctx) return DITREE_E_ARG;
+  const int rc = check_tree(ctx, tree);
+  if (rc) return rc;
+  if (!sparse) return set_err(ctx, DITREE_E_ARG, "sparse: descriptor missing");
+  return nn_argmin_sparse_impl(ctx, "nn_argmin_sparse", tree, nullptr, n_nodes, sparse, near, bound, queries, q_stride, B, out_idx,
+                               out_state, out_prev_action, out_has_prev, stream);
+}
+
+int32_t ditree_forest_nn_argmin_sparse(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
+                                       const ditree_sparse* sparse, const ditree_near* near, const ditree_bound* bound,
+                                       const double* queries, int32_t q_stride, int32_t B, int32_t* out_idx, double* out_state,
+                                       double* out_prev_action, uint8_t* out_has_prev, void* stream) {
+  if (!ctx) return DITREE_E_ARG;
+  const int rc = check_forest(ctx, tree, forest, B, "forest_nn_argmin_sparse");
+  if (rc) return rc;
+  if (!sparse) return set_err(ctx, DITREE_E_ARG, "sparse: descriptor missing");
+  return nn_argmin_sparse_impl(ctx, "forest_nn_argmin_sparse", tree, forest, 0, sparse, near, bound, queries, q_stride, B, out_idx,
+                               out_state, out_prev_action, out_has_prev, stream);
+}
+
+int32_t ditree_chunk_budget_sparse(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
+                                   const ditree_sparse* sparse, const ditree_bound* bound, const double* samples, int32_t B,
+                                   int32_t n_nodes, const int32_t* schedule_chunks, int32_t n_schedule, int32_t* parent_scratch,
+                                   int32_t* budget_out, void* stream) {
+  if (!ctx) return DITREE_E_ARG;
+  int rc = forest ? check_forest(ctx, tree, forest, B, "chunk_budget_sparse") : check_tree(ctx, tree);
+  if (rc) return rc;
+  if (!sparse) return set_err(ctx, DITREE_E_ARG, "sparse: descriptor missing");
+  rc = check_sparse(ctx, sparse, forest ? forest->n_trees : 1);
+  if (rc) return rc;
+  if (bound) {
+    rc = check_bound(ctx, bound, nullptr, true);
+    if (rc) return rc;
+  }
+  return chunk_budget_impl(ctx, "chunk_budget_sparse", tree, forest, n_nodes, samples, B, schedule_chunks, n_schedule,
+                           parent_scratch, budget_out, stream, bound, sparse);
+}
+
+// What both sparse rounds check behind their tree / forest and round check.
+static int check_round_sparse(ditree_ctx* ctx, const ditree_round* round, const ditree_round_params* p, const ditree_bound* bound,
+                              const ditree_near* near, const ditree_sparse* sparse, int T) {
+  if (!sparse) return set_err(ctx, DITREE_E_ARG, "sparse: descriptor missing");
+  int rc = check_sparse(ctx, sparse, T, round);
+  if (rc) return rc;
+  if (near) {
+    rc = check_near(ctx, near, round);
+    if (rc) return rc;
+  }
+  if (bound) {
+    rc = check_bound(ctx, bound, round);
+    if (rc) return rc;
+  }
+  if (p && p->chunk_budget)
+    return set_err(ctx, DITREE_E_ARG, "expand_round_sparse: chunk budgets are not built (p->chunk_budget must be NULL)");
+  return DITREE_OK;
+}
+
+int32_t ditree_expand_round_sparse(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round, const ditree_round_params* p,
+                                   const ditree_bound* bound, const ditree_near* near, const ditree_sparse* sparse, void* stream) {
+  if (!ctx) return DITREE_E_ARG;
+  int rc = check_round(ctx, round);
+  if (rc) return rc;
+  rc = check_round_sparse(ctx, round, p, bound, near, sparse, 1);
+  if (rc) return rc;
+  return expand_round_impl(ctx, tree, nullptr, round, p, stream, nullptr, bound, near, sparse);
+}
+
+int32_t ditree_forest_expand_round_sparse(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
+                                          const ditree_forest_scenes* scenes, const ditree_round* round,
+                                          const ditree_round_params* p, const ditree_bound* bound, const ditree_near* near,
+                                          const ditree_sparse* sparse, void* stream) {
+  if (!ctx) return DITREE_E_ARG;
+  int rc = check_round(ctx, round);
+  if (rc) return rc;
+  rc = check_forest(ctx, tree, forest, round->B, "forest_expand_round_sparse");
+  if (rc) return rc;
+  if (scenes) {
+    rc = check_scenes(ctx, forest, scenes, "forest_expand_round_sparse");
+    if (rc) return rc;
+  }
+  rc = check_round_sparse(ctx, round, p, bound, near, sparse, forest->n_trees);
+  if (rc) return rc;
+  return expand_round_impl(ctx, tree, forest, round, p, stream, scenes ? scenes->tree_scene : nullptr, bound, near, sparse);
 }
 
 int32_t ditree_forest_fallback_goals(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const double* goal_xy,

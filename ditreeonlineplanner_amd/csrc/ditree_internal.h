@@ -109,17 +109,18 @@ int set_err(ditree_ctx* ctx, int code, const std::string& msg);
 // geom_kernels.hip launchers (all asynchronous on `s`)
 void launch_maze_convert(const float* src, unsigned char* dst, int n, hipStream_t s);
 // key != NULL: the masked search of the "anytime_pruned" mode (only nodes with key[n] < cost[incumbent] take part); a single
-// tree's incumbent is read from `counters`, a forest's from each tree's row of its own counters
+// tree's incumbent is read from `counters`, a forest's from each tree's row of its own counters.  active != NULL (every search
+// below): only nodes with active[n] != 0 take part (include/ditree.h "sparse tree"), beside the key's mask where there is one
 void launch_nn_argmin(const double* queries, int q_stride, int B, const double* node_xy, int N,
                       int32_t* out_idx, const double* node_state, const double* node_last_action,
                       const uint8_t* node_has_prev, double* out_state, double* out_prev_action,
                       uint8_t* out_has_prev, hipStream_t s, int S = 6, int D = 2, const int32_t* key = nullptr,
-                      const int32_t* cost = nullptr, const int32_t* counters = nullptr);
+                      const int32_t* cost = nullptr, const int32_t* counters = nullptr, const uint8_t* active = nullptr);
 void launch_nn_forest(const double* queries, int q_stride, int B, const double* node_xy, const int32_t* off, int T,
                       const int32_t* counters, int C, int skip, int32_t* out_idx, const double* node_state,
                       const double* node_last_action, const uint8_t* node_has_prev, double* out_state, double* out_prev_action,
                       uint8_t* out_has_prev, hipStream_t s, int S = 6, int D = 2, const int32_t* key = nullptr,
-                      const int32_t* cost = nullptr);
+                      const int32_t* cost = nullptr, const uint8_t* active = nullptr);
 void launch_forest_fallback(const double* goals, int T, const double* node_xy, const int32_t* counters, int C, int32_t* out_idx,
                             hipStream_t s);
 // the near-parent forms of the two searches (include/ditree.h ditree_near): key / bcost as launch_nn_argmin's key / cost (NULL:
@@ -127,12 +128,13 @@ void launch_forest_fallback(const double* goals, int T, const double* node_xy, c
 void launch_nn_near(const double* queries, int q_stride, int B, const double* node_xy, int N, int32_t* out_idx,
                     const double* node_state, const double* node_last_action, const uint8_t* node_has_prev, double* out_state,
                     double* out_prev_action, uint8_t* out_has_prev, hipStream_t s, int S, int D, const int32_t* key,
-                    const int32_t* bcost, const int32_t* counters, const int32_t* cost, double radius, double reach);
+                    const int32_t* bcost, const int32_t* counters, const int32_t* cost, double radius, double reach,
+                    const uint8_t* active = nullptr);
 void launch_nn_forest_near(const double* queries, int q_stride, int B, const double* node_xy, const int32_t* off, int T,
                            const int32_t* counters, int C, int32_t* out_idx, const double* node_state,
                            const double* node_last_action, const uint8_t* node_has_prev, double* out_state, double* out_prev_action,
                            uint8_t* out_has_prev, hipStream_t s, int S, int D, const int32_t* key, const int32_t* bcost,
-                           const int32_t* cost, double radius, double reach);
+                           const int32_t* cost, double radius, double reach, const uint8_t* active = nullptr);
 // the bound of the "anytime_pruned" rounds travels to the kernels as the public descriptor (include/ditree.h ditree_bound)
 using BoundArg = ditree_bound;
 void launch_bound_keys(const double* xy, int first, int n, int C, const BoundArg& bd, hipStream_t s);
@@ -206,9 +208,16 @@ struct TreeSet {
   int T, C;
 };
 enum class AcceptMode { first, best, bounded };   // ditree_accept, ditree_accept_best, ditree_accept_bounded
+// the sparse tree travels to the kernels as the public descriptor (include/ditree.h ditree_sparse); its table words are unsigned
+// long long there, the type the 64-bit atomicMin takes
+using SparseArg = ditree_sparse;
+static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "sparse table words");
+// sp != NULL: ditree_accept_sparse's rule on top of the best or the bounded mode
 void launch_accept(const ditree_tree& t, const ditree_round& r, const TreeSet& ts, AcceptMode mode, int emulate_sticky,
                    int32_t* cost, const BoundArg* bd, const unsigned char* maze, int rows, int cols, const AheadArg& ahead,
-                   hipStream_t s);
+                   hipStream_t s, const SparseArg* sp = nullptr);
+void launch_sparse_rebuild(const ditree_tree& t, const TreeSet& ts, const int32_t* cost, const SparseArg& sp, int first, int n,
+                           hipStream_t s);
 void launch_obstacle_ahead(const unsigned char* maze, int rows, int cols, const double* state, int stride, int B,
                            const AheadArg& ts, uint8_t* out, hipStream_t s);
 // ditree_tree_rebase: the anchor, whether a fresh root (its state by value: the car's 6 doubles) goes in front of it, and the

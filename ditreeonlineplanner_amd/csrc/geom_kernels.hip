@@ -64,21 +64,25 @@ __device__ __forceinline__ int bound_h(double x, double y, double gx, double gy,
 // -- eight more independent coalesced i32 loads per trip beside the eight double2 loads; a closed node is masked exactly as an
 // index past N is.  Scan order, strict '<' and the reduction are unchanged, so with U = INT32_MAX the result is the unmasked
 // kernel's, and a scan without an open node ends as an all-NaN scan does (node 0).  MASK = false is the kernel as it was before
-// the flag: the three trailing arguments are not read.
-template <bool MASK>
+// the flag: the trailing arguments are not read.
+// MASK is a bit set: MASK_KEY the mask above, MASK_ACTIVE (include/ditree.h "sparse tree") only nodes with active[n] != 0 take part
+// -- eight byte loads per trip --, both: nodes that are active and open.
+#define MASK_KEY 1
+#define MASK_ACTIVE 2
+template <int MASK>
 __global__ void __launch_bounds__(256)
 nn_argmin_kernel(const double* __restrict__ queries, int q_stride, int B, const double2* __restrict__ node_xy,
                  int N, int32_t* __restrict__ out_idx, const double* __restrict__ node_state,
                  const double* __restrict__ node_last_action, const uint8_t* __restrict__ node_has_prev,
                  double* __restrict__ out_state, double* __restrict__ out_prev_action,
                  uint8_t* __restrict__ out_has_prev, int S, int D, const int32_t* __restrict__ key,
-                 const int32_t* __restrict__ cost, const int32_t* __restrict__ counters) {
+                 const int32_t* __restrict__ cost, const int32_t* __restrict__ counters, const uint8_t* __restrict__ active) {
   const int lane = threadIdx.x & 63;
   const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int q0 = wave * NN_QPW;
   if (q0 >= B) return;
   int U = 0x7fffffff;
-  if constexpr (MASK) U = bound_of(counters, cost);
+  if constexpr (MASK & MASK_KEY) U = bound_of(counters, cost);
   double qx[NN_QPW], qy[NN_QPW], best[NN_QPW];
   int bidx[NN_QPW];
 #pragma unroll
@@ -97,15 +101,21 @@ nn_argmin_kernel(const double* __restrict__ queries, int q_stride, int B, const 
 #pragma unroll
     for (int u = 0; u < 8; ++u) p[u] = node_xy[min(i + u * WAVE, N - 1)];
     int kk[8];
-    if constexpr (MASK) {
+    if constexpr (MASK & MASK_KEY) {
 #pragma unroll
       for (int u = 0; u < 8; ++u) kk[u] = key[min(i + u * WAVE, N - 1)];
+    }
+    uint8_t aa[8];
+    if constexpr (MASK & MASK_ACTIVE) {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) aa[u] = active[min(i + u * WAVE, N - 1)];
     }
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
       const int iu = i + u * WAVE;
       bool in = iu < N;
-      if constexpr (MASK) in = in && kk[u] < U;
+      if constexpr (MASK & MASK_KEY) in = in && kk[u] < U;
+      if constexpr (MASK & MASK_ACTIVE) in = in && aa[u] != 0;
       if (in) {
 #pragma unroll
         for (int k = 0; k < NN_QPW; ++k) {
@@ -142,12 +152,13 @@ nn_argmin_kernel(const double* __restrict__ queries, int q_stride, int B, const 
 void launch_nn_argmin(const double* queries, int q_stride, int B, const double* node_xy, int N, int32_t* out_idx,
                       const double* node_state, const double* node_last_action, const uint8_t* node_has_prev,
                       double* out_state, double* out_prev_action, uint8_t* out_has_prev, hipStream_t s, int S, int D,
-                      const int32_t* key, const int32_t* cost, const int32_t* counters) {
+                      const int32_t* key, const int32_t* cost, const int32_t* counters, const uint8_t* active) {
   int waves = (B + NN_QPW - 1) / NN_QPW;
   int blocks = (waves + 3) / 4;
-  hipLaunchKernelGGL(key ? nn_argmin_kernel<true> : nn_argmin_kernel<false>, dim3(blocks), dim3(256), 0, s, queries, q_stride, B,
-                     (const double2*)node_xy, N, out_idx, node_state, node_last_action, node_has_prev, out_state,
-                     out_prev_action, out_has_prev, S, D, key, cost, counters);
+  const auto kernel = active ? (key ? nn_argmin_kernel<MASK_KEY | MASK_ACTIVE> : nn_argmin_kernel<MASK_ACTIVE>)
+                             : (key ? nn_argmin_kernel<MASK_KEY> : nn_argmin_kernel<0>);
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, s, queries, q_stride, B, (const double2*)node_xy, N, out_idx, node_state,
+                     node_last_action, node_has_prev, out_state, out_prev_action, out_has_prev, S, D, key, cost, counters, active);
 }
 
 // Segmented nearest node of a forest (include/ditree.h ditree_forest): query q belongs to tree t -- the t whose candidate range
@@ -162,8 +173,8 @@ void launch_nn_argmin(const double* queries, int q_stride, int B, const double* 
 // the lower index, which the square's strict '<' would not.  The expansion search (NORM = false) keeps the squared distance:
 // it is pinned bit for bit to the KDTree goldens, and its instantiation is the kernel as it was before the flag.
 // MASK: nn_argmin_kernel's, with each tree's own bound U read from its counter row; key and cost are indexed by the global slot.
-// MASK = false leaves the two instantiations as they were before the flag: the two trailing arguments are not read.
-template <bool NORM, bool MASK = false>
+// MASK = 0 leaves the two instantiations as they were before the flag: the trailing arguments are not read.
+template <bool NORM, int MASK = 0>
 __global__ void __launch_bounds__(256)
 nn_forest_kernel(const double* __restrict__ queries, int q_stride, int B, const double2* __restrict__ node_xy,
                  const int32_t* __restrict__ off, int T, const int32_t* __restrict__ counters, int C, int skip,
@@ -171,7 +182,7 @@ nn_forest_kernel(const double* __restrict__ queries, int q_stride, int B, const 
                  const double* __restrict__ node_last_action, const uint8_t* __restrict__ node_has_prev,
                  double* __restrict__ out_state, double* __restrict__ out_prev_action,
                  uint8_t* __restrict__ out_has_prev, int S, int D, const int32_t* __restrict__ key,
-                 const int32_t* __restrict__ cost) {
+                 const int32_t* __restrict__ cost, const uint8_t* __restrict__ active) {
   const int lane = threadIdx.x & 63;
   const int q = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   if (q >= B) return;
@@ -191,21 +202,27 @@ nn_forest_kernel(const double* __restrict__ queries, int q_stride, int B, const 
   double best = __builtin_huge_val();
   int bidx = 0x7fffffff;
   int U = 0x7fffffff;
-  if constexpr (MASK) U = bound_of(counters + (size_t)t * 8, cost);
+  if constexpr (MASK & MASK_KEY) U = bound_of(counters + (size_t)t * 8, cost);
   for (int i = lane; i < n; i += 8 * WAVE) {
     double2 p[8];
 #pragma unroll
     for (int u = 0; u < 8; ++u) p[u] = node_xy[base + min(i + u * WAVE, n - 1)];
     int kk[8];
-    if constexpr (MASK) {
+    if constexpr (MASK & MASK_KEY) {
 #pragma unroll
       for (int u = 0; u < 8; ++u) kk[u] = key[base + min(i + u * WAVE, n - 1)];
+    }
+    uint8_t aa[8];
+    if constexpr (MASK & MASK_ACTIVE) {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) aa[u] = active[base + min(i + u * WAVE, n - 1)];
     }
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
       const int iu = i + u * WAVE;
       bool in = iu < n;
-      if constexpr (MASK) in = in && kk[u] < U;
+      if constexpr (MASK & MASK_KEY) in = in && kk[u] < U;
+      if constexpr (MASK & MASK_ACTIVE) in = in && aa[u] != 0;
       if (in) {
         double dx = qx - p[u].x, dy = qy - p[u].y;
         double d;
@@ -237,17 +254,20 @@ nn_forest_kernel(const double* __restrict__ queries, int q_stride, int B, const 
 void launch_nn_forest(const double* queries, int q_stride, int B, const double* node_xy, const int32_t* off, int T,
                       const int32_t* counters, int C, int skip, int32_t* out_idx, const double* node_state,
                       const double* node_last_action, const uint8_t* node_has_prev, double* out_state, double* out_prev_action,
-                      uint8_t* out_has_prev, hipStream_t s, int S, int D, const int32_t* key, const int32_t* cost) {
-  hipLaunchKernelGGL((key ? nn_forest_kernel<false, true> : nn_forest_kernel<false>), dim3((B + 3) / 4), dim3(256), 0, s, queries,
-                     q_stride, B, (const double2*)node_xy, off, T, counters, C, skip, out_idx, node_state, node_last_action,
-                     node_has_prev, out_state, out_prev_action, out_has_prev, S, D, key, cost);
+                      uint8_t* out_has_prev, hipStream_t s, int S, int D, const int32_t* key, const int32_t* cost,
+                      const uint8_t* active) {
+  const auto kernel = active ? (key ? nn_forest_kernel<false, MASK_KEY | MASK_ACTIVE> : nn_forest_kernel<false, MASK_ACTIVE>)
+                             : (key ? nn_forest_kernel<false, MASK_KEY> : nn_forest_kernel<false>);
+  hipLaunchKernelGGL(kernel, dim3((B + 3) / 4), dim3(256), 0, s, queries, q_stride, B, (const double2*)node_xy, off, T, counters, C,
+                     skip, out_idx, node_state, node_last_action, node_has_prev, out_state, out_prev_action, out_has_prev, S, D,
+                     key, cost, active);
 }
 // The fallback choice of every tree (planners/RRT.py:233-237): query t is tree t's goal, the scan covers its nodes 1.. with the
 // norm as the key.
 void launch_forest_fallback(const double* goals, int T, const double* node_xy, const int32_t* counters, int C, int32_t* out_idx,
                             hipStream_t s) {
   hipLaunchKernelGGL(nn_forest_kernel<true>, dim3((T + 3) / 4), dim3(256), 0, s, goals, 2, T, (const double2*)node_xy, nullptr, T,
-                     counters, C, 1, out_idx, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 6, 2, nullptr, nullptr);
+                     counters, C, 1, out_idx, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 6, 2, nullptr, nullptr, nullptr);
 }
 
 // ------------------------------------------------------------------------- near parent
@@ -268,9 +288,10 @@ void launch_forest_fallback(const double* goals, int T, const double* node_xy, c
 //           index.
 // res[k]: the parent's index in the segment, 0x7fffffff when no node had a distance that wins a '<' (all NaN, all closed, n = 0),
 // which the callers clamp as the existing scans do.  With equal costs g is monotone in d2 and the result is n*.
-template <bool MASK, int Q>
+template <int MASK, int Q>
 __device__ __forceinline__ void near_scan(const double2* __restrict__ xy, const int32_t* __restrict__ key,
-                                          const int32_t* __restrict__ cost, int n, int U, const double (&qx)[Q],
+                                          const uint8_t* __restrict__ active, const int32_t* __restrict__ cost, int n, int U,
+                                          const double (&qx)[Q],
                                           const double (&qy)[Q], double radius, double reach, int lane, int (&res)[Q]) {
   double best[Q];
   int bidx[Q];
@@ -284,15 +305,21 @@ __device__ __forceinline__ void near_scan(const double2* __restrict__ xy, const 
 #pragma unroll
     for (int u = 0; u < 8; ++u) p[u] = xy[min(i + u * WAVE, n - 1)];
     int kk[8];
-    if constexpr (MASK) {
+    if constexpr (MASK & MASK_KEY) {
 #pragma unroll
       for (int u = 0; u < 8; ++u) kk[u] = key[min(i + u * WAVE, n - 1)];
+    }
+    uint8_t aa[8];
+    if constexpr (MASK & MASK_ACTIVE) {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) aa[u] = active[min(i + u * WAVE, n - 1)];
     }
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
       const int iu = i + u * WAVE;
       bool in = iu < n;
-      if constexpr (MASK) in = in && kk[u] < U;
+      if constexpr (MASK & MASK_KEY) in = in && kk[u] < U;
+      if constexpr (MASK & MASK_ACTIVE) in = in && aa[u] != 0;
       if (in) {
 #pragma unroll
         for (int k = 0; k < Q; ++k) {
@@ -338,15 +365,21 @@ __device__ __forceinline__ void near_scan(const double2* __restrict__ xy, const 
 #pragma unroll
     for (int u = 0; u < 8; ++u) cc[u] = cost[min(i + u * WAVE, n - 1)];
     int kk[8];
-    if constexpr (MASK) {
+    if constexpr (MASK & MASK_KEY) {
 #pragma unroll
       for (int u = 0; u < 8; ++u) kk[u] = key[min(i + u * WAVE, n - 1)];
+    }
+    uint8_t aa[8];
+    if constexpr (MASK & MASK_ACTIVE) {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) aa[u] = active[min(i + u * WAVE, n - 1)];
     }
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
       const int iu = i + u * WAVE;
       bool in = iu < n;
-      if constexpr (MASK) in = in && kk[u] < U;
+      if constexpr (MASK & MASK_KEY) in = in && kk[u] < U;
+      if constexpr (MASK & MASK_ACTIVE) in = in && aa[u] != 0;
       if (in) {
         const double c = (double)cc[u];
 #pragma unroll
@@ -375,21 +408,22 @@ __device__ __forceinline__ void near_scan(const double2* __restrict__ xy, const 
   }
 }
 // nn_argmin_kernel with the near-parent rule: one wave per NN_QPW queries over nodes 0 .. N-1; MASK: only open nodes
-// (key[n] < U, U = bound_of(counters, bcost)) are candidates.  cost: the near descriptor's column.  No candidate -> node 0.
-template <bool MASK>
+// (key[n] < U, U = bound_of(counters, bcost)) are candidates, MASK_ACTIVE: only active ones.  cost: the near descriptor's column.
+// No candidate -> node 0.
+template <int MASK>
 __global__ void __launch_bounds__(256)
 nn_near_kernel(const double* __restrict__ queries, int q_stride, int B, const double2* __restrict__ node_xy, int N,
                int32_t* __restrict__ out_idx, const double* __restrict__ node_state,
                const double* __restrict__ node_last_action, const uint8_t* __restrict__ node_has_prev,
                double* __restrict__ out_state, double* __restrict__ out_prev_action, uint8_t* __restrict__ out_has_prev, int S,
                int D, const int32_t* __restrict__ key, const int32_t* __restrict__ bcost, const int32_t* __restrict__ counters,
-               const int32_t* __restrict__ cost, double radius, double reach) {
+               const int32_t* __restrict__ cost, double radius, double reach, const uint8_t* __restrict__ active) {
   const int lane = threadIdx.x & 63;
   const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int q0 = wave * NN_QPW;
   if (q0 >= B) return;
   int U = 0x7fffffff;
-  if constexpr (MASK) U = bound_of(counters, bcost);
+  if constexpr (MASK & MASK_KEY) U = bound_of(counters, bcost);
   double qx[NN_QPW], qy[NN_QPW];
   int res[NN_QPW];
 #pragma unroll
@@ -398,7 +432,7 @@ nn_near_kernel(const double* __restrict__ queries, int q_stride, int B, const do
     qx[k] = queries[(size_t)q * q_stride + 0];
     qy[k] = queries[(size_t)q * q_stride + 1];
   }
-  near_scan<MASK, NN_QPW>(node_xy, key, cost, N, U, qx, qy, radius, reach, lane, res);
+  near_scan<MASK, NN_QPW>(node_xy, key, active, cost, N, U, qx, qy, radius, reach, lane, res);
 #pragma unroll
   for (int k = 0; k < NN_QPW; ++k) {
     int ix = res[k];
@@ -417,16 +451,19 @@ nn_near_kernel(const double* __restrict__ queries, int q_stride, int B, const do
 void launch_nn_near(const double* queries, int q_stride, int B, const double* node_xy, int N, int32_t* out_idx,
                     const double* node_state, const double* node_last_action, const uint8_t* node_has_prev, double* out_state,
                     double* out_prev_action, uint8_t* out_has_prev, hipStream_t s, int S, int D, const int32_t* key,
-                    const int32_t* bcost, const int32_t* counters, const int32_t* cost, double radius, double reach) {
+                    const int32_t* bcost, const int32_t* counters, const int32_t* cost, double radius, double reach,
+                    const uint8_t* active) {
   int waves = (B + NN_QPW - 1) / NN_QPW;
   int blocks = (waves + 3) / 4;
-  hipLaunchKernelGGL(key ? nn_near_kernel<true> : nn_near_kernel<false>, dim3(blocks), dim3(256), 0, s, queries, q_stride, B,
-                     (const double2*)node_xy, N, out_idx, node_state, node_last_action, node_has_prev, out_state, out_prev_action,
-                     out_has_prev, S, D, key, bcost, counters, cost, radius, reach);
+  const auto kernel = active ? (key ? nn_near_kernel<MASK_KEY | MASK_ACTIVE> : nn_near_kernel<MASK_ACTIVE>)
+                             : (key ? nn_near_kernel<MASK_KEY> : nn_near_kernel<0>);
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, s, queries, q_stride, B, (const double2*)node_xy, N, out_idx, node_state,
+                     node_last_action, node_has_prev, out_state, out_prev_action, out_has_prev, S, D, key, bcost, counters, cost,
+                     radius, reach, active);
 }
 // nn_forest_kernel (NORM = false, skip = 0) with the near-parent rule: one wave per query over its tree's slots; MASK: under the
-// tree's own U.  No candidate -> the tree's root; a tree without a node -> -1, nothing gathered.
-template <bool MASK>
+// tree's own U, MASK_ACTIVE: over its active nodes.  No candidate -> the tree's root; a tree without a node -> -1, nothing gathered.
+template <int MASK>
 __global__ void __launch_bounds__(256)
 nn_forest_near_kernel(const double* __restrict__ queries, int q_stride, int B, const double2* __restrict__ node_xy,
                       const int32_t* __restrict__ off, int T, const int32_t* __restrict__ counters, int C,
@@ -434,7 +471,7 @@ nn_forest_near_kernel(const double* __restrict__ queries, int q_stride, int B, c
                       const double* __restrict__ node_last_action, const uint8_t* __restrict__ node_has_prev,
                       double* __restrict__ out_state, double* __restrict__ out_prev_action, uint8_t* __restrict__ out_has_prev,
                       int S, int D, const int32_t* __restrict__ key, const int32_t* __restrict__ bcost,
-                      const int32_t* __restrict__ cost, double radius, double reach) {
+                      const int32_t* __restrict__ cost, double radius, double reach, const uint8_t* __restrict__ active) {
   const int lane = threadIdx.x & 63;
   const int q = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   if (q >= B) return;
@@ -455,10 +492,11 @@ nn_forest_near_kernel(const double* __restrict__ queries, int q_stride, int B, c
     return;
   }
   int U = 0x7fffffff;
-  if constexpr (MASK) U = bound_of(counters + (size_t)t * 8, bcost);
+  if constexpr (MASK & MASK_KEY) U = bound_of(counters + (size_t)t * 8, bcost);
   const double qx[1] = {queries[(size_t)q * q_stride + 0]}, qy[1] = {queries[(size_t)q * q_stride + 1]};
   int res[1];
-  near_scan<MASK, 1>(node_xy + base, MASK ? key + base : nullptr, cost + base, n, U, qx, qy, radius, reach, lane, res);
+  near_scan<MASK, 1>(node_xy + base, (MASK & MASK_KEY) ? key + base : nullptr, (MASK & MASK_ACTIVE) ? active + base : nullptr,
+                     cost + base, n, U, qx, qy, radius, reach, lane, res);
   const int ix = base + (res[0] == 0x7fffffff ? 0 : res[0]);
   if (lane == 0) out_idx[q] = ix;
   if (node_state != nullptr) {
@@ -471,10 +509,12 @@ void launch_nn_forest_near(const double* queries, int q_stride, int B, const dou
                            const int32_t* counters, int C, int32_t* out_idx, const double* node_state,
                            const double* node_last_action, const uint8_t* node_has_prev, double* out_state, double* out_prev_action,
                            uint8_t* out_has_prev, hipStream_t s, int S, int D, const int32_t* key, const int32_t* bcost,
-                           const int32_t* cost, double radius, double reach) {
-  hipLaunchKernelGGL((key ? nn_forest_near_kernel<true> : nn_forest_near_kernel<false>), dim3((B + 3) / 4), dim3(256), 0, s, queries,
-                     q_stride, B, (const double2*)node_xy, off, T, counters, C, out_idx, node_state, node_last_action,
-                     node_has_prev, out_state, out_prev_action, out_has_prev, S, D, key, bcost, cost, radius, reach);
+                           const int32_t* cost, double radius, double reach, const uint8_t* active) {
+  const auto kernel = active ? (key ? nn_forest_near_kernel<MASK_KEY | MASK_ACTIVE> : nn_forest_near_kernel<MASK_ACTIVE>)
+                             : (key ? nn_forest_near_kernel<MASK_KEY> : nn_forest_near_kernel<0>);
+  hipLaunchKernelGGL(kernel, dim3((B + 3) / 4), dim3(256), 0, s, queries, q_stride, B, (const double2*)node_xy, off, T, counters, C,
+                     out_idx, node_state, node_last_action, node_has_prev, out_state, out_prev_action, out_has_prev, S, D, key,
+                     bcost, cost, radius, reach, active);
 }
 
 // ------------------------------------------------------------------------- local map
@@ -1442,10 +1482,29 @@ __device__ __forceinline__ bool tree_slice(const TreeSet& ts, const ditree_round
 //            candidate that did not collide gets a slot only if f < U, U the tree's bound as of the round's start, else it is
 //            pruned: node id -1, counted in stats[1] (since the tree's reset) and stats[3] (this round).  The overflow flag is
 //            raised by unpruned rows alone, because only they are ranked.
-template <AcceptMode MODE>
+//   SPARSE   (ditree_accept_sparse, best or bounded; include/ditree.h "sparse tree"): on entry sp->cand holds c and the cell of
+//            every candidate and sp->scratch the smallest (c, candidate) of every cell that has one (sparse_cost_kernel).  Behind
+//            the mode's own tests a candidate gets a slot only if it has no cell, reached the goal, or WON its cell: it is the
+//            cell's contender and the cell holds no node or a dearer one.  The rest is dominated: node id -1, stats[0] and [3].
+//            Once the ids are out, a winner with a slot becomes its cell's table entry and active, the node it displaced inactive
+//            (stats[1]; a new cell: stats[2]); every other new node is inactive.  Only the contender of a cell reads or writes the
+//            cell's table entry, so the order of the threads does not matter; the scratch entries go back to all ones behind the
+//            last read.
+struct SparseTree {                                    // the sparse descriptor's rows of the work-group's tree
+  unsigned long long* table;
+  unsigned long long* scratch;
+  int32_t* stats;
+};
+__device__ __forceinline__ unsigned long long sparse_key(int c, int id) {
+  return ((unsigned long long)(unsigned)c << 32) | (unsigned)id;
+}
+template <AcceptMode MODE, bool SPARSE = false>
 __device__ __forceinline__ void accept_scan_tree(const TreeSlice& sl, int cap, int32_t* __restrict__ num_visit,
-                                                 const ditree_round& r, int emulate_sticky, const int32_t* __restrict__ cost) {
+                                                 const ditree_round& r, int emulate_sticky, const int32_t* __restrict__ cost,
+                                                 const SparseTree* st = nullptr, const int32_t* __restrict__ cand = nullptr,
+                                                 uint8_t* __restrict__ active = nullptr) {
   __shared__ int s_first_goal, s_first_gac, s_iters, s_pruned;
+  __shared__ int s_sparse[3];                          // SPARSE: dominated, retired, new cells
   __shared__ int s_wave_sum[16];
   int32_t* __restrict__ counters = sl.counters;
   const int32_t* __restrict__ status = r.status + sl.lo;
@@ -1457,6 +1516,7 @@ __device__ __forceinline__ void accept_scan_tree(const TreeSlice& sl, int cap, i
     s_iters = 0;
     if constexpr (MODE == AcceptMode::first) { s_first_goal = 0x7fffffff; s_first_gac = 0x7fffffff; }
     if constexpr (MODE == AcceptMode::bounded) s_pruned = 0;
+    if constexpr (SPARSE) { s_sparse[0] = 0; s_sparse[1] = 0; s_sparse[2] = 0; }
   }
   __syncthreads();
   int last = B - 1, phantom = -1, goal_cand = -1, U = 0x7fffffff;
@@ -1488,11 +1548,23 @@ __device__ __forceinline__ void accept_scan_tree(const TreeSlice& sl, int cap, i
   for (int start = 0; start <= last; start += blockDim.x) {
     const int b = start + tid;
     int acc = 0, it = 0;
+    bool won = false;                                  // SPARSE: b won its cell
     if (b <= last) {
       const bool ph = MODE == AcceptMode::first && b == phantom;
       acc = ph ? 1 : ((status[b] & 0xff) != DITREE_ST_COLLIDED);
       if constexpr (MODE == AcceptMode::bounded) {
         if (acc && !(node_id[b] < U)) { acc = 0; atomicAdd(&s_pruned, 1); }
+      }
+      if constexpr (SPARSE) {
+        const int cell = cand[2 * (sl.lo + b) + 1];
+        if (acc && cell >= 0) {
+          const int c = cand[2 * (sl.lo + b)];
+          if (st->scratch[cell] == sparse_key(c, sl.lo + b)) {
+            const unsigned long long rep = st->table[cell];
+            won = rep == ~0ull || c < (int)(rep >> 32);
+          }
+          if (!won && (status[b] & 0xff) != DITREE_ST_GOAL) { acc = 0; atomicAdd(&s_sparse[0], 1); }
+        }
       }
       it = ph ? 1 : chunks_run[b];
       atomicAdd(&num_visit[parent[b]], 1);
@@ -1518,9 +1590,28 @@ __device__ __forceinline__ void accept_scan_tree(const TreeSlice& sl, int cap, i
       int id = acc ? (n0 + base + woff + v - acc) : -1;   // n0 + exclusive rank
       if (id >= cap) id = -1;
       node_id[b] = id < 0 ? -1 : sl.node_base + id;
+      if constexpr (SPARSE) {
+        if (id >= 0) {
+          const int gid = sl.node_base + id;
+          active[gid] = won ? 1 : 0;
+          if (won) {
+            const int cell = cand[2 * (sl.lo + b) + 1];
+            const unsigned long long rep = st->table[cell];
+            st->table[cell] = sparse_key(cand[2 * (sl.lo + b)], gid);
+            if (rep != ~0ull) { active[(int)(rep & 0xffffffffull)] = 0; atomicAdd(&s_sparse[1], 1); }
+            else atomicAdd(&s_sparse[2], 1);
+          }
+        }
+      }
     }
     base += chunk_total;
     __syncthreads();
+  }
+  if constexpr (SPARSE) {                              // every read of the contenders is behind the loop's last barrier
+    for (int b = tid; b < B; b += blockDim.x) {
+      const int cell = cand[2 * (sl.lo + b) + 1];
+      if (cell >= 0) st->scratch[cell] = ~0ull;
+    }
   }
   if constexpr (MODE == AcceptMode::first) {
     for (int b = last + 1 + tid; b < B; b += blockDim.x) node_id[b] = -1;
@@ -1539,6 +1630,12 @@ __device__ __forceinline__ void accept_scan_tree(const TreeSlice& sl, int cap, i
     counters[4] += last + 1;
     counters[7] = phantom < 0 ? -1 : sl.lo + phantom;
     if constexpr (MODE == AcceptMode::bounded) { sl.stats[1] += s_pruned; sl.stats[3] = s_pruned; }
+    if constexpr (SPARSE) {
+      st->stats[0] += s_sparse[0];
+      st->stats[1] += s_sparse[1];
+      st->stats[2] += s_sparse[2];
+      st->stats[3] = s_sparse[0];
+    }
   }
 }
 template <AcceptMode MODE>
@@ -1612,6 +1709,122 @@ accept_cost_kernel(ditree_tree t, ditree_round r, TreeSet ts, BoundArg bd) {
     r.node_id[b] = bd.cost[par] + ns + 1 + bound_h(ex, ey, bd.goal_xy[2 * tr], bd.goal_xy[2 * tr + 1], bd.goal_radius, bd.reach);
   }
 }
+// ---- sparse tree (include/ditree.h "sparse tree")
+// The cell of a state in tree tr, -1 without one.  Each operation is one rounded f64 operation (this unit does not contract), the
+// clamps are taken on the floored doubles, so a numpy restatement of the same expression gives the same cell bit for bit.  An
+// index past the table's stride cannot come out of a validated descriptor; it is refused here all the same.
+__device__ __forceinline__ int sparse_cell(const SparseArg& sp, int tr, double x, double y, double psi) {
+  if (!isfinite(x) || !isfinite(y) || !isfinite(psi)) return -1;
+  const double W = sp.extent[2 * tr], L = sp.extent[2 * tr + 1];
+  const int nx = sp.dims[2 * tr], ny = sp.dims[2 * tr + 1];
+  const double two_pi = 2.0 * 3.14159265358979323846;
+  double fx = floor((x + W / 2.0) / sp.cell), fy = floor((y + L / 2.0) / sp.cell);
+  fx = fx < 0.0 ? 0.0 : (fx > (double)(nx - 1) ? (double)(nx - 1) : fx);
+  fy = fy < 0.0 ? 0.0 : (fy > (double)(ny - 1) ? (double)(ny - 1) : fy);
+  const double a = psi - two_pi * floor(psi / two_pi);
+  double fh = floor(a / sp.w);
+  fh = fh < 0.0 ? 0.0 : (fh > (double)(sp.nh - 1) ? (double)(sp.nh - 1) : fh);
+  const long long cell = ((long long)fy * nx + (long long)fx) * sp.nh + (long long)fh;
+  return cell < (long long)sp.stride ? (int)cell : -1;
+}
+// the table words as the type the 64-bit atomicMin takes
+__device__ __forceinline__ unsigned long long* sparse_words(uint64_t* p, int tr, int stride) {
+  return reinterpret_cast<unsigned long long*>(p) + (size_t)tr * stride;
+}
+__device__ __forceinline__ SparseTree sparse_tree(const SparseArg& sp, int tr) {
+  return SparseTree{sparse_words(sp.table, tr, sp.stride), sparse_words(sp.scratch, tr, sp.stride), sp.stats + (size_t)tr * 4};
+}
+// The pre-pass of a sparse accept, one wave per candidate (accept_cost_kernel's shape and row count): c and the cell of the
+// candidate go to sp.cand, BOUND: f to node_id[b] as accept_cost_kernel leaves it.  A candidate that can still get a node by
+// winning its cell -- not collided, a cell, BOUND: f < U -- enters the contest of that cell: one 64-bit atomicMin of (c, b), so the
+// contender does not depend on the order of the waves.
+template <bool BOUND>
+__global__ void __launch_bounds__(64)
+sparse_cost_kernel(ditree_tree t, ditree_round r, TreeSet ts, const int32_t* __restrict__ cost, BoundArg bd, SparseArg sp) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int par = r.parent[b];
+  const int tr = par / ts.C;
+  if ((r.status[b] & 0xff) == DITREE_ST_COLLIDED) {
+    if (lane == 0) {
+      if constexpr (BOUND) r.node_id[b] = 0;
+      sp.cand[2 * b] = 0;
+      sp.cand[2 * b + 1] = -1;
+    }
+    return;
+  }
+  const int A = t.A, S = t.state_dim;
+  const double* cs = r.states + (size_t)b * t.n_chunks * (A + 1) * S;
+  const int rows_s = r.chunks_run[b] * (A + 1);
+  int ns = 0;
+  for (int row = 0; row < rows_s; ++row) {
+    const double v = lane < S ? cs[(size_t)row * S + lane] : 0.0;
+    if (__ballot(v != 0.0) != 0ull) ++ns;
+  }
+  if (lane == 0) {
+    const double* e = r.end_state + (size_t)b * S;
+    const int c = cost[par] + ns + 1;
+    bool in = true;
+    if constexpr (BOUND) {
+      const int U = bound_of(tree_counters(ts, tr), bd.cost);
+      const int f = U == 0x7fffffff ? 0 : c + bound_h(e[0], e[1], bd.goal_xy[2 * tr], bd.goal_xy[2 * tr + 1], bd.goal_radius, bd.reach);
+      r.node_id[b] = f;
+      in = f < U;
+    }
+    const int cell = sparse_cell(sp, tr, e[0], e[1], e[2]);
+    sp.cand[2 * b] = c;
+    sp.cand[2 * b + 1] = cell;
+    if (in && cell >= 0) atomicMin(sparse_words(sp.scratch, tr, sp.stride) + cell, sparse_key(c, b));
+  }
+}
+template <AcceptMode MODE>
+__global__ void __launch_bounds__(1024)
+accept_scan_sparse_kernel(ditree_tree t, ditree_round r, TreeSet ts, BoundArg bd, const int32_t* __restrict__ cost, SparseArg sp) {
+  TreeSlice sl;
+  if (!tree_slice<MODE == AcceptMode::bounded>(ts, r, bd.stats, sl)) return;
+  const SparseTree st = sparse_tree(sp, blockIdx.x);
+  accept_scan_tree<MODE, true>(sl, ts.C, t.num_visit, r, 0, cost, &st, sp.cand, sp.active);
+}
+// ditree_sparse_rebuild, three launches over trees [first, first + n) (blockIdx.y): the rows of the table and the scratch to all
+// ones and the stats row to zero; the minimum of (cost, slot) over the nodes of every cell; then a node is active iff it is its
+// cell's minimum, counted per wave into stats[2].
+__global__ void __launch_bounds__(256) sparse_clear_kernel(SparseArg sp, int first) {
+  const int tr = first + blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= sp.stride) return;
+  sp.table[(size_t)tr * sp.stride + i] = ~0ull;
+  sp.scratch[(size_t)tr * sp.stride + i] = ~0ull;
+  if (i < 4) sp.stats[(size_t)tr * 4 + i] = 0;
+}
+template <bool FLAG>
+__global__ void __launch_bounds__(256)
+sparse_nodes_kernel(ditree_tree t, TreeSet ts, const int32_t* __restrict__ cost, SparseArg sp, int first) {
+  const int tr = first + blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
+  int n = tree_counters(ts, tr)[0];
+  n = n > ts.C ? ts.C : n;
+  bool act = false;
+  if (i < n) {
+    const int id = tr * ts.C + i;
+    const double* s = t.state + (size_t)id * t.state_dim;
+    const int cell = sparse_cell(sp, tr, s[0], s[1], s[2]);
+    if (cell >= 0) {
+      unsigned long long* slot = sparse_words(sp.table, tr, sp.stride) + cell;
+      if constexpr (FLAG) act = *slot == sparse_key(cost[id], id);
+      else atomicMin(slot, sparse_key(cost[id], id));
+    }
+    if constexpr (FLAG) sp.active[id] = act ? 1 : 0;
+  }
+  if constexpr (FLAG) {
+    const int cnt = __popcll(__ballot(act));
+    if ((threadIdx.x & 63) == 0 && cnt > 0) atomicAdd(&sp.stats[(size_t)tr * 4 + 2], cnt);
+  }
+}
+void launch_sparse_rebuild(const ditree_tree& t, const TreeSet& ts, const int32_t* cost, const SparseArg& sp, int first, int n,
+                           hipStream_t s) {
+  hipLaunchKernelGGL(sparse_clear_kernel, dim3((sp.stride + 255) / 256, n), dim3(256), 0, s, sp, first);
+  const dim3 nodes((ts.C + 255) / 256, n);
+  hipLaunchKernelGGL(sparse_nodes_kernel<false>, nodes, dim3(256), 0, s, t, ts, cost, sp, first);
+  hipLaunchKernelGGL(sparse_nodes_kernel<true>, nodes, dim3(256), 0, s, t, ts, cost, sp, first);
+}
+
 // key[n] = cost[n] + h(xy[n]) for nodes [first, first + n) (ditree_bound_keys: the roots); node n belongs to tree n / C, C as
 // in a TreeSet.
 __global__ void bound_keys_kernel(const double2* __restrict__ xy, int first, int n, int C, BoundArg bd) {
@@ -1801,18 +2014,25 @@ void launch_round_unpack(const ditree_tree& t, const ditree_round& r, const doub
 }
 
 // The accept of a round on the trees `ts`: scan -> commit; best: with the cost column, then the pick; bounded (bd != NULL,
-// cost = bd->cost): the cost pre-pass first, the commit writes the key column too, the pick the stats rows.
+// cost = bd->cost): the cost pre-pass first, the commit writes the key column too, the pick the stats rows.  sp != NULL (best or
+// bounded): the sparse rule's pre-pass and scan in their place.
 void launch_accept(const ditree_tree& t, const ditree_round& r, const TreeSet& ts, AcceptMode mode, int emulate_sticky,
                    int32_t* cost, const BoundArg* bd, const unsigned char* maze, int rows, int cols, const AheadArg& ahead,
-                   hipStream_t s) {
+                   hipStream_t s, const SparseArg* sp) {
   const BoundArg b = bd ? *bd : BoundArg{};
   const dim3 trees(ts.T), cands(r.B);
   const bool bounded = mode == AcceptMode::bounded;
-  const auto scan = mode == AcceptMode::first  ? accept_scan_kernel<AcceptMode::first>
-                    : mode == AcceptMode::best ? accept_scan_kernel<AcceptMode::best>
-                                               : accept_scan_kernel<AcceptMode::bounded>;
-  if (bounded) hipLaunchKernelGGL(accept_cost_kernel, cands, dim3(64), 0, s, t, r, ts, b);
-  hipLaunchKernelGGL(scan, trees, dim3(1024), 0, s, t, r, ts, emulate_sticky, b);
+  if (sp) {            // best or bounded under the sparse rule: its own pre-pass and scan, then the mode's commit and pick
+    hipLaunchKernelGGL(bounded ? sparse_cost_kernel<true> : sparse_cost_kernel<false>, cands, dim3(64), 0, s, t, r, ts, cost, b, *sp);
+    hipLaunchKernelGGL(bounded ? accept_scan_sparse_kernel<AcceptMode::bounded> : accept_scan_sparse_kernel<AcceptMode::best>, trees,
+                       dim3(1024), 0, s, t, r, ts, b, cost, *sp);
+  } else {
+    const auto scan = mode == AcceptMode::first  ? accept_scan_kernel<AcceptMode::first>
+                      : mode == AcceptMode::best ? accept_scan_kernel<AcceptMode::best>
+                                                 : accept_scan_kernel<AcceptMode::bounded>;
+    if (bounded) hipLaunchKernelGGL(accept_cost_kernel, cands, dim3(64), 0, s, t, r, ts, b);
+    hipLaunchKernelGGL(scan, trees, dim3(1024), 0, s, t, r, ts, emulate_sticky, b);
+  }
   hipLaunchKernelGGL(bounded ? accept_commit_kernel<true> : accept_commit_kernel<false>, cands, dim3(64), 0, s, t, r, maze, rows,
                      cols, ahead, ts, cost, b);
   if (mode != AcceptMode::first)

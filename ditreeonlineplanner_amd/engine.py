@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import Bound, Near, Round, RoundParams, Tree, check, lib
+from ._lib import Bound, Near, Round, RoundParams, Sparse, Tree, check, lib
 from .ops import CAR_NORM, Context, _dbl, _flt, _ptr, local_axis
 
 CNT_NODES, CNT_GOAL, CNT_LATCH, CNT_ITERS, CNT_CANDS, CNT_STICKY, CNT_OVERFLOW, CNT_PHANTOM = range(8)
@@ -28,6 +28,11 @@ CNT_NODES, CNT_GOAL, CNT_LATCH, CNT_ITERS, CNT_CANDS, CNT_STICKY, CNT_OVERFLOW, 
 ST_BOUND, ST_PRUNED, ST_EXHAUSTED, ST_PRUNED_ROUND = range(4)
 NO_BOUND = 2 ** 31 - 1
 STATS_ROOT = np.array([NO_BOUND, 0, 0, 0], dtype=np.int32)
+# include/ditree.h ditree_sparse.stats: candidates dominated and nodes retired since the rebuild, active nodes, candidates
+# dominated by the last accept; a tree that holds its root alone has one active node
+SP_DOMINATED, SP_RETIRED, SP_ACTIVE, SP_DOMINATED_ROUND = range(4)
+SPARSE_ROOT = np.array([0, 0, 1, 0], dtype=np.int32)
+SPARSE_MAX_CELLS = 2 ** 22
 
 
 class DeviceTree:
@@ -36,10 +41,12 @@ class DeviceTree:
     first sampler call of a child sees with obs_history 3 -- the ant); ``cost``: keep every node's path cost (the rows
     ``tree_path`` returns for it), which the ``solution`` modes other than "first" rank goal nodes by; ``key``: keep beside it
     every node's key = cost + the rows it still needs at best (include/ditree.h "branch and bound": "anytime_pruned"), and a
-    stats row behind the counters, in the same small buffer, so that one copy reads both."""
+    stats row behind the counters, in the same small buffer, so that one copy reads both; ``active``: keep every node's active
+    flag of the sparse tree (include/ditree.h "sparse tree"), and its stats row in that buffer too."""
 
     def __init__(self, ctx: Context, capacity: int, n_chunks: int, A: int, track_obstacle_ahead: bool = False,
-                 state_dim: int = 6, action_dim: int = 2, hist: bool = False, cost: bool = False, key: bool = False):
+                 state_dim: int = 6, action_dim: int = 2, hist: bool = False, cost: bool = False, key: bool = False,
+                 active: bool = False):
         dev = ctx.device
         self.capacity, self.n_chunks, self.A = capacity, n_chunks, A
         self.S, self.D = S, D = int(state_dim), int(action_dim)
@@ -54,18 +61,22 @@ class DeviceTree:
         self.edge_actions = torch.zeros(capacity, n_chunks * A, D, dtype=f64, device=dev)
         self.edge_nstates = torch.zeros(capacity, dtype=i32, device=dev)
         self.edge_nactions = torch.zeros(capacity, dtype=i32, device=dev)
-        self._cnt_buf = torch.zeros(12 if key else 8, dtype=i32, device=dev)     # counters [+ the bound's stats row]
+        # counters [+ the bound's stats row] [+ the sparse tree's stats row]
+        self._cnt_buf = torch.zeros(8 + (4 if key else 0) + (4 if active else 0), dtype=i32, device=dev)
         self.counters = self._cnt_buf[:8]
-        self.stats = self._cnt_buf[8:] if key else None
+        self.stats = self._cnt_buf[8:12] if key else None
         self.stats_host = STATS_ROOT.copy() if key else None
+        self.sparse_stats = self._cnt_buf[-4:] if active else None
+        self.sparse_host = SPARSE_ROOT.copy() if active else None
         # RRT.py:202-205: per-node check_obstacle_ahead flag, kept only for run_type > 0
         self.obstacle_ahead = torch.zeros(capacity, dtype=u8, device=dev) if track_obstacle_ahead else None
         # rank holding each node's edge rows (sharded rounds keep trajectories on the producing rank); -1 = every rank
         self.edge_owner = torch.full((capacity,), -1, dtype=i32, device=dev)
         self.hist = torch.zeros(capacity, 3, S, dtype=f64, device=dev) if hist else None
         self.hist_n = torch.zeros(capacity, dtype=i32, device=dev) if hist else None
-        self.cost = torch.zeros(capacity, dtype=i32, device=dev) if cost or key else None   # not part of the descriptor
+        self.cost = torch.zeros(capacity, dtype=i32, device=dev) if cost or key or active else None   # not part of the descriptor
         self.key = torch.zeros(capacity, dtype=i32, device=dev) if key else None             # nor this (ditree_bound)
+        self.active = torch.zeros(capacity, dtype=u8, device=dev) if active else None        # nor this (ditree_sparse)
         self.desc = Tree(capacity, n_chunks, A, S, D, *[None if t is None else t.data_ptr() for t in (
             self.state, self.xy, self.parent, self.last_action, self.has_prev, self.num_visit,
             self.edge_states, self.edge_actions, self.edge_nstates, self.edge_nactions, self.obstacle_ahead,
@@ -104,13 +115,17 @@ class DeviceTree:
         if self.stats is not None:                      # the root's key is the engine's to set: it knows the goal
             self.stats.copy_(torch.as_tensor(STATS_ROOT))
             self.stats_host = STATS_ROOT.copy()
+        if self.sparse_stats is not None:               # the table and the flags are the engine's to rebuild: it knows the map
+            self.sparse_host = SPARSE_ROOT.copy()
         self.n_nodes_host = 1
 
     def read_counters(self):
-        c = self._cnt_buf.cpu().numpy()                 # one small copy: the counters and, where kept, the stats row
+        c = self._cnt_buf.cpu().numpy()                 # one small copy: the counters and, where kept, the stats rows
         self.n_nodes_host = int(c[CNT_NODES])
         if self.stats is not None:
-            self.stats_host = c[8:]
+            self.stats_host = c[8:12]
+        if self.sparse_stats is not None:
+            self.sparse_host = c[-4:]
         return c[:8]
 
 
@@ -320,6 +335,43 @@ def check_near(near_radius, near_reach, solution, ant=False, prop_duration=None)
     return radius, reach
 
 
+def sparse_grid(maze_shape, s_global, cell, headings):
+    """The grid of the sparse tree on a map of ``rows x cols`` cells scaled by ``s_global`` (include/ditree.h "sparse tree") ->
+    (W, L, nx, ny): the metres ``random_node_sample`` draws in, and ceil(W / cell), ceil(L / cell) cells."""
+    rows, cols = (int(v) for v in maze_shape)
+    W, L = float(s_global) * cols, float(s_global) * rows
+    nx, ny = int(np.ceil(W / cell)), int(np.ceil(L / cell))
+    if nx < 1 or ny < 1 or nx * ny * int(headings) > SPARSE_MAX_CELLS:
+        raise ValueError(f"sparse_cell={cell!r} with sparse_headings={headings} gives {nx} x {ny} x {headings} cells on a map of "
+                         f"{W} m x {L} m, more than {SPARSE_MAX_CELLS} per tree")
+    return W, L, nx, ny
+
+
+def check_sparse(sparse_cell, sparse_headings, solution, ant=False, prop_duration=None):
+    """The sparse tree (include/ditree.h "sparse tree") -> (cell [m], heading bins), or None when it is off.  Its scope is the
+    cost column's, as ``check_near``'s: a ``solution`` other than "first" (whose own scope ``check_solution`` holds: the car,
+    one rank, run_type 0) and a single ``prop_duration`` entry."""
+    if sparse_cell is None:
+        if sparse_headings is not None:
+            raise ValueError("sparse_headings belongs to sparse_cell (sparse_cell is None)")
+        return None
+    v = sparse_cell
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or v <= 0:
+        raise ValueError(f"sparse_cell must be a positive finite number of metres, got {v!r}")
+    h = 8 if sparse_headings is None else sparse_headings
+    if isinstance(h, bool) or not isinstance(h, (int, np.integer)) or not 1 <= h <= 64:
+        raise ValueError(f"sparse_headings must be an integer from 1 to 64, got {h!r}")
+    if ant:
+        raise NotImplementedError("sparse_cell: the car only (the ant's tree has no cost column)")
+    if solution == "first":
+        raise ValueError("sparse_cell needs a solution other than 'first' (the cost column belongs to 'best_of_round', 'anytime' "
+                         "and 'anytime_pruned')")
+    if prop_duration is not None and len(prop_duration) > 1:
+        raise NotImplementedError("sparse_cell: a single prop_duration entry (a schedule's chunk budgets are not built for the "
+                                  "rounds that mask their search)")
+    return float(v), int(h)
+
+
 def check_solution(solution, emulate_sticky_done, world_size=1, run_type=0):
     """The scope of the ``solution`` modes other than "first" (ditree_accept_best, ditree_accept_bounded): one rank, run_type 0,
     no sticky-done emulation (its phantom candidate belongs to the first-goal rule)."""
@@ -355,7 +407,10 @@ class Entries(NamedTuple):
     descriptors its calls take behind the tree's -- ``lead`` in every call (a forest's descriptor), ``scenes`` behind those
     in the expand call (a scene forest's descriptor; NULL for a plain forest's bounded round, whose entry point serves both
     kinds of forest).  ``near``: the rounds of an engine with ``near_radius`` go through ditree_[forest_]expand_round_near, which
-    serves every mode (the bound or NULL) and both kinds of forest; the accept and the fallback stay the mode's own."""
+    serves every mode (the bound or NULL) and both kinds of forest; the accept and the fallback stay the mode's own.
+    ``sparse``: the rounds and the accepts of an engine with ``sparse_cell`` go through ditree_[forest_]expand_round_sparse (the
+    bound or NULL, the near descriptor or NULL, the sparse one) and ditree_[forest_]accept_sparse (the cost column, the bound or
+    NULL, the sparse descriptor)."""
     expand: str
     accept: str
     accept_tail: Callable
@@ -365,7 +420,7 @@ class Entries(NamedTuple):
     scenes: tuple
 
     @classmethod
-    def of(cls, solution, ant, forest=None, scenes=None, near=False):
+    def of(cls, solution, ant, forest=None, scenes=None, near=False, sparse=False):
         f, a = ("forest_" if forest is not None else ""), ("_ant" if ant else "")
         lead = () if forest is None else (C.byref(forest),)
         sc = () if scenes is None else (C.byref(scenes),)
@@ -383,6 +438,10 @@ class Entries(NamedTuple):
         if near:             # one expand entry for every mode and kind of forest: [scenes or NULL], ..., the bound or NULL, near
             expand = f"ditree_{f}expand_round_near"
             sc = sc or ((None,) if forest is not None else ())
+        if sparse:           # as near: one expand entry, and one accept entry for the best and the bounded rule
+            expand, accept = f"ditree_{f}expand_round_sparse", f"ditree_{f}accept_sparse"
+            sc = sc or ((None,) if forest is not None else ())
+            tail = lambda e: (e.tree.cost.data_ptr(), C.byref(e.bound) if e.pruned else None, C.byref(e._sparse_desc()))  # noqa: E731
         fallback = "ditree_fallback_select" if forest is None else \
             "ditree_forest_fallback" + ("_goals" if scenes is not None else "") + a
         return cls(expand, accept, tail, fallback, f"ditree_{f}chunk_budget", lead, sc)
@@ -404,7 +463,7 @@ class ExpansionEngine:
                  pred_horizon=64, local_map_size=20, local_map_scale=0.2, s_global=1.0, batch=1024,
                  capacity=65536, k_steps=1, emulate_sticky_done=True, norm=CAR_NORM, rank=0, world_size=1,
                  process_group=None, early_exit=False, run_type=0, goal_scale=None, prop_duration=None, solution="first",
-                 reach=None, near_radius=None, near_reach=None):
+                 reach=None, near_radius=None, near_reach=None, sparse_cell=None, sparse_headings=None):
         check_solution(solution, emulate_sticky_done, world_size, run_type)
         self.solution = solution
         self.pruned = solution == "anytime_pruned"
@@ -414,6 +473,7 @@ class ExpansionEngine:
         if self.pruned and prop_duration is not None and len(prop_duration) > 1:
             raise NotImplementedError("solution='anytime_pruned': a single prop_duration entry (the chunk-budget search is not masked)")
         self.near = check_near(near_radius, near_reach, solution, self.HIST, prop_duration)
+        self.sparse = check_sparse(sparse_cell, sparse_headings, solution, self.HIST, prop_duration)
         self.ctx = ctx
         self.maze = np.asarray(maze, dtype=np.float32)
         # planners/RRT.py:26,149-152: per-visit edge lengths; the tree's edge capacity is the longest entry
@@ -439,7 +499,7 @@ class ExpansionEngine:
         self.init_main_path = None          # (P, >=2) reference path of an earlier plan (run_type > 0)
         self.tree = DeviceTree(ctx, capacity, self.n_chunks, self.A, track_obstacle_ahead=self.run_type > 0,
                                state_dim=self.STATE_DIM, action_dim=self.ACTION_DIM, hist=self.HIST,
-                               cost=solution != "first", key=self.pruned)
+                               cost=solution != "first", key=self.pruned, active=self.sparse is not None)
         # sharded rounds exchange ceil(batch / world) fixed slots per rank: size the round buffers for whole slots, so a batch
         # that does not divide by the rank count is fine (the last rank's tail slots stay unused)
         per = (batch + world_size - 1) // world_size
@@ -457,12 +517,15 @@ class ExpansionEngine:
         ctx.upload_maze(self.maze, owner=self)
         # a forest's descriptors exist by now (ForestTrees._init_forest, SceneTrees._init_scenes run before this constructor)
         fdesc = getattr(self, "fdesc", None)
-        self.entries = Entries.of(solution, self.HIST, fdesc, getattr(self, "sdesc", None), near=self.near is not None)
+        self.entries = Entries.of(solution, self.HIST, fdesc, getattr(self, "sdesc", None), near=self.near is not None,
+                                  sparse=self.sparse is not None)
         if self.pruned:
             if fdesc is None:
                 self._init_bound(1, 0, self.tree.stats)
             else:
                 self._init_bound(self.T, self.C, self.fstats)
+        if self.sparse is not None:
+            self._init_sparse()
         self.reset(start_state, goal_state)
 
     def _call(self, entry, *args):
@@ -479,7 +542,8 @@ class ExpansionEngine:
             kw.update(edge_length=self.H, dynamics=self.dynamics, model=self.model, ball_radius=self.ball_radius)
         else:
             kw.update(emulate_sticky_done=bool(self.sticky), prop_duration=self.schedule, solution=self.solution,
-                      reach=self.reach, near_radius=self.near and self.near[0], near_reach=self.near and self.near[1])
+                      reach=self.reach, near_radius=self.near and self.near[0], near_reach=self.near and self.near[1],
+                      sparse_cell=self.sparse and self.sparse[0], sparse_headings=self.sparse and self.sparse[1])
         return kw
 
     # ------------------------------------------------------------------ the bound of "anytime_pruned"
@@ -521,6 +585,80 @@ class ExpansionEngine:
         """Nodes whose key is at or past the incumbent's cost (0 without an incumbent); one reduction and one scalar copy."""
         return self._bound_stats()[2]()
 
+    # ------------------------------------------------------------------ the sparse tree of ``sparse_cell``
+    def _sparse_mazes(self):
+        """The maps a tree of this engine may grow on: they size the table."""
+        return [self.maze]
+
+    def _sparse_maze_of(self, t):
+        return self.maze
+
+    def _init_sparse(self):
+        """What the ditree_sparse descriptor points to, but for the tree's own arrays (the active column, the stats row: a
+        re-base swaps the two trees): per tree the map extents and the grid dims, the table and the contender words, and the
+        accept's candidate scratch."""
+        cell, nh = self.sparse
+        dev, T = self.ctx.device, getattr(self, "T", 1)
+        self._sparse_stride = max(nx * ny * nh for _, _, nx, ny in (sparse_grid(m.shape, self.s_global, cell, nh)
+                                                                    for m in self._sparse_mazes()))
+        self._sparse_extent = torch.zeros(T, 2, dtype=torch.float64, device=dev)
+        self._sparse_dims = torch.zeros(T, 2, dtype=torch.int32, device=dev)
+        self._sparse_dims_host = (C.c_int32 * (2 * T))()
+        self._sparse_table = torch.full((T, self._sparse_stride), -1, dtype=torch.int64, device=dev)       # all ones: no node
+        self._sparse_scratch = torch.full((T, self._sparse_stride), -1, dtype=torch.int64, device=dev)
+        self._sparse_cand = torch.zeros(2 * self.rb.B, dtype=torch.int32, device=dev)
+        self._sparse_roots = []
+
+    def _sparse_stats_rows(self):
+        return self.tree.sparse_stats
+
+    def _sparse_desc(self):
+        cell, nh = self.sparse
+        return Sparse(cell, 2.0 * np.pi / nh, nh, self._sparse_stride, self._sparse_extent.data_ptr(), self._sparse_dims.data_ptr(),
+                      self._sparse_dims_host, self._sparse_table.data_ptr(), self._sparse_scratch.data_ptr(),
+                      self.tree.active.data_ptr(), self._sparse_stats_rows().data_ptr(), self._sparse_cand.data_ptr())
+
+    def _sparse_sync(self):
+        """Before a launch that reads the sparse tree: the grid of every tree's map as it is now, and the table, the flags and
+        the stats row of every tree reset or re-based since, rebuilt on the device from the tree itself (purity: the active
+        nodes are a function of the tree)."""
+        if not self._sparse_roots:
+            return
+        cell, nh = self.sparse
+        T = getattr(self, "T", 1)
+        grids = [sparse_grid(self._sparse_maze_of(t).shape, self.s_global, cell, nh) for t in range(T)]
+        if max(nx * ny * nh for _, _, nx, ny in grids) > self._sparse_stride:      # a larger map since: every tree again
+            self._init_sparse()
+            self._sparse_roots = list(range(T))
+        for t, (W, L, nx, ny) in enumerate(grids):
+            self._sparse_dims_host[2 * t], self._sparse_dims_host[2 * t + 1] = nx, ny
+        self._sparse_extent.copy_(torch.as_tensor(np.array([g[:2] for g in grids], dtype=np.float64)))
+        self._sparse_dims.copy_(torch.as_tensor(np.array([g[2:] for g in grids], dtype=np.int32)))
+        roots = sorted(set(self._sparse_roots))
+        runs = [(0, T)] if len(roots) == T else [(t, 1) for t in roots]
+        for first, n in runs:
+            self._call("ditree_sparse_rebuild", *(self.entries.lead or (None,)), C.byref(self._sparse_desc()),
+                       self.tree.cost.data_ptr(), first, n)
+        self._sparse_roots = []
+
+    def _sparse_row(self):
+        return self.tree.sparse_host
+
+    @property
+    def dominated_candidates(self):
+        """``sparse_cell``: candidates that took no node because a node at most as dear holds their cell, since the reset."""
+        return int(self._sparse_row()[SP_DOMINATED])
+
+    @property
+    def retired_nodes(self):
+        """``sparse_cell``: nodes a cheaper one displaced as its cell's representative, since the reset."""
+        return int(self._sparse_row()[SP_RETIRED])
+
+    @property
+    def active_nodes(self):
+        """``sparse_cell``: the nodes the searches look at, one per occupied cell."""
+        return int(self._sparse_row()[SP_ACTIVE])
+
     # ------------------------------------------------------------------ state
     def reset(self, start_state, goal_state):
         self.start_state = np.asarray(start_state, dtype=np.float64).copy()
@@ -531,6 +669,8 @@ class ExpansionEngine:
         self.tree.reset(self.start_state)
         if self.pruned:
             self._bound_roots = [0]
+        if self.sparse is not None:
+            self._sparse_roots = [0]
         self.generation = getattr(self, "generation", 0) + 1      # consumers caching per-tree data (node_list) key on it
 
     def _derive_env_goal(self):
@@ -539,6 +679,8 @@ class ExpansionEngine:
     def update_maze(self, maze):
         self.maze = np.asarray(maze, dtype=np.float32)
         self.ctx.upload_maze(self.maze, owner=self)
+        if self.sparse is not None:                   # the cells follow the map's extents: every tree's table again
+            self._sparse_roots = list(range(getattr(self, "T", 1)))
 
     def ensure_maze(self):
         """The ctx's device maze must be THIS engine's before any launch that reads it (another planner, or a
@@ -576,7 +718,8 @@ class ExpansionEngine:
         if getattr(self, "_spare_tree", None) is None:
             self._spare_tree = DeviceTree(self.ctx, old.capacity, self.n_chunks, self.A,
                                           track_obstacle_ahead=old.obstacle_ahead is not None, state_dim=self.STATE_DIM,
-                                          action_dim=self.ACTION_DIM, hist=self.HIST, cost=old.cost is not None)
+                                          action_dim=self.ACTION_DIM, hist=self.HIST, cost=old.cost is not None,
+                                          active=old.active is not None)
             self._rebase_scratch = torch.zeros(3 * old.capacity, dtype=torch.int32, device=self.ctx.device)
         new = self._spare_tree
         n_old = old.n_nodes_host
@@ -598,6 +741,10 @@ class ExpansionEngine:
                 new.state[0] = s
                 new.xy[0] = s[:2]
         self.rebase_ids = self._rebase_scratch[2 * old.capacity:]      # old id -> new id (-1: dropped) until the next rebase
+        if self.sparse is not None:               # table, flags and stats of the re-based tree, from the tree itself
+            self._sparse_roots = [0]
+            self._sparse_sync()
+            new.read_counters()
         self.generation += 1
         kept = int(cnt[CNT_NODES]) - (1 if fresh_root else 0)
         return kept, n_old - kept
@@ -746,6 +893,9 @@ class ExpansionEngine:
         if self.near is not None:                     # the bound or NULL, then the near descriptor on the cost column of the
             near = Near(self.tree.cost.data_ptr(), *self.near)      # tree as it is now (a re-base swaps the two trees)
             tail = (*(tail or (None,)), C.byref(near))
+        if self.sparse is not None:                   # the bound or NULL, the near descriptor or NULL, then the sparse one
+            self._sparse_sync()
+            tail = (*tail, None, None)[:2] + (C.byref(self._sparse_desc()),)
         self._call(e.expand, *e.lead, *e.scenes, C.byref(rd), C.byref(rp), *tail)
 
     def _flow_only(self, rp, keep):
@@ -810,6 +960,8 @@ class ExpansionEngine:
         e = self.entries
         if self.pruned:
             self._bound_sync()
+        if self.sparse is not None:
+            self._sparse_sync()
         self._call(e.accept, *e.lead, C.byref(rd), *e.accept_tail(self))
         cnt = self.read_counters()                # one small D2H per round: n_nodes / goal (a forest: every tree's row)
         self._range_guard()

@@ -24,8 +24,8 @@ import numpy as np
 import torch
 
 from ._lib import MAX_ATLAS_CELLS, MAX_SCENES, ST_GOAL, Forest, ForestScenes
-from .engine import (CNT_GOAL, CNT_NODES, CNT_PHANTOM, STATS_ROOT, AntExpansionEngine, ExpansionEngine, ant_cell_centre,
-                     bound_stats, env_goal_of, tree_path)
+from .engine import (CNT_GOAL, CNT_NODES, CNT_PHANTOM, SP_ACTIVE, SP_DOMINATED, SP_RETIRED, SPARSE_ROOT, STATS_ROOT,
+                     AntExpansionEngine, ExpansionEngine, ant_cell_centre, bound_stats, env_goal_of, tree_path)
 from .ops import CAR_NORM, Context, _dbl
 
 
@@ -47,12 +47,14 @@ class ForestTrees:
             raise ValueError(f"n_trees * tree_capacity = {T * Cap} does not fit the int32 node numbering")
         self.T, self.C = T, Cap
         dev = ctx.device
-        # every tree's counter row and, behind them, every tree's stats row of the "anytime_pruned" bound: one small buffer, so
-        # that one copy per round reads both
-        self._fcnt_buf = torch.zeros(T * 12, dtype=torch.int32, device=dev)
+        # every tree's counter row and, behind them, every tree's stats row of the "anytime_pruned" bound and of the sparse tree:
+        # one small buffer, so that one copy per round reads them all
+        self._fcnt_buf = torch.zeros(T * 16, dtype=torch.int32, device=dev)
         self.fcounters = self._fcnt_buf[:T * 8].view(T, 8)
-        self.fstats = self._fcnt_buf[T * 8:].view(T, 4)
+        self.fstats = self._fcnt_buf[T * 8:T * 12].view(T, 4)
+        self.fsparse = self._fcnt_buf[T * 12:].view(T, 4)
         self.stats_host = np.tile(STATS_ROOT, (T, 1))
+        self.sparse_host = np.tile(SPARSE_ROOT, (T, 1))
         self.off_host = (C.c_int32 * (T + 1))()
         self.off_dev = torch.zeros(T + 1, dtype=torch.int32, device=dev)
         self.n_nodes_host = np.ones(T, dtype=np.int64)
@@ -83,6 +85,9 @@ class ForestTrees:
             self.fstats[t] = self._stats_row
             self.stats_host[t] = STATS_ROOT
             self._bound_roots.append(r)
+        if self.sparse is not None:                   # its table, flags and stats row follow on the device (_sparse_sync)
+            self.sparse_host[t] = SPARSE_ROOT
+            self._sparse_roots.append(t)
         self.fcounters[t] = self._root_row
         self.cnt_host[t] = self._ROOT
         self.n_nodes_host[t] = 1
@@ -121,6 +126,19 @@ class ForestTrees:
         """Nodes of tree t whose key is at or past its incumbent's cost (0 without an incumbent)."""
         return self._bound_stats(t)[2]()
 
+    def _sparse_stats_rows(self):
+        return self.fsparse
+
+    def dominated_candidates(self, t):
+        """``sparse_cell``: candidates of tree t that took no node because a node at most as dear holds their cell."""
+        return int(self.sparse_host[self._tree_index(t), SP_DOMINATED])
+
+    def retired_nodes(self, t):
+        return int(self.sparse_host[self._tree_index(t), SP_RETIRED])
+
+    def active_nodes(self, t):
+        return int(self.sparse_host[self._tree_index(t), SP_ACTIVE])
+
     def _tree_index(self, t):
         t = int(t)
         if not 0 <= t < self.T:
@@ -155,7 +173,8 @@ class ForestTrees:
         """-> the (T, 8) counter block, the caller's own copy (``cnt_host`` follows ``reset_tree``)."""
         buf = self._fcnt_buf.cpu().numpy()            # one small copy: the counter rows and the stats rows
         self.cnt_host = buf[:self.T * 8].reshape(self.T, 8)
-        self.stats_host = buf[self.T * 8:].reshape(self.T, 4)
+        self.stats_host = buf[self.T * 8:self.T * 12].reshape(self.T, 4)
+        self.sparse_host = buf[self.T * 12:].reshape(self.T, 4)
         self.n_nodes_host = self.cnt_host[:, CNT_NODES].astype(np.int64)
         return self.cnt_host.copy()
 
@@ -223,14 +242,15 @@ class ForestEngine(ForestTrees, ExpansionEngine):
     def __init__(self, ctx: Context, maze, start_state, goal_state, n_trees, tree_capacity, edge_length=64, action_horizon=8,
                  pred_horizon=64, local_map_size=20, local_map_scale=0.2, s_global=1.0, batch=1024, k_steps=1,
                  emulate_sticky_done=True, norm=CAR_NORM, early_exit=False, goal_scale=None, prop_duration=None, solution="first",
-                 reach=None, near_radius=None, near_reach=None):
+                 reach=None, near_radius=None, near_reach=None, sparse_cell=None, sparse_headings=None):
         capacity = self._init_forest(ctx, n_trees, tree_capacity)
         super().__init__(ctx, maze, start_state, goal_state, edge_length=edge_length, action_horizon=action_horizon,
                          pred_horizon=pred_horizon, local_map_size=local_map_size, local_map_scale=local_map_scale,
                          s_global=s_global, batch=batch, capacity=capacity, k_steps=k_steps,
                          emulate_sticky_done=emulate_sticky_done, norm=norm, early_exit=early_exit, run_type=0,
                          goal_scale=goal_scale, prop_duration=prop_duration, solution=solution, reach=reach,
-                         near_radius=near_radius, near_reach=near_reach)
+                         near_radius=near_radius, near_reach=near_reach, sparse_cell=sparse_cell,
+                         sparse_headings=sparse_headings)
 
     def expand_round(self, samples, cond_goal, noise=None, inject_actions=None, counts_per_tree=None, step_noise=None,
                      accept=True):
@@ -366,6 +386,12 @@ class SceneTrees:
 
     def tree_scene(self, t):
         return int(self.tree_scene_host[self._tree_index(t)])
+
+    def _sparse_mazes(self):                          # the sparse tree's table is sized for the largest scene
+        return self.scene_mazes
+
+    def _sparse_maze_of(self, t):
+        return self.scene_mazes[self.tree_scene(t)]
 
     def fallback_nodes(self):
         """planners/RRT.py:227-254 (run_type 0) for every tree, each against its own scene's goal_state[:2]."""

@@ -51,6 +51,18 @@ Constructor kwargs, ``plan() -> (path f32 (P,6)|None, actions f32 (A,2)|None)``,
                        of the cost column -- ``solution`` "best_of_round", "anytime" or "anytime_pruned" (then among the open
                        nodes), the car, one rank, run_type 0, a single ``prop_duration`` entry; ``plan_runs``,
                        ``plan_scenario_runs`` and ``reuse_tree`` included.
+  ``sparse_cell``      (default None: off, the planner as it is without the kwarg) metres.  The witness pruning of SST (Li,
+                       Littlefield, Bekris 2016) on a grid of ``sparse_cell`` x ``sparse_cell`` metres x ``sparse_headings``
+                       heading bins (an integer from 1 to 64, default 8) over the map (include/ditree.h "sparse tree"): of the
+                       nodes that end in one cell only the cheapest -- the cell's active node -- is looked at by the parent
+                       search (nearest node, ``near_radius``, with "anytime_pruned" among the open ones), and a candidate that
+                       lands in a cell whose node is at most as dear takes no node.  A goal-reaching candidate always gets its
+                       node, so the solutions and the incumbent rule are untouched; a displaced node stays in the tree with its
+                       subtree and its place in the fallback.  No random stream moves.  The tree stays small -- and may lose
+                       goals that the dense tree finds: large cells throw away the nodes that would have squeezed through.
+                       ``results`` gains ``dominated_candidates``, ``retired_nodes`` and ``active_nodes``.  Scope: that of
+                       ``near_radius``, with or without it; with ``reuse_tree`` the active nodes are derived again from the
+                       re-based tree.
 All of the reference's ``run_type`` values: 0 "Original"; 1 "Original+Ref" (obstacle-ahead flags per node, sampling
 biased to the part of ``init_main_path`` behind the obstacle, furthest-along-path fallback); 2 "OM+Ref" (sample
 positions drawn from the EDT prior); 3 "OM+LB+Ref" (prior log-blended with the start -> goal Gaussian, refreshed at
@@ -98,6 +110,7 @@ class RRT_Planner(BasePlanner):
         self.capacity = int(kwargs.get("capacity", 65536))
         self.solution = kwargs.get("solution", "first")
         self._check_near(kwargs)
+        self._check_sparse(kwargs)
         self._check_solution(kwargs)
         self._check_reuse(kwargs)
         sticky = kwargs.get("emulate_sticky_done", self.solution == "first")
@@ -121,7 +134,8 @@ class RRT_Planner(BasePlanner):
             emulate_sticky_done=sticky, early_exit=kwargs.get("early_exit", True),
             run_type=self.run_type, goal_scale=getattr(sampler, "local_map_size", None),
             rank=self.rank, world_size=self.world_size, process_group=self.process_group, solution=self.solution,
-            reach=self.bound_reach, near_radius=self.near_radius, near_reach=self.near_reach)
+            reach=self.bound_reach, near_radius=self.near_radius, near_reach=self.near_reach, sparse_cell=self.sparse_cell,
+            sparse_headings=self.sparse_headings)
         self._engine.env_goal = np.asarray(self.env.goal, dtype=np.float64)
         self._engine.ddpm = self._ddpm
 
@@ -185,6 +199,23 @@ class RRT_Planner(BasePlanner):
                                       "nearest node)")
         self.near_radius, self.near_speed = float(r), float(v)
         self.near_reach = self.near_speed * float(self.env_dt)        # metres a path row is assumed to cover
+
+    def _check_sparse(self, kwargs):
+        """``sparse_cell`` / ``sparse_headings``: refused by name where they are not built, before the device is touched."""
+        from ..engine import check_sparse, sparse_grid
+        self.sparse_cell = self.sparse_headings = None
+        if kwargs.get("sparse_cell") is None:
+            check_sparse(None, kwargs.get("sparse_headings"), self.solution)
+            return
+        cell, headings = check_sparse(kwargs["sparse_cell"], kwargs.get("sparse_headings"), self.solution, self.is_ant,
+                                      self.prop_duration_schedule)
+        world = int(kwargs.get("world_size", default_shard()[1]))
+        if world > 1:
+            raise NotImplementedError(f"sparse_cell: one rank (world_size {world})")
+        if self.run_type != 0:
+            raise NotImplementedError(f"sparse_cell: run_type 0 only (got run_type {self.run_type})")
+        self.sparse_cell, self.sparse_headings = cell, headings
+        sparse_grid(np.asarray(self.maze).shape, self.s_global, self.sparse_cell, self.sparse_headings)     # the table's size
 
     def _check_reuse(self, kwargs):
         """``reuse_tree``: refused by name where it is not built, before the device is touched."""
@@ -271,6 +302,8 @@ class RRT_Planner(BasePlanner):
             self.results.update(pruned_candidates=0, closed_nodes=0, bound_exhausted=False)
         if self.reuse_tree:
             self.results.update(reused_nodes=0, dropped_nodes=0)
+        if self.sparse_cell is not None:
+            self.results.update(dominated_candidates=0, retired_nodes=0, active_nodes=1)
         out = self.env.reset(options=self.options)
         if self.is_ant:
             if isinstance(out, tuple) and isinstance(out[0], dict) and "desired_goal" in out[0]:
@@ -551,6 +584,9 @@ class RRT_Planner(BasePlanner):
         if self.solution == "anytime_pruned":
             self.results.update(pruned_candidates=eng.pruned_candidates, closed_nodes=eng.closed_nodes(),
                                 bound_exhausted=bool(eng.exhausted))
+        if self.sparse_cell is not None:
+            self.results.update(dominated_candidates=eng.dominated_candidates, retired_nodes=eng.retired_nodes,
+                                active_nodes=eng.active_nodes)
         if goal is not None:
             if not self.is_ant:
                 self.env.done = True
@@ -675,7 +711,8 @@ def _scene_settings(pl):
             ("norm", e.norm.tobytes()), ("emulate_sticky_done", e.sticky), ("early_exit", e.early_exit),
             ("prop_duration", tuple(e.schedule)), ("batch", pl.batch), ("solution", getattr(pl, "solution", "first")),
             ("bound_speed", getattr(pl, "bound_speed", None)), ("near_radius", getattr(pl, "near_radius", None)),
-            ("near_speed", getattr(pl, "near_speed", None))]
+            ("near_speed", getattr(pl, "near_speed", None)), ("sparse_cell", getattr(pl, "sparse_cell", None)),
+            ("sparse_headings", getattr(pl, "sparse_headings", None))]
 
 
 def _check_scene_planners(planners):

@@ -97,7 +97,9 @@ def run_jobs(eng, jobs, batch, device):
     incumbent -- else the fallback.  Every dict carries ``solutions`` (goal nodes appended) and ``first_solution_candidates``
     (the run's candidates up to and including its first goal-reaching round, or None).  "anytime_pruned" is "anytime" with one
     more ending: a run whose tree has no open node left after a round (``eng.exhausted(t)``) finishes there with its incumbent,
-    and its tree takes the next job; its dict carries ``pruned_candidates``, ``closed_nodes`` and ``bound_exhausted`` too."""
+    and its tree takes the next job; its dict carries ``pruned_candidates``, ``closed_nodes`` and ``bound_exhausted`` too.
+    ``planner.sparse_cell`` (one value for all jobs): every dict carries ``dominated_candidates``, ``retired_nodes`` and
+    ``active_nodes`` of its tree as of the run's last accept."""
     import torch
     from ..common import map_utils
     from ..engine import ANYTIME, CNT_GOAL, CNT_ITERS
@@ -112,6 +114,7 @@ def run_jobs(eng, jobs, batch, device):
     first = solution == "first"
     anytime = solution in ANYTIME
     pruned = solution == "anytime_pruned"
+    sparse = getattr(jobs[0].planner, "sparse_cell", None) is not None
     results = [None] * len(jobs)
     queue = list(range(len(jobs)))[::-1]
     slots = [None] * T                    # per tree: [job index, RunStreams, drawn, start time, first_solution_candidates]
@@ -150,6 +153,9 @@ def run_jobs(eng, jobs, batch, device):
         if pruned:
             results[i].update(pruned_candidates=eng.pruned_candidates(t), closed_nodes=eng.closed_nodes(t),
                               bound_exhausted=bool(eng.exhausted(t)))
+        if sparse:
+            results[i].update(dominated_candidates=eng.dominated_candidates(t), retired_nodes=eng.retired_nodes(t),
+                              active_nodes=eng.active_nodes(t))
         start(t)
 
     with caller_states_kept():

@@ -32,7 +32,10 @@ extern "C" {
 #endif
 
 #define DITREE_VERSION 400          /* 0.4.0: runtime state / action width of the tree (car 6 / 2, ant 29 / 8), the ant round as a
-                                       real expansion round (collision, goal, accept), ant_rollout + stand-in model, row strides */
+                                       real expansion round (collision, goal, accept), ant_rollout + stand-in model, row strides.
+                                       Added since, without a new number (every addition is new symbols only): forests, scene
+                                       forests, branch and bound, near parent, re-planning on a kept tree, policy roll-outs, and
+                                       the sparse tree (ditree_sparse: one cheapest node per state cell) */
 
 #define DITREE_OK 0
 #define DITREE_E_ARG (-1)           /* bad argument (null pointer, size out of range) */
@@ -804,6 +807,92 @@ int32_t ditree_forest_expand_round_near(ditree_ctx* ctx, const ditree_tree* tree
                                         const ditree_forest_scenes* scenes, const ditree_round* round,
                                         const ditree_round_params* p, const ditree_bound* bound, const ditree_near* near,
                                         void* stream);
+
+/* ------------------------------------------------------------------ sparse tree: the planner's `sparse_cell`
+ * The witness pruning of SST (Li, Littlefield, Bekris 2016) on a grid: two nodes that end in the same small cell of (x, y, psi)
+ * are interchangeable, only the cheaper one -- the cell's REPRESENTATIVE -- goes on being expanded, and a candidate that lands
+ * where a cheaper node already stands takes no node at all.  It needs the cost column of ditree_accept_best.
+ * The cell of a state (x, y, psi, ..) in tree t, whose map spans W x L metres (extent row t) in nx x ny cells (dims row t):
+ *   ix = clamp(floor((x + W / 2) / cell), 0, nx - 1), iy the same with y, L and ny;
+ *   a  = psi - 2pi * floor(psi / 2pi), ih = clamp(floor(a / w), 0, nh - 1), 2pi = the double 2.0 * M_PI, w = 2pi / nh as the
+ *   caller computed it; the cell is (iy * nx + ix) * nh + ih < stride.  Every operation is a separately rounded IEEE f64 one (no
+ *   contraction); the clamps are taken on the floored doubles.  A state whose x, y or psi is not finite has no cell.
+ * ACTIVE nodes: node n is active iff it has a cell and (cost[n], n) is the lexicographic minimum over the nodes of its tree in
+ * that cell -- a pure function of the tree.  table[t * stride + cell] = ((uint64_t)cost[n] << 32) | n for the cell's active node
+ * n (the global slot), all ones for a cell without a node.  The root costs 1 and is always active.
+ * The accept (ditree_accept_sparse), per tree, behind what the mode does already (collided candidates get no node; with a bound,
+ * candidates with f >= U get none and are counted as pruned):
+ *   1. c(b) = cost[parent] + kept edge rows + 1, the cell of b = the cell of its end state.
+ *   2. Among the remaining candidates of one cell, goal-reaching ones included, the contender is the one with the smallest (c, b).
+ *   3. The contender WINS its cell iff the cell holds no node or c < the representative's cost (strict: an equal cost keeps the
+ *      older node).  A winner gets a node.
+ *   4. A goal-reaching candidate gets a node in any case; one that did not win its cell is appended inactive.
+ *   5. A candidate without a cell gets its node as without the descriptor and is never active.
+ *   6. Every other candidate gets node id -1 and counts as dominated.
+ *   7. Ids go out in candidate order, as in ditree_accept_best; a winner ranked past the tree's capacity gets no node and does
+ *      not become the representative (counters[6] is raised as ever).
+ *   8. After the call a winner that got a node is active and is its cell's table entry; the node it displaced is inactive
+ *      ("retired": it stays in the tree with its subtree, its paths and its place in the fallback).
+ * The searches of this section look at active nodes only (with a bound: active and open); scan order, strict '<' and the tie
+ * rules are those of the searches they mask.  A scan without a candidate ends as theirs does. */
+typedef struct {
+  double cell;                   /* > 0 and finite, metres */
+  double w;                      /* 2pi / nh */
+  int32_t nh;                    /* heading bins, 1 .. 64 */
+  int32_t stride;                /* table entries per tree: >= nx * ny * nh of every tree, <= 2^22 */
+  const double* extent;          /* [dev] (T, 2): W, L of each tree's map (a single tree: T = 1) */
+  const int32_t* dims;           /* [dev] (T, 2): nx, ny of each tree */
+  const int32_t* dims_host;      /* [host] (T, 2) the same numbers: validated before anything is launched */
+  uint64_t* table;               /* [dev] (T, stride): written by ditree_sparse_rebuild and the accept */
+  uint64_t* scratch;             /* [dev] (T, stride): the contenders of a round; all ones between calls (the rebuild sets it) */
+  uint8_t* active;               /* [dev] (capacity,) indexed by the global slot */
+  int32_t* stats;                /* [dev] (T, 4): [0] candidates dominated since the rebuild, [1] nodes retired since the rebuild,
+                                    [2] active nodes, [3] candidates dominated by the last accept */
+  int32_t* cand;                 /* [dev] (2 * B) scratch of the accept: c and the cell of every candidate of the round */
+} ditree_sparse;
+/* Every call of this section refuses by name (DITREE_E_ARG) before anything is launched: "sparse: descriptor missing",
+ * "sparse: cell must be > 0 and finite", "sparse: nh must be 1..64 and w > 0", "sparse: extent / dims missing", "sparse: table,
+ * scratch, active or stats missing", "sparse: stride must be 1..2^22", "sparse: nx * ny * nh of tree <t> exceeds the stride",
+ * "sparse: cost array missing", -- the accepts -- "sparse: cand scratch missing", "sparse: one rank (round->shard must be 0)", "sparse:
+ * a run_type-0 car tree (no obstacle flags or hist)"; with a bound or a near descriptor, their own refusals too. */
+
+/* table, active and stats of trees [first, first + n) from scratch, from the trees as they are (node counts read on the device;
+ * forest == NULL: the single tree, first = 0, n = 1): after a reset of a root, and after ditree_tree_rebase -- purity makes that
+ * exact; a retired node whose representative was dropped is active again.  stats rows become (0, 0, active nodes, 0). */
+int32_t ditree_sparse_rebuild(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const ditree_sparse* sparse,
+                              const int32_t* cost, int32_t first, int32_t n, void* stream);
+/* ditree_accept_best (bound == NULL) or ditree_accept_bounded (cost == bound->cost) with the rule above.  round->node_id is
+ * scratch during the call, as in ditree_accept_bounded. */
+int32_t ditree_accept_sparse(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round, int32_t* cost,
+                             const ditree_bound* bound, const ditree_sparse* sparse, void* stream);
+/* The same per tree of a forest; an empty range leaves the tree, its table rows and its stats row untouched. */
+int32_t ditree_forest_accept_sparse(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
+                                    const ditree_round* round, int32_t* cost, const ditree_bound* bound,
+                                    const ditree_sparse* sparse, void* stream);
+/* ditree_nn_argmin_bounded's arguments and outputs over the ACTIVE nodes: near == NULL the nearest node, else the near-parent
+ * rule; bound == NULL every active node, else the active and open ones. */
+int32_t ditree_nn_argmin_sparse(ditree_ctx* ctx, const ditree_tree* tree, const ditree_sparse* sparse, const ditree_near* near,
+                                const ditree_bound* bound, const double* queries, int32_t q_stride, int32_t B, int32_t n_nodes,
+                                int32_t* out_idx, double* out_state, double* out_prev_action, uint8_t* out_has_prev, void* stream);
+int32_t ditree_forest_nn_argmin_sparse(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
+                                       const ditree_sparse* sparse, const ditree_near* near, const ditree_bound* bound,
+                                       const double* queries, int32_t q_stride, int32_t B, int32_t* out_idx, double* out_state,
+                                       double* out_prev_action, uint8_t* out_has_prev, void* stream);
+/* ditree_chunk_budget (forest == NULL) or ditree_forest_chunk_budget (n_nodes not read) with the nearest ACTIVE node (bound !=
+ * NULL: active and open) as the parent whose visits are counted. */
+int32_t ditree_chunk_budget_sparse(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
+                                   const ditree_sparse* sparse, const ditree_bound* bound, const double* samples, int32_t B,
+                                   int32_t n_nodes, const int32_t* schedule_chunks, int32_t n_schedule, int32_t* parent_scratch,
+                                   int32_t* budget_out, void* stream);
+/* ditree_expand_round_near's round (bound and near each NULL or set) with the search over the active nodes; every other step is
+ * unchanged.  p->chunk_budget must be NULL, as there. */
+int32_t ditree_expand_round_sparse(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round, const ditree_round_params* p,
+                                   const ditree_bound* bound, const ditree_near* near, const ditree_sparse* sparse, void* stream);
+/* ditree_forest_expand_round_near's (scenes == NULL: a plain forest) with the search over each tree's active nodes. */
+int32_t ditree_forest_expand_round_sparse(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
+                                          const ditree_forest_scenes* scenes, const ditree_round* round,
+                                          const ditree_round_params* p, const ditree_bound* bound, const ditree_near* near,
+                                          const ditree_sparse* sparse, void* stream);
 
 /* ------------------------------------------------------------------ re-planning on a kept tree
  * The online driver re-plans from wherever the car stands on its plan (run_scenarios_with_lidar_DiTree.py:397-516).  Instead of
