@@ -127,28 +127,15 @@ static int ensure_car_scratch(ditree_ctx* ctx, int B, int lm, int P) { return en
 // chosen node's state, last action and flag are gathered into the three outputs.  nr != NULL: the near-parent rule
 // (include/ditree.h "near parent") over the same candidates instead of the nearest node.  sp != NULL: only the active nodes of the
 // sparse tree (include/ditree.h "sparse tree") are candidates.
-static void launch_nn(const ditree_tree* tree, const ditree_forest* f, int n_nodes, const ditree_bound* bd, const double* queries,
-                      int q_stride, int B, int32_t* out_idx, double* out_state, double* out_prev_action, uint8_t* out_has_prev,
-                      hipStream_t s, const ditree_near* nr = nullptr, const ditree_sparse* sp = nullptr) {
-  const double* node_state = out_state ? tree->state : nullptr;
-  const int32_t* key = bd ? bd->key : nullptr;
-  const int32_t* cost = bd ? bd->cost : nullptr;
-  const uint8_t* active = sp ? sp->active : nullptr;
-  if (nr && f)
-    launch_nn_forest_near(queries, q_stride, B, tree->xy, f->off, f->n_trees, f->counters, f->tree_capacity, out_idx, node_state,
-                          tree->last_action, tree->has_prev, out_state, out_prev_action, out_has_prev, s, tree->state_dim,
-                          tree->action_dim, key, cost, nr->cost, nr->radius, nr->reach, active);
-  else if (nr)
-    launch_nn_near(queries, q_stride, B, tree->xy, n_nodes, out_idx, node_state, tree->last_action, tree->has_prev, out_state,
-                   out_prev_action, out_has_prev, s, tree->state_dim, tree->action_dim, key, cost, tree->counters, nr->cost,
-                   nr->radius, nr->reach, active);
-  else if (f)
-    launch_nn_forest(queries, q_stride, B, tree->xy, f->off, f->n_trees, f->counters, f->tree_capacity, 0, out_idx, node_state,
-                     tree->last_action, tree->has_prev, out_state, out_prev_action, out_has_prev, s, tree->state_dim,
-                     tree->action_dim, key, cost, active);
-  else
-    launch_nn_argmin(queries, q_stride, B, tree->xy, n_nodes, out_idx, node_state, tree->last_action, tree->has_prev, out_state,
-                     out_prev_action, out_has_prev, s, tree->state_dim, tree->action_dim, key, cost, tree->counters, active);
+static void search_nodes(const ditree_tree* tree, const ditree_forest* f, int n_nodes, const ditree_bound* bd, const double* queries,
+                         int q_stride, int B, int32_t* out_idx, double* out_state, double* out_prev_action, uint8_t* out_has_prev,
+                         hipStream_t s, const ditree_near* nr = nullptr, const ditree_sparse* sp = nullptr) {
+  const NnArg a{queries, q_stride, B, (const double2*)tree->xy, out_state ? tree->state : nullptr, tree->last_action,
+                tree->has_prev, tree->state_dim, tree->action_dim, out_idx, out_state, out_prev_action, out_has_prev,
+                bd ? bd->key : nullptr, bd ? bd->cost : nullptr, sp ? sp->active : nullptr, nr ? nr->cost : nullptr,
+                nr ? nr->radius : 0.0, nr ? nr->reach : 0.0};
+  if (f) launch_nn(a, NnForest{f->off, f->n_trees, f->counters, f->tree_capacity, 0, false}, s);
+  else launch_nn(a, NnTree{n_nodes, tree->counters}, s);
 }
 
 // What a call that runs the sampler refuses before anything is launched: an incomplete schedule (t0 with dt, or with ddpm_coef
@@ -268,8 +255,9 @@ int32_t ditree_nn_argmin(ditree_ctx* ctx, const double* queries, int32_t q_strid
   if (node_state && (!node_last_action || !node_has_prev || !out_state || !out_prev_action || !out_has_prev))
     return set_err(ctx, DITREE_E_ARG, "nn_argmin: gather outputs incomplete");
   if (B == 0) return DITREE_OK;
-  launch_nn_argmin(queries, q_stride, B, node_xy, N, out_idx, node_state, node_last_action, node_has_prev, out_state,
-                   out_prev_action, out_has_prev, (hipStream_t)stream);
+  const NnArg a{queries, q_stride, B, (const double2*)node_xy, node_state, node_last_action, node_has_prev, 6, 2, out_idx,
+                out_state, out_prev_action, out_has_prev, nullptr, nullptr, nullptr, nullptr, 0.0, 0.0};
+  launch_nn(a, NnTree{N, nullptr}, (hipStream_t)stream);
   HIP_TRY(ctx, hipGetLastError());
   return DITREE_OK;
 }
@@ -538,42 +526,6 @@ static int accept_impl(ditree_ctx* ctx, const ditree_tree* tree, const ditree_fo
   return DITREE_OK;
 }
 
-int32_t ditree_accept(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round, int32_t emulate_sticky,
-                      void* stream) {
-  if (!ctx) return DITREE_E_ARG;
-  int rc = check_tree(ctx, tree);
-  if (rc) return rc;
-  rc = check_round(ctx, round);
-  if (rc) return rc;
-  if (round->B == 0) return DITREE_OK;
-  if (tree->obstacle_ahead && !ctx->maze) return set_err(ctx, DITREE_E_STATE, "accept: obstacle-ahead flags need the maze");
-  if (tree->hist && round->shard > 0 && (!round->hist || !round->hist_n))
-    return set_err(ctx, DITREE_E_ARG, "accept: a sharded round on a tree with `hist` needs the round's hist / hist_n arrays");
-  if (emulate_sticky && (tree->state_dim != 6 || tree->action_dim != 2))
-    return set_err(ctx, DITREE_E_ARG, "accept: the sticky-done emulation is the car env's (car_env.py:254,266)");
-  return accept_impl(ctx, tree, nullptr, round, AcceptMode::first, emulate_sticky, nullptr, nullptr, stream);
-}
-
-// What ditree_accept_best and ditree_forest_accept_best refuse by name before anything is launched.
-static int check_accept_best(ditree_ctx* ctx, const ditree_round* round, const int32_t* cost) {
-  if (!cost) return set_err(ctx, DITREE_E_ARG, "accept_best: cost array missing");
-  if (round->shard != 0) return set_err(ctx, DITREE_E_ARG, "accept_best: one rank (round->shard must be 0)");
-  return DITREE_OK;
-}
-
-int32_t ditree_accept_best(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round, int32_t* cost, void* stream) {
-  if (!ctx) return DITREE_E_ARG;
-  int rc = check_tree(ctx, tree);
-  if (rc) return rc;
-  rc = check_round(ctx, round);
-  if (rc) return rc;
-  rc = check_accept_best(ctx, round, cost);
-  if (rc) return rc;
-  if (round->B == 0) return DITREE_OK;
-  if (tree->obstacle_ahead && !ctx->maze) return set_err(ctx, DITREE_E_STATE, "accept_best: obstacle-ahead flags need the maze");
-  return accept_impl(ctx, tree, nullptr, round, AcceptMode::best, 0, cost, nullptr, stream);
-}
-
 // ---- re-planning on a kept tree (include/ditree.h): every host-side check runs before anything is launched; the node count
 // and the anchor's row counts live on the device and are checked there (dst->counters[0]).
 int32_t ditree_tree_rebase(ditree_ctx* ctx, const ditree_tree* src, const ditree_tree* dst, int32_t anchor,
@@ -793,7 +745,7 @@ static int ant_round_begin_impl(ditree_ctx* ctx, const ditree_tree* tree, const 
   if (rc) return rc;
   launch_round_begin(round->status, round->chunks_run, round->chunk_steps, B, tree->n_chunks, s);
   // RRT.py:141-147: nearest node -> curr_state (the live state of the round: round->end_state), prev_actions, prev_states
-  launch_nn(tree, f, p->n_nodes, nullptr, p->samples, ANT_S, B, round->parent, round->end_state, a.prev_action, a.has_prev, s);
+  search_nodes(tree, f, p->n_nodes, nullptr, p->samples, ANT_S, B, round->parent, round->end_state, a.prev_action, a.has_prev, s);
   launch_ant_gather_hist(round->parent, tree->hist, tree->hist_n, B, a.hist, a.hist_n, s);   // parents are global ids
   ctx->ant_n_run = B;
   ctx->ant_run_idx = nullptr;
@@ -1002,7 +954,7 @@ static int chunk_budget_impl(ditree_ctx* ctx, const char* who, const ditree_tree
     if (schedule_chunks[i] < 1 || schedule_chunks[i] > tree->n_chunks)
       return set_err(ctx, DITREE_E_ARG, w + ": a schedule entry exceeds the tree's edge capacity (n_chunks)");
   hipStream_t s = (hipStream_t)stream;
-  launch_nn(tree, f, n_nodes, bd, samples, tree->state_dim, B, parent_scratch, nullptr, nullptr, nullptr, s, nullptr, sp);
+  search_nodes(tree, f, n_nodes, bd, samples, tree->state_dim, B, parent_scratch, nullptr, nullptr, nullptr, s, nullptr, sp);
   launch_chunk_budget(parent_scratch, B, tree->num_visit, schedule_chunks, n_schedule, budget_out, s);
   HIP_TRY(ctx, hipGetLastError());
   return DITREE_OK;
@@ -1027,19 +979,13 @@ int32_t ditree_round_stats(ditree_ctx* ctx, int32_t* stats4) {
   return DITREE_OK;
 }
 
-// The car round of one tree, or (f != NULL, validated by the caller) of a forest: only the nearest-node step differs.  A scene
-// forest (tree_scene != NULL, validated by the caller) reads each row's maze and goal from the scene table instead.
-// bd != NULL (validated by the caller): the masked nearest-node search of the "anytime_pruned" mode.  nr != NULL (validated by
-// the caller): the near-parent rule in that search.  sp != NULL (validated by the caller): that search over the active nodes of
-// the sparse tree.
+// The car round behind car_round_entry, which has checked ctx, tree or forest, round and every descriptor passed on here: the
+// round of one tree, or (f != NULL) of a forest: only the nearest-node step differs.  A scene forest (tree_scene != NULL) reads
+// each row's maze and goal from the scene table instead.  bd != NULL: the masked nearest-node search of the "anytime_pruned"
+// mode.  nr != NULL: the near-parent rule in that search.  sp != NULL: that search over the active nodes of the sparse tree.
 static int expand_round_impl(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* f, const ditree_round* round,
                              const ditree_round_params* p, void* stream, const int32_t* tree_scene = nullptr,
                              const ditree_bound* bd = nullptr, const ditree_near* nr = nullptr, const ditree_sparse* sp = nullptr) {
-  if (!ctx) return DITREE_E_ARG;
-  int rc = check_tree(ctx, tree);
-  if (rc) return rc;
-  rc = check_round(ctx, round);
-  if (rc) return rc;
   if (!tree_scene && !ctx->maze) return set_err(ctx, DITREE_E_STATE, "expand_round: no maze uploaded");
   if (!p || !p->samples || !p->cond_goal || !p->norm || (!tree_scene && !p->goal_xy) || !p->axis ||
       (!f && (p->n_nodes <= 0 || p->n_nodes > tree->capacity)) || p->P < tree->A || (!p->noise && !p->inject_actions))
@@ -1047,11 +993,10 @@ static int expand_round_impl(ditree_ctx* ctx, const ditree_tree* tree, const dit
   if (tree->state_dim != 6 || tree->action_dim != 2)
     return set_err(ctx, DITREE_E_ARG, "expand_round: the car round needs a tree with state_dim 6 / action_dim 2 (ant: ditree_expand_round_ant)");
   const int B = round->B, A = tree->A, nC = tree->n_chunks, P = p->P;
-  if (!p->inject_actions) {
-    rc = check_sampler(ctx, "expand_round", p->t0, p->dt, p->ddpm_coef, p->step_noise, p->K, P, p->lm_n, 2, 7,
-                       " (B, n_chunks, K, P, 2)", "; the car engine needs action_dim 2, cond 7)");
-    if (rc) return rc;
-  }
+  int rc = p->inject_actions ? DITREE_OK
+                              : check_sampler(ctx, "expand_round", p->t0, p->dt, p->ddpm_coef, p->step_noise, p->K, P, p->lm_n, 2, 7,
+                                              " (B, n_chunks, K, P, 2)", "; the car engine needs action_dim 2, cond 7)");
+  if (rc) return rc;
   if (B == 0) return DITREE_OK;
   hipStream_t s = (hipStream_t)stream;
   rc = ensure_car_scratch(ctx, B, p->lm_n, P);
@@ -1071,7 +1016,7 @@ static int expand_round_impl(ditree_ctx* ctx, const ditree_tree* tree, const dit
   }
   const double gx = tree_scene ? 0.0 : p->goal_xy[0], gy = tree_scene ? 0.0 : p->goal_xy[1];   // scenes: each row's own goal
   launch_round_begin(round->status, round->chunks_run, round->chunk_steps, B, nC, s);
-  launch_nn(tree, f, p->n_nodes, bd, p->samples, 6, B, round->parent, c.state, c.prev_action, c.has_prev, s, nr, sp);
+  search_nodes(tree, f, p->n_nodes, bd, p->samples, 6, B, round->parent, c.state, c.prev_action, c.has_prev, s, nr, sp);
   const int64_t st_stride = (int64_t)nC * (A + 1) * 6, ac_stride = (int64_t)nC * A * 2;
   // One call of the round's chunk body on a row set: local map -> conditioning -> sampler (or the action tape) -> rollout.  Plain
   // chunk loop: every row at chunk j.  Pool: the ready list, each row at the chunk its chunks_run counter names (j = -1; the
@@ -1131,11 +1076,6 @@ static int expand_round_impl(ditree_ctx* ctx, const ditree_tree* tree, const dit
   return DITREE_OK;
 }
 
-int32_t ditree_expand_round(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round,
-                            const ditree_round_params* p, void* stream) {
-  return expand_round_impl(ctx, tree, nullptr, round, p, stream);
-}
-
 // ---- forests (include/ditree.h "forests"): every check runs on the host before anything is launched.
 // B >= 0: the round's candidate count must equal off[T]; B < 0: the offsets are not read.
 // ant: the tree must be an ant forest's (check_ant_forest) instead of a car tree.
@@ -1168,42 +1108,6 @@ static int check_forest(ditree_ctx* ctx, const ditree_tree* tree, const ditree_f
   return DITREE_OK;
 }
 
-int32_t ditree_forest_expand_round(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
-                                   const ditree_round* round, const ditree_round_params* p, void* stream) {
-  if (!ctx) return DITREE_E_ARG;
-  int rc = check_round(ctx, round);
-  if (rc) return rc;
-  rc = check_forest(ctx, tree, forest, round->B, "forest_expand_round");
-  if (rc) return rc;
-  return expand_round_impl(ctx, tree, forest, round, p, stream);
-}
-
-int32_t ditree_forest_accept(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const ditree_round* round,
-                             int32_t emulate_sticky, void* stream) {
-  if (!ctx) return DITREE_E_ARG;
-  int rc = check_round(ctx, round);
-  if (rc) return rc;
-  rc = check_forest(ctx, tree, forest, round->B, "forest_accept");
-  if (rc) return rc;
-  if (round->shard > 0 || tree->obstacle_ahead || tree->hist)
-    return set_err(ctx, DITREE_E_ARG, "forest_accept: a forest is one rank's run_type-0 car tree (no shards, obstacle flags or hist)");
-  return accept_impl(ctx, tree, forest, round, AcceptMode::first, emulate_sticky, nullptr, nullptr, stream);
-}
-
-int32_t ditree_forest_accept_best(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const ditree_round* round,
-                                  int32_t* cost, void* stream) {
-  if (!ctx) return DITREE_E_ARG;
-  int rc = check_round(ctx, round);
-  if (rc) return rc;
-  rc = check_forest(ctx, tree, forest, round->B, "forest_accept_best");
-  if (rc) return rc;
-  rc = check_accept_best(ctx, round, cost);
-  if (rc) return rc;
-  if (tree->obstacle_ahead || tree->hist)
-    return set_err(ctx, DITREE_E_ARG, "forest_accept_best: a forest is one rank's run_type-0 car tree (no obstacle flags or hist)");
-  return accept_impl(ctx, tree, forest, round, AcceptMode::best, 0, cost, nullptr, stream);
-}
-
 int32_t ditree_forest_chunk_budget(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const double* samples,
                                    int32_t B, const int32_t* schedule_chunks, int32_t n_schedule, int32_t* parent_scratch,
                                    int32_t* budget_out, void* stream) {
@@ -1221,7 +1125,7 @@ int32_t ditree_forest_nn_argmin(ditree_ctx* ctx, const ditree_tree* tree, const 
   if (rc) return rc;
   if (B == 0) return DITREE_OK;
   if (!queries || !out_idx || q_stride < 2) return set_err(ctx, DITREE_E_ARG, "forest_nn_argmin: bad argument");
-  launch_nn(tree, forest, 0, nullptr, queries, q_stride, B, out_idx, nullptr, nullptr, nullptr, (hipStream_t)stream);
+  search_nodes(tree, forest, 0, nullptr, queries, q_stride, B, out_idx, nullptr, nullptr, nullptr, (hipStream_t)stream);
   HIP_TRY(ctx, hipGetLastError());
   return DITREE_OK;
 }
@@ -1330,19 +1234,6 @@ static int check_scenes(ditree_ctx* ctx, const ditree_forest* f, const ditree_fo
   return DITREE_OK;
 }
 
-int32_t ditree_forest_expand_round_scenes(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
-                                          const ditree_forest_scenes* scenes, const ditree_round* round,
-                                          const ditree_round_params* p, void* stream) {
-  if (!ctx) return DITREE_E_ARG;
-  int rc = check_round(ctx, round);
-  if (rc) return rc;
-  rc = check_forest(ctx, tree, forest, round->B, "forest_expand_round_scenes");
-  if (rc) return rc;
-  rc = check_scenes(ctx, forest, scenes, "forest_expand_round_scenes");
-  if (rc) return rc;
-  return expand_round_impl(ctx, tree, forest, round, p, stream, scenes->tree_scene);
-}
-
 // ---- branch and bound (include/ditree.h "branch and bound"): what every call of the section refuses by name before anything
 // is launched.  round: the calls that take one (NULL otherwise); search: the nearest-node calls read key, cost and counters only.
 static int check_bound(ditree_ctx* ctx, const ditree_bound* bd, const ditree_round* round, bool search = false) {
@@ -1375,102 +1266,6 @@ int32_t ditree_bound_keys(ditree_ctx* ctx, const ditree_tree* tree, const ditree
   return DITREE_OK;
 }
 
-// The masked nearest-node search behind both bounded entry points (`who` in the messages) after their tree / forest check.
-static int nn_argmin_bounded_impl(ditree_ctx* ctx, const char* who, const ditree_tree* tree, const ditree_forest* f, int n_nodes,
-                                  const ditree_bound* bound, const double* queries, int q_stride, int B, int32_t* out_idx,
-                                  double* out_state, double* out_prev_action, uint8_t* out_has_prev, void* stream) {
-  const int rc = check_bound(ctx, bound, nullptr, true);
-  if (rc) return rc;
-  if (B == 0) return DITREE_OK;
-  const bool gather = out_state || out_prev_action || out_has_prev;
-  if (!queries || !out_idx || B < 0 || q_stride < 2 || (!f && (n_nodes <= 0 || n_nodes > tree->capacity)) ||
-      (gather && (!out_state || !out_prev_action || !out_has_prev)))
-    return set_err(ctx, DITREE_E_ARG, std::string(who) + ": bad argument (the three gather outputs come together)");
-  launch_nn(tree, f, n_nodes, bound, queries, q_stride, B, out_idx, out_state, out_prev_action, out_has_prev, (hipStream_t)stream);
-  HIP_TRY(ctx, hipGetLastError());
-  return DITREE_OK;
-}
-
-int32_t ditree_nn_argmin_bounded(ditree_ctx* ctx, const ditree_tree* tree, const ditree_bound* bound, const double* queries,
-                                 int32_t q_stride, int32_t B, int32_t n_nodes, int32_t* out_idx, double* out_state,
-                                 double* out_prev_action, uint8_t* out_has_prev, void* stream) {
-  if (!ctx) return DITREE_E_ARG;
-  const int rc = check_tree(ctx, tree);
-  if (rc) return rc;
-  return nn_argmin_bounded_impl(ctx, "nn_argmin_bounded", tree, nullptr, n_nodes, bound, queries, q_stride, B, out_idx, out_state,
-                                out_prev_action, out_has_prev, stream);
-}
-
-int32_t ditree_forest_nn_argmin_bounded(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
-                                        const ditree_bound* bound, const double* queries, int32_t q_stride, int32_t B,
-                                        int32_t* out_idx, double* out_state, double* out_prev_action, uint8_t* out_has_prev,
-                                        void* stream) {
-  if (!ctx) return DITREE_E_ARG;
-  const int rc = check_forest(ctx, tree, forest, B, "forest_nn_argmin_bounded");
-  if (rc) return rc;
-  return nn_argmin_bounded_impl(ctx, "forest_nn_argmin_bounded", tree, forest, 0, bound, queries, q_stride, B, out_idx, out_state,
-                                out_prev_action, out_has_prev, stream);
-}
-
-int32_t ditree_expand_round_bounded(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round,
-                                    const ditree_round_params* p, const ditree_bound* bound, void* stream) {
-  if (!ctx) return DITREE_E_ARG;
-  int rc = check_round(ctx, round);
-  if (rc) return rc;
-  rc = check_bound(ctx, bound, round);
-  if (rc) return rc;
-  if (p && p->chunk_budget)
-    return set_err(ctx, DITREE_E_ARG, "expand_round_bounded: chunk budgets are not built (p->chunk_budget must be NULL)");
-  return expand_round_impl(ctx, tree, nullptr, round, p, stream, nullptr, bound);
-}
-
-int32_t ditree_forest_expand_round_bounded(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
-                                           const ditree_forest_scenes* scenes, const ditree_round* round,
-                                           const ditree_round_params* p, const ditree_bound* bound, void* stream) {
-  if (!ctx) return DITREE_E_ARG;
-  int rc = check_round(ctx, round);
-  if (rc) return rc;
-  rc = check_forest(ctx, tree, forest, round->B, "forest_expand_round_bounded");
-  if (rc) return rc;
-  if (scenes) {
-    rc = check_scenes(ctx, forest, scenes, "forest_expand_round_bounded");
-    if (rc) return rc;
-  }
-  rc = check_bound(ctx, bound, round);
-  if (rc) return rc;
-  if (p && p->chunk_budget)
-    return set_err(ctx, DITREE_E_ARG, "expand_round_bounded: chunk budgets are not built (p->chunk_budget must be NULL)");
-  return expand_round_impl(ctx, tree, forest, round, p, stream, scenes ? scenes->tree_scene : nullptr, bound);
-}
-
-int32_t ditree_accept_bounded(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round, const ditree_bound* bound,
-                              void* stream) {
-  if (!ctx) return DITREE_E_ARG;
-  int rc = check_tree(ctx, tree);
-  if (rc) return rc;
-  rc = check_round(ctx, round);
-  if (rc) return rc;
-  rc = check_bound(ctx, bound, round);
-  if (rc) return rc;
-  if (tree->obstacle_ahead || tree->hist)
-    return set_err(ctx, DITREE_E_ARG, "accept_bounded: a run_type-0 car tree (no obstacle flags or hist)");
-  return accept_impl(ctx, tree, nullptr, round, AcceptMode::bounded, 0, bound->cost, bound, stream);
-}
-
-int32_t ditree_forest_accept_bounded(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
-                                     const ditree_round* round, const ditree_bound* bound, void* stream) {
-  if (!ctx) return DITREE_E_ARG;
-  int rc = check_round(ctx, round);
-  if (rc) return rc;
-  rc = check_forest(ctx, tree, forest, round->B, "forest_accept_bounded");
-  if (rc) return rc;
-  rc = check_bound(ctx, bound, round);
-  if (rc) return rc;
-  if (tree->obstacle_ahead || tree->hist)
-    return set_err(ctx, DITREE_E_ARG, "forest_accept_bounded: a forest is one rank's run_type-0 car tree (no obstacle flags or hist)");
-  return accept_impl(ctx, tree, forest, round, AcceptMode::bounded, 0, bound->cost, bound, stream);
-}
-
 // ---- near parent (include/ditree.h "near parent"): what every call of the section refuses by name before anything is launched.
 // round: the calls that take one (NULL otherwise).
 static int check_near(ditree_ctx* ctx, const ditree_near* nr, const ditree_round* round) {
@@ -1480,89 +1275,6 @@ static int check_near(ditree_ctx* ctx, const ditree_near* nr, const ditree_round
   if (!(nr->reach > 0.0) || !std::isfinite(nr->reach)) return set_err(ctx, DITREE_E_ARG, "near: reach must be > 0 and finite");
   if (round && round->shard != 0) return set_err(ctx, DITREE_E_ARG, "near: one rank (round->shard must be 0)");
   return DITREE_OK;
-}
-
-// The near-parent search behind both entry points (`who` in the messages) after their tree / forest check.  bound: NULL, or the
-// mask of the "anytime_pruned" mode.
-static int nn_argmin_near_impl(ditree_ctx* ctx, const char* who, const ditree_tree* tree, const ditree_forest* f, int n_nodes,
-                               const ditree_near* near, const ditree_bound* bound, const double* queries, int q_stride, int B,
-                               int32_t* out_idx, double* out_state, double* out_prev_action, uint8_t* out_has_prev, void* stream) {
-  int rc = check_near(ctx, near, nullptr);
-  if (rc) return rc;
-  if (bound) {
-    rc = check_bound(ctx, bound, nullptr, true);
-    if (rc) return rc;
-  }
-  if (B == 0) return DITREE_OK;
-  const bool gather = out_state || out_prev_action || out_has_prev;
-  if (!queries || !out_idx || B < 0 || q_stride < 2 || (!f && (n_nodes <= 0 || n_nodes > tree->capacity)) ||
-      (gather && (!out_state || !out_prev_action || !out_has_prev)))
-    return set_err(ctx, DITREE_E_ARG, std::string(who) + ": bad argument (the three gather outputs come together)");
-  launch_nn(tree, f, n_nodes, bound, queries, q_stride, B, out_idx, out_state, out_prev_action, out_has_prev, (hipStream_t)stream,
-            near);
-  HIP_TRY(ctx, hipGetLastError());
-  return DITREE_OK;
-}
-
-int32_t ditree_nn_argmin_near(ditree_ctx* ctx, const ditree_tree* tree, const ditree_near* near, const ditree_bound* bound,
-                              const double* queries, int32_t q_stride, int32_t B, int32_t n_nodes, int32_t* out_idx,
-                              double* out_state, double* out_prev_action, uint8_t* out_has_prev, void* stream) {
-  if (!ctx) return DITREE_E_ARG;
-  const int rc = check_tree(ctx, tree);
-  if (rc) return rc;
-  return nn_argmin_near_impl(ctx, "nn_argmin_near", tree, nullptr, n_nodes, near, bound, queries, q_stride, B, out_idx, out_state,
-                             out_prev_action, out_has_prev, stream);
-}
-
-int32_t ditree_forest_nn_argmin_near(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const ditree_near* near,
-                                     const ditree_bound* bound, const double* queries, int32_t q_stride, int32_t B,
-                                     int32_t* out_idx, double* out_state, double* out_prev_action, uint8_t* out_has_prev,
-                                     void* stream) {
-  if (!ctx) return DITREE_E_ARG;
-  const int rc = check_forest(ctx, tree, forest, B, "forest_nn_argmin_near");
-  if (rc) return rc;
-  return nn_argmin_near_impl(ctx, "forest_nn_argmin_near", tree, forest, 0, near, bound, queries, q_stride, B, out_idx, out_state,
-                             out_prev_action, out_has_prev, stream);
-}
-
-int32_t ditree_expand_round_near(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round, const ditree_round_params* p,
-                                 const ditree_bound* bound, const ditree_near* near, void* stream) {
-  if (!ctx) return DITREE_E_ARG;
-  int rc = check_round(ctx, round);
-  if (rc) return rc;
-  rc = check_near(ctx, near, round);
-  if (rc) return rc;
-  if (bound) {
-    rc = check_bound(ctx, bound, round);
-    if (rc) return rc;
-  }
-  if (p && p->chunk_budget)
-    return set_err(ctx, DITREE_E_ARG, "expand_round_near: chunk budgets are not built (p->chunk_budget must be NULL)");
-  return expand_round_impl(ctx, tree, nullptr, round, p, stream, nullptr, bound, near);
-}
-
-int32_t ditree_forest_expand_round_near(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
-                                        const ditree_forest_scenes* scenes, const ditree_round* round,
-                                        const ditree_round_params* p, const ditree_bound* bound, const ditree_near* near,
-                                        void* stream) {
-  if (!ctx) return DITREE_E_ARG;
-  int rc = check_round(ctx, round);
-  if (rc) return rc;
-  rc = check_forest(ctx, tree, forest, round->B, "forest_expand_round_near");
-  if (rc) return rc;
-  if (scenes) {
-    rc = check_scenes(ctx, forest, scenes, "forest_expand_round_near");
-    if (rc) return rc;
-  }
-  rc = check_near(ctx, near, round);
-  if (rc) return rc;
-  if (bound) {
-    rc = check_bound(ctx, bound, round);
-    if (rc) return rc;
-  }
-  if (p && p->chunk_budget)
-    return set_err(ctx, DITREE_E_ARG, "expand_round_near: chunk budgets are not built (p->chunk_budget must be NULL)");
-  return expand_round_impl(ctx, tree, forest, round, p, stream, scenes ? scenes->tree_scene : nullptr, bound, near);
 }
 
 // ---- sparse tree (include/ditree.h "sparse tree"): what every call of the section refuses by name before anything is
@@ -1609,90 +1321,85 @@ int32_t ditree_sparse_rebuild(ditree_ctx* ctx, const ditree_tree* tree, const di
   return DITREE_OK;
 }
 
-// The tail of both sparse accepts after their tree / forest and round check.
-static int accept_sparse_impl(ditree_ctx* ctx, const char* who, const ditree_tree* tree, const ditree_forest* f,
-                              const ditree_round* round, int32_t* cost, const ditree_bound* bound, const ditree_sparse* sparse,
-                              void* stream) {
-  int rc = check_sparse(ctx, sparse, f ? f->n_trees : 1, round, true, cost, true);
-  if (rc) return rc;
-  if (bound) {
-    rc = check_bound(ctx, bound, round);
-    if (rc) return rc;
-    if (bound->cost != cost) return set_err(ctx, DITREE_E_ARG, std::string(who) + ": cost must be bound->cost");
-  }
-  if (tree->state_dim != 6 || tree->action_dim != 2 || tree->obstacle_ahead || tree->hist)
-    return set_err(ctx, DITREE_E_ARG, "sparse: a run_type-0 car tree (no obstacle flags or hist)");
-  return accept_impl(ctx, tree, f, round, bound ? AcceptMode::bounded : AcceptMode::best, 0, cost, bound, stream, sparse);
+// ---- the entry points of the car's searches, rounds and accepts: one check each, in the order of include/ditree.h "check order".
+// What an entry requires: REQ_FOREST a forest in place of the one tree, the others a descriptor that is checked even when NULL
+// (its check names it missing); a descriptor the entry does not require is checked when present.
+enum : unsigned { REQ_FOREST = 1, REQ_SCENES = 2, REQ_SPARSE = 4, REQ_NEAR = 8, REQ_BOUND = 16 };
+
+static int check_trees(ditree_ctx* ctx, const char* who, const ditree_tree* tree, const ditree_forest* f, unsigned required, int B) {
+  return (required & REQ_FOREST) ? check_forest(ctx, tree, f, B, who) : check_tree(ctx, tree);
+}
+// sparse, near, bound over T trees.  round: the calls that take one (NULL: a search or a budget, which read key, cost and counters
+// of the bound only); accept: the accepts, whose sparse rule needs the cost column and the candidate scratch.
+static int check_descriptors(ditree_ctx* ctx, const ditree_sparse* sparse, const ditree_near* near, const ditree_bound* bound,
+                             unsigned required, int T, const ditree_round* round, const int32_t* cost = nullptr,
+                             bool accept = false) {
+  int rc = DITREE_OK;
+  if (sparse || (required & REQ_SPARSE)) rc = check_sparse(ctx, sparse, T, round, accept, cost, accept);
+  if (!rc && (near || (required & REQ_NEAR))) rc = check_near(ctx, near, round);
+  if (!rc && (bound || (required & REQ_BOUND))) rc = check_bound(ctx, bound, round, round == nullptr);
+  return rc;
 }
 
-int32_t ditree_accept_sparse(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round, int32_t* cost,
-                             const ditree_bound* bound, const ditree_sparse* sparse, void* stream) {
+// The six searches with descriptors (`who` in the messages; f == NULL: the first n_nodes nodes of the one tree).
+static int nn_entry(ditree_ctx* ctx, const char* who, const ditree_tree* tree, const ditree_forest* f, int n_nodes,
+                    const ditree_sparse* sparse, const ditree_near* near, const ditree_bound* bound, unsigned required,
+                    const double* queries, int q_stride, int B, int32_t* out_idx, double* out_state, double* out_prev_action,
+                    uint8_t* out_has_prev, void* stream) {
   if (!ctx) return DITREE_E_ARG;
-  int rc = check_tree(ctx, tree);
+  int rc = check_trees(ctx, who, tree, f, required, B);
   if (rc) return rc;
-  rc = check_round(ctx, round);
+  rc = check_descriptors(ctx, sparse, near, bound, required, f ? f->n_trees : 1, nullptr);
   if (rc) return rc;
-  return accept_sparse_impl(ctx, "accept_sparse", tree, nullptr, round, cost, bound, sparse, stream);
-}
-
-int32_t ditree_forest_accept_sparse(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
-                                    const ditree_round* round, int32_t* cost, const ditree_bound* bound,
-                                    const ditree_sparse* sparse, void* stream) {
-  if (!ctx) return DITREE_E_ARG;
-  int rc = check_round(ctx, round);
-  if (rc) return rc;
-  rc = check_forest(ctx, tree, forest, round->B, "forest_accept_sparse");
-  if (rc) return rc;
-  return accept_sparse_impl(ctx, "forest_accept_sparse", tree, forest, round, cost, bound, sparse, stream);
-}
-
-// The searches over the active nodes behind both entry points (`who` in the messages) after their tree / forest check.
-static int nn_argmin_sparse_impl(ditree_ctx* ctx, const char* who, const ditree_tree* tree, const ditree_forest* f, int n_nodes,
-                                 const ditree_sparse* sparse, const ditree_near* near, const ditree_bound* bound,
-                                 const double* queries, int q_stride, int B, int32_t* out_idx, double* out_state,
-                                 double* out_prev_action, uint8_t* out_has_prev, void* stream) {
-  int rc = check_sparse(ctx, sparse, f ? f->n_trees : 1);
-  if (rc) return rc;
-  if (near) {
-    rc = check_near(ctx, near, nullptr);
-    if (rc) return rc;
-  }
-  if (bound) {
-    rc = check_bound(ctx, bound, nullptr, true);
-    if (rc) return rc;
-  }
   if (B == 0) return DITREE_OK;
   const bool gather = out_state || out_prev_action || out_has_prev;
   if (!queries || !out_idx || B < 0 || q_stride < 2 || (!f && (n_nodes <= 0 || n_nodes > tree->capacity)) ||
       (gather && (!out_state || !out_prev_action || !out_has_prev)))
     return set_err(ctx, DITREE_E_ARG, std::string(who) + ": bad argument (the three gather outputs come together)");
-  launch_nn(tree, f, n_nodes, bound, queries, q_stride, B, out_idx, out_state, out_prev_action, out_has_prev, (hipStream_t)stream,
-            near, sparse);
+  search_nodes(tree, f, n_nodes, bound, queries, q_stride, B, out_idx, out_state, out_prev_action, out_has_prev, (hipStream_t)stream,
+               near, sparse);
   HIP_TRY(ctx, hipGetLastError());
   return DITREE_OK;
 }
 
+int32_t ditree_nn_argmin_bounded(ditree_ctx* ctx, const ditree_tree* tree, const ditree_bound* bound, const double* queries,
+                                 int32_t q_stride, int32_t B, int32_t n_nodes, int32_t* out_idx, double* out_state,
+                                 double* out_prev_action, uint8_t* out_has_prev, void* stream) {
+  return nn_entry(ctx, "nn_argmin_bounded", tree, nullptr, n_nodes, nullptr, nullptr, bound, REQ_BOUND, queries, q_stride, B, out_idx,
+                  out_state, out_prev_action, out_has_prev, stream);
+}
+int32_t ditree_forest_nn_argmin_bounded(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
+                                        const ditree_bound* bound, const double* queries, int32_t q_stride, int32_t B,
+                                        int32_t* out_idx, double* out_state, double* out_prev_action, uint8_t* out_has_prev,
+                                        void* stream) {
+  return nn_entry(ctx, "forest_nn_argmin_bounded", tree, forest, 0, nullptr, nullptr, bound, REQ_FOREST | REQ_BOUND, queries, q_stride,
+                  B, out_idx, out_state, out_prev_action, out_has_prev, stream);
+}
+int32_t ditree_nn_argmin_near(ditree_ctx* ctx, const ditree_tree* tree, const ditree_near* near, const ditree_bound* bound,
+                              const double* queries, int32_t q_stride, int32_t B, int32_t n_nodes, int32_t* out_idx,
+                              double* out_state, double* out_prev_action, uint8_t* out_has_prev, void* stream) {
+  return nn_entry(ctx, "nn_argmin_near", tree, nullptr, n_nodes, nullptr, near, bound, REQ_NEAR, queries, q_stride, B, out_idx,
+                  out_state, out_prev_action, out_has_prev, stream);
+}
+int32_t ditree_forest_nn_argmin_near(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const ditree_near* near,
+                                     const ditree_bound* bound, const double* queries, int32_t q_stride, int32_t B,
+                                     int32_t* out_idx, double* out_state, double* out_prev_action, uint8_t* out_has_prev,
+                                     void* stream) {
+  return nn_entry(ctx, "forest_nn_argmin_near", tree, forest, 0, nullptr, near, bound, REQ_FOREST | REQ_NEAR, queries, q_stride, B,
+                  out_idx, out_state, out_prev_action, out_has_prev, stream);
+}
 int32_t ditree_nn_argmin_sparse(ditree_ctx* ctx, const ditree_tree* tree, const ditree_sparse* sparse, const ditree_near* near,
                                 const ditree_bound* bound, const double* queries, int32_t q_stride, int32_t B, int32_t n_nodes,
                                 int32_t* out_idx, double* out_state, double* out_prev_action, uint8_t* out_has_prev, void* stream) {
-  if (!ctx) return DITREE_E_ARG;
-  const int rc = check_tree(ctx, tree);
-  if (rc) return rc;
-  if (!sparse) return set_err(ctx, DITREE_E_ARG, "sparse: descriptor missing");
-  return nn_argmin_sparse_impl(ctx, "nn_argmin_sparse", tree, nullptr, n_nodes, sparse, near, bound, queries, q_stride, B, out_idx,
-                               out_state, out_prev_action, out_has_prev, stream);
+  return nn_entry(ctx, "nn_argmin_sparse", tree, nullptr, n_nodes, sparse, near, bound, REQ_SPARSE, queries, q_stride, B, out_idx,
+                  out_state, out_prev_action, out_has_prev, stream);
 }
-
 int32_t ditree_forest_nn_argmin_sparse(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
                                        const ditree_sparse* sparse, const ditree_near* near, const ditree_bound* bound,
                                        const double* queries, int32_t q_stride, int32_t B, int32_t* out_idx, double* out_state,
                                        double* out_prev_action, uint8_t* out_has_prev, void* stream) {
-  if (!ctx) return DITREE_E_ARG;
-  const int rc = check_forest(ctx, tree, forest, B, "forest_nn_argmin_sparse");
-  if (rc) return rc;
-  if (!sparse) return set_err(ctx, DITREE_E_ARG, "sparse: descriptor missing");
-  return nn_argmin_sparse_impl(ctx, "forest_nn_argmin_sparse", tree, forest, 0, sparse, near, bound, queries, q_stride, B, out_idx,
-                               out_state, out_prev_action, out_has_prev, stream);
+  return nn_entry(ctx, "forest_nn_argmin_sparse", tree, forest, 0, sparse, near, bound, REQ_FOREST | REQ_SPARSE, queries, q_stride, B,
+                  out_idx, out_state, out_prev_action, out_has_prev, stream);
 }
 
 int32_t ditree_chunk_budget_sparse(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
@@ -1702,62 +1409,173 @@ int32_t ditree_chunk_budget_sparse(ditree_ctx* ctx, const ditree_tree* tree, con
   if (!ctx) return DITREE_E_ARG;
   int rc = forest ? check_forest(ctx, tree, forest, B, "chunk_budget_sparse") : check_tree(ctx, tree);
   if (rc) return rc;
-  if (!sparse) return set_err(ctx, DITREE_E_ARG, "sparse: descriptor missing");
-  rc = check_sparse(ctx, sparse, forest ? forest->n_trees : 1);
+  rc = check_descriptors(ctx, sparse, nullptr, bound, REQ_SPARSE, forest ? forest->n_trees : 1, nullptr);
   if (rc) return rc;
-  if (bound) {
-    rc = check_bound(ctx, bound, nullptr, true);
-    if (rc) return rc;
-  }
   return chunk_budget_impl(ctx, "chunk_budget_sparse", tree, forest, n_nodes, samples, B, schedule_chunks, n_schedule,
                            parent_scratch, budget_out, stream, bound, sparse);
 }
 
-// What both sparse rounds check behind their tree / forest and round check.
-static int check_round_sparse(ditree_ctx* ctx, const ditree_round* round, const ditree_round_params* p, const ditree_bound* bound,
-                              const ditree_near* near, const ditree_sparse* sparse, int T) {
-  if (!sparse) return set_err(ctx, DITREE_E_ARG, "sparse: descriptor missing");
-  int rc = check_sparse(ctx, sparse, T, round);
-  if (rc) return rc;
-  if (near) {
-    rc = check_near(ctx, near, round);
-    if (rc) return rc;
-  }
-  if (bound) {
-    rc = check_bound(ctx, bound, round);
-    if (rc) return rc;
-  }
-  if (p && p->chunk_budget)
-    return set_err(ctx, DITREE_E_ARG, "expand_round_sparse: chunk budgets are not built (p->chunk_budget must be NULL)");
-  return DITREE_OK;
-}
-
-int32_t ditree_expand_round_sparse(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round, const ditree_round_params* p,
-                                   const ditree_bound* bound, const ditree_near* near, const ditree_sparse* sparse, void* stream) {
+// The nine car rounds.  who: the family's name without the forest's prefix, as the chunk-budget refusal of the rounds with a
+// descriptor spells it; the forest's and the scenes' messages carry "forest_" + who.
+static int car_round_entry(ditree_ctx* ctx, const char* who, const ditree_tree* tree, const ditree_forest* forest,
+                           const ditree_forest_scenes* scenes, const ditree_round* round, const ditree_round_params* p,
+                           const ditree_bound* bound, const ditree_near* near, const ditree_sparse* sparse, unsigned required,
+                           void* stream) {
   if (!ctx) return DITREE_E_ARG;
   int rc = check_round(ctx, round);
   if (rc) return rc;
-  rc = check_round_sparse(ctx, round, p, bound, near, sparse, 1);
+  const std::string fw = (required & REQ_FOREST) ? std::string("forest_") + who : std::string();   // a single tree has no use for it
+  rc = check_trees(ctx, fw.c_str(), tree, forest, required, round->B);
   if (rc) return rc;
-  return expand_round_impl(ctx, tree, nullptr, round, p, stream, nullptr, bound, near, sparse);
+  if (scenes || (required & REQ_SCENES)) {
+    rc = check_scenes(ctx, forest, scenes, fw.c_str());
+    if (rc) return rc;
+  }
+  rc = check_descriptors(ctx, sparse, near, bound, required, forest ? forest->n_trees : 1, round);
+  if (rc) return rc;
+  if ((required & (REQ_SPARSE | REQ_NEAR | REQ_BOUND)) && p && p->chunk_budget)
+    return set_err(ctx, DITREE_E_ARG, std::string(who) + ": chunk budgets are not built (p->chunk_budget must be NULL)");
+  return expand_round_impl(ctx, tree, forest, round, p, stream, scenes ? scenes->tree_scene : nullptr, bound, near, sparse);
 }
 
+int32_t ditree_expand_round(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round,
+                            const ditree_round_params* p, void* stream) {
+  return car_round_entry(ctx, "expand_round", tree, nullptr, nullptr, round, p, nullptr, nullptr, nullptr, 0, stream);
+}
+int32_t ditree_forest_expand_round(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
+                                   const ditree_round* round, const ditree_round_params* p, void* stream) {
+  return car_round_entry(ctx, "expand_round", tree, forest, nullptr, round, p, nullptr, nullptr, nullptr, REQ_FOREST, stream);
+}
+int32_t ditree_forest_expand_round_scenes(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
+                                          const ditree_forest_scenes* scenes, const ditree_round* round,
+                                          const ditree_round_params* p, void* stream) {
+  return car_round_entry(ctx, "expand_round_scenes", tree, forest, scenes, round, p, nullptr, nullptr, nullptr, REQ_FOREST | REQ_SCENES,
+                         stream);
+}
+int32_t ditree_expand_round_bounded(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round,
+                                    const ditree_round_params* p, const ditree_bound* bound, void* stream) {
+  return car_round_entry(ctx, "expand_round_bounded", tree, nullptr, nullptr, round, p, bound, nullptr, nullptr, REQ_BOUND, stream);
+}
+int32_t ditree_forest_expand_round_bounded(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
+                                           const ditree_forest_scenes* scenes, const ditree_round* round,
+                                           const ditree_round_params* p, const ditree_bound* bound, void* stream) {
+  return car_round_entry(ctx, "expand_round_bounded", tree, forest, scenes, round, p, bound, nullptr, nullptr, REQ_FOREST | REQ_BOUND,
+                         stream);
+}
+int32_t ditree_expand_round_near(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round, const ditree_round_params* p,
+                                 const ditree_bound* bound, const ditree_near* near, void* stream) {
+  return car_round_entry(ctx, "expand_round_near", tree, nullptr, nullptr, round, p, bound, near, nullptr, REQ_NEAR, stream);
+}
+int32_t ditree_forest_expand_round_near(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
+                                        const ditree_forest_scenes* scenes, const ditree_round* round,
+                                        const ditree_round_params* p, const ditree_bound* bound, const ditree_near* near,
+                                        void* stream) {
+  return car_round_entry(ctx, "expand_round_near", tree, forest, scenes, round, p, bound, near, nullptr, REQ_FOREST | REQ_NEAR, stream);
+}
+int32_t ditree_expand_round_sparse(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round, const ditree_round_params* p,
+                                   const ditree_bound* bound, const ditree_near* near, const ditree_sparse* sparse, void* stream) {
+  return car_round_entry(ctx, "expand_round_sparse", tree, nullptr, nullptr, round, p, bound, near, sparse, REQ_SPARSE, stream);
+}
 int32_t ditree_forest_expand_round_sparse(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
                                           const ditree_forest_scenes* scenes, const ditree_round* round,
                                           const ditree_round_params* p, const ditree_bound* bound, const ditree_near* near,
                                           const ditree_sparse* sparse, void* stream) {
+  return car_round_entry(ctx, "expand_round_sparse", tree, forest, scenes, round, p, bound, near, sparse, REQ_FOREST | REQ_SPARSE,
+                         stream);
+}
+
+// The eight car accepts: the shared part of their check (`who` in the forest's messages); each adds its family's own rules.
+static int accept_entry(ditree_ctx* ctx, const char* who, const ditree_tree* tree, const ditree_forest* forest,
+                        const ditree_round* round, unsigned required, const int32_t* cost = nullptr,
+                        const ditree_bound* bound = nullptr, const ditree_sparse* sparse = nullptr) {
   if (!ctx) return DITREE_E_ARG;
   int rc = check_round(ctx, round);
   if (rc) return rc;
-  rc = check_forest(ctx, tree, forest, round->B, "forest_expand_round_sparse");
+  rc = check_trees(ctx, who, tree, forest, required, round->B);
   if (rc) return rc;
-  if (scenes) {
-    rc = check_scenes(ctx, forest, scenes, "forest_expand_round_sparse");
-    if (rc) return rc;
-  }
-  rc = check_round_sparse(ctx, round, p, bound, near, sparse, forest->n_trees);
+  return check_descriptors(ctx, sparse, nullptr, bound, required, forest ? forest->n_trees : 1, round, cost, true);
+}
+// What ditree_accept_best and ditree_forest_accept_best refuse by name before anything is launched.
+static int check_accept_best(ditree_ctx* ctx, const ditree_round* round, const int32_t* cost) {
+  if (!cost) return set_err(ctx, DITREE_E_ARG, "accept_best: cost array missing");
+  if (round->shard != 0) return set_err(ctx, DITREE_E_ARG, "accept_best: one rank (round->shard must be 0)");
+  return DITREE_OK;
+}
+
+int32_t ditree_accept(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round, int32_t emulate_sticky,
+                      void* stream) {
+  const int rc = accept_entry(ctx, "accept", tree, nullptr, round, 0);
   if (rc) return rc;
-  return expand_round_impl(ctx, tree, forest, round, p, stream, scenes ? scenes->tree_scene : nullptr, bound, near, sparse);
+  if (round->B == 0) return DITREE_OK;
+  if (tree->obstacle_ahead && !ctx->maze) return set_err(ctx, DITREE_E_STATE, "accept: obstacle-ahead flags need the maze");
+  if (tree->hist && round->shard > 0 && (!round->hist || !round->hist_n))
+    return set_err(ctx, DITREE_E_ARG, "accept: a sharded round on a tree with `hist` needs the round's hist / hist_n arrays");
+  if (emulate_sticky && (tree->state_dim != 6 || tree->action_dim != 2))
+    return set_err(ctx, DITREE_E_ARG, "accept: the sticky-done emulation is the car env's (car_env.py:254,266)");
+  return accept_impl(ctx, tree, nullptr, round, AcceptMode::first, emulate_sticky, nullptr, nullptr, stream);
+}
+int32_t ditree_forest_accept(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const ditree_round* round,
+                             int32_t emulate_sticky, void* stream) {
+  const int rc = accept_entry(ctx, "forest_accept", tree, forest, round, REQ_FOREST);
+  if (rc) return rc;
+  if (round->shard > 0 || tree->obstacle_ahead || tree->hist)
+    return set_err(ctx, DITREE_E_ARG, "forest_accept: a forest is one rank's run_type-0 car tree (no shards, obstacle flags or hist)");
+  return accept_impl(ctx, tree, forest, round, AcceptMode::first, emulate_sticky, nullptr, nullptr, stream);
+}
+int32_t ditree_accept_best(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round, int32_t* cost, void* stream) {
+  int rc = accept_entry(ctx, "accept_best", tree, nullptr, round, 0);
+  if (rc) return rc;
+  rc = check_accept_best(ctx, round, cost);
+  if (rc) return rc;
+  if (round->B == 0) return DITREE_OK;
+  if (tree->obstacle_ahead && !ctx->maze) return set_err(ctx, DITREE_E_STATE, "accept_best: obstacle-ahead flags need the maze");
+  return accept_impl(ctx, tree, nullptr, round, AcceptMode::best, 0, cost, nullptr, stream);
+}
+int32_t ditree_forest_accept_best(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const ditree_round* round,
+                                  int32_t* cost, void* stream) {
+  int rc = accept_entry(ctx, "forest_accept_best", tree, forest, round, REQ_FOREST);
+  if (rc) return rc;
+  rc = check_accept_best(ctx, round, cost);
+  if (rc) return rc;
+  if (tree->obstacle_ahead || tree->hist)
+    return set_err(ctx, DITREE_E_ARG, "forest_accept_best: a forest is one rank's run_type-0 car tree (no obstacle flags or hist)");
+  return accept_impl(ctx, tree, forest, round, AcceptMode::best, 0, cost, nullptr, stream);
+}
+int32_t ditree_accept_bounded(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round, const ditree_bound* bound,
+                              void* stream) {
+  const int rc = accept_entry(ctx, "accept_bounded", tree, nullptr, round, REQ_BOUND, nullptr, bound);
+  if (rc) return rc;
+  if (tree->obstacle_ahead || tree->hist)
+    return set_err(ctx, DITREE_E_ARG, "accept_bounded: a run_type-0 car tree (no obstacle flags or hist)");
+  return accept_impl(ctx, tree, nullptr, round, AcceptMode::bounded, 0, bound->cost, bound, stream);
+}
+int32_t ditree_forest_accept_bounded(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
+                                     const ditree_round* round, const ditree_bound* bound, void* stream) {
+  const int rc = accept_entry(ctx, "forest_accept_bounded", tree, forest, round, REQ_FOREST | REQ_BOUND, nullptr, bound);
+  if (rc) return rc;
+  if (tree->obstacle_ahead || tree->hist)
+    return set_err(ctx, DITREE_E_ARG, "forest_accept_bounded: a forest is one rank's run_type-0 car tree (no obstacle flags or hist)");
+  return accept_impl(ctx, tree, forest, round, AcceptMode::bounded, 0, bound->cost, bound, stream);
+}
+// The tail of both sparse accepts (`who` in the messages; f == NULL: the one tree).
+static int accept_sparse(ditree_ctx* ctx, const char* who, const ditree_tree* tree, const ditree_forest* f, unsigned required,
+                         const ditree_round* round, int32_t* cost, const ditree_bound* bound, const ditree_sparse* sparse,
+                         void* stream) {
+  const int rc = accept_entry(ctx, who, tree, f, round, required | REQ_SPARSE, cost, bound, sparse);
+  if (rc) return rc;
+  if (bound && bound->cost != cost) return set_err(ctx, DITREE_E_ARG, std::string(who) + ": cost must be bound->cost");
+  if (tree->state_dim != 6 || tree->action_dim != 2 || tree->obstacle_ahead || tree->hist)
+    return set_err(ctx, DITREE_E_ARG, "sparse: a run_type-0 car tree (no obstacle flags or hist)");
+  return accept_impl(ctx, tree, f, round, bound ? AcceptMode::bounded : AcceptMode::best, 0, cost, bound, stream, sparse);
+}
+int32_t ditree_accept_sparse(ditree_ctx* ctx, const ditree_tree* tree, const ditree_round* round, int32_t* cost,
+                             const ditree_bound* bound, const ditree_sparse* sparse, void* stream) {
+  return accept_sparse(ctx, "accept_sparse", tree, nullptr, 0, round, cost, bound, sparse, stream);
+}
+int32_t ditree_forest_accept_sparse(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest,
+                                    const ditree_round* round, int32_t* cost, const ditree_bound* bound,
+                                    const ditree_sparse* sparse, void* stream) {
+  return accept_sparse(ctx, "forest_accept_sparse", tree, forest, REQ_FOREST, round, cost, bound, sparse, stream);
 }
 
 int32_t ditree_forest_fallback_goals(ditree_ctx* ctx, const ditree_tree* tree, const ditree_forest* forest, const double* goal_xy,

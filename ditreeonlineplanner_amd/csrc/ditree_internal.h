@@ -108,33 +108,45 @@ int set_err(ditree_ctx* ctx, int code, const std::string& msg);
 
 // geom_kernels.hip launchers (all asynchronous on `s`)
 void launch_maze_convert(const float* src, unsigned char* dst, int n, hipStream_t s);
-// key != NULL: the masked search of the "anytime_pruned" mode (only nodes with key[n] < cost[incumbent] take part); a single
-// tree's incumbent is read from `counters`, a forest's from each tree's row of its own counters.  active != NULL (every search
-// below): only nodes with active[n] != 0 take part (include/ditree.h "sparse tree"), beside the key's mask where there is one
-void launch_nn_argmin(const double* queries, int q_stride, int B, const double* node_xy, int N,
-                      int32_t* out_idx, const double* node_state, const double* node_last_action,
-                      const uint8_t* node_has_prev, double* out_state, double* out_prev_action,
-                      uint8_t* out_has_prev, hipStream_t s, int S = 6, int D = 2, const int32_t* key = nullptr,
-                      const int32_t* cost = nullptr, const int32_t* counters = nullptr, const uint8_t* active = nullptr);
-void launch_nn_forest(const double* queries, int q_stride, int B, const double* node_xy, const int32_t* off, int T,
-                      const int32_t* counters, int C, int skip, int32_t* out_idx, const double* node_state,
-                      const double* node_last_action, const uint8_t* node_has_prev, double* out_state, double* out_prev_action,
-                      uint8_t* out_has_prev, hipStream_t s, int S = 6, int D = 2, const int32_t* key = nullptr,
-                      const int32_t* cost = nullptr, const uint8_t* active = nullptr);
+// The argument block of the nearest-node searches, passed to the kernels by value: B query rows of q_stride doubles (x, y
+// first), the node columns, and where the result goes.  state == NULL: only out_idx is written; else the chosen node's state,
+// last action and flag are gathered into the three outputs (S <= 64, D <= 32).
+struct NnArg {
+  const double* queries;
+  int q_stride, B;
+  const double2* xy;
+  const double* state;
+  const double* last_action;
+  const uint8_t* has_prev;
+  int S, D;
+  int32_t* out_idx;
+  double* out_state;
+  double* out_prev_action;
+  uint8_t* out_has_prev;
+  const int32_t* key;       // != NULL: the mask of the "anytime_pruned" mode, only nodes with key[n] < bcost[incumbent] take part
+  const int32_t* bcost;     //          (the incumbent as the segment's counter row names it)
+  const uint8_t* active;    // != NULL: only nodes with active[n] != 0 take part (include/ditree.h "sparse tree")
+  const int32_t* cost;      // != NULL: the near-parent rule (include/ditree.h ditree_near) with this cost column, radius and reach
+  double radius, reach;
+};
+// Which nodes a search covers: the first N of one tree (counters: its counter row, read under the key's mask only), or for
+// every query its own tree of a forest -- T trees of C slots, tree t from slot `skip` up to its counter row's node count; off:
+// the candidate offsets (NULL: query t belongs to tree t); norm: the fallback's key instead of the squared distance.
+struct NnTree {
+  int N;
+  const int32_t* counters;
+};
+struct NnForest {
+  const int32_t* off;
+  int T;
+  const int32_t* counters;
+  int C, skip;
+  bool norm;
+};
+void launch_nn(const NnArg& a, const NnTree& seg, hipStream_t s);
+void launch_nn(const NnArg& a, const NnForest& seg, hipStream_t s);
 void launch_forest_fallback(const double* goals, int T, const double* node_xy, const int32_t* counters, int C, int32_t* out_idx,
                             hipStream_t s);
-// the near-parent forms of the two searches (include/ditree.h ditree_near): key / bcost as launch_nn_argmin's key / cost (NULL:
-// unmasked), cost / radius / reach the near descriptor's
-void launch_nn_near(const double* queries, int q_stride, int B, const double* node_xy, int N, int32_t* out_idx,
-                    const double* node_state, const double* node_last_action, const uint8_t* node_has_prev, double* out_state,
-                    double* out_prev_action, uint8_t* out_has_prev, hipStream_t s, int S, int D, const int32_t* key,
-                    const int32_t* bcost, const int32_t* counters, const int32_t* cost, double radius, double reach,
-                    const uint8_t* active = nullptr);
-void launch_nn_forest_near(const double* queries, int q_stride, int B, const double* node_xy, const int32_t* off, int T,
-                           const int32_t* counters, int C, int32_t* out_idx, const double* node_state,
-                           const double* node_last_action, const uint8_t* node_has_prev, double* out_state, double* out_prev_action,
-                           uint8_t* out_has_prev, hipStream_t s, int S, int D, const int32_t* key, const int32_t* bcost,
-                           const int32_t* cost, double radius, double reach, const uint8_t* active = nullptr);
 // the bound of the "anytime_pruned" rounds travels to the kernels as the public descriptor (include/ditree.h ditree_bound)
 using BoundArg = ditree_bound;
 void launch_bound_keys(const double* xy, int first, int n, int C, const BoundArg& bd, hipStream_t s);

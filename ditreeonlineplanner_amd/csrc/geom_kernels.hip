@@ -38,9 +38,10 @@ __device__ __forceinline__ void stage_maze(unsigned char* lds, const unsigned ch
   __syncthreads();
 }
 
-// ------------------------------------------------------------------------- nearest node
-// One wave per group of QPW queries; lanes stride the node array (coalesced 16-B loads),
-// then a 64-lane arg-min reduction carrying (distance, index); ties -> lowest index.
+// ------------------------------------------------------------------------- nearest node, near parent
+// One scan trip (scan_nodes), one nearest pass (nearest), one near-parent search on top of it (near_parent), one tree lookup
+// (tree_of_query) and one gather epilogue (write_parent) behind the four kernels: nn_argmin_kernel / nn_near_kernel serve a single
+// tree with NN_QPW queries per wave, nn_forest_kernel / nn_forest_near_kernel a forest with one query per wave.
 #define NN_QPW 4
 // The bound of a branch-and-bound round (include/ditree.h ditree_bound): U = cost[incumbent] as the tree's counter row names
 // it, INT32_MAX without one.  The counter row is not written between a round's nearest-node search and its accept's pick, so
@@ -63,150 +64,24 @@ __device__ __forceinline__ int bound_h(double x, double y, double gx, double gy,
 // MASK (the planner's "anytime_pruned" mode, ditree_nn_argmin_bounded): only open nodes, key[n] < U, take part in the compare
 // -- eight more independent coalesced i32 loads per trip beside the eight double2 loads; a closed node is masked exactly as an
 // index past N is.  Scan order, strict '<' and the reduction are unchanged, so with U = INT32_MAX the result is the unmasked
-// kernel's, and a scan without an open node ends as an all-NaN scan does (node 0).  MASK = false is the kernel as it was before
-// the flag: the trailing arguments are not read.
+// kernel's, and a scan without an open node ends as an all-NaN scan does (node 0).
 // MASK is a bit set: MASK_KEY the mask above, MASK_ACTIVE (include/ditree.h "sparse tree") only nodes with active[n] != 0 take part
 // -- eight byte loads per trip --, both: nodes that are active and open.
 #define MASK_KEY 1
 #define MASK_ACTIVE 2
-template <int MASK>
-__global__ void __launch_bounds__(256)
-nn_argmin_kernel(const double* __restrict__ queries, int q_stride, int B, const double2* __restrict__ node_xy,
-                 int N, int32_t* __restrict__ out_idx, const double* __restrict__ node_state,
-                 const double* __restrict__ node_last_action, const uint8_t* __restrict__ node_has_prev,
-                 double* __restrict__ out_state, double* __restrict__ out_prev_action,
-                 uint8_t* __restrict__ out_has_prev, int S, int D, const int32_t* __restrict__ key,
-                 const int32_t* __restrict__ cost, const int32_t* __restrict__ counters, const uint8_t* __restrict__ active) {
-  const int lane = threadIdx.x & 63;
-  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int q0 = wave * NN_QPW;
-  if (q0 >= B) return;
-  int U = 0x7fffffff;
-  if constexpr (MASK & MASK_KEY) U = bound_of(counters, cost);
-  double qx[NN_QPW], qy[NN_QPW], best[NN_QPW];
-  int bidx[NN_QPW];
-#pragma unroll
-  for (int k = 0; k < NN_QPW; ++k) {
-    int q = min(q0 + k, B - 1);
-    qx[k] = queries[(size_t)q * q_stride + 0];
-    qy[k] = queries[(size_t)q * q_stride + 1];
-    best[k] = __builtin_huge_val();
-    bidx[k] = 0x7fffffff;
-  }
-  // eight nodes per trip: their loads are independent (one load - wait - compare round per node exposes a memory round trip
-  // N / 64 times: 1.1 ms of a round at 10^5 nodes), only the running minima chain; indices past N are clamped for the load and
-  // masked for the compare, the scan order per lane is unchanged (increasing index, strict '<': lowest index wins)
-  for (int i = lane; i < N; i += 8 * WAVE) {
-    double2 p[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) p[u] = node_xy[min(i + u * WAVE, N - 1)];
-    int kk[8];
-    if constexpr (MASK & MASK_KEY) {
-#pragma unroll
-      for (int u = 0; u < 8; ++u) kk[u] = key[min(i + u * WAVE, N - 1)];
-    }
-    uint8_t aa[8];
-    if constexpr (MASK & MASK_ACTIVE) {
-#pragma unroll
-      for (int u = 0; u < 8; ++u) aa[u] = active[min(i + u * WAVE, N - 1)];
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int iu = i + u * WAVE;
-      bool in = iu < N;
-      if constexpr (MASK & MASK_KEY) in = in && kk[u] < U;
-      if constexpr (MASK & MASK_ACTIVE) in = in && aa[u] != 0;
-      if (in) {
-#pragma unroll
-        for (int k = 0; k < NN_QPW; ++k) {
-          double dx = qx[k] - p[u].x, dy = qy[k] - p[u].y;
-          double d = dx * dx + dy * dy;
-          if (d < best[k]) { best[k] = d; bidx[k] = iu; }     // strict: keeps the lowest index per lane
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < NN_QPW; ++k) {
-    double d = best[k];
-    int ix = bidx[k];
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-      double od = __shfl_xor(d, m);
-      int oi = __shfl_xor(ix, m);
-      if (od < d || (od == d && oi < ix)) { d = od; ix = oi; }
-    }
-    // NaN distances never win a '<'; an all-NaN scan leaves 0x7fffffff -> clamp to node 0
-    if (ix == 0x7fffffff) ix = 0;
-    int q = q0 + k;
-    if (q < B) {
-      if (lane == 0) out_idx[q] = ix;
-      if (node_state != nullptr) {
-        if (lane < S) out_state[(size_t)q * S + lane] = node_state[(size_t)ix * S + lane];               // S <= 64
-        if (lane >= 32 && lane < 32 + D) out_prev_action[(size_t)q * D + (lane - 32)] = node_last_action[(size_t)ix * D + (lane - 32)];
-        if (lane == 63) out_has_prev[q] = node_has_prev[ix];
-      }
-    }
-  }
-}
-void launch_nn_argmin(const double* queries, int q_stride, int B, const double* node_xy, int N, int32_t* out_idx,
-                      const double* node_state, const double* node_last_action, const uint8_t* node_has_prev,
-                      double* out_state, double* out_prev_action, uint8_t* out_has_prev, hipStream_t s, int S, int D,
-                      const int32_t* key, const int32_t* cost, const int32_t* counters, const uint8_t* active) {
-  int waves = (B + NN_QPW - 1) / NN_QPW;
-  int blocks = (waves + 3) / 4;
-  const auto kernel = active ? (key ? nn_argmin_kernel<MASK_KEY | MASK_ACTIVE> : nn_argmin_kernel<MASK_ACTIVE>)
-                             : (key ? nn_argmin_kernel<MASK_KEY> : nn_argmin_kernel<0>);
-  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, s, queries, q_stride, B, (const double2*)node_xy, N, out_idx, node_state,
-                     node_last_action, node_has_prev, out_state, out_prev_action, out_has_prev, S, D, key, cost, counters, active);
-}
-
-// Segmented nearest node of a forest (include/ditree.h ditree_forest): query q belongs to tree t -- the t whose candidate range
-// [off[t], off[t+1]) holds q, or t = q without offsets (one query per tree) -- and searches only that tree's node slots
-// [t*C + skip, t*C + n_t), n_t read from the tree's counter row.  Queries of one wave may belong to different trees (at one
-// candidate per run they always do), so every wave takes one query; the scan keeps nn_argmin_kernel's eight independent node
-// loads per trip, strict '<' per lane and the (distance, index) reduction, so the result is nn_argmin_kernel's on the segment
-// alone (an all-NaN scan clamps to the segment's first slot).  A segment with no node gives -1 and gathers nothing.
-// NORM: the key of the fallback choice (planners/RRT.py:233-237, np.argmin of np.linalg.norm(state[:2] - goal)) instead of the
-// squared distance: sqrt(fma(dy, dy, dx*dx)) as fallback_select_kernel and oracle/rrt.py::fallback_node compute it.  sqrt merges
-// neighbouring doubles, so two nodes whose squares differ in the last place can have equal norms; the reference then returns
-// the lower index, which the square's strict '<' would not.  The expansion search (NORM = false) keeps the squared distance:
-// it is pinned bit for bit to the KDTree goldens, and its instantiation is the kernel as it was before the flag.
-// MASK: nn_argmin_kernel's, with each tree's own bound U read from its counter row; key and cost are indexed by the global slot.
-// MASK = 0 leaves the two instantiations as they were before the flag: the trailing arguments are not read.
-template <bool NORM, int MASK = 0>
-__global__ void __launch_bounds__(256)
-nn_forest_kernel(const double* __restrict__ queries, int q_stride, int B, const double2* __restrict__ node_xy,
-                 const int32_t* __restrict__ off, int T, const int32_t* __restrict__ counters, int C, int skip,
-                 int32_t* __restrict__ out_idx, const double* __restrict__ node_state,
-                 const double* __restrict__ node_last_action, const uint8_t* __restrict__ node_has_prev,
-                 double* __restrict__ out_state, double* __restrict__ out_prev_action,
-                 uint8_t* __restrict__ out_has_prev, int S, int D, const int32_t* __restrict__ key,
-                 const int32_t* __restrict__ cost, const uint8_t* __restrict__ active) {
-  const int lane = threadIdx.x & 63;
-  const int q = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  if (q >= B) return;
-  int t = q;
-  if (off != nullptr) {                                // the last tree whose range starts at or before q (skips empty ranges)
-    int lo = 0, hi = T - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (off[mid] <= q) lo = mid; else hi = mid - 1;
-    }
-    t = lo;
-  }
-  const int base = t * C + skip;
-  int n = counters[t * 8] - skip;
-  n = n > C - skip ? C - skip : n;                     // never past the tree's own slots
-  const double qx = queries[(size_t)q * q_stride + 0], qy = queries[(size_t)q * q_stride + 1];
-  double best = __builtin_huge_val();
-  int bidx = 0x7fffffff;
-  int U = 0x7fffffff;
-  if constexpr (MASK & MASK_KEY) U = bound_of(counters + (size_t)t * 8, cost);
+// The one scan trip of the nearest pass: lane `lane` of a wave strides the n nodes of the segment that starts at slot `base`
+// of xy / key / active, eight nodes per trip.  Their loads are independent (one load - wait - compare round per node exposes
+// a memory round trip n / 64 times: 1.1 ms of a round at 10^5 nodes), only the visitor's running minima chain: eight double2
+// loads, eight key loads under MASK_KEY, eight byte loads under MASK_ACTIVE.  Indices past n are clamped for the load and
+// masked for the compare; visit(index, xy) sees the nodes that take part in increasing index.  `base` is a 32-bit term of the
+// index, not an offset of the pointers: that costs nn_forest_kernel<false, 3> 15 VGPRs and a step (profiles/NOTES.md).
+template <int MASK, class Visit>
+__device__ __forceinline__ void scan_nodes(const double2* __restrict__ xy, const int32_t* __restrict__ key,
+                                           const uint8_t* __restrict__ active, int base, int n, int U, int lane, Visit visit) {
   for (int i = lane; i < n; i += 8 * WAVE) {
     double2 p[8];
 #pragma unroll
-    for (int u = 0; u < 8; ++u) p[u] = node_xy[base + min(i + u * WAVE, n - 1)];
+    for (int u = 0; u < 8; ++u) p[u] = xy[base + min(i + u * WAVE, n - 1)];
     int kk[8];
     if constexpr (MASK & MASK_KEY) {
 #pragma unroll
@@ -223,76 +98,23 @@ nn_forest_kernel(const double* __restrict__ queries, int q_stride, int B, const 
       bool in = iu < n;
       if constexpr (MASK & MASK_KEY) in = in && kk[u] < U;
       if constexpr (MASK & MASK_ACTIVE) in = in && aa[u] != 0;
-      if (in) {
-        double dx = qx - p[u].x, dy = qy - p[u].y;
-        double d;
-        if constexpr (NORM) d = sqrt(fma(dy, dy, dx * dx));
-        else d = dx * dx + dy * dy;
-        if (d < best) { best = d; bidx = iu; }
-      }
+      if (in) visit(iu, p[u]);
     }
   }
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    double od = __shfl_xor(best, m);
-    int oi = __shfl_xor(bidx, m);
-    if (od < best || (od == best && oi < bidx)) { best = od; bidx = oi; }
-  }
-  if (n <= 0) {
-    if (lane == 0) out_idx[q] = -1;
-    return;
-  }
-  if (bidx == 0x7fffffff) bidx = 0;
-  const int ix = base + bidx;
-  if (lane == 0) out_idx[q] = ix;
-  if (node_state != nullptr) {
-    if (lane < S) out_state[(size_t)q * S + lane] = node_state[(size_t)ix * S + lane];
-    if (lane >= 32 && lane < 32 + D) out_prev_action[(size_t)q * D + (lane - 32)] = node_last_action[(size_t)ix * D + (lane - 32)];
-    if (lane == 63) out_has_prev[q] = node_has_prev[ix];
-  }
 }
-void launch_nn_forest(const double* queries, int q_stride, int B, const double* node_xy, const int32_t* off, int T,
-                      const int32_t* counters, int C, int skip, int32_t* out_idx, const double* node_state,
-                      const double* node_last_action, const uint8_t* node_has_prev, double* out_state, double* out_prev_action,
-                      uint8_t* out_has_prev, hipStream_t s, int S, int D, const int32_t* key, const int32_t* cost,
-                      const uint8_t* active) {
-  const auto kernel = active ? (key ? nn_forest_kernel<false, MASK_KEY | MASK_ACTIVE> : nn_forest_kernel<false, MASK_ACTIVE>)
-                             : (key ? nn_forest_kernel<false, MASK_KEY> : nn_forest_kernel<false>);
-  hipLaunchKernelGGL(kernel, dim3((B + 3) / 4), dim3(256), 0, s, queries, q_stride, B, (const double2*)node_xy, off, T, counters, C,
-                     skip, out_idx, node_state, node_last_action, node_has_prev, out_state, out_prev_action, out_has_prev, S, D,
-                     key, cost, active);
-}
-// The fallback choice of every tree (planners/RRT.py:233-237): query t is tree t's goal, the scan covers its nodes 1.. with the
-// norm as the key.
-void launch_forest_fallback(const double* goals, int T, const double* node_xy, const int32_t* counters, int C, int32_t* out_idx,
-                            hipStream_t s) {
-  hipLaunchKernelGGL(nn_forest_kernel<true>, dim3((T + 3) / 4), dim3(256), 0, s, goals, 2, T, (const double2*)node_xy, nullptr, T,
-                     counters, C, 1, out_idx, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 6, 2, nullptr, nullptr, nullptr);
-}
-
-// ------------------------------------------------------------------------- near parent
-// The "choose parent" search (include/ditree.h "near parent"): among the nodes NEAR the query, the one through which the query
-// is reached in the fewest path rows.  One scan body for both kernels below: a wave serves Q queries over the n nodes behind
-// xy / key / cost (already offset to the segment), in two passes of nn_argmin_kernel's shape -- eight independent double2 loads
-// per trip, eight key loads under the mask, indices past n clamped for the load and masked for the compare.
-//   pass 1: nn_argmin_kernel's scan and its 64-lane (d2, index) reduction -> n*, the nearest node, in every lane; then
-//           tau2 = (sqrt(d2(n*)) + radius)^2, once per query.
-//   pass 2: the same nodes again, with eight cost loads.  A node takes part when d2 <= tau2, or when it is n* itself (by index:
-//           a rounding of t * t below d2(n*) cannot drop it).  Of these only a node that can still win pays the FP64 sqrt and
-//           the divide of g = cost + sqrt(d2) / reach: every candidate has d2 >= d2(n*), and sqrt, / and + round monotonically,
-//           so g >= cost + sqrt(d2(n*)) / reach, one add per node; above the lane's running minimum the node is out (equal: it
-//           may still tie, and is evaluated).  Near nodes are scattered over the lanes, so without this bound the branch is
-//           taken by a third of the wave-steps at a radius of one cell (one near lane is enough); with it, by the few nodes
-//           whose cost is within radius / reach rows of the lane's best.  The running minimum is (g, d2) with strict '<', so a
-//           lane keeps its lowest index; the reduction carries (g, d2, index): ties in g go to the smaller d2, then to the lower
-//           index.
-// res[k]: the parent's index in the segment, 0x7fffffff when no node had a distance that wins a '<' (all NaN, all closed, n = 0),
-// which the callers clamp as the existing scans do.  With equal costs g is monotone in d2 and the result is n*.
-template <int MASK, int Q>
-__device__ __forceinline__ void near_scan(const double2* __restrict__ xy, const int32_t* __restrict__ key,
-                                          const uint8_t* __restrict__ active, const int32_t* __restrict__ cost, int n, int U,
-                                          const double (&qx)[Q],
-                                          const double (&qy)[Q], double radius, double reach, int lane, int (&res)[Q]) {
+// The nearest of the n nodes to each of a wave's Q queries: the scan with strict '<' per lane (a lane keeps its lowest index),
+// then the 64-lane arg-min reduction carrying (distance, index), ties -> lowest index.  best[k] / bidx[k] hold the result in
+// every lane; NaN distances never win a '<', so a scan without a winner (all NaN, all closed, all inactive, n = 0) leaves
+// 0x7fffffff, which the callers clamp to the segment's first node.
+// NORM: the key of the fallback choice (planners/RRT.py:233-237, np.argmin of np.linalg.norm(state[:2] - goal)) instead of the
+// squared distance: sqrt(fma(dy, dy, dx*dx)) as fallback_select_kernel and oracle/rrt.py::fallback_node compute it.  sqrt merges
+// neighbouring doubles, so two nodes whose squares differ in the last place can have equal norms; the reference then returns
+// the lower index, which the square's strict '<' would not.  The expansion search (NORM = false) keeps the squared distance:
+// it is pinned bit for bit to the KDTree goldens.
+template <int MASK, int Q, bool NORM, class Found>
+__device__ __forceinline__ void nearest(const double2* __restrict__ xy, const int32_t* __restrict__ key,
+                                        const uint8_t* __restrict__ active, int base, int n, int U, const double (&qx)[Q],
+                                        const double (&qy)[Q], int lane, Found found) {
   double best[Q];
   int bidx[Q];
 #pragma unroll
@@ -300,38 +122,16 @@ __device__ __forceinline__ void near_scan(const double2* __restrict__ xy, const 
     best[k] = __builtin_huge_val();
     bidx[k] = 0x7fffffff;
   }
-  for (int i = lane; i < n; i += 8 * WAVE) {
-    double2 p[8];
+  scan_nodes<MASK>(xy, key, active, base, n, U, lane, [&](int iu, const double2& p) __attribute__((always_inline)) {
 #pragma unroll
-    for (int u = 0; u < 8; ++u) p[u] = xy[min(i + u * WAVE, n - 1)];
-    int kk[8];
-    if constexpr (MASK & MASK_KEY) {
-#pragma unroll
-      for (int u = 0; u < 8; ++u) kk[u] = key[min(i + u * WAVE, n - 1)];
+    for (int k = 0; k < Q; ++k) {
+      double dx = qx[k] - p.x, dy = qy[k] - p.y;
+      double d;
+      if constexpr (NORM) d = sqrt(fma(dy, dy, dx * dx));
+      else d = dx * dx + dy * dy;
+      if (d < best[k]) { best[k] = d; bidx[k] = iu; }     // strict: keeps the lowest index per lane
     }
-    uint8_t aa[8];
-    if constexpr (MASK & MASK_ACTIVE) {
-#pragma unroll
-      for (int u = 0; u < 8; ++u) aa[u] = active[min(i + u * WAVE, n - 1)];
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int iu = i + u * WAVE;
-      bool in = iu < n;
-      if constexpr (MASK & MASK_KEY) in = in && kk[u] < U;
-      if constexpr (MASK & MASK_ACTIVE) in = in && aa[u] != 0;
-      if (in) {
-#pragma unroll
-        for (int k = 0; k < Q; ++k) {
-          double dx = qx[k] - p[u].x, dy = qy[k] - p[u].y;
-          double d = dx * dx + dy * dy;
-          if (d < best[k]) { best[k] = d; bidx[k] = iu; }
-        }
-      }
-    }
-  }
-  double tau2[Q], gfloor[Q];
-  bool any = false;
+  });
 #pragma unroll
   for (int k = 0; k < Q; ++k) {
     double d = best[k];
@@ -342,6 +142,32 @@ __device__ __forceinline__ void near_scan(const double2* __restrict__ xy, const 
       int oi = __shfl_xor(ix, m);
       if (od < d || (od == d && oi < ix)) { d = od; ix = oi; }
     }
+    found(k, d, ix);
+  }
+}
+// The "choose parent" search (include/ditree.h "near parent"): among the nodes NEAR the query, the one through which the query
+// is reached in the fewest path rows, in two passes over the same nodes.
+//   pass 1: nearest() -> n*, the nearest node, in every lane; then tau2 = (sqrt(d2(n*)) + radius)^2, once per query.
+//   pass 2: the same nodes again, with the cost loads.  A node takes part when d2 <= tau2, or when it is n* itself (by index:
+//           a rounding of t * t below d2(n*) cannot drop it).  Of these only a node that can still win pays the FP64 sqrt and
+//           the divide of g = cost + sqrt(d2) / reach: every candidate has d2 >= d2(n*), and sqrt, / and + round monotonically,
+//           so g >= cost + sqrt(d2(n*)) / reach, one add per node; above the lane's running minimum the node is out (equal: it
+//           may still tie, and is evaluated).  Near nodes are scattered over the lanes, so without this bound the branch is
+//           taken by a third of the wave-steps at a radius of one cell (one near lane is enough); with it, by the few nodes
+//           whose cost is within radius / reach rows of the lane's best.  The running minimum is (g, d2) with strict '<', so a
+//           lane keeps its lowest index; the reduction carries (g, d2, index): ties in g go to the smaller d2, then to the lower
+//           index.
+// res[k]: the parent's index in the segment, 0x7fffffff when no node had a distance that wins a '<' (all NaN, all closed, n = 0),
+// which the callers clamp as nearest()'s.  With equal costs g is monotone in d2 and the result is n*.
+template <int MASK, int Q>
+__device__ __forceinline__ void near_parent(const double2* __restrict__ xy, const int32_t* __restrict__ key,
+                                            const uint8_t* __restrict__ active, const int32_t* __restrict__ cost, int base, int n, int U,
+                                            const double (&qx)[Q], const double (&qy)[Q], double radius, double reach, int lane,
+                                            int (&res)[Q]) {
+  int bidx[Q];
+  double tau2[Q], gfloor[Q];
+  bool any = false;
+  nearest<MASK, Q, false>(xy, key, active, base, n, U, qx, qy, lane, [&](int k, double d, int ix) __attribute__((always_inline)) {
     bidx[k] = ix;                                       // n* in every lane
     const double sd = sqrt(d);
     const double t = sd + radius;
@@ -349,7 +175,7 @@ __device__ __forceinline__ void near_scan(const double2* __restrict__ xy, const 
     gfloor[k] = sd / reach;                             // g(n) >= cost[n] + gfloor for every candidate n
     any = any || ix != 0x7fffffff;
     res[k] = 0x7fffffff;
-  }
+  });
   if (!any) return;                                     // wave-uniform: no query of the wave has a nearest node
   double bg[Q], bd[Q];
 #pragma unroll
@@ -357,22 +183,27 @@ __device__ __forceinline__ void near_scan(const double2* __restrict__ xy, const 
     bg[k] = __builtin_huge_val();
     bd[k] = __builtin_huge_val();
   }
+  // Pass 2 keeps its own copy of scan_nodes' trip (plus the eight cost loads).  Run through the shared trip, the compiler folds
+  // the bound test into the near test and every node pays the FP64 add: nn_near_kernel then takes 6 % longer at a radius of
+  // 0.5 m (10^5 and 10^6 nodes) and 8 % less at 2 m; with the near test marked unlikely it is the other way round.  Neither
+  // is the time it had, so this loop stays as it was (profiles/NOTES.md, "Nearest-node search: one scan body").  For one query
+  // per wave (nn_forest_near_kernel) both forms compile to the same instructions, so that kernel loses nothing by sharing it.
   for (int i = lane; i < n; i += 8 * WAVE) {
     double2 p[8];
 #pragma unroll
-    for (int u = 0; u < 8; ++u) p[u] = xy[min(i + u * WAVE, n - 1)];
+    for (int u = 0; u < 8; ++u) p[u] = xy[base + min(i + u * WAVE, n - 1)];
     int cc[8];
 #pragma unroll
-    for (int u = 0; u < 8; ++u) cc[u] = cost[min(i + u * WAVE, n - 1)];
+    for (int u = 0; u < 8; ++u) cc[u] = cost[base + min(i + u * WAVE, n - 1)];
     int kk[8];
     if constexpr (MASK & MASK_KEY) {
 #pragma unroll
-      for (int u = 0; u < 8; ++u) kk[u] = key[min(i + u * WAVE, n - 1)];
+      for (int u = 0; u < 8; ++u) kk[u] = key[base + min(i + u * WAVE, n - 1)];
     }
     uint8_t aa[8];
     if constexpr (MASK & MASK_ACTIVE) {
 #pragma unroll
-      for (int u = 0; u < 8; ++u) aa[u] = active[min(i + u * WAVE, n - 1)];
+      for (int u = 0; u < 8; ++u) aa[u] = active[base + min(i + u * WAVE, n - 1)];
     }
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
@@ -407,114 +238,129 @@ __device__ __forceinline__ void near_scan(const double2* __restrict__ xy, const 
     res[k] = ix;
   }
 }
-// nn_argmin_kernel with the near-parent rule: one wave per NN_QPW queries over nodes 0 .. N-1; MASK: only open nodes
-// (key[n] < U, U = bound_of(counters, bcost)) are candidates, MASK_ACTIVE: only active ones.  cost: the near descriptor's column.
-// No candidate -> node 0.
-template <int MASK>
-__global__ void __launch_bounds__(256)
-nn_near_kernel(const double* __restrict__ queries, int q_stride, int B, const double2* __restrict__ node_xy, int N,
-               int32_t* __restrict__ out_idx, const double* __restrict__ node_state,
-               const double* __restrict__ node_last_action, const uint8_t* __restrict__ node_has_prev,
-               double* __restrict__ out_state, double* __restrict__ out_prev_action, uint8_t* __restrict__ out_has_prev, int S,
-               int D, const int32_t* __restrict__ key, const int32_t* __restrict__ bcost, const int32_t* __restrict__ counters,
-               const int32_t* __restrict__ cost, double radius, double reach, const uint8_t* __restrict__ active) {
+// The tree of candidate row q of a forest: the last tree whose range [off[t], off[t+1]) starts at or before q (empty ranges are
+// skipped); without offsets, one row per tree.
+__device__ __forceinline__ int tree_of_query(const int32_t* __restrict__ off, int T, int q) {
+  if (off == nullptr) return q;
+  int lo = 0, hi = T - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (off[mid] <= q) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+// What a search leaves for query q, by the whole wave: the chosen node's index and, where the caller gathers (a.state != NULL),
+// its state (lanes < S; S <= 64), last action (lanes 32 .. 32 + D) and flag (lane 63).
+__device__ __forceinline__ void write_parent(const NnArg& a, int q, int ix, int lane) {
+  if (lane == 0) a.out_idx[q] = ix;
+  if (a.state != nullptr) {
+    if (lane < a.S) a.out_state[(size_t)q * a.S + lane] = a.state[(size_t)ix * a.S + lane];
+    if (lane >= 32 && lane < 32 + a.D) a.out_prev_action[(size_t)q * a.D + (lane - 32)] = a.last_action[(size_t)ix * a.D + (lane - 32)];
+    if (lane == 63) a.out_has_prev[q] = a.has_prev[ix];
+  }
+}
+// The search of one tree: one wave per group of NN_QPW queries over nodes 0 .. N-1.  NEAR: the near-parent rule instead of the
+// nearest node.  No candidate -> node 0.
+template <int MASK, bool NEAR>
+__device__ __forceinline__ void tree_search(const NnArg& a, const NnTree& seg) {
   const int lane = threadIdx.x & 63;
   const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int q0 = wave * NN_QPW;
-  if (q0 >= B) return;
+  if (q0 >= a.B) return;
   int U = 0x7fffffff;
-  if constexpr (MASK & MASK_KEY) U = bound_of(counters, bcost);
+  if constexpr (MASK & MASK_KEY) U = bound_of(seg.counters, a.bcost);
   double qx[NN_QPW], qy[NN_QPW];
-  int res[NN_QPW];
 #pragma unroll
   for (int k = 0; k < NN_QPW; ++k) {
-    int q = min(q0 + k, B - 1);
-    qx[k] = queries[(size_t)q * q_stride + 0];
-    qy[k] = queries[(size_t)q * q_stride + 1];
+    int q = min(q0 + k, a.B - 1);
+    qx[k] = a.queries[(size_t)q * a.q_stride + 0];
+    qy[k] = a.queries[(size_t)q * a.q_stride + 1];
   }
-  near_scan<MASK, NN_QPW>(node_xy, key, active, cost, N, U, qx, qy, radius, reach, lane, res);
+  auto chosen = [&](int k, int ix) __attribute__((always_inline)) {
+    if (q0 + k < a.B) write_parent(a, q0 + k, ix == 0x7fffffff ? 0 : ix, lane);
+  };
+  if constexpr (NEAR) {
+    int res[NN_QPW];
+    near_parent<MASK, NN_QPW>(a.xy, a.key, a.active, a.cost, 0, seg.N, U, qx, qy, a.radius, a.reach, lane, res);
 #pragma unroll
-  for (int k = 0; k < NN_QPW; ++k) {
-    int ix = res[k];
-    if (ix == 0x7fffffff) ix = 0;
-    int q = q0 + k;
-    if (q < B) {
-      if (lane == 0) out_idx[q] = ix;
-      if (node_state != nullptr) {
-        if (lane < S) out_state[(size_t)q * S + lane] = node_state[(size_t)ix * S + lane];               // S <= 64
-        if (lane >= 32 && lane < 32 + D) out_prev_action[(size_t)q * D + (lane - 32)] = node_last_action[(size_t)ix * D + (lane - 32)];
-        if (lane == 63) out_has_prev[q] = node_has_prev[ix];
-      }
-    }
+    for (int k = 0; k < NN_QPW; ++k) chosen(k, res[k]);
+  } else {
+    nearest<MASK, NN_QPW, false>(a.xy, a.key, a.active, 0, seg.N, U, qx, qy, lane,
+                                 [&](int k, double, int ix) __attribute__((always_inline)) { chosen(k, ix); });
   }
 }
-void launch_nn_near(const double* queries, int q_stride, int B, const double* node_xy, int N, int32_t* out_idx,
-                    const double* node_state, const double* node_last_action, const uint8_t* node_has_prev, double* out_state,
-                    double* out_prev_action, uint8_t* out_has_prev, hipStream_t s, int S, int D, const int32_t* key,
-                    const int32_t* bcost, const int32_t* counters, const int32_t* cost, double radius, double reach,
-                    const uint8_t* active) {
-  int waves = (B + NN_QPW - 1) / NN_QPW;
-  int blocks = (waves + 3) / 4;
-  const auto kernel = active ? (key ? nn_near_kernel<MASK_KEY | MASK_ACTIVE> : nn_near_kernel<MASK_ACTIVE>)
-                             : (key ? nn_near_kernel<MASK_KEY> : nn_near_kernel<0>);
-  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, s, queries, q_stride, B, (const double2*)node_xy, N, out_idx, node_state,
-                     node_last_action, node_has_prev, out_state, out_prev_action, out_has_prev, S, D, key, bcost, counters, cost,
-                     radius, reach, active);
-}
-// nn_forest_kernel (NORM = false, skip = 0) with the near-parent rule: one wave per query over its tree's slots; MASK: under the
-// tree's own U, MASK_ACTIVE: over its active nodes.  No candidate -> the tree's root; a tree without a node -> -1, nothing gathered.
-template <int MASK>
-__global__ void __launch_bounds__(256)
-nn_forest_near_kernel(const double* __restrict__ queries, int q_stride, int B, const double2* __restrict__ node_xy,
-                      const int32_t* __restrict__ off, int T, const int32_t* __restrict__ counters, int C,
-                      int32_t* __restrict__ out_idx, const double* __restrict__ node_state,
-                      const double* __restrict__ node_last_action, const uint8_t* __restrict__ node_has_prev,
-                      double* __restrict__ out_state, double* __restrict__ out_prev_action, uint8_t* __restrict__ out_has_prev,
-                      int S, int D, const int32_t* __restrict__ key, const int32_t* __restrict__ bcost,
-                      const int32_t* __restrict__ cost, double radius, double reach, const uint8_t* __restrict__ active) {
+// The segmented search of a forest (include/ditree.h ditree_forest): query q belongs to tree t = tree_of_query and searches only
+// that tree's node slots [t*C + skip, t*C + n_t), n_t read from the tree's counter row (never past the tree's own slots), under
+// the tree's own bound U; key, cost and active are indexed by the global slot.  Queries of one wave may belong to different trees
+// (at one candidate per run they always do), so every wave takes one query; the scan is tree_search's, so the result is
+// tree_search's on the segment alone (no candidate -> the segment's first slot).  A segment with no node gives -1 and gathers nothing.
+template <bool NORM, int MASK, bool NEAR>
+__device__ __forceinline__ void forest_search(const NnArg& a, const NnForest& seg) {
   const int lane = threadIdx.x & 63;
   const int q = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  if (q >= B) return;
-  int t = q;
-  if (off != nullptr) {                                // the last tree whose range starts at or before q (skips empty ranges)
-    int lo = 0, hi = T - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (off[mid] <= q) lo = mid; else hi = mid - 1;
-    }
-    t = lo;
-  }
-  const int base = t * C;
-  int n = counters[t * 8];
-  n = n > C ? C : n;                                   // never past the tree's own slots
+  if (q >= a.B) return;
+  const int t = tree_of_query(seg.off, seg.T, q);
+  const int base = t * seg.C + seg.skip;
+  int n = seg.counters[t * 8] - seg.skip;
+  n = n > seg.C - seg.skip ? seg.C - seg.skip : n;
   if (n <= 0) {
-    if (lane == 0) out_idx[q] = -1;
+    if (lane == 0) a.out_idx[q] = -1;
     return;
   }
   int U = 0x7fffffff;
-  if constexpr (MASK & MASK_KEY) U = bound_of(counters + (size_t)t * 8, bcost);
-  const double qx[1] = {queries[(size_t)q * q_stride + 0]}, qy[1] = {queries[(size_t)q * q_stride + 1]};
+  if constexpr (MASK & MASK_KEY) U = bound_of(seg.counters + (size_t)t * 8, a.bcost);
+  const double qx[1] = {a.queries[(size_t)q * a.q_stride + 0]}, qy[1] = {a.queries[(size_t)q * a.q_stride + 1]};
   int res[1];
-  near_scan<MASK, 1>(node_xy + base, (MASK & MASK_KEY) ? key + base : nullptr, (MASK & MASK_ACTIVE) ? active + base : nullptr,
-                     cost + base, n, U, qx, qy, radius, reach, lane, res);
-  const int ix = base + (res[0] == 0x7fffffff ? 0 : res[0]);
-  if (lane == 0) out_idx[q] = ix;
-  if (node_state != nullptr) {
-    if (lane < S) out_state[(size_t)q * S + lane] = node_state[(size_t)ix * S + lane];
-    if (lane >= 32 && lane < 32 + D) out_prev_action[(size_t)q * D + (lane - 32)] = node_last_action[(size_t)ix * D + (lane - 32)];
-    if (lane == 63) out_has_prev[q] = node_has_prev[ix];
+  if constexpr (NEAR) near_parent<MASK, 1>(a.xy, a.key, a.active, a.cost, base, n, U, qx, qy, a.radius, a.reach, lane, res);
+  else nearest<MASK, 1, NORM>(a.xy, a.key, a.active, base, n, U, qx, qy, lane, [&](int, double, int ix) { res[0] = ix; });
+  write_parent(a, q, base + (res[0] == 0x7fffffff ? 0 : res[0]), lane);
+}
+// The four kernels: MASK = 0 reads none of key / bcost / active, and only the near kernels read cost / radius / reach.
+// nn_argmin_kernel names the waves per SIMD it has always had (4 with both masks, 5 otherwise): left to itself the MASK_ACTIVE
+// instantiation takes 98 VGPRs, two over the step.
+template <int MASK>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MASK == (MASK_KEY | MASK_ACTIVE) ? 4 : 5)))
+nn_argmin_kernel(NnArg a, NnTree seg) { tree_search<MASK, false>(a, seg); }
+template <int MASK>
+__global__ void __launch_bounds__(256) nn_near_kernel(NnArg a, NnTree seg) { tree_search<MASK, true>(a, seg); }
+template <bool NORM, int MASK = 0>
+__global__ void __launch_bounds__(256) nn_forest_kernel(NnArg a, NnForest seg) { forest_search<NORM, MASK, false>(a, seg); }
+template <int MASK>
+__global__ void __launch_bounds__(256) nn_forest_near_kernel(NnArg a, NnForest seg) { forest_search<false, MASK, true>(a, seg); }
+
+// f(the MASK of a search with these columns, as a compile-time constant)
+template <class F>
+static void with_mask(const void* key, const void* active, F f) {
+  if (active) {
+    if (key) f(std::integral_constant<int, MASK_KEY | MASK_ACTIVE>{}); else f(std::integral_constant<int, MASK_ACTIVE>{});
+  } else {
+    if (key) f(std::integral_constant<int, MASK_KEY>{}); else f(std::integral_constant<int, 0>{});
   }
 }
-void launch_nn_forest_near(const double* queries, int q_stride, int B, const double* node_xy, const int32_t* off, int T,
-                           const int32_t* counters, int C, int32_t* out_idx, const double* node_state,
-                           const double* node_last_action, const uint8_t* node_has_prev, double* out_state, double* out_prev_action,
-                           uint8_t* out_has_prev, hipStream_t s, int S, int D, const int32_t* key, const int32_t* bcost,
-                           const int32_t* cost, double radius, double reach, const uint8_t* active) {
-  const auto kernel = active ? (key ? nn_forest_near_kernel<MASK_KEY | MASK_ACTIVE> : nn_forest_near_kernel<MASK_ACTIVE>)
-                             : (key ? nn_forest_near_kernel<MASK_KEY> : nn_forest_near_kernel<0>);
-  hipLaunchKernelGGL(kernel, dim3((B + 3) / 4), dim3(256), 0, s, queries, q_stride, B, (const double2*)node_xy, off, T, counters, C,
-                     out_idx, node_state, node_last_action, node_has_prev, out_state, out_prev_action, out_has_prev, S, D, key,
-                     bcost, cost, radius, reach, active);
+void launch_nn(const NnArg& a, const NnTree& seg, hipStream_t s) {
+  const int waves = (a.B + NN_QPW - 1) / NN_QPW;
+  with_mask(a.key, a.active, [&](auto m) {
+    constexpr int M = decltype(m)::value;
+    hipLaunchKernelGGL(a.cost ? nn_near_kernel<M> : nn_argmin_kernel<M>, dim3((waves + 3) / 4), dim3(256), 0, s, a, seg);
+  });
+}
+void launch_nn(const NnArg& a, const NnForest& seg, hipStream_t s) {
+  if (seg.norm) {
+    hipLaunchKernelGGL(nn_forest_kernel<true>, dim3((a.B + 3) / 4), dim3(256), 0, s, a, seg);
+    return;
+  }
+  with_mask(a.key, a.active, [&](auto m) {
+    constexpr int M = decltype(m)::value;
+    hipLaunchKernelGGL((a.cost ? nn_forest_near_kernel<M> : nn_forest_kernel<false, M>), dim3((a.B + 3) / 4), dim3(256), 0, s, a, seg);
+  });
+}
+// The fallback choice of every tree (planners/RRT.py:233-237): query t is tree t's goal, the scan covers its nodes 1.. with the
+// norm as the key.
+void launch_forest_fallback(const double* goals, int T, const double* node_xy, const int32_t* counters, int C, int32_t* out_idx,
+                            hipStream_t s) {
+  const NnArg a{goals, 2, T, (const double2*)node_xy, nullptr, nullptr, nullptr, 6, 2, out_idx,
+                nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0.0, 0.0};
+  launch_nn(a, NnForest{nullptr, T, counters, C, 1, true}, s);
 }
 
 // ------------------------------------------------------------------------- local map
@@ -573,18 +419,12 @@ void launch_local_map_scenes(const SceneArg& sc, const double* state, const int3
   hipLaunchKernelGGL(local_map_kernel<true>, dim3(B), dim3(256), lds, s, (const unsigned char*)sc.table, 0, 0, state, state_stride, active,
                      idx, n, axis, s_global, 1, out);
 }
-// The scene of every candidate row: tree_scene[t] for the tree whose range [off[t], off[t+1]) holds the row (the last tree
-// whose range starts at or before it: empty ranges are skipped, as in nn_forest_kernel).
+// The scene of every candidate row: tree_scene[t] for the tree whose range [off[t], off[t+1]) holds the row (tree_of_query).
 __global__ void row_scene_kernel(const int32_t* __restrict__ off, int T, const int32_t* __restrict__ tree_scene, int B,
                                  int32_t* __restrict__ row_scene) {
   const int q = blockIdx.x * blockDim.x + threadIdx.x;
   if (q >= B) return;
-  int lo = 0, hi = T - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (off[mid] <= q) lo = mid; else hi = mid - 1;
-  }
-  row_scene[q] = tree_scene[lo];
+  row_scene[q] = tree_scene[tree_of_query(off, T, q)];
 }
 void launch_row_scene(const int32_t* off, int T, const int32_t* tree_scene, int B, int32_t* row_scene, hipStream_t s) {
   hipLaunchKernelGGL(row_scene_kernel, dim3((B + 255) / 256), dim3(256), 0, s, off, T, tree_scene, B, row_scene);

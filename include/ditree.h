@@ -42,6 +42,10 @@ extern "C" {
 #define DITREE_E_HIP (-2)           /* a HIP runtime call failed */
 #define DITREE_E_STATE (-3)         /* call order (no maze / no weights uploaded) */
 #define DITREE_E_NOMEM (-4)
+/* Check order.  The car's searches with a descriptor (ditree_[forest_]nn_argmin_{bounded,near,sparse}), its rounds
+ * (ditree_[forest_]expand_round[_scenes|_bounded|_near|_sparse]) and its accepts (ditree_[forest_]accept[_best|_bounded|_sparse])
+ * test their arguments in one order and report the first fault: ctx, round, tree or forest, scenes, sparse, near, bound, then
+ * the call's own rules.  An input with one fault gets that fault's code and text whatever the order. */
 
 /* per-chunk / per-candidate status codes written by the rollout kernels */
 #define DITREE_ST_NOT_RUN (-1)

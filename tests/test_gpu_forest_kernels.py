@@ -1,5 +1,5 @@
-"""GPU: the forest kernels (nn_forest_kernel, accept_scan_kernel<first> / accept_commit_kernel on a forest's trees,
-row_scene_kernel and the SCENES rollout) against plain numpy / Python written here and the oracle's own functions, at the tree sizes real runs reach:
+"""GPU: the forest kernels (nn_forest_kernel, i.e. forest_search over tree_of_query, nearest and write_parent; accept_scan_kernel<first> /
+accept_commit_kernel on a forest's trees, row_scene_kernel, tree_of_query's third user, and the SCENES rollout) against plain numpy / Python written here and the oracle's own functions, at the tree sizes real runs reach:
 trees past the 512-node trip of the search, 256 trees of one candidate, 2 500 candidates of one tree, a full scene table.
 The entry points are called directly on tree contents and rounds written straight into the device arrays.  Every comparison is
 exact (indices, flags, counters, copied doubles) except the scene rollout's states (1e-9, test_rollout_chunk_vs_oracle's bound).
@@ -239,6 +239,34 @@ def test_row_scene_search_against_searchsorted(ctx, T, layouts):
         assert np.array_equal(got, want) and (got == _lib.ST_GOAL).all()
         assert np.array_equal(forest.rb.parent[:B].cpu().numpy(), tree_of_row * 2)
         assert np.array_equal(forest.rb.chunk_steps[:B, 0].cpu().numpy(), exp["n_steps"].reshape(64, 64)[root_scene, row_scene])
+
+
+def test_tree_lookup_with_empty_ranges_in_front_and_between(ctx):
+    """The one tree lookup of the kernels (tree_of_query) on off = [0, 0, 3, 3, 4, 9], five trees with an empty range in front
+    and one in the middle, against np.searchsorted(off, q, 'right') - 1: through the forest nearest-node search (every tree holds
+    only its root, so the parent names the tree) and through a scene-forest round (its parents, and row_scene_kernel read through
+    the rollout as above: GOAL exactly when the row was judged by its own tree's scene)."""
+    from ditreeonlineplanner_amd import _lib
+    from ditreeonlineplanner_amd.forest import SceneForestEngine
+    counts, T, Cap = [0, 3, 0, 1, 5], 5, 2
+    off = np.concatenate([[0], np.cumsum(counts)])
+    assert list(off) == [0, 0, 3, 3, 4, 9]
+    B = int(off[-1])
+    tree_of_row = np.searchsorted(off, np.arange(B), "right") - 1
+    assert list(tree_of_row) == [1, 1, 1, 3, 4, 4, 4, 4, 4]
+    forest = SceneForestEngine(ctx, marker_scenes(), T, Cap, edge_length=8, action_horizon=8, batch=B)
+    for t in range(T):
+        forest.reset_tree(t, 13 * t + 5)                          # five different scenes
+    forest._set_offsets(counts)
+    got = forest_nn(ctx, forest, np.random.default_rng(7).uniform(-9.0, 9.0, (B, 2)), 2)
+    assert np.array_equal(got, tree_of_row * Cap)
+    samples = np.zeros((B, 6))
+    forest.rb.status.fill_(-5)
+    forest.expand_round(dev(samples), dev(samples[:, :2]),
+                        inject_actions=torch.zeros((B, 1, forest.P, 2), dtype=torch.float64, device="cuda"),
+                        counts_per_tree=counts, accept=False)
+    assert np.array_equal(forest.rb.parent[:B].cpu().numpy(), tree_of_row * Cap)
+    assert (forest.rb.status[:B].cpu().numpy() == _lib.ST_GOAL).all()
 
 
 # ====================================================================== 2. fallback

@@ -1,5 +1,6 @@
 """GPU: the masked nearest-node search of ``solution="anytime_pruned"`` (ditree_nn_argmin_bounded,
-ditree_forest_nn_argmin_bounded: nn_argmin_kernel<true>, nn_forest_kernel<false, true>) and the key kernel (ditree_bound_keys)
+ditree_forest_nn_argmin_bounded: nn_argmin_kernel<MASK_KEY>, nn_forest_kernel<false, MASK_KEY>, i.e. scan_nodes under the key's
+mask behind tree_search / forest_search) and the key kernel (ditree_bound_keys)
 against the numpy restatement of tests/anytime_pruned_ref.py.  Every comparison is exact.
 
 Sizes: a trip of the scan covers 512 nodes (64 lanes x 8 loads) and a wave serves four queries, so N runs around one lane

@@ -1,5 +1,5 @@
-"""GPU: the near-parent search (ditree_nn_argmin_near, ditree_forest_nn_argmin_near: nn_near_kernel, nn_forest_near_kernel)
-against the sequential restatement of tests/near_parent_ref.py, parent index for index.  Every comparison is exact.
+"""GPU: the near-parent search (ditree_nn_argmin_near, ditree_forest_nn_argmin_near: nn_near_kernel, nn_forest_near_kernel,
+both near_parent -- nearest, then the second pass with the cost column --) against the sequential restatement of tests/near_parent_ref.py, parent index for index.  Every comparison is exact.
 
 Sizes: a trip of either pass covers 512 nodes (64 lanes x 8 loads) and a wave serves four queries, so N runs over one and two
 nodes, around one lane row (63 / 64 / 65), around a trip (511 / 512 / 513), over several trips (4097) and over a tree of real
