@@ -25,11 +25,12 @@ def _splitmix64(x):
         return z ^ (z >> np.uint64(31))
 
 
-def device_noise(seed, counter, K, T, sigma):
-    """The on-device generator of ditree_mppi_step (noise == NULL): eps (K, T, 2), a pure function of (seed, counter, k, t)."""
+def device_noise(seed, counter, K, T, sigma, k0=0):
+    """The on-device generator of ditree_mppi_step (noise == NULL): eps (K, T, 2), a pure function of (seed, counter, GLOBAL
+    k = k0 + row, t)."""
     with np.errstate(over="ignore"):
         h = _splitmix64(np.uint64(seed) ^ _splitmix64(np.uint64(counter)))
-        k = np.arange(K, dtype=np.uint64).reshape(-1, 1)
+        k = (np.arange(K, dtype=np.uint64) + np.uint64(k0)).reshape(-1, 1)
         t = np.arange(T, dtype=np.uint64).reshape(1, -1)
         h = _splitmix64(h ^ ((k * np.uint64(0xD1B54A32D192ED03)) & _M))
         h = _splitmix64(h ^ t)
@@ -42,13 +43,16 @@ def device_noise(seed, counter, K, T, sigma):
 
 
 def rollout_costs(maze, state, U, path_xy, goal_xy, noise, lam, sigma, w_track, w_progress, w_collision, w_goal,
-                  window_back, window_fwd):
-    """-> (costs (K,), flags (K,) 0 / 1 goal / 2 collided, i0).  noise (K, T, 2); rollout 0 runs without noise."""
+                  window_back, window_fwd, k0=0, with_ends=False):
+    """-> (costs (K,), flags (K,) 0 / 1 goal / 2 collided, i0).  noise (K, T, 2); GLOBAL rollout 0 (k0 + k == 0) runs without
+    noise.  with_ends: a fourth value (end_step (K,), both (K,), last_ip (K,)) -- the step at which the rollout ended (T - 1 when
+    nothing ended it), whether that step was inside the goal radius AND colliding, and the rollout's last nearest path index."""
     state = np.asarray(state, dtype=np.float64)
     U = np.asarray(U, dtype=np.float64)
     path = np.asarray(path_xy, dtype=np.float64)
     eps = np.array(noise, dtype=np.float64)
-    eps[0] = 0.0
+    if k0 == 0:
+        eps[0] = 0.0
     K, T = eps.shape[:2]
     P = len(path)
     d0 = (path[:, 0] - state[0]) ** 2 + (path[:, 1] - state[1]) ** 2
@@ -58,6 +62,8 @@ def rollout_costs(maze, state, U, path_xy, goal_xy, noise, lam, sigma, w_track, 
     ip = np.full(K, i0, dtype=np.int64)
     flags = np.zeros(K, dtype=np.int32)
     alive = np.ones(K, dtype=bool)
+    end_step = np.full(K, T - 1, dtype=np.int64)
+    both = np.zeros(K, dtype=bool)
     for t in range(T):
         idx = np.nonzero(alive)[0]
         if idx.size == 0:
@@ -84,14 +90,19 @@ def rollout_costs(maze, state, U, path_xy, goal_xy, noise, lam, sigma, w_track, 
         cost[idx[only_goal]] = cost[idx[only_goal]] - w_goal
         flags[idx[only_goal]] = 1
         alive[idx[coll | reached]] = False
+        end_step[idx[coll | reached]] = t
+        both[idx[coll & reached]] = True
     cost = cost + w_progress * (P - 1 - ip).astype(np.float64)
+    if with_ends:
+        return cost, flags, i0, (end_step, both, ip.copy())
     return cost, flags, i0
 
 
-def update(U, costs, noise, lam):
+def update(U, costs, noise, lam, k0=0):
     """-> (U_new, normalised weights, beta, eta, effective sample size)."""
     eps = np.array(noise, dtype=np.float64)
-    eps[0] = 0.0
+    if k0 == 0:
+        eps[0] = 0.0
     beta = float(np.min(costs))
     w = np.exp(-(costs - beta) / lam)
     eta = float(np.sum(w))
@@ -138,8 +149,9 @@ def device_noise_ant(seed, counter, k0, K, T, sigma):
 
 
 def rollout_costs_ant(maze, state, U, path_xy, desired_xy, noise, lam, sigma, w_track, w_progress, w_collision, w_goal, window_back,
-                      window_fwd, s_global=4.0, ball_radius=1.2, goal_radius=None, k0=0):
-    """-> (costs (K,), flags (K,), i0); noise (K, T, 8); GLOBAL rollout 0 (k0 + k == 0) runs without noise."""
+                      window_fwd, s_global=4.0, ball_radius=1.2, goal_radius=None, k0=0, with_ends=False):
+    """-> (costs (K,), flags (K,), i0); noise (K, T, 8); GLOBAL rollout 0 (k0 + k == 0) runs without noise.  with_ends: as
+    rollout_costs."""
     from . import ant as OA
     state = np.asarray(state, dtype=np.float64)
     U = np.asarray(U, dtype=np.float64)
@@ -158,6 +170,8 @@ def rollout_costs_ant(maze, state, U, path_xy, desired_xy, noise, lam, sigma, w_
     ip = np.full(K, i0, dtype=np.int64)
     flags = np.zeros(K, dtype=np.int32)
     alive = np.ones(K, dtype=bool)
+    end_step = np.full(K, T - 1, dtype=np.int64)
+    both = np.zeros(K, dtype=bool)
     for t in range(T):
         idx = np.nonzero(alive)[0]
         if idx.size == 0:
@@ -185,7 +199,11 @@ def rollout_costs_ant(maze, state, U, path_xy, desired_xy, noise, lam, sigma, w_
         cost[idx[only_goal]] = cost[idx[only_goal]] - w_goal
         flags[idx[only_goal]] = 1
         alive[idx[coll | reached]] = False
+        end_step[idx[coll | reached]] = t
+        both[idx[coll & reached]] = True
     cost = cost + w_progress * (P - 1 - ip).astype(np.float64)
+    if with_ends:
+        return cost, flags, i0, (end_step, both, ip.copy())
     return cost, flags, i0
 
 
