@@ -151,6 +151,20 @@ class PolicyParams(C.Structure):
                 ("ddpm_coef", C.POINTER(C.c_float)), ("step_noise", C.c_void_p)]
 
 
+class Polish(C.Structure):
+    """include/ditree.h ditree_polish: the plans of one ditree_polish_plans call and its settings."""
+    _fields_ = [("n_plans", C.c_int32), ("state_dim", C.c_int32), ("action_dim", C.c_int32), ("capacity", C.c_int32),
+                ("K", C.c_int32), ("N", C.c_int32), ("hold", C.c_int32), ("sigma", C.c_double * 2), ("seed", C.c_uint64),
+                ("scene", C.c_void_p), ("scene_host", C.POINTER(C.c_int32)), ("x0", C.c_void_p), ("goal_xy", C.c_void_p),
+                ("tape", C.c_void_p), ("rows", C.c_void_p), ("rows_host", C.POINTER(C.c_int32)), ("states", C.c_void_p),
+                ("arrival", C.c_void_p), ("status", C.c_void_p), ("trace", C.c_void_p), ("noise", C.c_void_p),
+                ("noise_blocks", C.c_int32), ("first_row", C.c_void_p)]
+
+
+POLISH_OK, POLISH_NO_ARRIVAL, POLISH_COLLIDES, POLISH_START_IN_GOAL, POLISH_NOT_F32 = 0, 1, 2, 3, 4
+POLISH_TRACE = 6             # include/ditree.h DITREE_POLISH_TRACE
+POLISH_MAX_CELLS = 16384     # include/ditree.h DITREE_POLISH_MAX_CELLS
+
 EP_RUNNING, EP_SUCCESS, EP_COLLIDED, EP_OUT_OF_STEPS = 0, 1, 2, 3
 
 MPPI_ROLLOUTS, MPPI_MIN, MPPI_SUMS, MPPI_APPLY, MPPI_EXECUTE, MPPI_ALL = 1, 2, 4, 8, 16, 31
@@ -266,6 +280,7 @@ SIGNATURES = {
     "ditree_forest_fallback_goals_ant": (_i32, [_vp, C.POINTER(Tree), C.POINTER(Forest), _pd, _vp, _vp]),
     "ditree_policy_begin": (_i32, [_vp, C.POINTER(PolicyBatch), _vp]),
     "ditree_policy_chunk": (_i32, [_vp, C.POINTER(PolicyBatch), C.POINTER(PolicyParams), C.POINTER(_i32), _vp]),
+    "ditree_polish_plans": (_i32, [_vp, C.POINTER(Polish), _vp]),
 }
 
 _LIB = None

@@ -33,6 +33,7 @@ UNITS = [
     ("ant_kernels.hip", ["-ffp-contract=off"]),
     ("ant_scene_kernels.hip", ["-ffp-contract=off"]),
     ("policy_rollout_kernels.hip", ["-ffp-contract=off"]),
+    ("polish_kernels.hip", ["-ffp-contract=off"]),
     ("ditree_api.hip", []),
     ("conv_tiles.hip", []),
     ("denoise_small_kernels.hip", []),

@@ -210,6 +210,7 @@ void ditree_ctx_destroy(ditree_ctx* ctx) {
   if (ctx->path_dev) hipFree(ctx->path_dev);
   if (ctx->mppi_partial) hipFree(ctx->mppi_partial);
   if (ctx->mppi_minkey) hipFree(ctx->mppi_minkey);
+  if (ctx->polish_partial) hipFree(ctx->polish_partial);
   if (ctx->scene_tab) hipFree(ctx->scene_tab);
   if (ctx->row_scene) hipFree(ctx->row_scene);
   delete ctx;

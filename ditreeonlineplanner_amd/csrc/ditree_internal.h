@@ -83,6 +83,8 @@ struct ditree_ctx {
   const int32_t* ant_run_idx = nullptr;
   double* mppi_partial = nullptr;   // partial sums of the MPPI update, sized for the ant (256 slices of 3 + 8 * 64 doubles)
   unsigned long long* mppi_minkey = nullptr;   // running minimum of the rollout costs (order-preserving integer image)
+  void* polish_partial = nullptr;     // plan polishing: one (tau, k, arriving) record per (plan, K-slice) of the current iteration
+  size_t polish_partial_cap = 0;      // bytes
   DenoiserState* dn = nullptr;
   // scene table (ditree_upload_scenes): atlas of u8 cell codes, (n_scenes,) records, and a (row_scene_cap,) row -> scene scratch
   SceneTable* scene_tab = nullptr;                 // device block: header, records, atlas (DITREE_MAX_ATLAS_CELLS bytes)

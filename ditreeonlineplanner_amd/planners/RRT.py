@@ -596,6 +596,30 @@ class RRT_Planner(BasePlanner):
             return self.handle_goal_not_reached(iters, start_time)
         return self.handle_goal_reached(node, iters, start_time)
 
+    # ------------------------------------------------------------------ polish the plan found
+    def polish(self, **settings):
+        """Shorten the last plan's action tape by sampled roll-outs on the device (polish.polish_plans; include/ditree.h "plan
+        polishing") against the planner's current maze, start and goal.  ``settings``: ``rollouts``, ``iterations``, ``sigma``,
+        ``hold``, ``seed`` (defaults: polish.DEFAULTS -- settings picked from a sweep, not tuned truths).
+
+        Replaces ``results["path"]`` (float32 (rows + 1, 6): the start state plus one state per action -- no node row appears
+        twice), ``results["actions"]`` and ``results["path_time"]`` (``len(path) * env_dt`` on the new path), adds
+        ``results["polish"]`` (``status``, ``rows_in``, ``rows_out``, ``arrival_in``, ``arrival_out``, ``trace``) and returns
+        ``(path, actions)``.  A plan without a goal node (``status`` "no_goal": a fallback path, or no path) or one whose
+        actions do not replay to the goal from the start state ("no_arrival", "collides", "start_in_goal") comes back
+        unchanged.  The car, one rank; ``plan()`` itself is untouched."""
+        if self.is_ant:
+            raise NotImplementedError("polish: the car (env_id='carmaze') only; the ant's plans are not polished")
+        from ..polish import polish_plans
+        res = self.results
+        if res.get("actions") is None or self._engine.goal_node is None:
+            res["polish"] = _polish_report(None, res.get("actions"))
+            return res.get("path"), res.get("actions")
+        r = polish_plans(self.ctx, self.maze, self.start_node.state[None, :6], np.asarray(self.env.goal, dtype=np.float64)[None, :2],
+                         [res["actions"]], **settings)[0]
+        _apply_polish(res, r, self.env_dt)
+        return res["path"], res["actions"]
+
     # ------------------------------------------------------------------ many seeded runs at once
     def _forest_engine(self, T, tree_capacity, batch):
         """The ForestEngine (ant: AntForestEngine) of ``plan_runs`` (kept between calls of the same shape): the single-tree
@@ -655,6 +679,56 @@ class RRT_Planner(BasePlanner):
         results = [None] * len(seeds)
         run_jobs(eng, [Job(self, s, (results, i)) for i, s in enumerate(seeds)], self.batch, self.ctx.device)
         return results
+
+
+def _polish_report(r, actions):
+    """``results["polish"]`` from one polish_plans result (None: the plan has no goal node and nothing was run)."""
+    if r is None:
+        n = 0 if actions is None else len(actions)
+        return dict(status="no_goal", rows_in=n, rows_out=n, arrival_in=None, arrival_out=None, trace=None)
+    return {k: r[k] for k in ("status", "rows_in", "rows_out", "arrival_in", "arrival_out", "trace")}
+
+
+def _apply_polish(res, r, env_dt):
+    """Write one polish_plans result into a ``results`` dict; a refused plan keeps its path and actions."""
+    res["polish"] = _polish_report(r, res.get("actions"))
+    if r["status"] == "ok":
+        res["path"], res["actions"] = r["path"], r["actions"]
+        res["path_time"] = len(r["path"]) * env_dt
+
+
+def polish_runs(planners, results, **settings):
+    """Polish every goal-reaching run of a ``plan_runs`` result (``planners``: that planner, ``results``: its list of run
+    dicts) or of a ``plan_scenario_runs`` result (a list of planners and one list of run dicts per planner) in ONE
+    ``polish_plans`` call: each run against its planner's maze, start and goal, with the same ``settings`` -- so a run ends
+    as ``RRT_Planner.polish`` leaves the same plan.  The run dicts are updated in place (``path``, ``actions``,
+    ``path_time``, ``polish``) and ``results`` is returned; a run without a goal node gets ``polish`` with status "no_goal"."""
+    from ..polish import polish_plans
+    single = isinstance(planners, RRT_Planner)
+    pls = [planners] if single else list(planners)
+    per = [results] if single else list(results)
+    if len(per) != len(pls):
+        raise ValueError(f"polish_runs: one list of runs per planner ({len(pls)}), got {len(per)}")
+    for pl in pls:
+        if pl.is_ant:
+            raise NotImplementedError("polish_runs: the car (env_id='carmaze') only; the ant's plans are not polished")
+        if pl.ctx is not pls[0].ctx:
+            raise ValueError("polish_runs: all planners must share one ctx")
+    jobs = []
+    for pl, runs in zip(pls, per):
+        for run in runs:
+            if run.get("goal_reached") and run.get("actions") is not None:
+                jobs.append((pl, run))
+            else:
+                run["polish"] = _polish_report(None, run.get("actions"))
+    if jobs:
+        mazes = pls[0].maze if len(pls) == 1 else [pl.maze for pl, _ in jobs]
+        out = polish_plans(pls[0].ctx, mazes, np.stack([pl.start_node.state[:6] for pl, _ in jobs]),
+                           np.stack([np.asarray(pl.env.goal, dtype=np.float64)[:2] for pl, _ in jobs]),
+                           [run["actions"] for _, run in jobs], **settings)
+        for (pl, run), r in zip(jobs, out):
+            _apply_polish(run, r, pl.env_dt)
+    return results
 
 
 def _forest_like(cls, e, *args, **kw):

@@ -1105,6 +1105,85 @@ int32_t ditree_policy_begin(ditree_ctx* ctx, const ditree_policy_batch* batch, v
 int32_t ditree_policy_chunk(ditree_ctx* ctx, const ditree_policy_batch* batch, const ditree_policy_params* p,
                             int32_t* n_active_out /*[host]*/, void* stream);
 
+/* ------------------------------------------------------------------ plan polishing: shorten a found plan's action tape
+ * A post-processing step of the build's own (no counterpart in the reference: PARITY UNPINNED, like MPPI; DESIGN.md section 3
+ * "Plan polishing"; the numpy restatement is tests/polish_ref.py) on the pinned pieces: the car step (car_env.py:356-396), the
+ * two-ball collision test (common/map_utils.py:103-115), the goal radius (car_env.py:341-354), and ditree_mppi_step's normal
+ * generator.  A plan is a start state x0, a goal, a maze and an action tape U (T rows of 2).
+ *   Rolling a tape: X[0] = x0; row t = 0 .. T - 1: X[t + 1] = car_step(X[t], clip(U[t])), then the collision test and the goal
+ *     test of the expansion rounds on X[t + 1], collision first (a colliding row is a collision even inside the radius).
+ *     d_t = sqrt(fma(dy, dy, dx * dx)) of X[t] against the goal, the rounds' goal norm.
+ *   A tape ARRIVES at s rows when X[s] is the first state inside the radius (d_s < 0.5) and no X[1 .. s] collides; its arrival
+ *     time is tau = (s - 1) + (d_{s-1} - 0.5) / (d_{s-1} - d_s)  [rows, continuous].
+ *   Replay: the input tape is rolled.  It is refused -- its status set, every other output of the plan untouched, no iteration
+ *     run on it -- when it collides, does not arrive within its rows, starts inside the radius (d_0 < 0.5), or holds a row up to
+ *     its arrival that is not f32-exact (u != (double)(float)u: the planner's actions are float32, and so is every tape this
+ *     call writes).  Else the incumbent is the tape cut to its s rows: T* = s, tau*, states X*[0 .. T*].
+ *   Iteration n = 0 .. N - 1, candidate k = 0 .. K - 1:
+ *     first perturbed row a = H(seed, n, k) mod T*, with splitmix64 as ditree_mppi_step's generator uses it
+ *       (x += 0x9E3779B97F4A7C15; z = x; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB;
+ *       z ^ z >> 31):   h = splitmix64(seed ^ splitmix64(n));  h = splitmix64(h ^ k * 0xD1B54A32D192ED03);
+ *       H = splitmix64(h ^ 0xA24BAED4963EE407);
+ *     noise eps[k, b] for the block b = t div hold of the ABSOLUTE row index t = ditree_mppi_step's generator at (seed,
+ *       counter = n, k, t = b, sigma);
+ *     candidate action u_k[t] = (double)(float) clip(U*[t] + (t >= a ? eps[k, t div hold] : 0)), the clip the env's (the
+ *       replay keeps the input's rows as given, so a row outside the env's range is stored clipped once a candidate wins);
+ *     the candidate is rolled for at most T* rows.  It is integrated from X*[a] on (rows < a are the incumbent's own), which
+ *       gives what rolling its whole tape from x0 gives.
+ *   Select: the winner is the arriving candidate with the smallest tau, ties to the lowest k; if tau_k < tau* STRICTLY its
+ *     tape cut to its s rows and its states become the incumbent, else nothing changes.
+ *   Hence: the result is a rolled, collision-free, arriving tape; rows never grow; tau never grows; sigma = 0 returns the
+ *   replayed plan.
+ * Two launches per iteration (roll-outs: a grid of K-slices x plans, one candidate per lane, each work-group's (tau, k) minimum
+ * and arriving count; commit: one work-group per plan reduces the slices in index order, applies the strict test and re-rolls
+ * the winner once into tape / states / trace), all N iterations enqueued without a host read: T* and tau* live in rows and
+ * arrival.  Results are a pure function of the arguments (a second identical call leaves the same bits), and a plan's results
+ * do not depend on the other plans of the call.
+ *   n_plans plans; scene == NULL: all against the maze of ditree_upload_maze; else plan i against the maze of scene scene[i] of
+ *     ditree_upload_scenes (the table's goal column is not read: goals are per plan).  Every maze used holds at most
+ *     DITREE_POLISH_MAX_CELLS cells (it is staged in LDS).
+ *   x0 [dev] (n_plans, 6), goal_xy [dev] (n_plans, 2) f64; tape [dev] (n_plans, capacity, 2) f64 in / out, rows [0, T*) count;
+ *     rows [dev] (n_plans,) i32 in: the rows of each input tape, 1 .. capacity, out: T*; rows_host [host] the input values again,
+ *     validated before anything is launched; states [dev] (n_plans, capacity + 1, 6) f64, rows 0 .. T* written; arrival [dev] (n_plans, 2) f64 = tau of the replay, tau*; status [dev] (n_plans,) i32
+ *     DITREE_POLISH_*; trace [dev] (n_plans, N, DITREE_POLISH_TRACE) f64 per iteration: winner k (-1: nothing arrived), its tau
+ *     (+inf then), accepted 0 / 1, T* and tau* after the iteration, arriving candidates.
+ *   noise [dev] (N, K, noise_blocks, 2) f64 or NULL, first_row [dev] (N, K) i32 or NULL replace the generator and the hash for
+ *     every plan alike (tests): a = r mod T* for r = first_row[n, k] >= 0, max(T* + r, 0) for r < 0 (-1: the last row).
+ * DITREE_E_ARG by name: a null pointer, n_plans < 1, state_dim / action_dim other than the car's 6 / 2 (the ant is not built),
+ * K not a positive multiple of 64, N < 0, hold < 1, sigma not finite or negative, capacity < 1, a tape longer than the
+ * capacity, noise_blocks * hold < capacity with noise, a scene id out of range, a maze past DITREE_POLISH_MAX_CELLS;
+ * DITREE_E_STATE without the maze / scene table asked for. */
+#define DITREE_POLISH_OK 0
+#define DITREE_POLISH_NO_ARRIVAL 1      /* the tape's rows end outside the goal radius */
+#define DITREE_POLISH_COLLIDES 2
+#define DITREE_POLISH_START_IN_GOAL 3   /* d_0 < 0.5 */
+#define DITREE_POLISH_NOT_F32 4         /* a row up to the arrival is not f32-exact */
+#define DITREE_POLISH_TRACE 6
+#define DITREE_POLISH_MAX_CELLS 16384
+typedef struct {
+  int32_t n_plans;
+  int32_t state_dim, action_dim;     /* 6, 2 */
+  int32_t capacity;                  /* rows per plan in `tape`; `states` holds capacity + 1 */
+  int32_t K, N, hold;                /* candidates per iteration, iterations, rows per noise block */
+  double sigma[2];
+  uint64_t seed;
+  const int32_t* scene;              /* [dev] (n_plans,) or NULL */
+  const int32_t* scene_host;         /* [host] the same ids */
+  const double* x0;
+  const double* goal_xy;
+  double* tape;
+  int32_t* rows;
+  const int32_t* rows_host;          /* [host] the rows of every input tape */
+  double* states;
+  double* arrival;
+  int32_t* status;
+  double* trace;
+  const double* noise;
+  int32_t noise_blocks;
+  const int32_t* first_row;
+} ditree_polish;
+int32_t ditree_polish_plans(ditree_ctx* ctx, const ditree_polish* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
